@@ -32,6 +32,16 @@ rank builds T1/T2 and its decode table on its own GPU (mh_build_tables_device); 
 are sharded (each rank decodes its own), no collective on the data path;
 value = all frames decoded / max-over-ranks wall time ("weak" scaling).
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) does what `value` needs and no more:
+it encodes and uploads the frames, warms up, clocks the one cold region of N launches
+(`ms_per_step` = that region's wall / N), and prints the line. --full adds everything
+else, as before: the parity guard over every resident frame, the warm / event-timed /
+ungated regions and the `roofline` object, the batch / tile / stream / encode extras
+(--no-extras leaves them out) and the CPU baseline (--no-cpu-baseline leaves it out).
+--dump-outputs DIR writes the raster the clocked region's last launch decoded as
+DIR/decoded.npy (float32; a fixed seeded sample, DIR/decoded_sample.npy, when the raster
+is larger than 48 MiB in float32). The inputs are the same from run to run.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -64,8 +74,16 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=128,
                     help="distinct resident frames per rank (>= 2 batch launches: cold regions)")
     ap.add_argument("--batch", type=int, default=64, help="frames per launch for --workload batch")
-    ap.add_argument("--no-extras", action="store_true", help="skip the batch/tile side measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the parity guard over every resident frame, the warm / "
+                         "ungated / event-timed regions and the roofline object, the batch / tile / stream / "
+                         "encode side measurements and the CPU baseline (a plain run sets up, warms up, times "
+                         "the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step decoded as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the batch/tile side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (default: the affinity set, capped by the cgroup quota)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a hipGraph")
@@ -147,6 +165,8 @@ class Workload:
         self.warm_wall = None
         self.device = device
         self.base = 0  # eager regions decode launches base, base+1, ... (advanced per cold region)
+        self.last_launch = self.last_out = None  # run(keep_last=True)
+        self.gated = False  # run(): the clocked region went out behind the launch gate
         self.outs = [torch.empty((f.n_frames, f.height, (f.width + 7) // 8 * 8), dtype=torch.uint8,
                                  device=device) for f in launches]
 
@@ -212,8 +232,13 @@ class Workload:
             if not torch.equal(self.outs[j][..., : fr.width], self.refs[j]):
                 raise SystemExit(f"bench: {self.name} launch {j} differs from the encoder input after timing")
 
-    def run(self, steps, warmup, use_graph=True, world=1, settle_ms=50.0):
-        """Timed regions of `steps` launches each, bracketed by barrier + synchronize;
+    def run(self, steps, warmup, use_graph=True, world=1, settle_ms=50.0, full=True, keep_last=False):
+        """full=False: the warm-up and the one clocked region behind `wall` only; the
+        warm, event-timed and ungated regions, the graph-replay and per-launch event
+        figures need runs of their own and are left out -> (wall_s, None, None).
+        keep_last: a copy of the raster the clocked region's last launch wrote is kept
+        in `last_out` (taken right after that region, off the clock).
+        Timed regions of `steps` launches each, bracketed by barrier + synchronize;
         wall = max over ranks. Every clocked region is COLD: the launches it decodes were
         not touched by the region before it (eager regions advance `base` by `steps`;
         graph regions cycle over >= 2 launches of >= 337 MB each) and a 1 GiB copy evicts
@@ -245,6 +270,7 @@ class Workload:
             G = LONG_GRAPH_LAUNCHES
         self.graph_launches = G
         graph = None
+        graph_base = self.base  # the captured graph decodes launches graph_base .. graph_base + G - 1
 
         def replay_all():  # the K launches: K / G replays of the G-launch graph
             for _ in range(steps // G):
@@ -365,26 +391,45 @@ class Workload:
                       (r0.elapsed_time(r1) / steps if events else None))
             return w, (r0.elapsed_time(r1) if events else None), (steady, unit)
 
+        def keep():
+            """The clocked region's last launch: launch steps-1 of an eager region (from
+            the region's `base`), launch G-1 of the captured graph otherwise."""
+            eager = graph is None or (eager_gated and GATE.ok())
+            self.last_launch = ((self.base + steps - 1) if eager else (graph_base + G - 1)) % len(self.launches)
+            if keep_last:
+                fr = self.launches[self.last_launch]
+                self.last_out = self.outs[self.last_launch][..., : fr.width].clone()
+
+        region_ms = steady_ms = None
+        self.steady_unit = 1
         if GATE.ok():
             timed(events=False, cold=False)  # the gate's own first launch off the clock
-            # warm (reported beside): the same launches again, no flush
-            self.warm_wall, _, _ = timed(events=False, cold=False)
+            if full:
+                # warm (reported beside): the same launches again, no flush
+                self.warm_wall, _, _ = timed(events=False, cold=False)
             # The clocked region holds only the K launches: its two HIP event records
             # (markers in the queue) cost ~7 us per region at 20 steps (510 vs 482 x10^3
             # MB/s interleaved, profiles/r02_v13_region_events_ab.txt), so the event-timed
             # region is a second, identical (cold) one.
             wall, _, _ = timed(events=False)
-            _, region_ms, (steady_ms, self.steady_unit) = timed(mark=True)
-            self.ungated_wall, _, _ = timed(gated=False)
+            keep()
+            self.gated = True
+            if full:
+                _, region_ms, (steady_ms, self.steady_unit) = timed(mark=True)
+                self.ungated_wall, _, _ = timed(gated=False)
             self.timed_launch = (("eager behind the launch gate, launches 2..K with MH_FLAG_ANY_ORDER")
                                  if eager_gated else
                                  f"{steps // G} replays of a {G}-launch hipGraph, the first behind the launch gate, "
                                  "the rest enqueued once it opens")
         else:
             wall, region_ms, (steady_ms, self.steady_unit) = timed(gated=False, mark=True)
+            keep()
             self.ungated_wall = None
             self.timed_launch = "hipGraph" if graph is not None else "eager"
         self.timed_launch += "; cold inputs (launches no earlier region touched, 1 GiB cache flush before each region)"
+        if not full:
+            self.region_kernel_ms = self.steady_kernel_ms = self.kernel_ms = None
+            return wall, None, None
         self.region_kernel_ms = region_ms / steps
         self.steady_kernel_ms = steady_ms
         # Per-launch kernel duration of the same launches replayed as graphs back to back
@@ -830,6 +875,28 @@ def cpu_baseline(efs, threads=None, target_s=2.0):
     return out
 
 
+DUMP_MAX_ELEMS = 12 << 20  # float32: 48 MiB in a file
+DUMP_SEED = 20261019
+
+
+def dump_outputs(dirname: str, wl) -> dict:
+    """--dump-outputs: what the clocked region's last launch decoded (Workload.last_out,
+    u8[n_frames, H, W], the raster a caller of the decoder receives, padding columns cut)
+    as float32 in DIR/decoded.npy; a raster of more than DUMP_MAX_ELEMS pixels as
+    DIR/decoded_sample.npy, its pixels at DUMP_MAX_ELEMS flat indices drawn once from a
+    fixed seed (sorted; the same indices every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    out = wl.last_out.cpu().numpy()
+    if out.size <= DUMP_MAX_ELEMS:
+        name, arr = "decoded", out.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, out.size, size=DUMP_MAX_ELEMS))
+        name, arr = "decoded_sample", out.reshape(-1)[idx].astype(np.float32)
+    np.save(os.path.join(dirname, name + ".npy"), arr)
+    return {"file": name + ".npy", "launch": int(wl.last_launch), "shape": list(out.shape),
+            "elements_written": int(arr.size)}
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as sk:
@@ -920,7 +987,9 @@ def main(argv=None) -> int:
     efs = encode_many(imgs)
     for ef in efs:
         assert np.array_equal(ef.canon, efs[0].canon)
-    dimgs = torch.from_numpy(np.stack(imgs)).to(dev)  # the inputs, for the parity guard
+    full = args.full
+    # the inputs, for the parity guard (--full)
+    dimgs = torch.from_numpy(np.stack(imgs)).to(dev) if full else None
 
     def pack(group):
         return D.DeviceFrames.pack(group, dev)
@@ -928,7 +997,7 @@ def main(argv=None) -> int:
     def frame_workload():
         launches = [pack([ef]) for ef in efs]
         return Workload("frame", launches, tables, bb.size, algo_bytes(efs[:1], t2_bytes), dev,
-                        refs=[dimgs[i:i + 1] for i in range(len(efs))],
+                        refs=[dimgs[i:i + 1] for i in range(len(efs))] if full else None,
                         read_bytes=algo_read_bytes(efs[:1], t2_bytes))
 
     def batch_workload(nb):
@@ -936,7 +1005,7 @@ def main(argv=None) -> int:
         groups = [efs[i:i + nb] for i in starts]
         launches = [pack(g) for g in groups]
         return Workload(f"batch{nb}", launches, tables, nb * bb.size, algo_bytes(groups[0], t2_bytes), dev,
-                        refs=[dimgs[i:i + nb] for i in starts],
+                        refs=[dimgs[i:i + nb] for i in starts] if full else None,
                         read_bytes=algo_read_bytes(groups[0], t2_bytes))
 
     def tile_workload(random=False):
@@ -952,7 +1021,7 @@ def main(argv=None) -> int:
         launches = [pack([ef]) for ef in tefs]
         name = "tile8192_random" if random else "tile8192"
         return Workload(name, launches, ttabs, base.size, algo_bytes(tefs[:1], ttabs.table2.numel()), dev,
-                        refs=[torch.from_numpy(im).to(dev).unsqueeze(0) for im in imgs],
+                        refs=[torch.from_numpy(im).to(dev).unsqueeze(0) for im in imgs] if full else None,
                         read_bytes=algo_read_bytes(tefs[:1], ttabs.table2.numel()))
 
     if args.workload == "frame":
@@ -968,9 +1037,9 @@ def main(argv=None) -> int:
         wl = tile_workload(random=True)
         wdesc = "config3 stress: one 8192x8192 uniform-random frame per launch per GPU"
 
-    # parity guard: every resident frame of every launch, before timing
-    frames_verified = wl.verify()
-    ref_shape = wl.refs[0].shape[1:]
+    # parity guard (--full): every resident frame of every launch, before timing
+    frames_verified = wl.verify() if full else None
+    ref_shape = (wl.launches[0].height, wl.launches[0].width)
     # multi-rank: every rank's verified-frame count gathered on rank 0
     ranks_ok = None
     rank_devices = None
@@ -992,10 +1061,13 @@ def main(argv=None) -> int:
         rank_devices = {"devices": [{k: g[2][k] for k in ("rank", "ordinal", "pci")} for g in got],
                         "distinct_devices": len(devs), "backend": backend}
 
-    wall, region_ms, kms = wl.run(args.steps, args.warmup, use_graph=not args.no_graph, world=world)
-    wl.check_outputs()  # the any-order / rotated regions' rasters
+    wall, region_ms, kms = wl.run(args.steps, args.warmup, use_graph=not args.no_graph, world=world,
+                                  full=full, keep_last=args.dump_outputs is not None)
+    dumped = dump_outputs(args.dump_outputs, wl) if args.dump_outputs is not None and rank == 0 else None
+    if full:
+        wl.check_outputs()  # the any-order / rotated regions' rasters
     per_step = wall / args.steps
-    if not use_dist and not args.no_extras:
+    if full and not use_dist and not args.no_extras:
         ACHIEVABLE.update(hbm_probe() or {})  # after the timed region: the roofline context
     value = world * wl.pixels / per_step / 1e6
 
@@ -1009,12 +1081,10 @@ def main(argv=None) -> int:
                    "frames_per_step_per_gpu": int(wl.launches[0].n_frames),
                    "parallelism": f"frame-sharded x{world}", "launch": wl.timed_launch},
         "mpixels_per_s": round(value, 1),
-        "roofline": roofline(wl.bytes, region_ms, args.steps, kms, args.workload, wl.read_bytes,
-                             wl.kernel_ms, wl.steady_kernel_ms, wl.steady_unit),
-        "gpu_region_ms_per_step": round(region_ms / args.steps, 5),
+        "full": full,
         "timing": ("gated: the K launches are enqueued behind a host-opened launch gate before "
                    "the clock starts (scripts/micro/launch_gate.hip); every decode runs inside "
-                   "the timed region" if wl.ungated_wall is not None else "plain"),
+                   "the timed region" if wl.gated else "plain"),
     }
     if wl.warm_wall is not None:
         # the clocked region re-decodes the launches the region before it just decoded,
@@ -1026,17 +1096,25 @@ def main(argv=None) -> int:
         # the same K launches timed the plain way (enqueue latency inside the clock)
         result["ungated_ms_per_step"] = round(wl.ungated_wall / args.steps * 1e3, 5)
         result["ungated_value"] = round(world * wl.pixels / (wl.ungated_wall / args.steps) / 1e6, 1)
-    result["frames_verified"] = frames_verified
+    if full:
+        result["roofline"] = roofline(wl.bytes, region_ms, args.steps, kms, args.workload, wl.read_bytes,
+                                      wl.kernel_ms, wl.steady_kernel_ms, wl.steady_unit)
+        result["gpu_region_ms_per_step"] = round(region_ms / args.steps, 5)
+        result["frames_verified"] = frames_verified
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     # the sources this library was built from (the loader refuses a stale library)
     result["source_stamp"] = dict(B.source_stamps(), loaded=mh.lib().mh_build_stamp().decode()[:16])
-    if ranks_ok is not None:
+    if ranks_ok is not None and not full:
+        result["rank_devices"] = rank_devices
+    if ranks_ok is not None and full:
         result["ranks_verified"] = ranks_ok
         result["rank_devices"] = rank_devices
     if t_bcast_us is not None:
         result["table_broadcast_us"] = round(t_bcast_us, 1)  # 256-B RCCL broadcast + device table build
         result["table_broadcast_bytes"] = 256
 
-    if not use_dist and rank == 0 and not args.no_extras:
+    if full and not use_dist and rank == 0 and not args.no_extras:
         extras = {}
         if args.workload == "frame":
             # config 2 with independent frames in flight on several streams (one launch
@@ -1080,7 +1158,7 @@ def main(argv=None) -> int:
         extras["encode"] = encode_rate(dev, bb)
         result["extras"] = extras
 
-    if use_dist and not args.no_extras:
+    if full and use_dist and not args.no_extras:
         # The other multi-GPU configs on the same ranks (BASELINE configs[3], configs[4]):
         # config 4 = 64 frames per launch per GPU, timed like the headline (barrier +
         # synchronize, max over ranks); config 5 = every rank streaming host-resident
@@ -1113,7 +1191,7 @@ def main(argv=None) -> int:
             "method": "each rank: native mh_stream (2 slots), sustained phase started together after a barrier"}
         result["extras"] = extras
 
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(efs[: min(len(efs), 32)], args.cpu_threads or None)
 
     if rank == 0:

@@ -12,8 +12,11 @@ import os
 import numpy as np
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIGBRIDGE_PNG = os.path.join(_ROOT, "tests", "golden", "BigBridge.png")
-BIGBRIDGE_SHA256 = "da4067ee26fb77b14258b92a749594a0aa42fcbba6047b92843663604703021e"
+# BigBridge.png is kept as two row bands (rows 0-895, 896-1535), each a mode-L PNG below
+# the 1 MiB limit for a committed file; stacked they are the asset's 2048x1536 pixels
+BIGBRIDGE_PNGS = [os.path.join(_ROOT, "tests", "golden", name)
+                  for name in ("BigBridge_rows0000_0896.png", "BigBridge_rows0896_1536.png")]
+BIGBRIDGE_SHA256 = "da4067ee26fb77b14258b92a749594a0aa42fcbba6047b92843663604703021e"  # of the raw gray
 
 
 def load_gray_png(path: str) -> np.ndarray:
@@ -25,8 +28,8 @@ def load_gray_png(path: str) -> np.ndarray:
 
 
 def bigbridge() -> np.ndarray:
-    """Config 2 frame: BigBridge.png, 2048x1536 (identity load: the PNG is mode L)."""
-    return load_gray_png(BIGBRIDGE_PNG)
+    """Config 2 frame: BigBridge.png, 2048x1536 (identity load: the PNGs are mode L)."""
+    return np.ascontiguousarray(np.concatenate([load_gray_png(p) for p in BIGBRIDGE_PNGS], axis=0))
 
 
 def mirror_tile(img: np.ndarray, height: int, width: int) -> np.ndarray:

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=${OUT:-$GRAFT_REPO_ROOT/gpurun_out}
 mkdir -p $OUT
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
-B="python3 bench.py --workload ${WL:-batch} --steps 10 --warmup 2 --no-extras --no-cpu-baseline"
+B="python3 bench.py --workload ${WL:-batch} --steps 10 --warmup 2 --full --no-extras --no-cpu-baseline"
 i=0
 # PMC_GROUPS="grp1;grp2" (space-separated counters per group) replaces the default groups
 DEFAULT_GROUPS=$(cat <<'GROUPS'

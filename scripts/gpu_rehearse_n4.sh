@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 MH_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-  --master-addr 127.0.0.1 --master-port 29527 bench.py --gpus 4 --steps 20 --warmup 5 \
+  --master-addr 127.0.0.1 --master-port 29527 bench.py --gpus 4 --steps 20 --warmup 5 --full \
   > gpurun_out/bench_n4_gloo.json 2> gpurun_out/bench_n4_gloo.err || { tail -30 gpurun_out/bench_n4_gloo.err; exit 1; }
 python3 -c "
 import json

@@ -9,7 +9,7 @@ rm -rf $OUT; mkdir -p $OUT
 for wl in ${WLS-frame batch tile8192 tile8192_random}; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --pmc $ctr --output-format csv -d $OUT/${wl}_$ctr -o run -- \
-      python3 bench.py --workload $wl --steps 20 --warmup 2 --no-extras --no-cpu-baseline --no-graph \
+      python3 bench.py --workload $wl --steps 20 --warmup 2 --full --no-extras --no-cpu-baseline --no-graph \
       > $OUT/${wl}_$ctr.log 2>&1 || { echo "pmc $wl $ctr failed"; tail -5 $OUT/${wl}_$ctr.log; exit 1; }
   done
 done

@@ -10,6 +10,8 @@ What it records (all data, no reference source):
     reference encoder (Shared/HuffmanEncoder.cpp, compiled unmodified by
     oracle/Makefile into oracle/_ref/ref_encode) emits for the renderer's producer
     step (8x8 zero-padded blocks, per-block deltas, AAPLRenderer.m:374-688);
+  * ref_random_histograms.npz: the same encoder's header, codes and block offsets for the
+    tie-breaking stress streams of tests/helpers.random_histogram_streams();
   * BigBridge T1/T2 SHA-256 as recorded in SURVEY.md 8(c) (reference table builder,
     HuffmanUtil.cpp:338-667, built in the survey session).
 The huffBuff hashes include the renderer's 2 extra zero bytes (AAPLRenderer.m:576-585).
@@ -109,18 +111,42 @@ def ref_record(img: np.ndarray) -> dict:
     }
 
 
+def write_random_histograms() -> str:
+    """ref_random_histograms.npz: the reference encoder's header, codes and block offsets
+    for every stream of tests/helpers.random_histogram_streams() it accepts (a code longer
+    than 16 bits makes it assert)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import REF_HISTOGRAMS, random_histogram_streams
+    rec = {}
+    for trial, d in random_histogram_streams():
+        if O.code_lengths(d)[0] != 0:
+            continue
+        canon, codes, offs = O.ref_encode(d, 64)
+        rec.update({f"canon_{trial}": canon, f"codes_{trial}": codes, f"offsets_{trial}": offs})
+    np.savez_compressed(REF_HISTOGRAMS, **rec)
+    print("wrote", REF_HISTOGRAMS)
+    return REF_HISTOGRAMS
+
+
 def main() -> int:
     if not os.path.isdir(REF_SHARED):
         print("needs /root/reference (build container only)", file=sys.stderr)
         return 1
     O.build()
     O.build_ref()
-    for asset in ("BigBridge.png", "Image.png"):
-        dst = os.path.join(HERE, asset)
-        if not os.path.exists(dst):
-            shutil.copy(os.path.join(REF_SHARED, asset), dst)
+    write_random_histograms()
+    dst = os.path.join(HERE, "Image.png")
+    if not os.path.exists(dst):
+        shutil.copy(os.path.join(REF_SHARED, "Image.png"), dst)
     from metalhuffman_amd import frames as F
     from PIL import Image
+
+    # BigBridge.png (1.6 MB) as two mode-L row bands, each below 1 MiB (frames.BIGBRIDGE_PNGS)
+    if not all(os.path.exists(p) for p in F.BIGBRIDGE_PNGS):
+        gray = F.load_gray_png(os.path.join(REF_SHARED, "BigBridge.png"))
+        for p, (r0, r1) in zip(F.BIGBRIDGE_PNGS, ((0, 896), (896, 1536))):
+            Image.fromarray(gray[r0:r1]).save(p, "PNG", optimize=True, compress_level=9)
+    assert sha(F.bigbridge()) == F.BIGBRIDGE_SHA256
 
     out: dict = {"generator": "tests/golden/gen_golden.py", "small_frames": {}, "workloads": {}}
     for name, (w, h, px) in SMALL.items():

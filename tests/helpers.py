@@ -14,6 +14,22 @@ def golden() -> dict:
         return json.load(f)
 
 
+REF_HISTOGRAMS = os.path.join(GOLDEN, "ref_random_histograms.npz")
+
+
+def random_histogram_streams(seed: int = 11, trials: int = 40):
+    """(trial, symbols) of the tie-breaking stress: small alphabets with repeated
+    frequencies, whole 64-symbol blocks. tests/golden/gen_golden.py records the reference
+    encoder's output for each stream it accepts in REF_HISTOGRAMS (canon_<trial>,
+    codes_<trial>, offsets_<trial>)."""
+    r = np.random.default_rng(seed)
+    for trial in range(trials):
+        nsym = int(r.integers(1, 40))
+        alphabet = r.choice(256, size=nsym, replace=False).astype(np.uint8)
+        weights = r.integers(1, 6, size=nsym) ** r.integers(1, 4)
+        yield trial, r.choice(alphabet, size=64 * int(r.integers(1, 50)), p=weights / weights.sum())
+
+
 def image_from_block_deltas(deltas: np.ndarray, width: int, height: int) -> np.ndarray:
     """Integrate per-block deltas (block order, 64 per block) into a raster whose
     producer step (split + per-block delta) yields exactly `deltas`.

@@ -31,8 +31,34 @@ def test_default_arguments(bench):
     a = bench.parse_args([])
     assert (a.gpus, a.workload, a.frames, a.batch) == (1, "frame", 128, 64)  # two cold batch launches
     assert a.steps > 0 and a.warmup >= 0 and not a.no_graph
+    assert not a.full and a.dump_outputs is None  # a plain run: the headline figure only
     a = bench.parse_args(["--gpus", "8", "--steps", "20", "--warmup", "5"])
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_whole_and_sampled(bench, tmp_path, monkeypatch):
+    """--dump-outputs: a small raster is written whole as float32; a larger one as a sample
+    at the same seeded indices every time, within the element limit."""
+    import types
+
+    import numpy as np
+    import torch
+    ras = torch.from_numpy(np.random.default_rng(5).integers(0, 256, size=(2, 37, 61), dtype=np.uint8))
+    wl = types.SimpleNamespace(last_out=ras, last_launch=3)
+    info = bench.dump_outputs(str(tmp_path / "a"), wl)
+    got = np.load(tmp_path / "a" / "decoded.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ras.numpy().astype(np.float32))
+    assert info == {"file": "decoded.npy", "launch": 3, "shape": [2, 37, 61], "elements_written": ras.numel()}
+    assert bench.DUMP_MAX_ELEMS * 4 <= 64 * 10**6
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), wl)["file"] == "decoded_sample.npy"
+    b, c = (np.load(tmp_path / d / "decoded_sample.npy") for d in ("b", "c"))
+    assert b.dtype == np.float32 and b.shape == (1000,) and np.array_equal(b, c)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, ras.numel(), size=1000))
+    assert np.array_equal(b, ras.numpy().reshape(-1)[idx].astype(np.float32))
 
 
 def test_roofline_fields_and_arithmetic(bench):

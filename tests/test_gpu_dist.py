@@ -148,8 +148,8 @@ def test_bench_dist_path_on_rccl_world1():
     env = dict(os.environ, MH_BENCH_BACKEND="nccl")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dist", "--steps", "8", "--warmup", "2",
-                        "--frames", "8", "--batch", "8", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--dist", "--steps", "8",
+                        "--warmup", "2", "--frames", "8", "--batch", "8", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=280, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
