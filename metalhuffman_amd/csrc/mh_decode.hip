@@ -39,6 +39,9 @@ namespace {
 #ifndef MH_DIAG_CLOCK           // diagnostic builds only: core-clock cycles of the single-frame
 #define MH_DIAG_CLOCK 0         //    decode in stamp slot 5 (scripts/diag_stamps.py --clock)
 #endif
+#ifndef MH_DIAG_ARGS            // diagnostic builds only: small-launch kernels stamp slot 5 once their
+#define MH_DIAG_ARGS 0          //    output arguments are in registers (scripts/diag_stamps.py --args)
+#endif
 #ifndef MH_DIAG_DROP_STORES     // diagnostic builds only: every row store out of range (dropped)
 #define MH_DIAG_DROP_STORES 0
 #endif
@@ -986,10 +989,75 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
 // single-level 14-bit table drops the escape test. Workgroups of 4 waves (one per
 // SIMD; 192 for a 2048x1536 frame) beat 8 (two waves per SIMD, fewer table copies):
 // 5.74 vs 5.89 us (profiles/r01_v15_small_step_ab.txt).
+// Two entries share the decode (small_decode): mh_decode_frame_kernel for one frame without
+// a frame-offset array, mh_decode_small_kernel for every other small launch.
 constexpr int kSmallWaves = 4;  // waves per workgroup (one tile each)
 constexpr int kSmallMaxTilesPerCU = 4;   // launches up to this many tiles per CU
 __shared__ __attribute__((aligned(16))) uint16_t s_lut_small[kLut14Entries];  // 14-bit, or 13-bit L1+L2
 static_assert(kLutBytes <= kLut14Bytes, "the 13-bit table fits the small kernel's LUT space");
+
+// The small-launch kernels' common tail, entered behind the table barrier with the tile's
+// span in flight in R: stage it, decode the tile with the step flavour the lengths word
+// picks (flat8 / l14, kernel-uniform), and (diagnostic builds) write the wave's stamps.
+template <bool kDelta>
+__device__ __forceinline__ void small_decode(const DecodeArgs &a, const Tile &t, uint32_t lane,
+                                             const v4u32 (&R)[kStageChunks], bool live, bool staged, bool flat8,
+                                             bool l14, uint8_t *stage, const uint8_t *lut, uint32_t gw MH_TS_PARAM) {
+  if (!live) return;  // no barrier below
+#if MH_DIAG_STAMPS && MH_DIAG_ARGS
+  // slot 5: the output arguments are in registers (behind the kernarg segment's scalar
+  // load where the kernel reads them from memory), in front of out_tile's divisions
+  asm volatile("" ::"s"(a.out), "s"((uint32_t)a.out_pitch), "s"((uint32_t)a.out_frame_bytes), "s"(a.bw));
+  MH_STAMP(5);
+#endif
+  const OutTile ot = out_tile(a, t, lane);
+  const __amdgpu_buffer_rsrc_t out = ot.rsrc;
+  const uint32_t row0 = ot.row0;
+  // the small kernel's step flavours (all with write-through row stores)
+  using Small14 = StepCfg<kLut14Bits, false, false, false, kSmallStoreAux, true>;
+  using Small13 = StepCfg<kLutBits, false, true, false, kSmallStoreAux, true>;
+  using SmallFlat8 = StepCfg<kLutBits, false, false, false, kSmallStoreAux, false, true>;
+#if MH_DIAG_STAMPS && MH_DIAG_CLOCK
+  unsigned long long c3 = 0;
+#endif
+  if (staged) {
+    span_write(t, lane, R, stage);
+    wave_sync();
+    MH_STAMP(3);
+#if MH_DIAG_STAMPS && MH_DIAG_CLOCK
+    c3 = __builtin_amdgcn_s_memtime();
+#endif
+    LdsWords src{stage};
+    if (flat8)
+      decode_block<kDelta, SmallFlat8>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
+    else if (l14)
+      decode_block<kDelta, Small14>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
+    else
+      decode_block<kDelta, Small13>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
+  } else if (flat8) {
+    decode_halves<kDelta, SmallFlat8>(a, t, lane, lut, stage, out, row0, !t.valid);
+  } else if (l14) {
+    decode_halves<kDelta, Small14>(a, t, lane, lut, stage, out, row0, !t.valid);
+  } else {
+    decode_halves<kDelta, Small13>(a, t, lane, lut, stage, out, row0, !t.valid);
+  }
+#if MH_DIAG_STAMPS
+  MH_STAMP(4);
+#if MH_DIAG_CLOCK
+  ts[5] = staged ? __builtin_amdgcn_s_memtime() - c3 : 0ull;  // core clocks of the decode
+#elif !MH_DIAG_ARGS
+  ts[5] = ts[4];
+#endif
+  __builtin_amdgcn_s_waitcnt(0);
+  MH_STAMP(6);
+  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // HW_REG_XCC_ID[3:0]
+  ts[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)__smid() << 32) | blockIdx.x;
+  if (lane == 0 && gw < (uint32_t)kDiagWaves)
+    for (int i = 0; i < kDiagSlots; ++i) g_stamps[gw * kDiagSlots + i] = ts[i];
+#else
+  (void)gw;
+#endif
+}
 
 template <bool kDelta>
 // The kernel arguments the first loads depend on come first, as scalars: the code object
@@ -1060,54 +1128,99 @@ __global__ void __launch_bounds__(64 * kSmallWaves) mh_decode_small_kernel(
   MH_STAMP(2);
   // a flat 8-bit identity table (code c = symbol c; the builder sets the word only when
   // every first-level entry says so): byte arithmetic from the staged span (kernel-uniform)
-  const bool flat8 = lens.z != 0u;
-  if (!live) return;  // no barrier below
-  const OutTile ot = out_tile(a, t, lane);
-  const __amdgpu_buffer_rsrc_t out = ot.rsrc;
-  const uint32_t row0 = ot.row0;
-  // the small kernel's step flavours (all with write-through row stores)
-  using Small14 = StepCfg<kLut14Bits, false, false, false, kSmallStoreAux, true>;
-  using Small13 = StepCfg<kLutBits, false, true, false, kSmallStoreAux, true>;
-  using SmallFlat8 = StepCfg<kLutBits, false, false, false, kSmallStoreAux, false, true>;
-#if MH_DIAG_STAMPS && MH_DIAG_CLOCK
-  unsigned long long c3 = 0;
-#endif
-  if (staged) {
-    span_write(t, lane, R, stage);
-    wave_sync();
-    MH_STAMP(3);
-#if MH_DIAG_STAMPS && MH_DIAG_CLOCK
-    c3 = __builtin_amdgcn_s_memtime();
-#endif
-    LdsWords src{stage};
-    if (flat8)
-      decode_block<kDelta, SmallFlat8>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
-    else if (l14)
-      decode_block<kDelta, Small14>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
-    else
-      decode_block<kDelta, Small13>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
-  } else if (flat8) {
-    decode_halves<kDelta, SmallFlat8>(a, t, lane, lut, stage, out, row0, !t.valid);
-  } else if (l14) {
-    decode_halves<kDelta, Small14>(a, t, lane, lut, stage, out, row0, !t.valid);
-  } else {
-    decode_halves<kDelta, Small13>(a, t, lane, lut, stage, out, row0, !t.valid);
-  }
+  small_decode<kDelta>(a, t, lane, R, live, staged, lens.z != 0u, l14, stage, lut,
+                       blockIdx.x * nwaves + wave MH_TS_ARG);
+}
+
+// ---- one frame, prepared table, no frame-offset array: the single-frame entry ----
+// The same decode as mh_decode_small_kernel with no scalar round trip on the wave's
+// start path:
+//   * the whole argument list is 14 dwords -- five pointers, then four dwords, no
+//     padding -- which is what the kernarg preload holds (16 user SGPRs less the
+//     kernarg pointer), so every argument is in an SGPR at wave launch and the kernel
+//     never reads the kernarg segment. Everything else is derived: tiles from nb,
+//     out_frame_bytes = h * pitch. launch() bounds what the narrow fields hold
+//     (codes_bytes <= 0xFFFFFFF0 and pitch <= 2^20 in mh_decode, bw <= 8192,
+//     h <= MH_MAX_DIM = 65535);
+//   * the table's loads do not wait for the lengths word: the 14-bit table is loaded
+//     unconditionally right behind the offsets; the word (scalar loads issued at entry)
+//     is first read behind the span's loads and the table's LDS stores. A table with a code
+//     over 14 bits (kernel-uniform, rare) then copies the 13-bit two-level table over
+//     the 14-bit one before the barrier -- each thread overwrites only chunks it wrote
+//     itself, and a wave's LDS stores stay in order.
+// Waits before / after: profiles/frame_entry_prologue_waits.txt; stamps and A/B against
+// mh_decode_small_kernel: profiles/frame_entry_stamps.txt, frame_entry_ab.txt.
+constexpr uint32_t kFrameBwShift = 16;  // p_bw_h = bw << 16 | h
+static_assert(MH_MAX_DIM <= 0xFFFFu && (MH_MAX_DIM + 7) / 8 < (1u << (32 - kFrameBwShift)),
+              "bw and h share one dword");
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kSmallWaves) mh_decode_frame_kernel(
+    const uint32_t *p_offsets, const uint16_t *p_lut, const uint8_t *p_codes, uint8_t *p_out,
+    const uint8_t *p_block_init, uint32_t p_nb, uint32_t p_codes_bytes, uint32_t p_pitch, uint32_t p_bw_h) {
+  DecodeArgs a{};  // t1 / t2 / frame_off stay null: the body reads none of them with a prepared table
+  a.offsets = p_offsets;
+  a.lut = p_lut;
+  a.codes = p_codes;
+  a.out = p_out;
+  a.block_init = p_block_init;
+  a.nb = p_nb;
+  a.codes_bytes = p_codes_bytes;
+  a.out_pitch = p_pitch;
+  a.bw = p_bw_h >> kFrameBwShift;
+  a.h = p_bw_h & ((1u << kFrameBwShift) - 1u);
+  a.out_frame_bytes = (uint64_t)a.h * p_pitch;
+  a.tiles_per_frame = a.total_tiles = (p_nb + 63u) / 64u;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  constexpr uint32_t nwaves = kSmallWaves;
+  uint8_t *stage = s_stage + wave * kStageBytes;
+  const uint8_t *lut = reinterpret_cast<const uint8_t *>(s_lut_small);
+  const uint8_t *prepared = reinterpret_cast<const uint8_t *>(a.lut);
 #if MH_DIAG_STAMPS
-  MH_STAMP(4);
-#if MH_DIAG_CLOCK
-  ts[5] = staged ? __builtin_amdgcn_s_memtime() - c3 : 0ull;  // core clocks of the decode
-#else
-  ts[5] = ts[4];
+  unsigned long long ts[kDiagSlots] = {};
 #endif
-  __builtin_amdgcn_s_waitcnt(0);
-  MH_STAMP(6);
-  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // HW_REG_XCC_ID[3:0]
-  ts[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)__smid() << 32) | blockIdx.x;
-  const uint32_t gw = blockIdx.x * nwaves + wave;
-  if (lane == 0 && gw < (uint32_t)kDiagWaves)
-    for (int i = 0; i < kDiagSlots; ++i) g_stamps[gw * kDiagSlots + i] = ts[i];
-#endif
+  MH_STAMP(0);
+
+  // [longest code, shortest code, flat8] (mh_lut.hpp): the two words used, as two scalar
+  // loads read below. (One 4-word load leaves two result registers dead; the compiler
+  // reuses one and waits for the load before writing it -- in front of the span's loads.)
+  const uint32_t *lens = reinterpret_cast<const uint32_t *>(prepared + kMaxLenOff);
+  const uint32_t max_len = lens[0], flat8 = lens[2];
+  const uint32_t tile = min(blockIdx.x * nwaves + wave, a.total_tiles);
+  TileHdr h;
+  hdr_issue(a, tile, lane, h);
+  constexpr int kLutLoads = kLut14Bytes / 16 / (64 * kSmallWaves);  // 8
+  static_assert(kLut14Bytes == kLutLoads * 16 * 64 * kSmallWaves, "whole table per pass");
+  v4u32 L[kLutLoads];
+  {
+    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(prepared + kLut14Off, (uint32_t)kLut14Bytes);
+#pragma unroll
+    for (int k = 0; k < kLutLoads; ++k)
+      L[k] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)((threadIdx.x + 64u * kSmallWaves * k) * 16u), 0, 0);
+  }
+  const Tile t = hdr_resolve(a, h, lane);
+  MH_STAMP(1);
+  const bool live = t.tile < a.total_tiles;
+  const bool staged = live && t.span <= (uint32_t)kStageBytes;
+  v4u32 R[kStageChunks];
+  span_issue(a, t, lane, R, staged);
+  v4u32 *dst = reinterpret_cast<v4u32 *>(s_lut_small);
+#pragma unroll
+  for (int k = 0; k < kLutLoads; ++k) dst[threadIdx.x + 64u * kSmallWaves * k] = L[k];
+  // keep the lengths word's wait below the span's loads and the table's stores
+  __builtin_amdgcn_sched_barrier(0);
+  const bool l14 = max_len <= (uint32_t)kLut14Bits;
+  if (__builtin_expect(!l14, 0)) {
+    constexpr uint32_t kChunks = kLutBytes / 16;
+    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(prepared, (uint32_t)kLutBytes);
+#pragma unroll 1
+    for (uint32_t c = threadIdx.x; c < kChunks; c += 64u * kSmallWaves)
+      dst[c] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)(c * 16u), 0, 0);
+  }
+  lds_barrier();  // LDS only, as in mh_decode_small_kernel
+  MH_STAMP(2);
+  small_decode<kDelta>(a, t, lane, R, live, staged, flat8 != 0u, l14, stage, lut,
+                       blockIdx.x * nwaves + wave MH_TS_ARG);
 }
 
 #if MH_LANE_PAIRS
@@ -1513,6 +1626,14 @@ int launch(const DecodeArgs &a0, hipStream_t s, bool lane_pairs, bool any_order)
     // table (measured: 8-wave groups beat one 3-wave group per CU by ~5 %)
     const uint32_t nw = kSmallWaves;
     a.n_groups = (a.total_tiles + nw - 1) / nw;
+    if (a.total_tiles == a.tiles_per_frame && !a.frame_off) {
+      // one frame, no frame-offset array: the entry whose arguments are all preloaded.
+      // mh_decode has bounded what the 32-bit arguments hold (codes_bytes, pitch, dims).
+      MH_LAUNCH(mh_decode_frame_kernel<kDelta>, dim3(a.n_groups), dim3(nw * 64), s, any_order, a.offsets, a.lut,
+                a.codes, a.out, a.block_init, a.nb, (uint32_t)a.codes_bytes, (uint32_t)a.out_pitch,
+                (a.bw << kFrameBwShift) | a.h);
+      return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+    }
     MH_LAUNCH(mh_decode_small_kernel<kDelta>, dim3(a.n_groups), dim3(nw * 64), s, any_order, a.offsets,
               a.frame_off, a.block_init, a.lut, a.nb, a.tiles_per_frame, a.total_tiles, a);
     return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;

@@ -26,6 +26,8 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--tag", default="")
 ap.add_argument("--clock", action="store_true",
                 help="MH_DIAG_CLOCK build: slot 5 holds the decode's core-clock cycles (s_memtime)")
+ap.add_argument("--args", action="store_true",
+                help="MH_DIAG_ARGS build (small launches): slot 5 is stamped once the output arguments are in registers")
 ap.add_argument("--tile8192", action="store_true", help="config 3: one 8192x8192 BigBridge mirror tile")
 ap.add_argument("--random8192", action="store_true",
                 help="config 3 stress: one 8192x8192 uniform-random frame (flat 8-bit table: the flat8 loop; "
@@ -82,6 +84,10 @@ if args.clock:  # slot 5 = s_memtime cycles between stamps 3 and 4 (staged tiles
     print(f"decode core cycles p50 {np.median(cyc[ok]):.0f} p90 {np.percentile(cyc[ok], 90):.0f}; "
           f"per symbol p50 {np.median(cyc[ok]) / 64:.1f}; clock MHz p10 {np.percentile(mhz, 10):.0f} "
           f"p50 {np.median(mhz):.0f} p90 {np.percentile(mhz, 90):.0f}")
+    st[:, 5] = st[:, 4]
+if args.args:  # slot 5 = the small-launch kernels' output arguments in registers (behind stamp 2)
+    d = (st[:, 5].astype(np.int64) - st[:, 2].astype(np.int64)) * 0.01
+    print(f"lut->out args p50 {np.median(d):7.2f}  p90 {np.percentile(d, 90):7.2f}  max {d.max():7.2f}")
     st[:, 5] = st[:, 4]
 names = ["entry", "hdr", "lut", "staged", "tile0", "loop", "drain"]
 for i, nm in enumerate(names):

@@ -4,7 +4,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 : > gpurun_out/pmc_kernels.txt
-for spec in batch:mh_decode_kernel frame:mh_decode_small_kernel tile8192:mh_decode_kernel; do
+for spec in batch:mh_decode_kernel frame:mh_decode_frame_kernel tile8192:mh_decode_kernel; do
   IFS=: read wl kern <<< "$spec"
   rm -rf gpurun_out/pmc_$wl
   WL=$wl OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$wl bash scripts/gpu_profile.sh || exit 1

@@ -1,4 +1,5 @@
-"""Per-launch HBM bytes of the decode kernels (mh_decode_kernel, mh_decode_small_kernel)
+"""Per-launch HBM bytes of the decode kernels (mh_decode_kernel, mh_decode_small_kernel,
+mh_decode_frame_kernel)
 from rocprofv3 --pmc CSVs (gpu_traffic.sh).
 
 gfx950 corrections (MI355X_MICROARCH.md, HBM section): FETCH_SIZE/WRITE_SIZE are in
@@ -12,6 +13,7 @@ import os
 import statistics
 import sys
 
+DECODE_KERNELS = ("mh_decode_kernel", "mh_decode_small_kernel", "mh_decode_frame_kernel")
 root = sys.argv[1]
 res = {}
 kernels = {}
@@ -30,9 +32,9 @@ for d in sorted(glob.glob(os.path.join(root, "*_*_SIZE"))):
                 for k in ("enc_split_kernel", "enc_code_kernel", "enc_one_kernel"):
                     if k in kn:
                         enc.setdefault(k, {}).setdefault(ctr, []).append(float(r["Counter_Value"]))
-            elif "mh_decode_kernel" in kn or "mh_decode_small_kernel" in kn:
+            elif any(k in kn for k in DECODE_KERNELS):
                 vals.append(float(r["Counter_Value"]))
-                kernels[wl] = "mh_decode_small_kernel" if "small" in kn else "mh_decode_kernel"
+                kernels[wl] = next(k for k in DECODE_KERNELS if k in kn)
     if vals:
         res.setdefault(wl, {})[ctr] = statistics.median(vals) * 1024.0
         res[wl]["dispatches"] = len(vals)
