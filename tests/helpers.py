@@ -1,6 +1,7 @@
 """Shared helpers for the test suite (CPU and GPU)."""
 from __future__ import annotations
 
+import dataclasses
 import json
 import os
 
@@ -70,6 +71,17 @@ def long_span_deltas(width: int, height: int, seed: int = 0) -> np.ndarray:
     return d
 
 
+def shift_stream(ef, k: int):
+    """The same frame with its code stream moved k bits later (k leading zero bits) and
+    every block offset with it: blocks off the byte grid, which no reference producer
+    writes but the buffer contract allows."""
+    from metalhuffman_amd import _native as N
+    bits = np.unpackbits(ef.codes[: ef.payload_bytes])
+    moved = np.packbits(np.concatenate([np.zeros(k, np.uint8), bits]))
+    codes = np.concatenate([moved, np.zeros(N.MH_CODES_PAD, np.uint8)])
+    return dataclasses.replace(ef, codes=codes, block_offsets=(ef.block_offsets + np.uint32(k)).astype(np.uint32))
+
+
 def lane_pair_oversize_deltas(seed: int = 0) -> np.ndarray:
     """512x512 deltas whose first 32 blocks hold 249 rare symbols x 8 (15-bit codes under
     a geometric chain of 7 common symbols): that 32-block lane-pair tile spans 3,735 B,
@@ -121,3 +133,95 @@ def refill_extreme_deltas(n_symbols: int, width: int, height: int, seed: int = 0
         pool = left
     assert np.array_equal(np.bincount(out, minlength=256), want), "histogram changed"
     return out
+
+
+# ---- write containment (include/metalhuffman.h: where a decode may store) -------------
+#
+# A decode of n frames into d_out with a caller's pitch and frame stride may write frame
+# f, row y < H, columns [0, written_cols) and nothing else. containment_plan lays such a
+# raster out inside one buffer with guard bytes in front of and behind it, filled with a
+# position-dependent pattern; check_containment then looks at every byte of the buffer.
+
+
+@dataclasses.dataclass(frozen=True)
+class ContainmentPlan:
+    n_frames: int
+    W: int
+    H: int
+    pitch: int
+    stride: int
+    lead: int
+    tail: int
+    written_cols: int
+    size: int                 # bytes of the whole buffer
+    d_out: int                # offset of d_out inside it (= lead)
+    pattern: np.ndarray       # u8[size]: the fill
+    may_write: np.ndarray     # bool[size]: frame f, row y < H, columns [0, written_cols)
+
+    def frame_view(self, buf: np.ndarray, cols: int) -> np.ndarray:
+        """[n_frames, H, cols] view of buf's rasters (no copy)."""
+        return np.lib.stride_tricks.as_strided(buf[self.d_out:], (self.n_frames, self.H, cols),
+                                               (self.stride, self.pitch, 1), writeable=buf.flags.writeable)
+
+
+def containment_plan(n_frames: int, W: int, H: int, pitch: int, stride: int, lead: int, tail: int,
+                     written_cols: int) -> ContainmentPlan:
+    """Buffer layout for a decode of n_frames W x H frames at d_out = buffer + lead, rows
+    `pitch` apart and frames `stride` apart, followed by `tail` guard bytes behind the last
+    frame's last row. written_cols: round_up(W, 8) for the GPU decoder (whole 8-pixel block
+    rows), W for the CPU decoder."""
+    assert n_frames >= 1 and W >= 1 and H >= 1 and lead >= 0 and tail >= 0
+    assert W <= written_cols <= pitch, "rows must not overlap"
+    assert n_frames == 1 or stride >= H * pitch, "frames must not overlap"
+    size = lead + (n_frames - 1) * stride + H * pitch + tail
+    pattern = ((np.arange(size, dtype=np.uint64) * 167 + 13) & 0xFF).astype(np.uint8)
+    may = np.zeros(size, bool)
+    np.lib.stride_tricks.as_strided(may[lead:], (n_frames, H, written_cols), (stride, pitch, 1))[...] = True
+    assert int(may.sum()) == n_frames * H * written_cols
+    pattern.setflags(write=False)
+    may.setflags(write=False)
+    return ContainmentPlan(n_frames, W, H, pitch, stride, lead, tail, written_cols, size, lead, pattern, may)
+
+
+def _containment_region(plan: ContainmentPlan, i: int) -> str:
+    """Where byte i of the buffer (outside the may-write mask) lies, in words."""
+    if i < plan.lead:
+        return f"lead guard, {plan.lead - i} byte(s) in front of d_out"
+    rel = i - plan.lead
+    f = min(rel // plan.stride, plan.n_frames - 1) if plan.n_frames > 1 else 0
+    r = rel - f * plan.stride
+    y, x = divmod(r, plan.pitch)
+    where = f"frame {f}, row {y}, column {x}"
+    if y < plan.H:
+        return f"row padding (columns >= {plan.written_cols}), {where}"
+    if y < -(-plan.H // 8) * 8 and x < plan.written_cols:
+        return f"rows below H (a block row's rows >= {plan.H}), {where}"
+    if f < plan.n_frames - 1:
+        return f"inter-frame gap behind frame {f}, {where}"
+    return f"tail guard behind the last frame, {where}"
+
+
+def check_containment(buf_after: np.ndarray, plan: ContainmentPlan, expected_frames) -> None:
+    """Assert that buf_after (the plan's buffer after a decode) holds the fill pattern at
+    every byte the decode may not write, and expected_frames[f] (H x W) in columns [0, W)
+    of every frame row. Columns [W, written_cols) are written with unspecified bytes."""
+    buf = np.asarray(buf_after)
+    assert buf.dtype == np.uint8 and buf.shape == (plan.size,), (buf.dtype, buf.shape)
+    assert len(expected_frames) == plan.n_frames
+    bad = np.flatnonzero((buf != plan.pattern) & ~plan.may_write)
+    if bad.size:
+        i = int(bad[0])
+        raise AssertionError(f"write outside the raster: {_containment_region(plan, i)}; first offending byte at "
+                             f"buffer offset {i} (d_out{i - plan.d_out:+d}): {int(buf[i]):#04x}, the fill is "
+                             f"{int(plan.pattern[i]):#04x}; {bad.size} byte(s) in all, last at offset {int(bad[-1])}")
+    got = plan.frame_view(buf, plan.W)
+    for f in range(plan.n_frames):
+        want = np.asarray(expected_frames[f])
+        assert want.shape == (plan.H, plan.W), (f, want.shape)
+        if not np.array_equal(got[f], want):
+            ys, xs = np.nonzero(got[f] != want)
+            y, x = int(ys[0]), int(xs[0])
+            i = plan.d_out + f * plan.stride + y * plan.pitch + x
+            raise AssertionError(f"wrong pixel: frame {f}, row {y}, column {x}, buffer offset {i}: "
+                                 f"{int(got[f, y, x]):#04x}, expected {int(want[y, x]):#04x}; "
+                                 f"{ys.size} wrong pixel(s) in this frame")

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from helpers import (fibonacci_deltas, golden, image_from_block_deltas, long_span_deltas,
-                     refill_extreme_deltas)
+                     refill_extreme_deltas, shift_stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -342,18 +342,6 @@ def test_batch_kernel_flat_table(mh, oracle, device):
     assert np.array_equal(out[3], _oracle_decode(oracle, efs[3]))
 
 
-def _shift_stream(ef, k: int):
-    """The same frame with its code stream moved k bits later (k leading zero bits) and
-    every block offset with it: blocks off the byte grid, which no reference producer
-    writes but the buffer contract allows."""
-    import dataclasses
-    from metalhuffman_amd import _native as N
-    bits = np.unpackbits(ef.codes[: ef.payload_bytes])
-    moved = np.packbits(np.concatenate([np.zeros(k, np.uint8), bits]))
-    codes = np.concatenate([moved, np.zeros(N.MH_CODES_PAD, np.uint8)])
-    return dataclasses.replace(ef, codes=codes, block_offsets=(ef.block_offsets + np.uint32(k)).astype(np.uint32))
-
-
 @pytest.mark.parametrize("n", [1, 5])
 @pytest.mark.parametrize("fmt", ["delta", "no_delta", "block_init", "edges", "flat4", "off_grid"])
 def test_flat8_paths(mh, oracle, device, fmt, n):
@@ -363,8 +351,10 @@ def test_flat8_paths(mh, oracle, device, fmt, n):
     code loads). Formats: delta, raw symbols, per-block init bytes (attached to flat frames:
     the reference's init-byte producer always makes symbol 0 shorter), partial edge
     blocks and rows past H (1032x1008 frames decoded as 1027x1001: the same block grid),
-    a flat 4-bit table (16 symbols: the general flat step), and blocks off the byte grid
-    (the general flat step, from the slow loop)."""
+    a flat 4-bit table (16 symbols: no flat8 word, so the lookup chain -- Lut13Flat, the
+    escape-free step on the swizzled stage, in the batch kernel; the 14-bit table in the
+    single-frame kernel), and blocks off the byte grid (the staged funnel-shift byte step:
+    Batch8 from the batch kernel's slow loop, SmallFlat8 in the single-frame kernel)."""
     import dataclasses
     from metalhuffman_amd import frames as F
     kw = {}
@@ -382,7 +372,7 @@ def test_flat8_paths(mh, oracle, device, fmt, n):
     L = efs[0].canon[efs[0].canon > 0]
     assert L.min() == L.max() == (4 if fmt == "flat4" else 8), (L.min(), L.max())
     if fmt == "off_grid":
-        efs = [_shift_stream(ef, 3 + i) for i, ef in enumerate(efs)]
+        efs = [shift_stream(ef, 3 + i) for i, ef in enumerate(efs)]
     elif fmt == "block_init":
         r = np.random.default_rng(8)
         efs = [dataclasses.replace(ef, block_init=r.integers(0, 256, ef.n_blocks, dtype=np.uint8)) for ef in efs]
