@@ -106,7 +106,8 @@ typedef struct {
   uint32_t block_height; /* ceil(height / 8) */
 } mh_dims;
 
-/* One frame, or a batch of frames that share one table pair and one size.
+/* One frame, or a batch of frames of one size that share one table pair (mh_decode)
+ * or bring a prepared table each (mh_decode_frames, which ignores the table fields).
  * Frame f's block offsets are d_block_offsets[f*NB .. f*NB+NB) (bit offsets
  * relative to frame f's first code byte); its code bytes start at
  * d_codes + frame_code_offsets[f] (16-byte aligned). */
@@ -186,6 +187,44 @@ int mh_build_tables_device(const uint8_t *d_canon_header, mh_lookup_symbol *d_ta
                            uint16_t *d_lut, int32_t *d_status, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Batches with one Huffman table per frame (video, tiles of a scan, whatever  */
+/* mh_encode_frames_device_async produced): encode batch -> mh_build_luts_device */
+/* -> mh_decode_frames are three asynchronous steps on one stream, no host     */
+/* synchronisation in between. Not covered: mh_check and mh_stream with        */
+/* per-frame tables, the multi-GPU paths, and an in-kernel table build from    */
+/* T1/T2 for this entry (it needs prepared tables).                           */
+
+/* n prepared tables (mh_prepare_lut's buffer) from n 256-byte canonical headers in ONE
+ * launch: header i at d_canon_headers + 256 i -> d_luts + i * lut_stride_bytes, byte-identical
+ * to what mh_build_tables_device writes to d_lut for that header. d_status[i] (optional) as
+ * mh_build_tables_device's d_status; a rejected header leaves the prepared table of all-zero
+ * tables. lut_stride_bytes: multiple of 16, >= mh_lut_bytes(). d_luts 16-byte aligned.
+ * 1 <= n_headers <= 65535. The launch is sized to about one resident round of the device
+ * (clamp(CUs / n_headers, 1, 32) workgroups per header). Asynchronous on `stream`. */
+int mh_build_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,
+                         uint64_t lut_stride_bytes, int32_t *d_status, void *stream);
+
+/* mh_decode for a batch whose frame f has its own prepared table d_luts + f * lut_stride_bytes.
+ * frame->d_table1 / d_table2 / table2_entries / d_lut are ignored (may be NULL / 0).
+ * d_frame_status (optional, device int32[n_frames]): a frame whose word is non-zero is not
+ * decoded and no byte of its raster is written (the batched encoder's / table build's status
+ * array goes here unchanged). Same output contract, alignment rules and error codes as mh_decode
+ * (n_frames == 1 with NULL d_frame_code_offsets included), and: NULL d_luts ->
+ * MH_ERR_INVALID_ARG; d_luts or lut_stride_bytes not a multiple of 16 -> MH_ERR_ALIGN;
+ * lut_stride_bytes < mh_lut_bytes() -> MH_ERR_CAPACITY. flags: MH_FLAG_NO_DELTA |
+ * MH_FLAG_ANY_ORDER only (MH_FLAG_LANE_PAIRS -> MH_ERR_INVALID_ARG). One kernel launch of
+ * n_frames * G workgroups of 8 waves, G = clamp(ceil(R / n_frames), 1, ceil(tiles / 8)) with R the
+ * workgroups resident on the device at once and tiles = ceil(NB / 64); asynchronous. */
+int mh_decode_frames(const mh_frame *frame, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                     const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch,
+                     size_t out_frame_stride, void *stream);
+
+/* The launch shape mh_decode_frames would use on `stream`'s device (no launch): workgroups
+ * per frame (G above) and waves per workgroup. For tests and tools. */
+int mh_decode_frames_shape(const mh_frame *frame, void *stream, uint32_t *groups_per_frame,
+                           uint32_t *waves_per_group);
+
+/* ---------------------------------------------------------------------- */
 /* GPU encoder (the producer side on the device; output byte-identical to   */
 /* mh_encode_frame: HuffmanEncoder.cpp:310-381, HuffmanUtil.cpp:1051-1131,  */
 /* AAPLRenderer.m:374-688).                                                 */
@@ -245,8 +284,9 @@ size_t mh_encode_frames_workspace_bytes(uint32_t width, uint32_t height, uint32_
  * d_block_offsets + f * NB, d_block_init + f * NB (optional), d_status[f]
  * (optional; the values of mh_encode_frame_device_async), and d_frame_code_offsets
  * (optional, n_frames + 1 u64 = f * codes_frame_stride): the slots are then one
- * mh_frame batch for mh_decode (all frames must share one canonical table to be
- * decoded in one launch, e.g. block shuffles of one image). A rejected frame writes
+ * mh_frame batch: for mh_decode_frames with one table per frame (mh_build_luts_device over
+ * d_canon_headers; d_status goes in as d_frame_status), or for mh_decode when all frames
+ * happen to share one canonical table (block shuffles of one image). A rejected frame writes
  * no codes or offsets and does not affect the others. d_workspace: 256-byte aligned,
  * mh_encode_frames_workspace_bytes(), any content (every part is written before it
  * is read within the call; MH_ENCODE_WORKSPACE_ZEROED is accepted and changes nothing).

@@ -8,7 +8,10 @@ of mdejong/MetalHuffman).
   * codec.Huffman                   the reference's `Huffman` facade (Shared/Huffman.h)
   * decoder.decode / DeviceFrames   GPU decode of one frame or a batch
   * decoder.DeviceTables            T1/T2 + prepared table (uploaded, or built on the device)
+  * decoder.decode_frames / DeviceTableSet   a batch with a table per frame, one launch
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
+  * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
+                                    n tables -> decode on one stream, no host sync
   * stream                          streaming from host memory (config 5)
   * dist                            frame sharding, single-frame bands, table broadcast
 """

@@ -36,6 +36,7 @@ EXPORTS = (
     "mh_container_header", "mh_parse_container_header", "mh_check",
     "mh_decode_huffman_bits", "mh_decode_huffman_bits_from_tables", "mh_decode_frame_cpu",
     "mh_build_stamp",
+    "mh_build_luts_device", "mh_decode_frames", "mh_decode_frames_shape",
 )
 
 
@@ -126,6 +127,10 @@ def lib() -> ctypes.CDLL:
         L.mh_lut_bits.restype = ctypes.c_int
         L.mh_prepare_lut.argtypes = [_vp, _vp, ctypes.c_uint32, _vp, _vp]
         L.mh_build_tables_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.mh_build_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]
+        L.mh_decode_frames.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_size_t,
+                                       ctypes.c_size_t, _vp]
+        L.mh_decode_frames_shape.argtypes = [ctypes.POINTER(mh_frame), _vp, _u32p, _u32p]
         L.mh_stream_create.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint64, ctypes.c_uint32,
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp)]
         L.mh_stream_submit.argtypes = [_vp, _vp, ctypes.c_uint64, _vp, _vp, _u32p]

@@ -982,6 +982,87 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
 #endif
 }
 
+#if !MH_LANE_PAIRS
+// ---- a batch with one prepared table per frame (mh_decode_frames) ----------------
+// The batch kernel's machinery with another decomposition: workgroup g serves ONE frame,
+// f = g / G, as slice j = g % G of it, so it copies frame f's table (luts + f * stride)
+// into LDS once and never crosses a frame. Wave w decodes tiles f*tpf + j*8 + w, stepping
+// by 8*G, below (f+1)*tpf: the persistent loops run on a workgroup-local DecodeArgs whose
+// total_tiles is the frame's end (frame_of's one-frame shortcut then holds for f = 0 only,
+// where it is right; every other frame divides). Always 8 waves, so four 16-byte loads per
+// thread cover the table; waves without a tile idle behind the barrier. The step flavour
+// comes from the frame's own [longest, shortest, flat8] word, per workgroup. A frame whose
+// status word is non-zero (rejected by the encoder or the table build) is left alone: the
+// workgroup returns before any store. The grid is n_frames * G, not persistent across
+// frames.
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_multitable_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, uint64_t p_lut_stride, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    const DecodeArgs a0) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t G = p_groups;
+  const uint32_t f = blockIdx.x / G, slice = blockIdx.x - f * G;
+  DecodeArgs a = a0;
+  a.offsets = p_offsets;
+  a.frame_off = p_frame_off;
+  a.block_init = p_block_init;
+  a.lut = reinterpret_cast<const uint16_t *>(p_luts + (uint64_t)f * p_lut_stride);
+  a.nb = p_nb;
+  a.tiles_per_frame = p_tiles_per_frame;
+  a.total_tiles = (f + 1u) * p_tiles_per_frame;  // this workgroup's tiles end with its frame
+  constexpr uint32_t nwaves = kMaxWavesPerWG, nthreads = nwaves * 64u;
+  a.nwaves = nwaves;
+  a.grid = G;
+  const uint32_t gstride = G * nwaves;
+  uint8_t *stage = s_stage + wave * kStageBytes;
+  const uint8_t *lut = reinterpret_cast<const uint8_t *>(s_lut);
+#if MH_DIAG_STAMPS
+  unsigned long long ts[kDiagSlots] = {};
+#endif
+  MH_STAMP(0);
+
+  const uint32_t t0 = min(f * p_tiles_per_frame + slice * nwaves + wave, a.total_tiles);
+  TileHdr hc;
+  // The frame's status word, then its table's lengths word, then the table: vector loads
+  // through descriptors (the status one empty without a status array), the oldest first, so
+  // each has landed by the time the table's loads have (as the batch kernel's lengths word).
+  const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
+      uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
+  const v4u32 lw = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(a.lut, (uint32_t)kPreparedBytes),
+                                                         kMaxLenOff, 0, 0);
+  constexpr uint32_t kLutChunks = kLutBytes / 16, kLutPer = 4;
+  static_assert(nthreads * kLutPer >= kLutChunks, "four loads per thread cover the table");
+  v4u32 L[kLutPer];
+  {
+    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(a.lut, (uint32_t)kLutBytes);
+#pragma unroll
+    for (uint32_t k = 0; k < kLutPer; ++k)
+      L[k] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)((threadIdx.x + k * nthreads) * 16u), 0, 0);
+  }
+  hdr_issue(a, t0, lane, hc);
+  if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
+  const uint32_t mx = __builtin_amdgcn_readfirstlane(lw.x), mn = __builtin_amdgcn_readfirstlane(lw.y);
+  const uint32_t f8 = __builtin_amdgcn_readfirstlane(lw.z);
+  {
+    v4u32 *dstv = reinterpret_cast<v4u32 *>(s_lut);
+#pragma unroll
+    for (uint32_t k = 0; k < kLutPer; ++k)
+      if (threadIdx.x + k * nthreads < kLutChunks) dstv[threadIdx.x + k * nthreads] = L[k];
+    if (!f8) lds_barrier();  // the flat 8-bit identity table decodes without the table in LDS
+  }
+  if (f8)
+    flat8_loop<kDelta>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG);
+  else if (mx == mn)
+    batch_loop<kDelta, Lut13Flat>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+  else if (mx <= (uint32_t)kLutBits)
+    batch_loop<kDelta, Lut13NoEsc>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+  else
+    batch_loop<kDelta, Lut13>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+}
+#endif  // !MH_LANE_PAIRS
+
 // ---- small launches (<= one wave per SIMD, e.g. one 2048x1536 frame) -------------
 // Every wave decodes one tile, one wave per SIMD: the wave's own instruction stream
 // (the per-symbol dependency chain and the instructions beside it), not LDS or VALU
@@ -1548,17 +1629,21 @@ struct DeviceInfo {
   std::mutex m;
   std::atomic<int> cus{0};  // nonzero once the entry is complete
   int occ[2][kMaxWavesPerWG + 1] = {};
+  int occ_frames[2] = {};  // mh_decode_multitable_kernel at 8 waves (raw / delta)
 };
 DeviceInfo g_devinfo[kMaxDevices];
 
-template <bool kDelta>
-int occupancy_query(int nw) {
+template <class Kernel>
+int occupancy_of(Kernel kernel, int nw) {
   int blocks = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, mh_decode_kernel<kDelta>, nw * 64, 0) !=
-          hipSuccess ||
-      blocks < 1)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, nw * 64, 0) != hipSuccess || blocks < 1)
     blocks = 1;
   return blocks;
+}
+
+template <bool kDelta>
+int occupancy_query(int nw) {
+  return occupancy_of(mh_decode_kernel<kDelta>, nw);
 }
 
 // The device a launch on `s` runs on (the stream's, or the caller's current one).
@@ -1587,6 +1672,10 @@ const DeviceInfo *device_info(hipStream_t s) {
     d.occ[0][nw] = occupancy_query<false>(nw);
     d.occ[1][nw] = occupancy_query<true>(nw);
   }
+#if !MH_LANE_PAIRS
+  d.occ_frames[0] = occupancy_of(mh_decode_multitable_kernel<false>, kMaxWavesPerWG);
+  d.occ_frames[1] = occupancy_of(mh_decode_multitable_kernel<true>, kMaxWavesPerWG);
+#endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
   return &d;
@@ -1653,6 +1742,91 @@ int launch(const DecodeArgs &a0, hipStream_t s, bool lane_pairs, bool any_order)
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 
+// The argument checks of the decode entry points, all before any HIP call. `luts`: the
+// per-frame-table entry (mh_decode_frames), which ignores the frame's own table fields and
+// checks d_luts / lut_stride in their place, rule by rule in the same order.
+int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
+                      uint32_t allowed_flags, bool luts, const uint16_t *d_luts, uint64_t lut_stride) {
+  if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
+  if (luts ? !d_luts : (!fr->d_table1 || !fr->d_table2)) return MH_ERR_INVALID_ARG;
+  if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
+  if (fr->flags & ~allowed_flags) return MH_ERR_INVALID_ARG;
+  const mh_dims &d = fr->dims;
+  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
+      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
+    return MH_ERR_DIMS;
+  if (!luts && (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
+                fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
+    return MH_ERR_TABLE;
+  if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & 7u) || ((uintptr_t)d_out & 7u) ||
+      (fr->n_frames > 1 && (out_frame_stride & 7u)))
+    return MH_ERR_ALIGN;
+  if (luts ? (((uintptr_t)d_luts & 15u) || (lut_stride & 15u)) : (((uintptr_t)fr->d_lut & 15u) != 0))
+    return MH_ERR_ALIGN;
+  if (out_pitch < d.width || out_pitch > (1u << 20) ||
+      (fr->n_frames > 1 && out_frame_stride < out_pitch * d.height))
+    return MH_ERR_CAPACITY;
+  if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
+  if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
+    return MH_ERR_CAPACITY;
+  if (luts && lut_stride < (uint64_t)kPreparedBytes) return MH_ERR_CAPACITY;  // mh_lut_bytes()
+  return MH_OK;
+}
+
+// DecodeArgs from a checked frame (tables excepted); MH_ERR_CAPACITY past 2^31 - 1 tiles.
+int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
+                     DecodeArgs &a) {
+  const mh_dims &d = fr->dims;
+  a.offsets = fr->d_block_offsets;
+  a.codes = fr->d_codes;
+  a.frame_off = fr->d_frame_code_offsets;
+  a.codes_bytes = fr->codes_bytes;
+  a.block_init = fr->d_block_init;
+  a.out = d_out;
+  a.out_pitch = out_pitch;
+  a.out_frame_stride = out_frame_stride;
+  a.out_frame_bytes = (uint64_t)d.height * out_pitch;
+  a.w = d.width;
+  a.h = d.height;
+  a.bw = d.block_width;
+  a.bh = d.block_height;
+  a.nb = d.block_width * d.block_height;
+  a.tiles_per_frame = (a.nb + 63) / 64;
+  const uint64_t total = (uint64_t)a.tiles_per_frame * fr->n_frames;
+  if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  a.total_tiles = (uint32_t)total;
+  return MH_OK;
+}
+
+#if !MH_LANE_PAIRS
+// mh_decode_frames' launch shape: G workgroups of 8 waves per frame,
+//   G = clamp(ceil(R / n_frames), 1, ceil(tiles_per_frame / 8)),
+// R = the workgroups resident on the device at once (CUs x the kernel's occupancy): about
+// one resident round when the frames are few, one workgroup per frame when they are many.
+int frames_shape(uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s, uint32_t *groups) {
+  const DeviceInfo *di = device_info(s);
+  if (!di) return MH_ERR_HIP;
+  const uint64_t resident = (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)di->occ_frames[delta ? 1 : 0];
+  const uint64_t want = (resident + n_frames - 1) / n_frames;
+  const uint64_t most = (tiles_per_frame + (uint32_t)kMaxWavesPerWG - 1) / (uint32_t)kMaxWavesPerWG;
+  *groups = (uint32_t)(want < 1 ? 1 : want > most ? most : want);
+  return MH_OK;
+}
+
+template <bool kDelta>
+int launch_frames(const DecodeArgs &a, uint32_t n_frames, const uint8_t *luts, uint64_t lut_stride,
+                  const int32_t *status, hipStream_t s, bool any_order) {
+  uint32_t G = 0;
+  const int rc = frames_shape(n_frames, a.tiles_per_frame, kDelta, s, &G);
+  if (rc != MH_OK) return rc;
+  const uint64_t grid = (uint64_t)G * n_frames;
+  if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  MH_LAUNCH(mh_decode_multitable_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
+            a.offsets, a.frame_off, a.block_init, luts, status, lut_stride, a.nb, a.tiles_per_frame, G, a);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+#endif
+
 }  // namespace
 
 extern "C" {
@@ -1705,56 +1879,57 @@ int mh_diag_decode_lanepairs(const mh_frame *fr, uint8_t *d_out, size_t out_pitc
 int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
               void *stream) {
 #endif
-  if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes || !fr->d_table1 || !fr->d_table2)
-    return MH_ERR_INVALID_ARG;
-  if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
   // MH_FLAG_LANE_PAIRS: honoured by the diagnostic library only; the product library accepts
   // it (callers built against round-4 libraries pass it) and decodes with the default kernels
-  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER | MH_FLAG_LANE_PAIRS)) return MH_ERR_INVALID_ARG;
-  const mh_dims &d = fr->dims;
-  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
-      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
-    return MH_ERR_DIMS;
-  if (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
-      fr->table2_entries > MH_TABLE2_MAX_ENTRIES)
-    return MH_ERR_TABLE;
-  if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & 7u) || ((uintptr_t)d_out & 7u) ||
-      (fr->n_frames > 1 && (out_frame_stride & 7u)) || ((uintptr_t)fr->d_lut & 15u))
-    return MH_ERR_ALIGN;
-  if (out_pitch < d.width || out_pitch > (1u << 20) ||
-      (fr->n_frames > 1 && out_frame_stride < out_pitch * d.height))
-    return MH_ERR_CAPACITY;
-  if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
-  if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
-    return MH_ERR_CAPACITY;
-
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride,
+                             MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER | MH_FLAG_LANE_PAIRS, false, nullptr, 0);
+  if (rc != MH_OK) return rc;
   DecodeArgs a{};
-  a.offsets = fr->d_block_offsets;
-  a.codes = fr->d_codes;
-  a.frame_off = fr->d_frame_code_offsets;
-  a.codes_bytes = fr->codes_bytes;
   a.t1 = reinterpret_cast<const uint16_t *>(fr->d_table1);
   a.t2 = reinterpret_cast<const uint16_t *>(fr->d_table2);
   a.lut = fr->d_lut;
-  a.block_init = fr->d_block_init;
-  a.out = d_out;
-  a.out_pitch = out_pitch;
-  a.out_frame_stride = out_frame_stride;
-  a.out_frame_bytes = (uint64_t)d.height * out_pitch;
   a.t2_entries = fr->table2_entries;
-  a.w = d.width;
-  a.h = d.height;
-  a.bw = d.block_width;
-  a.bh = d.block_height;
-  a.nb = d.block_width * d.block_height;
-  a.tiles_per_frame = (a.nb + 63) / 64;
-  const uint64_t total = (uint64_t)a.tiles_per_frame * fr->n_frames;
-  if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  a.total_tiles = (uint32_t)total;
+  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
+  if (rc != MH_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const bool lp = (fr->flags & MH_FLAG_LANE_PAIRS) != 0;
   const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
   return (fr->flags & MH_FLAG_NO_DELTA) ? launch<false>(a, s, lp, ao) : launch<true>(a, s, lp, ao);
 }
+
+#if !MH_LANE_PAIRS
+int mh_decode_frames(const mh_frame *fr, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                     const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
+                     void *stream) {
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, true,
+                             d_luts, lut_stride_bytes);
+  if (rc != MH_OK) return rc;
+  DecodeArgs a{};  // t1 / t2 / lut stay null: every workgroup takes its frame's table from d_luts
+  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
+  if (rc != MH_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
+  const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return (fr->flags & MH_FLAG_NO_DELTA)
+             ? launch_frames<false>(a, fr->n_frames, luts, lut_stride_bytes, d_frame_status, s, ao)
+             : launch_frames<true>(a, fr->n_frames, luts, lut_stride_bytes, d_frame_status, s, ao);
+}
+
+int mh_decode_frames_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame,
+                           uint32_t *waves_per_group) {
+  if (!fr || !groups_per_frame || !waves_per_group || fr->n_frames == 0) return MH_ERR_INVALID_ARG;
+  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
+  const mh_dims &d = fr->dims;
+  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
+      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
+    return MH_ERR_DIMS;
+  const uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
+  const int rc = frames_shape(fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
+                              groups_per_frame);
+  if (rc != MH_OK) return rc;
+  *waves_per_group = kMaxWavesPerWG;
+  return MH_OK;
+}
+#endif  // !MH_LANE_PAIRS
 
 }  // extern "C"

@@ -33,10 +33,25 @@ namespace {
 // P0 (the first 13-bit prefix of a code longer than 13 bits) and the longest /
 // shortest code words come from the canonical codes themselves, so the slices need
 // no exchange. Launch: kTableGroups workgroups of 1024 threads.
+//
+// A batch of headers (mh_build_luts_device): blockIdx.y is the header index -- header,
+// tables, status and prepared table (lut_stride bytes apart) are offset by it -- and
+// gridDim.x stays the number of slices of ONE prepared table. T1 / T2 / t2_entries may be
+// NULL (only the prepared tables are wanted): their writes are skipped.
 constexpr uint32_t kTableGroups = 32;
 __global__ void __launch_bounds__(1024) mh_build_tables_kernel(const uint8_t *canon, uint16_t *t1,
                                                                uint16_t *t2, uint32_t *t2_entries,
-                                                               int32_t *status, uint8_t *lut) {
+                                                               int32_t *status, uint8_t *lut,
+                                                               uint64_t lut_stride) {
+  {
+    const uint32_t hdr = blockIdx.y;
+    canon += (uint64_t)hdr * 256u;
+    if (t1) t1 += (uint64_t)hdr * 256u;
+    if (t2) t2 += (uint64_t)hdr * MH_TABLE2_MAX_ENTRIES;
+    if (t2_entries) t2_entries += hdr;
+    if (status) status += hdr;
+    if (lut) lut += (uint64_t)hdr * lut_stride;
+  }
   __shared__ __attribute__((aligned(16))) uint16_t s_t2[MH_TABLE2_MAX_ENTRIES];
   __shared__ __attribute__((aligned(16))) uint16_t s_t1[256];
   __shared__ uint32_t s_group[256], s_wcnt[4][17], s_gcnt[4];
@@ -165,20 +180,25 @@ __global__ void __launch_bounds__(1024) mh_build_tables_kernel(const uint8_t *ca
   __syncthreads();
   TAB_STAMP(8);
   if (blockIdx.x == 0) {
-    // out: T1, T2 over its whole capacity (zero past the used subtables)
-    if (((uintptr_t)t1 & 15u) == 0) {
-      if (tid < 32) reinterpret_cast<uint4 *>(t1)[tid] = reinterpret_cast<const uint4 *>(s_t1)[tid];
-    } else if (tid < 256) {
-      t1[tid] = s_t1[tid];
+    // out: T1, T2 over its whole capacity (zero past the used subtables), where asked for
+    if (t1) {
+      if (((uintptr_t)t1 & 15u) == 0) {
+        if (tid < 32) reinterpret_cast<uint4 *>(t1)[tid] = reinterpret_cast<const uint4 *>(s_t1)[tid];
+      } else if (tid < 256) {
+        t1[tid] = s_t1[tid];
+      }
     }
-    if (((uintptr_t)t2 & 15u) == 0) {
-      uint4 *v = reinterpret_cast<uint4 *>(t2);
-      for (uint32_t i = tid; i < kT2Vec; i += blockDim.x) v[i] = i < used_vec ? s_t2v[i] : make_uint4(0, 0, 0, 0);
-    } else {
-      for (uint32_t i = tid; i < (uint32_t)MH_TABLE2_MAX_ENTRIES; i += blockDim.x) t2[i] = i < used_vec * 8 ? s_t2[i] : 0;
+    if (t2) {
+      if (((uintptr_t)t2 & 15u) == 0) {
+        uint4 *v = reinterpret_cast<uint4 *>(t2);
+        for (uint32_t i = tid; i < kT2Vec; i += blockDim.x) v[i] = i < used_vec ? s_t2v[i] : make_uint4(0, 0, 0, 0);
+      } else {
+        for (uint32_t i = tid; i < (uint32_t)MH_TABLE2_MAX_ENTRIES; i += blockDim.x)
+          t2[i] = i < used_vec * 8 ? s_t2[i] : 0;
+      }
     }
     if (tid == 0) {
-      *t2_entries = bad ? 256u : (s_ngroups + 1u) * 256u;
+      if (t2_entries) *t2_entries = bad ? 256u : (s_ngroups + 1u) * 256u;
       if (status) *status = bad ? ((s_bad & 1u) ? MH_ERR_CODE_TOO_LONG : MH_ERR_TABLE) : MH_OK;
     }
     if (lut && tid < 4) {  // [longest code, shortest code, flat8, 0] (mh_lut.hpp)
@@ -242,6 +262,28 @@ extern "C" int mh_build_tables_device(const uint8_t *d_canon_header, mh_lookup_s
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(mh_build_tables_kernel, dim3(d_lut ? kTableGroups : 1), dim3(1024), 0, s, d_canon_header,
                      reinterpret_cast<uint16_t *>(d_table1), reinterpret_cast<uint16_t *>(d_table2),
-                     d_table2_entries, d_status, reinterpret_cast<uint8_t *>(d_lut));
+                     d_table2_entries, d_status, reinterpret_cast<uint8_t *>(d_lut), (uint64_t)0);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+// n prepared tables in one launch: grid (g, n), g slices per table. The kernel holds
+// ~131.5 KB of LDS (one workgroup per CU), so g * n is kept to about one resident round:
+// g = clamp(CUs / n, 1, kTableGroups) -- 64 headers on 256 CUs build in 256 workgroups,
+// not 64 x 32.
+extern "C" int mh_build_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,
+                                    uint64_t lut_stride_bytes, int32_t *d_status, void *stream) {
+  if (!d_canon_headers || !d_luts || n_headers == 0 || n_headers > 65535u) return MH_ERR_INVALID_ARG;
+  if (((uintptr_t)d_luts & 15u) || (lut_stride_bytes & 15u)) return MH_ERR_ALIGN;
+  if (lut_stride_bytes < mh_lut_bytes()) return MH_ERR_CAPACITY;
+  hipStream_t s = (hipStream_t)stream;
+  int dev = -1, cus = 0;
+  if (!(s && hipStreamGetDevice(s, &dev) == hipSuccess) && hipGetDevice(&dev) != hipSuccess) return MH_ERR_HIP;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+    return MH_ERR_HIP;
+  uint32_t g = (uint32_t)cus / n_headers;
+  g = g < 1 ? 1 : g > kTableGroups ? kTableGroups : g;
+  hipLaunchKernelGGL(mh_build_tables_kernel, dim3(g, n_headers), dim3(1024), 0, s, d_canon_headers,
+                     (uint16_t *)nullptr, (uint16_t *)nullptr, (uint32_t *)nullptr, d_status,
+                     reinterpret_cast<uint8_t *>(d_luts), lut_stride_bytes);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }

@@ -8,6 +8,7 @@ device-memory / stream plumbing; nothing here computes on the CPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import dataclasses
 from typing import Optional, Sequence
@@ -103,8 +104,57 @@ class DeviceTables:
 
 
 @dataclasses.dataclass
+class DeviceTableSet:
+    """n prepared tables, one per frame of a batch, for decode_frames (mh_decode_frames):
+    table i at luts[i], status[i] its build status (non-zero: header rejected, the table
+    is all zero and decode_frames skips the frame)."""
+    luts: torch.Tensor       # u8[n, stride], stride a multiple of 16 >= mh_lut_bytes()
+    status: torch.Tensor     # int32[n]
+
+    @property
+    def n_tables(self) -> int:
+        return int(self.luts.shape[0])
+
+    @property
+    def stride(self) -> int:
+        return int(self.luts.shape[1])
+
+    @classmethod
+    def from_canonical_headers(cls, canon, device="cuda",
+                               stream: Optional[torch.cuda.Stream] = None) -> "DeviceTableSet":
+        """Build the n prepared tables ON the device from n 256-byte canonical headers
+        (u8[n, 256], tensor or array) in one launch (mh_build_luts_device). Asynchronous;
+        check_status() syncs and raises when a header was rejected."""
+        dev = _dev(device)
+        if isinstance(canon, torch.Tensor):
+            hdr = canon.to(dev, torch.uint8).contiguous()
+        else:
+            hdr = torch.from_numpy(np.ascontiguousarray(canon, np.uint8)).to(dev)
+        if hdr.dim() != 2 or hdr.shape[1] != 256 or hdr.shape[0] < 1:
+            raise ValueError("canonical headers are u8[n, 256]")
+        n = int(hdr.shape[0])
+        stride = (int(N.lib().mh_lut_bytes()) + 15) // 16 * 16
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            luts = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+        N.check(N.lib().mh_build_luts_device(hdr.data_ptr(), n, luts.data_ptr(), stride, status.data_ptr(),
+                                             _stream_ptr(stream, dev)), "mh_build_luts_device")
+        ts = cls(luts, status)
+        ts._headers = hdr  # read by the launch in flight
+        return ts
+
+    def check_status(self) -> None:
+        """Synchronises; raises MHError naming the frames whose header was rejected."""
+        st = self.status.cpu().tolist()
+        bad = [i for i, s in enumerate(st) if s]
+        if bad:
+            raise N.MHError(int(st[bad[0]]), f"mh_build_luts_device: frame(s) {bad[:8]} rejected")
+
+
+@dataclasses.dataclass
 class DeviceFrames:
-    """n frames of one size that share one table pair, packed for mh_decode."""
+    """n frames of one size packed for mh_decode (one shared table pair) or, packed with
+    shared_table=False, for mh_decode_frames (a table per frame)."""
     width: int
     height: int
     n_frames: int
@@ -121,8 +171,10 @@ class DeviceFrames:
         return bw * bh
 
     @classmethod
-    def pack(cls, frames: Sequence[EncodedFrame], device="cuda") -> "DeviceFrames":
-        """Upload frames (host arrays) into one packed device batch."""
+    def pack(cls, frames: Sequence[EncodedFrame], device="cuda", shared_table: bool = True) -> "DeviceFrames":
+        """Upload frames (host arrays) into one packed device batch. shared_table=True
+        (default): the frames must share one canonical table (decode()); False: any
+        headers, for decode_frames() with a DeviceTableSet."""
         dev = _dev(device)
         if not frames:
             raise ValueError("no frames")
@@ -130,7 +182,7 @@ class DeviceFrames:
         for f in frames:
             if (f.width, f.height, f.flags) != (w, h, fl):
                 raise ValueError("a batch holds frames of one size and one format")
-            if not np.array_equal(f.canon, frames[0].canon):
+            if shared_table and not np.array_equal(f.canon, frames[0].canon):
                 raise ValueError("a batch shares one canonical table")
         starts = [0]
         for f in frames:
@@ -238,10 +290,108 @@ def check(frames: DeviceFrames, tables: DeviceTables,
     return rep.to(torch.int64) & 0xFFFFFFFF
 
 
-def decode_frames(encoded: Sequence[EncodedFrame], device="cuda") -> np.ndarray:
-    """Convenience: upload, decode, copy back; returns [n, H, W] uint8 on the host."""
+def _frames_entry(frames: DeviceFrames, extra_flags: int = 0):
+    """(mh_frame, device index) for mh_decode_frames: the table fields stay NULL. Cached on
+    `frames` like _frame_entry's structs."""
+    refs = (frames.block_offsets, frames.codes, frames.frame_code_offsets, frames.block_init)
+    key = (id(refs[0]), id(refs[1]), id(refs[2]), id(refs[3]), frames.width, frames.height, frames.n_frames,
+           frames.flags)
+    cache = frames.__dict__.get("_frs_cache")
+    if cache is None or cache[0] != key:
+        dev = frames.codes.device
+        if dev.type != "cuda" or any(t is not None and t.device != dev for t in refs):
+            raise ValueError("the frames' buffers must live on one HIP device")
+        cache = (key, refs, {}, dev.index)
+        frames.__dict__["_frs_cache"] = cache
+    fr = cache[2].get(extra_flags)
+    if fr is None:
+        bw, bh = block_grid(frames.width, frames.height)
+        ptr = [t.data_ptr() if t is not None else None for t in refs]
+        fr = N.mh_frame(ptr[0], ptr[1], frames.codes.numel(), ptr[2], None, None, 0, None, ptr[3],
+                        N.mh_dims(frames.width, frames.height, bw, bh), frames.n_frames,
+                        frames.flags | extra_flags)
+        cache[2][extra_flags] = fr
+    return fr, cache[3]
+
+
+def decode_frames_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
+                        extra_flags: int = 0) -> tuple:
+    """(workgroups per frame, waves per workgroup) decode_frames would launch with
+    (mh_decode_frames_shape)."""
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
+    N.check(N.lib().mh_decode_frames_shape(ctypes.byref(fr), sp, ctypes.byref(g), ctypes.byref(w)),
+            "mh_decode_frames_shape")
+    return int(g.value), int(w.value)
+
+
+def decode_frames(frames, table_set="cuda", out: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0, skip_rejected: bool = True):
+    """Two uses, told apart by the first argument:
+
+    decode_frames(frames: DeviceFrames, table_set: DeviceTableSet, out=None, stream=None,
+    extra_flags=0, skip_rejected=True) -> the device raster out[n, H, pitch] (decode()'s `out`
+    contract), frame f decoded with its own table table_set.luts[f] in one launch
+    (mh_decode_frames). skip_rejected: table_set.status goes in as the per-frame status, so
+    a frame whose word is non-zero is skipped and its raster left untouched.
+
+    decode_frames(encoded: Sequence[EncodedFrame], device="cuda") -> [n, H, W] uint8 on the
+    host: the convenience for frames that share one table (upload, decode, copy back);
+    decode_frames_mixed is its twin for lists with different headers."""
+    if not isinstance(frames, DeviceFrames):
+        return _decode_frames_host(frames, table_set)
+    if not isinstance(table_set, DeviceTableSet):
+        raise TypeError("decode_frames(DeviceFrames, ...) takes a DeviceTableSet")
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_frames")
+    if (table_set.n_tables != frames.n_frames or table_set.luts.get_device() != dev_index
+            or table_set.luts.dtype is not torch.uint8 or not table_set.luts.is_contiguous()
+            or table_set.status.get_device() != dev_index or table_set.status.dtype is not torch.int32
+            or table_set.status.numel() != frames.n_frames or not table_set.status.is_contiguous()):
+        raise ValueError(f"the table set must hold {frames.n_frames} tables on cuda:{dev_index}")
+    pitch = (frames.width + 7) // 8 * 8
+    h = frames.height
+    if out is None:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            out = torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=frames.codes.device)
+    else:
+        sh = out.shape
+        if (out.dtype is not torch.uint8 or len(sh) < 2 or sh[-1] != pitch or sh[-2] != h
+                or out.get_device() != dev_index or not out.is_contiguous()
+                or out.numel() < frames.n_frames * h * pitch):
+            raise ValueError(f"out must be a contiguous uint8 [{frames.n_frames}, {h}, {pitch}] "
+                             f"tensor on cuda:{dev_index}")
+    if stream is not None:
+        sp = stream.cuda_stream
+    elif _raw_stream is not None:
+        sp = _raw_stream(dev_index)
+    else:
+        sp = torch.cuda.current_stream(dev_index).cuda_stream
+    rc = N.lib().mh_decode_frames(ctypes.byref(fr), table_set.luts.data_ptr(), table_set.stride,
+                                  table_set.status.data_ptr() if skip_rejected else None, out.data_ptr(), pitch,
+                                  h * pitch, sp)
+    if rc:
+        N.check(rc, "mh_decode_frames")
+    return out
+
+
+def _decode_frames_host(encoded: Sequence[EncodedFrame], device="cuda") -> np.ndarray:
     t1, t2 = encoded[0].tables()
     tabs = DeviceTables.upload(t1, t2, device)
     frames = DeviceFrames.pack(encoded, device)
     out = decode(frames, tabs)
+    return out[..., : frames.width].cpu().numpy()
+
+
+def decode_frames_mixed(encoded: Sequence[EncodedFrame], device="cuda") -> np.ndarray:
+    """Convenience for frames with different headers: upload, build the tables on the
+    device, decode in one launch, copy back; returns [n, H, W] uint8 on the host. Raises
+    MHError when a header is rejected."""
+    frames = DeviceFrames.pack(encoded, device, shared_table=False)
+    tabs = DeviceTableSet.from_canonical_headers(np.stack([np.asarray(f.canon, np.uint8) for f in encoded]),
+                                                 frames.codes.device)
+    out = decode_frames(frames, tabs)
+    tabs.check_status()
     return out[..., : frames.width].cpu().numpy()

@@ -150,7 +150,8 @@ class BatchEncoder:
     gets its own histogram, tree and codes (byte-identical to codec.encode_frame, frame
     by frame), in three launches whatever n_frames. Codes land in fixed 16-byte
     aligned slots of `slot` bytes (the capacity), so the result is one DeviceFrames
-    batch for decode() when the frames share a table (e.g. block shuffles)."""
+    batch: AsyncEncodedBatch.decode() decodes it with a table per frame, decode() when the
+    frames share a table (e.g. block shuffles)."""
 
     def __init__(self, width: int, height: int, n_frames: int, device="cuda"):
         self.device = _dev(device)
@@ -215,7 +216,8 @@ class AsyncEncodedBatch:
     flags: int
 
     def frames(self, check: bool = True) -> DeviceFrames:
-        """All slots as one DeviceFrames batch (valid when the frames share a table).
+        """All slots as one DeviceFrames batch: for decoder.decode_frames with table_set()
+        (a table per frame), or for decoder.decode when the frames share a table.
 
         check=True (default) synchronises once: it raises MHError if any frame was
         rejected (that frame's slot and block offsets were never written, so decoding
@@ -234,6 +236,26 @@ class AsyncEncodedBatch:
             payload = int(self.codes.numel()) - self.n_frames * N.MH_CODES_PAD
         return DeviceFrames(self.width, self.height, self.n_frames, self.block_offsets, self.codes,
                             self.frame_code_offsets, self.block_init, self.flags, payload)
+
+    def table_set(self, stream: Optional[torch.cuda.Stream] = None):
+        """One prepared table per frame, built on the device from the device headers in one
+        launch (mh_build_luts_device); asynchronous. Its status is the encoder's word where
+        the encoder rejected the frame (the header of such a frame is unspecified), else the
+        table build's -- combined on the device, so decode() skips exactly those frames."""
+        from .decoder import DeviceTableSet
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ts = DeviceTableSet.from_canonical_headers(self.canon, self.canon.device, stream)
+            ts.status = torch.where(self.status != 0, self.status, ts.status)
+        return ts
+
+    def decode(self, out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+        """encode batch -> n tables -> decode batch on one stream, no host synchronisation:
+        returns the raster [n, H, pitch] (decode()'s `out` contract). A rejected frame is skipped
+        on the device (its raster keeps what `out` held); the tables stay in `self.tables`, whose
+        check_status() synchronises and names such frames."""
+        from .decoder import decode_frames
+        self.tables = self.table_set(stream)
+        return decode_frames(self.frames(check=False), self.tables, out=out, stream=stream)
 
     def frame(self, f: int) -> DeviceEncodedFrame:
         """Frame f (synchronises; raises MHError on a rejected frame)."""
