@@ -190,9 +190,12 @@ int mh_build_tables_device(const uint8_t *d_canon_header, mh_lookup_symbol *d_ta
 /* Batches with one Huffman table per frame (video, tiles of a scan, whatever  */
 /* mh_encode_frames_device_async produced): encode batch -> mh_build_luts_device */
 /* -> mh_decode_frames are three asynchronous steps on one stream, no host     */
-/* synchronisation in between. Not covered: mh_check and mh_stream with        */
-/* per-frame tables, the multi-GPU paths, and an in-kernel table build from    */
-/* T1/T2 for this entry (it needs prepared tables).                           */
+/* synchronisation in between; mh_decode_headers is the same decode in one     */
+/* step, straight from the canonical headers, and mh_stream_create_headers     */
+/* streams such frames from host memory. Not covered: mh_check with per-frame  */
+/* tables, stream groups and the multi-GPU paths with per-frame tables, and an */
+/* in-kernel table build from T1/T2 for mh_decode_frames (it needs prepared    */
+/* tables).                                                                    */
 
 /* n prepared tables (mh_prepare_lut's buffer) from n 256-byte canonical headers in ONE
  * launch: header i at d_canon_headers + 256 i -> d_luts + i * lut_stride_bytes, byte-identical
@@ -223,6 +226,40 @@ int mh_decode_frames(const mh_frame *frame, const uint16_t *d_luts, uint64_t lut
  * per frame (G above) and waves per workgroup. For tests and tools. */
 int mh_decode_frames_shape(const mh_frame *frame, void *stream, uint32_t *groups_per_frame,
                            uint32_t *waves_per_group);
+
+/* mh_decode_frames without the prepared tables: frame f's table comes from its canonical
+ * header d_canon_headers + 256 f (device), built in LDS by every workgroup that decodes a
+ * slice of the frame -- no mh_build_luts_device launch, no table in memory. Output contract,
+ * alignment rules, flag set (MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER), error codes, check order
+ * and launch shape rule are mh_decode_frames' (all checks before any HIP call); NULL
+ * d_canon_headers -> MH_ERR_INVALID_ARG; frame->d_table1 / d_table2 / table2_entries / d_lut
+ * are ignored. d_frame_status (optional input) as in mh_decode_frames: a non-zero word means
+ * the frame is not decoded, no byte of its raster is written and its d_header_status word is
+ * not written. d_header_status (optional output, device int32[n_frames], must not alias
+ * d_frame_status -> MH_ERR_INVALID_ARG): for every frame not skipped, MH_OK,
+ * MH_ERR_CODE_TOO_LONG (a length over 16) or MH_ERR_TABLE (Kraft sum over 1), the verdicts of
+ * mh_build_tables_device, written by one workgroup of the frame. A rejected header never
+ * writes the frame's raster, with or without d_header_status. An incomplete code (Kraft sum
+ * under 1, e.g. one symbol) is valid: windows no code matches are the zero-width entry, as in
+ * the prepared table. One kernel launch; asynchronous. */
+int mh_decode_headers(const mh_frame *frame, const uint8_t *d_canon_headers,
+                      const int32_t *d_frame_status, int32_t *d_header_status,
+                      uint8_t *d_out, size_t out_pitch, size_t out_frame_stride, void *stream);
+
+/* mh_decode_frames_shape for mh_decode_headers (the same rule with that kernel's occupancy).
+ * For tests and tools. */
+int mh_decode_headers_shape(const mh_frame *frame, void *stream, uint32_t *groups_per_frame,
+                            uint32_t *waves_per_group);
+
+/* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
+ * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a
+ * prepared table) and the 16-byte lengths word at their prepared-table offsets in
+ * d_luts + i * lut_stride_bytes, byte-identical to mh_build_luts_device's there; every other
+ * byte of the slot is left untouched. A rejected header writes a zero table and the lengths
+ * word of an all-zero table (as mh_build_luts_device does), plus its status. Argument rules:
+ * mh_build_luts_device's. */
+int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,
+                          uint64_t lut_stride_bytes, int32_t *d_status, void *stream);
 
 /* ---------------------------------------------------------------------- */
 /* GPU encoder (the producer side on the device; output byte-identical to   */
@@ -336,6 +373,33 @@ int mh_stream_slot_time(mh_stream *s, uint32_t slot, float *ms);
 int mh_stream_device(mh_stream *s);               /* the HIP device it runs on */
 int mh_stream_synchronize(mh_stream *s);
 int mh_stream_destroy(mh_stream *s);
+
+/* The stream in table-per-frame mode: every frame brings its own 256-byte canonical header
+ * (what mh_encode_frame and the GPU encoders write per frame). proto: dims, flags and whether
+ * frames carry init bytes, as mh_stream_create; its table fields are ignored and may be NULL.
+ * A slot is one allocation [status, 16 B][header, 256 B][block offsets, padded to 16 B][codes]
+ * and its decode is one mh_decode_headers launch (n_frames = 1) that writes the header's
+ * verdict into the slot's status word -- launched directly by default (it measured faster than
+ * its graph replay); MH_STREAM_GRAPHS=1 in the environment replays it from
+ * a per-slot captured graph, 0 means direct launches as in table mode. Creating the stream
+ * stores nothing into the rasters. mh_stream_output / slot_stream / compute_stream / wait / slot_time / device /
+ * synchronize / destroy work on such a stream unchanged; mh_stream_submit returns
+ * MH_ERR_INVALID_ARG on it, as mh_stream_submit_header does on a table-mode stream. Stream
+ * groups stay table-mode only. */
+int mh_stream_create_headers(const mh_frame *proto, uint64_t codes_capacity, uint32_t n_slots,
+                             uint8_t *const *d_outputs, mh_stream **out);
+/* mh_stream_submit with the frame's header (256 host bytes; same capacity and init-byte
+ * rules). When the host buffers lie header | block offsets padded to 16 B | codes in one
+ * buffer -- h_block_offsets == h_canon_header + 256 and h_codes == h_block_offsets +
+ * round_up(4*NB, 16) -- the frame moves in one DMA; otherwise in one copy per part. */
+int mh_stream_submit_header(mh_stream *s, const uint8_t *h_canon_header, const uint8_t *h_codes,
+                            uint64_t codes_bytes, const uint32_t *h_block_offsets,
+                            const uint8_t *h_block_init, uint32_t *slot);
+/* Waits for the slot's decode and returns its header's verdict in *status: MH_OK,
+ * MH_ERR_CODE_TOO_LONG or MH_ERR_TABLE. A rejected header leaves the slot's raster exactly
+ * as it was; the next frame submitted to the slot decodes normally. MH_OK for a slot never
+ * used and on a table-mode stream. */
+int mh_stream_slot_status(mh_stream *s, uint32_t slot, int32_t *status);
 
 /* Stream groups (config 5 on N GPUs of one node): n_members streams, member i on
  * HIP device devices[i] with protos[i] (tables and d_lut resident on that device),

@@ -9,10 +9,11 @@ of mdejong/MetalHuffman).
   * decoder.decode / DeviceFrames   GPU decode of one frame or a batch
   * decoder.DeviceTables            T1/T2 + prepared table (uploaded, or built on the device)
   * decoder.decode_frames / DeviceTableSet   a batch with a table per frame, one launch
+  * decoder.decode_headers          the same batch straight from its canonical headers (table built in-kernel)
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync
-  * stream                          streaming from host memory (config 5)
+  * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
 """
 from ._native import EXPORTS, LIB_PATH, MH_CODES_PAD, MH_FLAG_LANE_PAIRS, MH_FLAG_NO_DELTA, MHError, lib

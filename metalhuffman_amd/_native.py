@@ -37,6 +37,8 @@ EXPORTS = (
     "mh_decode_huffman_bits", "mh_decode_huffman_bits_from_tables", "mh_decode_frame_cpu",
     "mh_build_stamp",
     "mh_build_luts_device", "mh_decode_frames", "mh_decode_frames_shape",
+    "mh_decode_headers", "mh_decode_headers_shape", "mh_header_luts_device",
+    "mh_stream_create_headers", "mh_stream_submit_header", "mh_stream_slot_status",
 )
 
 
@@ -131,6 +133,14 @@ def lib() -> ctypes.CDLL:
         L.mh_decode_frames.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_size_t,
                                        ctypes.c_size_t, _vp]
         L.mh_decode_frames_shape.argtypes = [ctypes.POINTER(mh_frame), _vp, _u32p, _u32p]
+        L.mh_decode_headers.argtypes = [ctypes.POINTER(mh_frame), _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                        ctypes.c_size_t, _vp]
+        L.mh_decode_headers_shape.argtypes = [ctypes.POINTER(mh_frame), _vp, _u32p, _u32p]
+        L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]
+        L.mh_stream_create_headers.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint64, ctypes.c_uint32,
+                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp)]
+        L.mh_stream_submit_header.argtypes = [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _u32p]
+        L.mh_stream_slot_status.argtypes = [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
         L.mh_stream_create.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint64, ctypes.c_uint32,
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp)]
         L.mh_stream_submit.argtypes = [_vp, _vp, ctypes.c_uint64, _vp, _vp, _u32p]

@@ -1061,6 +1061,252 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   else
     batch_loop<kDelta, Lut13>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
 }
+
+// ---- a batch decoded straight from canonical headers (mh_decode_headers) ---------
+// The 13-bit table is a pure function of the header's 256 code lengths, so a workgroup
+// builds it in LDS itself: no table launch, no prepared buffer, no trip of the table
+// through memory.
+//
+// Canonical codes are ordered by (length, symbol), so in the 16-bit window space the
+// codes of length l fill [F[l], F[l+1]) with F[l+1] = F[l] + (count[l] << (16 - l)) -- the
+// recurrence code = (code + count) << 1 of mh_tables.hip left-justified -- and windows at
+// or above F[17] match no code. A window's code length is therefore 1 + the number of
+// boundaries F[2..17] at or below it (16 compares against wave-uniform values), and its
+// symbol is sorted[base[l] + (window >> (16 - l))], `sorted` the symbols in (length,
+// symbol) order and base[l] = (symbols shorter than l) - first[l].
+//
+// The builder's scratch lives in the staging windows, which are idle until the first span
+// is written behind the table's barrier.
+struct HeaderScratch {
+  uint32_t wcnt[4][16];  // codes of length l (index l - 1) among symbols 64 w .. 64 w + 63
+  uint32_t too_long[4];  // wave w saw a length over 16
+  int32_t base[16];
+  uint8_t sorted[256];
+};
+static_assert(sizeof(HeaderScratch) <= kStageBytes, "the builder's scratch fits one staging window");
+
+struct HeaderFacts {
+  uint32_t mx, mn, flat8;  // the prepared table's lengths word (mh_lut.hpp, mh_tables.hip's sampling rule)
+  int32_t status;          // MH_OK, MH_ERR_CODE_TOO_LONG or MH_ERR_TABLE, as mh_build_tables_device
+};
+
+// The 13-bit table (first level, escapes from P0, second level: mh_lut.hpp) of one header
+// into `lut`, by a workgroup of 8 waves; L: symbol tid's code length (threads >= 256: 0).
+// Every thread returns the same facts. A rejected header returns behind the first barrier
+// with `lut` untouched; so does the flat 8-bit identity code when `skip_flat8` (it decodes
+// without a table). Otherwise the caller's barrier follows the fill.
+__device__ __forceinline__ HeaderFacts header_build(uint32_t L, uint16_t *lut, HeaderScratch *sc, uint32_t tid,
+                                                    bool skip_flat8) {
+  const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // codes per length and each symbol's rank among equal lengths: one ballot per length per wave
+  uint32_t in_wave = 0;
+  if (wave < 4) {
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint64_t tl = __ballot(L > 16);
+    uint32_t mine = 0;
+    for (uint32_t l = 1; l <= 16; ++l) {
+      const uint64_t m = __ballot(L == l);
+      if (L == l) in_wave = (uint32_t)__popcll(m & below);
+      if (lane == l - 1) mine = (uint32_t)__popcll(m);
+    }
+    if (lane < 16) sc->wcnt[wave][lane] = mine;
+    if (lane == 16) sc->too_long[wave] = tl != 0;
+  }
+  lds_barrier();
+  // every wave for itself, lane l - 1 for length l: the count, the left-justified first code
+  // F[l] (exclusive prefix sum of count << (16 - l)) and the symbols shorter than l
+  const uint32_t li = lane & 15u, sh = 15u - li;
+  const uint32_t cnt = lane < 16 ? sc->wcnt[0][li] + sc->wcnt[1][li] + sc->wcnt[2][li] + sc->wcnt[3][li] : 0u;
+  const uint32_t v = cnt << sh;
+  uint32_t incl = v, upto = cnt;
+#pragma unroll
+  for (uint32_t d = 1; d < 16; d <<= 1) {
+    const uint32_t y = __shfl_up(incl, d), z = __shfl_up(upto, d);
+    if (lane >= d) {
+      incl += y;
+      upto += z;
+    }
+  }
+  const uint32_t F = incl - v, shorter = upto - cnt;
+  const uint32_t kraft = __builtin_amdgcn_readlane(incl, 15);
+  const bool too_long = __ballot(sc->too_long[lane & 3u] != 0u) != 0;
+  HeaderFacts hf;
+  hf.status = too_long ? MH_ERR_CODE_TOO_LONG : kraft > 65536u ? MH_ERR_TABLE : MH_OK;
+  // longest / shortest code as mh_prepare_lut samples them (windows at multiples of 4): a
+  // length counts when one of its codes starts there -- the k-th code of length l starts at
+  // F + (k << (16 - l)), and F is a multiple of 4 up to 14 bits
+  const uint32_t seen = (uint32_t)__ballot(lane < 16 && cnt > (((0u - F) & 3u) >> sh)) & 0xFFFFu;
+  hf.mx = seen ? 32u - (uint32_t)__clz(seen) : 0u;
+  hf.mn = seen ? (uint32_t)__ffs(seen) : 255u;
+  hf.flat8 = __builtin_amdgcn_readlane(cnt, 7) == 256u;  // all 256 symbols at 8 bits: code c = symbol c
+  if (hf.status != MH_OK) {
+    hf.mx = 0;
+    hf.mn = 255;
+    hf.flat8 = 0;
+    return hf;
+  }
+  if (skip_flat8 && hf.flat8) return hf;
+  // P0: the first 13-bit prefix of a code longer than 13 bits
+  const uint32_t longs = (uint32_t)__ballot(lane < 16 && lane >= (uint32_t)kLutBits && cnt != 0u);
+  const uint32_t P0 = longs ? __builtin_amdgcn_readlane(F, __ffs(longs) - 1) >> kL2Bits : (uint32_t)kL1Entries;
+  uint32_t E[16];  // F[2..17], wave-uniform
+#pragma unroll
+  for (int i = 0; i < 16; ++i) E[i] = __builtin_amdgcn_readlane(incl, i);
+  if (wave < 4) {
+    const uint32_t lx = (L - 1u) & 15u;
+    uint32_t pos = __shfl(shorter, lx) + in_wave;
+    for (uint32_t w = 0; w < wave; ++w) pos += sc->wcnt[w][lx];
+    if (L) sc->sorted[pos & 255u] = (uint8_t)tid;
+  }
+  if (tid < 16) sc->base[tid] = (int32_t)(shorter - (F >> sh));
+  lds_barrier();
+  // the step word of a 16-bit window (0: no code matches, the zero-width entry)
+  const auto entry = [&](uint32_t w, uint32_t len) -> uint32_t {
+    const uint32_t lc = min(len, 16u);
+    const uint32_t pos = (uint32_t)(sc->base[lc - 1u] + (int32_t)(w >> (16u - lc))) & 255u;
+    const uint32_t sym = sc->sorted[pos];
+    return len > 16u ? 0u : ((sym << 8) - len) & 0xFFFFu;
+  };
+  const auto length_of = [&](uint32_t w) -> uint32_t {
+    uint32_t len = 1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) len += (uint32_t)(w >= E[i]);
+    return len;
+  };
+  const auto pack8 = [](const uint32_t (&x)[8]) -> v4u32 {
+    v4u32 o;
+    o.x = x[0] | (x[1] << 16);
+    o.y = x[2] | (x[3] << 16);
+    o.z = x[4] | (x[5] << 16);
+    o.w = x[6] | (x[7] << 16);
+    return o;
+  };
+  v4u32 *lutv = reinterpret_cast<v4u32 *>(lut);
+  // First level: each thread owns two 16-byte chunks (8 prefixes = 64 windows each). A code
+  // of <= 10 bits covers the whole chunk (one 16-byte store of its step word); a chunk that
+  // no code reaches is zero; only chunks among the 11-13-bit codes or across P0 resolve
+  // their entries one by one.
+  constexpr uint32_t kL1Chunks = (uint32_t)kL1Entries / 8u;
+  static_assert(kL1Chunks == 2u * 64u * kMaxWavesPerWG, "two first-level chunks per thread");
+#pragma unroll 1
+  for (uint32_t c = tid; c < kL1Chunks; c += 64u * kMaxWavesPerWG) {
+    const uint32_t w0 = c << 6, len0 = length_of(w0);
+    v4u32 o;
+    if (len0 <= 10u) {
+      const uint32_t e = entry(w0, len0), e2 = e | (e << 16);
+      o.x = o.y = o.z = o.w = e2;
+    } else if (len0 > 16u && P0 == (uint32_t)kL1Entries) {
+      o.x = o.y = o.z = o.w = 0u;
+    } else {
+      uint32_t x[8];
+#pragma unroll
+      for (uint32_t j = 0; j < 8; ++j) {
+        const uint32_t p = c * 8u + j, sub = p - P0 + 1u;
+        const uint32_t w = p << kL2Bits;
+        const uint32_t e = entry(w, length_of(w));
+        x[j] = p >= P0 ? (sub < (uint32_t)kL2Subtables ? sub : 0u) : e;
+      }
+      o = pack8(x);
+    }
+    lutv[c] = o;
+  }
+  // Second level (130 chunks: subtable 0, <= 128 long-code prefixes, padding), on the last
+  // threads -- the first four waves did the ballots
+  constexpr uint32_t kL2Chunks = (uint32_t)(kLutEntries - kL1Entries) / 8u;
+  const uint32_t j2 = 64u * kMaxWavesPerWG - 1u - tid;
+  if (j2 < kL2Chunks) {
+    const uint32_t nl2 = ((uint32_t)kL1Entries - P0) << kL2Bits;
+    v4u32 o;
+    o.x = o.y = o.z = o.w = 0u;
+    if (j2 >= 1u && j2 < (uint32_t)kL2Subtables && (j2 - 1u) * 8u < nl2) {
+      uint32_t x[8];
+#pragma unroll
+      for (uint32_t i = 0; i < 8; ++i) {
+        const uint32_t w = (P0 << kL2Bits) + (j2 - 1u) * 8u + i;
+        x[i] = entry(w, length_of(w));
+      }
+      o = pack8(x);
+    }
+    lutv[kL1Chunks + j2] = o;
+  }
+  return hf;
+}
+
+// mh_decode_multitable_kernel with another prologue: the workgroup loads frame f's 256 code
+// lengths (and its first tile header), builds the table in LDS (header_build) and takes the
+// step flavour from the facts the builder returns. Slice 0 of every frame that is not skipped
+// by its status word writes the header's verdict; a rejected header returns before any store
+// to the raster.
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_headers_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_headers,
+    const int32_t *p_status, int32_t *p_header_status, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    const DecodeArgs a0) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t G = p_groups;
+  const uint32_t f = blockIdx.x / G, slice = blockIdx.x - f * G;
+  DecodeArgs a = a0;
+  a.offsets = p_offsets;
+  a.frame_off = p_frame_off;
+  a.block_init = p_block_init;
+  a.lut = nullptr;
+  a.nb = p_nb;
+  a.tiles_per_frame = p_tiles_per_frame;
+  a.total_tiles = (f + 1u) * p_tiles_per_frame;  // this workgroup's tiles end with its frame
+  constexpr uint32_t nwaves = kMaxWavesPerWG;
+  a.nwaves = nwaves;
+  a.grid = G;
+  const uint32_t gstride = G * nwaves;
+  uint8_t *stage = s_stage + wave * kStageBytes;
+  const uint8_t *lut = reinterpret_cast<const uint8_t *>(s_lut);
+#if MH_DIAG_STAMPS
+  unsigned long long ts[kDiagSlots] = {};
+#endif
+  MH_STAMP(0);
+
+  const uint32_t t0 = min(f * p_tiles_per_frame + slice * nwaves + wave, a.total_tiles);
+  TileHdr hc;
+  // the frame's status word, its code lengths (threads past 255 read out of range: 0), then the
+  // first tile header: vector loads, the oldest first
+  const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
+      uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
+  const uint32_t L = __builtin_amdgcn_raw_buffer_load_b8(uniform_rsrc(p_headers + (uint64_t)f * 256u, 256u),
+                                                         (int)threadIdx.x, 0, 0) & 0xFFu;
+  hdr_issue(a, t0, lane, hc);
+  if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
+  const HeaderFacts hf = header_build(L, s_lut, reinterpret_cast<HeaderScratch *>(s_stage), threadIdx.x, true);
+  if (p_header_status && slice == 0 && threadIdx.x == 0) p_header_status[f] = hf.status;
+  if (hf.status != MH_OK) return;  // workgroup-uniform: a rejected header, no store to the raster
+  lds_barrier();  // the table is complete, and nobody reads the scratch in the staging windows any more
+  if (hf.flat8)
+    flat8_loop<kDelta>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG);
+  else if (hf.mx == hf.mn)
+    batch_loop<kDelta, Lut13Flat>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+  else if (hf.mx <= (uint32_t)kLutBits)
+    batch_loop<kDelta, Lut13NoEsc>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+  else
+    batch_loop<kDelta, Lut13>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+}
+
+// mh_header_luts_device: header_build's table and facts copied out at their prepared-table
+// offsets, one workgroup per header, so a test can compare them with mh_build_luts_device's.
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG) mh_header_luts_kernel(const uint8_t *headers, uint8_t *luts,
+                                                                             uint64_t lut_stride, int32_t *status) {
+  const uint32_t hdr = blockIdx.x, tid = threadIdx.x;
+  const uint32_t L = tid < 256u ? headers[(uint64_t)hdr * 256u + tid] : 0u;
+  const HeaderFacts hf = header_build(L, s_lut, reinterpret_cast<HeaderScratch *>(s_stage), tid, false);
+  __syncthreads();
+  uint8_t *dst = luts + (uint64_t)hdr * lut_stride;
+  const v4u32 *src = reinterpret_cast<const v4u32 *>(s_lut);
+  v4u32 zero;
+  zero.x = zero.y = zero.z = zero.w = 0u;
+  for (uint32_t i = tid; i < (uint32_t)kLutBytes / 16u; i += blockDim.x)
+    reinterpret_cast<v4u32 *>(dst)[i] = hf.status == MH_OK ? src[i] : zero;
+  if (tid < 4)
+    reinterpret_cast<uint32_t *>(dst + kMaxLenOff)[tid] = tid == 0 ? hf.mx : tid == 1 ? hf.mn : tid == 2 ? hf.flat8 : 0u;
+  if (status && tid == 0) status[hdr] = hf.status;
+}
 #endif  // !MH_LANE_PAIRS
 
 // ---- small launches (<= one wave per SIMD, e.g. one 2048x1536 frame) -------------
@@ -1630,6 +1876,7 @@ struct DeviceInfo {
   std::atomic<int> cus{0};  // nonzero once the entry is complete
   int occ[2][kMaxWavesPerWG + 1] = {};
   int occ_frames[2] = {};  // mh_decode_multitable_kernel at 8 waves (raw / delta)
+  int occ_headers[2] = {};  // mh_decode_headers_kernel at 8 waves (raw / delta)
 };
 DeviceInfo g_devinfo[kMaxDevices];
 
@@ -1675,6 +1922,8 @@ const DeviceInfo *device_info(hipStream_t s) {
 #if !MH_LANE_PAIRS
   d.occ_frames[0] = occupancy_of(mh_decode_multitable_kernel<false>, kMaxWavesPerWG);
   d.occ_frames[1] = occupancy_of(mh_decode_multitable_kernel<true>, kMaxWavesPerWG);
+  d.occ_headers[0] = occupancy_of(mh_decode_headers_kernel<false>, kMaxWavesPerWG);
+  d.occ_headers[1] = occupancy_of(mh_decode_headers_kernel<true>, kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -1803,10 +2052,13 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
 //   G = clamp(ceil(R / n_frames), 1, ceil(tiles_per_frame / 8)),
 // R = the workgroups resident on the device at once (CUs x the kernel's occupancy): about
 // one resident round when the frames are few, one workgroup per frame when they are many.
-int frames_shape(uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s, uint32_t *groups) {
+// `headers`: the shape of mh_decode_headers, the same rule with its kernel's occupancy.
+int frames_shape(uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s, uint32_t *groups,
+                 bool headers = false) {
   const DeviceInfo *di = device_info(s);
   if (!di) return MH_ERR_HIP;
-  const uint64_t resident = (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)di->occ_frames[delta ? 1 : 0];
+  const int occ = (headers ? di->occ_headers : di->occ_frames)[delta ? 1 : 0];
+  const uint64_t resident = (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)occ;
   const uint64_t want = (resident + n_frames - 1) / n_frames;
   const uint64_t most = (tiles_per_frame + (uint32_t)kMaxWavesPerWG - 1) / (uint32_t)kMaxWavesPerWG;
   *groups = (uint32_t)(want < 1 ? 1 : want > most ? most : want);
@@ -1823,6 +2075,19 @@ int launch_frames(const DecodeArgs &a, uint32_t n_frames, const uint8_t *luts, u
   if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
   MH_LAUNCH(mh_decode_multitable_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
             a.offsets, a.frame_off, a.block_init, luts, status, lut_stride, a.nb, a.tiles_per_frame, G, a);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+template <bool kDelta>
+int launch_headers(const DecodeArgs &a, uint32_t n_frames, const uint8_t *headers, const int32_t *status,
+                   int32_t *header_status, hipStream_t s, bool any_order) {
+  uint32_t G = 0;
+  const int rc = frames_shape(n_frames, a.tiles_per_frame, kDelta, s, &G, true);
+  if (rc != MH_OK) return rc;
+  const uint64_t grid = (uint64_t)G * n_frames;
+  if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  MH_LAUNCH(mh_decode_headers_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
+            a.offsets, a.frame_off, a.block_init, headers, status, header_status, a.nb, a.tiles_per_frame, G, a);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 #endif
@@ -1929,6 +2194,52 @@ int mh_decode_frames_shape(const mh_frame *fr, void *stream, uint32_t *groups_pe
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
   return MH_OK;
+}
+
+int mh_decode_headers(const mh_frame *fr, const uint8_t *d_canon_headers, const int32_t *d_frame_status,
+                      int32_t *d_header_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
+                      void *stream) {
+  if (d_header_status && d_header_status == d_frame_status) return MH_ERR_INVALID_ARG;
+  // mh_decode_frames' checks in its order; the headers stand where d_luts does (NULL ->
+  // MH_ERR_INVALID_ARG) and have no alignment or stride rule of their own
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, true,
+                             d_canon_headers ? reinterpret_cast<const uint16_t *>(uintptr_t{16}) : nullptr,
+                             (uint64_t)kPreparedBytes);
+  if (rc != MH_OK) return rc;
+  DecodeArgs a{};  // t1 / t2 / lut stay null: every workgroup builds its frame's table from the header
+  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
+  if (rc != MH_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return (fr->flags & MH_FLAG_NO_DELTA)
+             ? launch_headers<false>(a, fr->n_frames, d_canon_headers, d_frame_status, d_header_status, s, ao)
+             : launch_headers<true>(a, fr->n_frames, d_canon_headers, d_frame_status, d_header_status, s, ao);
+}
+
+int mh_decode_headers_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame,
+                            uint32_t *waves_per_group) {
+  if (!fr || !groups_per_frame || !waves_per_group || fr->n_frames == 0) return MH_ERR_INVALID_ARG;
+  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
+  const mh_dims &d = fr->dims;
+  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
+      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
+    return MH_ERR_DIMS;
+  const uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
+  const int rc = frames_shape(fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
+                              groups_per_frame, true);
+  if (rc != MH_OK) return rc;
+  *waves_per_group = kMaxWavesPerWG;
+  return MH_OK;
+}
+
+int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,
+                          uint64_t lut_stride_bytes, int32_t *d_status, void *stream) {
+  if (!d_canon_headers || !d_luts || n_headers == 0 || n_headers > 65535u) return MH_ERR_INVALID_ARG;
+  if (((uintptr_t)d_luts & 15u) || (lut_stride_bytes & 15u)) return MH_ERR_ALIGN;
+  if (lut_stride_bytes < mh_lut_bytes()) return MH_ERR_CAPACITY;
+  hipLaunchKernelGGL(mh_header_luts_kernel, dim3(n_headers), dim3(kMaxWavesPerWG * 64), 0, (hipStream_t)stream,
+                     d_canon_headers, reinterpret_cast<uint8_t *>(d_luts), lut_stride_bytes, d_status);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 #endif  // !MH_LANE_PAIRS
 

@@ -23,52 +23,9 @@
 
 #include "../../include/metalhuffman.h"
 
-struct mh_stream {
-  struct Slot {
-    uint8_t *base = nullptr;    // [block offsets, padded to 16 B][codes]
-    uint8_t *codes = nullptr;
-    uint32_t *offsets = nullptr;
-    uint8_t *init = nullptr;
-    uint8_t *out = nullptr;
-    bool own_out = true;
-    hipEvent_t start = nullptr;  // before the slot's copy (timing event)
-    hipEvent_t done = nullptr;   // after the slot's decode (timing event)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t stream = nullptr;  // this slot's copies + decode, in order
-    bool used = false;
-  };
-  int device = 0;
-  uint32_t last = 0;  // slot of the most recent submit
-  mh_frame proto{};
-  uint64_t cap = 0;
-  uint64_t nb = 0;
-  uint64_t off_bytes = 0;  // nb * 4 rounded up to 16
-  size_t pitch = 0, out_bytes = 0;
-  uint32_t next = 0;
-  bool graphs = true;
-  std::vector<Slot> slots;
-};
+#include "mh_stream_internal.hpp"  // struct mh_stream, DeviceGuard
 
 namespace {
-
-// Makes `dev` current for the scope (and restores the caller's device): every
-// stream call may come from any host thread with any current device.
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) {
-      ok = false;
-      return;
-    }
-    if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 void release(mh_stream *s) {
   if (!s) return;
@@ -197,6 +154,7 @@ int mh_stream_submit(mh_stream *s, const uint8_t *h_codes, uint64_t codes_bytes,
                      const uint32_t *h_block_offsets, const uint8_t *h_block_init,
                      uint32_t *slot_out) {
   if (!s || !h_codes || !h_block_offsets) return MH_ERR_INVALID_ARG;
+  if (s->headers) return MH_ERR_INVALID_ARG;  // a header-mode stream: mh_stream_submit_header
   if (codes_bytes < MH_CODES_PAD || codes_bytes > s->cap) return MH_ERR_CAPACITY;
   if (!h_block_init != !s->slots[0].init) return MH_ERR_INVALID_ARG;
   const uint32_t k = s->next;

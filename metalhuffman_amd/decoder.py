@@ -377,6 +377,70 @@ def decode_frames(frames, table_set="cuda", out: Optional[torch.Tensor] = None,
     return out
 
 
+def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
+                         extra_flags: int = 0) -> tuple:
+    """(workgroups per frame, waves per workgroup) decode_headers would launch with
+    (mh_decode_headers_shape)."""
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
+    N.check(N.lib().mh_decode_headers_shape(ctypes.byref(fr), sp, ctypes.byref(g), ctypes.byref(w)),
+            "mh_decode_headers_shape")
+    return int(g.value), int(w.value)
+
+
+def decode_headers(frames: DeviceFrames, canons, out: Optional[torch.Tensor] = None,
+                   frame_status: Optional[torch.Tensor] = None, header_status: Optional[torch.Tensor] = None,
+                   stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> torch.Tensor:
+    """Decode a batch straight from its canonical headers (mh_decode_headers): frame f's table is
+    built inside the decode kernel from canons[f] -- no DeviceTableSet. canons: device u8[n, 256]
+    tensor, or a host array (uploaded here). frame_status (optional int32[n] on the device): a
+    non-zero word skips the frame. header_status (optional int32[n] on the device, not the same
+    tensor): receives each decoded frame's verdict, 0, -3 or -5; a rejected frame's raster is
+    left untouched. Returns the device raster out[n, H, pitch] (decode()'s `out` contract)."""
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_headers")
+    dev = frames.codes.device
+    if isinstance(canons, torch.Tensor):
+        hdr = canons
+    else:
+        hdr = torch.from_numpy(np.ascontiguousarray(canons, np.uint8)).to(dev)
+    if (hdr.dtype is not torch.uint8 or hdr.dim() != 2 or tuple(hdr.shape) != (frames.n_frames, 256)
+            or hdr.get_device() != dev_index or not hdr.is_contiguous()):
+        raise ValueError(f"canons must be a contiguous uint8 [{frames.n_frames}, 256] tensor on cuda:{dev_index}")
+    for name, st in (("frame_status", frame_status), ("header_status", header_status)):
+        if st is not None and (st.dtype is not torch.int32 or st.numel() != frames.n_frames
+                               or st.get_device() != dev_index or not st.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int32 [{frames.n_frames}] tensor on cuda:{dev_index}")
+    pitch = (frames.width + 7) // 8 * 8
+    h = frames.height
+    if out is None:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            out = torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=dev)
+    else:
+        sh = out.shape
+        if (out.dtype is not torch.uint8 or len(sh) < 2 or sh[-1] != pitch or sh[-2] != h
+                or out.get_device() != dev_index or not out.is_contiguous()
+                or out.numel() < frames.n_frames * h * pitch):
+            raise ValueError(f"out must be a contiguous uint8 [{frames.n_frames}, {h}, {pitch}] "
+                             f"tensor on cuda:{dev_index}")
+    if stream is not None:
+        sp = stream.cuda_stream
+    elif _raw_stream is not None:
+        sp = _raw_stream(dev_index)
+    else:
+        sp = torch.cuda.current_stream(dev_index).cuda_stream
+    rc = N.lib().mh_decode_headers(ctypes.byref(fr), hdr.data_ptr(),
+                                   frame_status.data_ptr() if frame_status is not None else None,
+                                   header_status.data_ptr() if header_status is not None else None,
+                                   out.data_ptr(), pitch, h * pitch, sp)
+    if rc:
+        N.check(rc, "mh_decode_headers")
+    frames.__dict__["_hdr_keep"] = hdr  # read by the launch in flight
+    return out
+
+
 def _decode_frames_host(encoded: Sequence[EncodedFrame], device="cuda") -> np.ndarray:
     t1, t2 = encoded[0].tables()
     tabs = DeviceTables.upload(t1, t2, device)

@@ -80,6 +80,55 @@ class FrameStream:
             pass
 
 
+class HeaderFrameStream(FrameStream):
+    """FrameStream in table-per-frame mode (mh_stream_create_headers): every submit brings the
+    frame's own 256-byte canonical header, and the slot's decode (one mh_decode_headers launch,
+    direct by default, a graph replay with MH_STREAM_GRAPHS=1) builds the table from it. No
+    DeviceTables. Creating the stream stores nothing into the rasters."""
+
+    def __init__(self, width: int, height: int, codes_capacity: int, slots: int = 2, flags: int = 0,
+                 block_init: bool = False, device="cuda", outputs=None):
+        dev = _dev(device)
+        self.device, self.width, self.height = dev, width, height
+        self.pitch = (width + 7) // 8 * 8
+        self.outputs = list(outputs) if outputs is not None else [
+            torch.empty((height, self.pitch), dtype=torch.uint8, device=dev) for _ in range(slots)]
+        if len(self.outputs) != slots:
+            raise ValueError("one output raster per slot")
+        proto = N.mh_frame()
+        proto.dims = N.mh_dims(width, height, (width + 7) // 8, (height + 7) // 8)
+        proto.n_frames = 1
+        proto.flags = flags
+        self._init_dummy = torch.zeros(8, dtype=torch.uint8, device=dev) if block_init else None
+        proto.d_block_init = self._init_dummy.data_ptr() if block_init else None
+        outs = (ctypes.c_void_p * slots)(*[t.data_ptr() for t in self.outputs])
+        self._tables = None
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(dev):
+            N.check(N.lib().mh_stream_create_headers(ctypes.byref(proto), int(codes_capacity), slots,
+                                                     outs, ctypes.byref(self._h)), "mh_stream_create_headers")
+
+    def submit(self, header: torch.Tensor, codes: torch.Tensor, offsets: torch.Tensor,
+               init: Optional[torch.Tensor] = None) -> int:
+        """Queue one frame from host tensors (pinned for an asynchronous DMA): header u8[256],
+        codes u8 (payload + MH_CODES_PAD zero bytes), offsets u32/int32[NB]. The three views
+        pinned_frame_with_header returns move in one DMA."""
+        if header.numel() != 256:
+            raise ValueError("the canonical header has 256 entries")
+        slot = ctypes.c_uint32(0)
+        N.check(N.lib().mh_stream_submit_header(self._h, header.data_ptr(), codes.data_ptr(), codes.numel(),
+                                                offsets.data_ptr(), init.data_ptr() if init is not None else None,
+                                                ctypes.byref(slot)), "mh_stream_submit_header")
+        return int(slot.value)
+
+    def slot_status(self, slot: int) -> int:
+        """The verdict on the header of the slot's last frame (waits for its decode): 0, -3 (a
+        length over 16) or -5 (not a prefix code). A rejected frame leaves the raster as it was."""
+        st = ctypes.c_int32(0)
+        N.check(N.lib().mh_stream_slot_status(self._h, slot, ctypes.byref(st)), "mh_stream_slot_status")
+        return int(st.value)
+
+
 class FrameStreamGroup:
     """Frames round-robined over several devices (config 5 on N GPUs): one native
     stream per member (mh_stream_group_*), member i on devices[i] with its own copy
@@ -176,3 +225,16 @@ def pinned_frame(ef) -> tuple[torch.Tensor, torch.Tensor]:
     buf[: offs.size * 4].copy_(torch.from_numpy(offs.view(np.uint8)))
     buf[ob:].copy_(torch.from_numpy(np.ascontiguousarray(ef.codes)))
     return buf[ob:], buf[: offs.size * 4].view(torch.int32)
+
+
+def pinned_frame_with_header(ef) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Host-pinned (header, codes, block offsets) of an EncodedFrame in one buffer laid out as
+    a header-mode stream's slots are ([header, 256 B][offsets, padded to 16 B][codes]), so a
+    HeaderFrameStream.submit is one DMA."""
+    offs = np.ascontiguousarray(ef.block_offsets, np.uint32)
+    ob = (offs.size * 4 + 15) // 16 * 16
+    buf = torch.zeros(256 + ob + ef.codes.size, dtype=torch.uint8).pin_memory()
+    buf[:256].copy_(torch.from_numpy(np.ascontiguousarray(ef.canon, np.uint8)))
+    buf[256: 256 + offs.size * 4].copy_(torch.from_numpy(offs.view(np.uint8)))
+    buf[256 + ob:].copy_(torch.from_numpy(np.ascontiguousarray(ef.codes)))
+    return buf[:256], buf[256 + ob:], buf[256: 256 + offs.size * 4].view(torch.int32)
