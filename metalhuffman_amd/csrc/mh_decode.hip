@@ -45,9 +45,21 @@ namespace {
 #ifndef MH_DIAG_DROP_STORES     // diagnostic builds only: every row store out of range (dropped)
 #define MH_DIAG_DROP_STORES 0
 #endif
+#ifndef MH_DIAG_ROWS            // diagnostic builds only: core-clock stamps at every row boundary of the
+#define MH_DIAG_ROWS 0          //    small-launch kernels' staged decode (scripts/diag_stamps.py --rows)
+#endif
+#if MH_DIAG_ROWS && !MH_DIAG_STAMPS
+#error "MH_DIAG_ROWS is a mode of the MH_DIAG_STAMPS build"
+#endif
 #ifndef MH_LANE_PAIRS           // 1: the lane-pair diagnostic library only (libmh_diag_lanepairs.so,
 #define MH_LANE_PAIRS 0         //    metalhuffman_amd/build.py), which exports mh_diag_decode_lanepairs
 #endif
+#ifndef MH_LAZY_ROWS_PER_ITER   // A/B builds: 1, 2 or 8 (8: the chain fully unrolled, as before the row loop)
+#define MH_LAZY_ROWS_PER_ITER 4
+#endif
+constexpr int kLazyRowsPerIter = MH_LAZY_ROWS_PER_ITER;  // rows per trip of the small-launch chain's row loop
+static_assert(kLazyRowsPerIter == 1 || kLazyRowsPerIter == 2 || kLazyRowsPerIter == 4 || kLazyRowsPerIter == 8,
+              "a block's 8 rows in whole trips");
 constexpr int kStageBytes = 4352;             // per-wave LDS window (max tile span)
 constexpr int kMaxWavesPerWG = 8;             // batch kernel workgroup width
 constexpr int kMinWavesPerEU = 6;             // register cap: 6 waves/SIMD = what the LDS budget admits
@@ -188,6 +200,11 @@ __shared__ uint32_t s_p0;
 #if MH_DIAG_STAMPS
 constexpr int kDiagWaves = 8192, kDiagSlots = 8;
 __device__ unsigned long long g_stamps[kDiagWaves * kDiagSlots];
+#if MH_DIAG_ROWS
+// per wave: s_memtime (low word) behind each of the 8 row stores of decode_block, then at its entry
+constexpr int kDiagRowSlots = 16;
+__device__ uint32_t g_rows[kDiagWaves * kDiagRowSlots];
+#endif
 #define MH_STAMP(i) (ts[i] = __builtin_amdgcn_s_memrealtime())
 #else
 #define MH_STAMP(i) ((void)0)
@@ -238,6 +255,15 @@ using Lut13NoEsc = StepCfg<kLutBits, true, false>;
 // block the same size, so lanes sit a multiple of 128 B apart): swizzled stage
 using Lut13Flat = StepCfg<kLutBits, true, false, true>;
 
+#if MH_DIAG_ROWS  // lane r of *rowv: the core clock behind row r's store; lane 8: at the chain's entry
+#define MH_ROWS_PARAM , uint32_t *rowv = nullptr
+#define MH_ROW_STAMP(r) \
+  if (rowv) *rowv = (threadIdx.x & 63u) == (r) ? (uint32_t)__builtin_amdgcn_s_memtime() : *rowv
+#else
+#define MH_ROWS_PARAM
+#define MH_ROW_STAMP(r) ((void)0)
+#endif
+
 // One lane decodes one 8x8 block: 64 serial steps of AAPLShaders.metal:241-268
 // (cursor advance + delta fold); each finished 8-pixel block row is stored at once.
 //
@@ -252,7 +278,7 @@ using Lut13Flat = StepCfg<kLutBits, true, false, true>;
 template <bool kDelta, class Cfg, class Src>
 __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut, uint32_t p,
                                              uint32_t prev, __amdgpu_buffer_rsrc_t out,
-                                             uint32_t row0, uint32_t pitch, bool dead) {
+                                             uint32_t row0, uint32_t pitch, bool dead MH_ROWS_PARAM) {
   if constexpr (Cfg::kFlat8) {
     // 64 one-byte codes from bit p of the staged (big-endian word) span: 17 words, each
     // output word a 64-bit funnel shift (any bit alignment); code c is symbol c
@@ -359,10 +385,17 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
     S += d * 8u;                                                                    \
     if constexpr (!Cfg::kMasked) nw = rd(wa + 8);                                   \
   }
-#define MH_STEP_L(J, OW)                                                            \
+  // The lazy step in two halves, so that the row loop can end right behind a lookup:
+  // MH_ISSUE_L reads the entry at the cursor into eL, MH_TAIL_L is the rest of that step.
+#define MH_ISSUE_L() MH_ISSUE_LQ(const)
+#define MH_ISSUE_LQ(Q)                                                              \
   {                                                                                 \
     const uint64_t x = (((uint64_t)hi) << 32) | lo;                                 \
-    MH_LOOKUP((uint32_t)(x >> (S & 63u)) & Cfg::kMask)                              \
+    eL = *(Q __attribute__((address_space(3))) uint16_t *)((lds_u8)lut + ((uint32_t)(x >> (S & 63u)) & Cfg::kMask)); \
+  }
+#define MH_TAIL_L(J, OW)                                                            \
+  {                                                                                 \
+    uint32_t e = eL;                                                                \
     /* off the chain: refill from the cursor this lookup used */                    \
     const bool c = (S & 0xFFu) <= kRefill;                                         \
     hi = c ? lo : hi;                                                               \
@@ -394,23 +427,73 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
   // dead lanes store at >= 2^31 + r * pitch: past every output descriptor's range
   // (<= 0x7FFFFFF0 bytes), so the hardware drops them -- one select per tile, not per row
   const uint32_t rbase = (dead || MH_DIAG_DROP_STORES) ? 0x80000000u : row0;
+  // Unconditional 8-byte row store (exact vmcnt counting): lanes without a
+  // block and rows below the frame use offsets outside the descriptor's range,
+  // which the hardware drops. A right-edge block writes its 8 bytes into the
+  // row's pitch padding (pitch >= round_up(W, 8)).
+  typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
+  const auto store_row = [&](uint32_t o0, uint32_t o1, uint32_t off) {
+    v2u32 v;
+    v.x = o0;
+    v.y = o1;
+    __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)off, 0, Cfg::kAux);
+  };
+  MH_ROW_STAMP(8);
+  if constexpr (Cfg::kLazy) {
+    // The small-launch chain is a real loop over rows (kLazyRowsPerIter rows per trip; a row's
+    // 8 steps stay unrolled): every wave runs the chain once, so unrolled it fetched ~7 KB of
+    // code in a straight line per launch, and the first launch after other work stalled on it
+    // (profiles/chain_rows_stamps.txt). The loop is rotated: a trip ends
+    // with the lookup of the next row's first symbol, so the back-edge lies in that read's LDS
+    // shadow; it still costs ~80 cycles when taken, which is why a trip is 4 rows and not 1 or 2
+    // (profiles/chain_loop_stamps.txt). The lookup behind the last row reads a valid table
+    // entry (the address is masked) and is dropped.
+    uint32_t eL;
+    uint32_t off = rbase;  // the row's store offset, advancing by pitch
+    MH_ISSUE_L();
+#pragma unroll 1
+    for (uint32_t r = 0; r < 8; r += (uint32_t)kLazyRowsPerIter) {
+#pragma unroll
+      for (uint32_t q = 0; q < (uint32_t)kLazyRowsPerIter; ++q) {
+        uint32_t o0 = 0, o1 = 0;
+        uint32_t sv[4];  // S after each symbol of the current output word (delta mode)
+        (void)sv;
+        MH_TAIL_L(0, o0);
+        MH_ISSUE_L();
+        MH_TAIL_L(1, o0);
+        MH_ISSUE_L();
+        MH_TAIL_L(2, o0);
+        MH_ISSUE_L();
+        MH_TAIL_L(3, o0);
+        if (kDelta) o0 = pack_prev4(sv[0], sv[1], sv[2], sv[3]);
+        MH_ISSUE_L();
+        MH_TAIL_L(0, o1);
+        MH_ISSUE_L();
+        MH_TAIL_L(1, o1);
+        MH_ISSUE_L();
+        MH_TAIL_L(2, o1);
+        MH_ISSUE_L();
+        MH_TAIL_L(3, o1);
+        if (kDelta) o1 = pack_prev4(sv[0], sv[1], sv[2], sv[3]);
+        // A trip's last lookup is a volatile read: it stays in front of the back-edge (a plain
+        // one, dead on the loop's exit, is sunk into the next trip's head, behind the branch),
+        // and the row store stays behind it, off the chain.
+        if (q + 1 == (uint32_t)kLazyRowsPerIter && kLazyRowsPerIter < 8) {
+          MH_ISSUE_LQ(const volatile);
+        } else {
+          MH_ISSUE_L();
+        }
+        store_row(o0, o1, off);
+        off += pitch;
+        MH_ROW_STAMP(r + q);
+      }
+    }
+  } else {
 #pragma unroll
   for (uint32_t r = 0; r < 8; ++r) {
     uint32_t o0 = 0, o1 = 0;
     uint32_t sv[4];  // S after each symbol of the current output word (delta mode)
     (void)sv;
-    if constexpr (Cfg::kLazy) {
-      MH_STEP_L(0, o0);
-      MH_STEP_L(1, o0);
-      MH_STEP_L(2, o0);
-      MH_STEP_L(3, o0);
-      if (kDelta) o0 = pack_prev4(sv[0], sv[1], sv[2], sv[3]);
-      MH_STEP_L(0, o1);
-      MH_STEP_L(1, o1);
-      MH_STEP_L(2, o1);
-      MH_STEP_L(3, o1);
-      if (kDelta) o1 = pack_prev4(sv[0], sv[1], sv[2], sv[3]);
-    } else {
     if (r) {
       MH_STEP_R(0, o0);
     } else {
@@ -425,23 +508,15 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
     MH_STEP_R(2, o1);
     MH_STEP(3, o1);
     if (kDelta) o1 = pack_prev4(sv[0], sv[1], sv[2], sv[3]);
-    }
-    // Unconditional 8-byte row store (exact vmcnt counting): lanes without a
-    // block and rows below the frame use offsets outside the descriptor's range,
-    // which the hardware drops. A right-edge block writes its 8 bytes into the
-    // row's pitch padding (pitch >= round_up(W, 8)).
-    {
-      typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
-      v2u32 v;
-      v.x = o0;
-      v.y = o1;
-      const uint32_t off = rbase + r * pitch;
-      __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)off, 0, Cfg::kAux);
-    }
+    store_row(o0, o1, rbase + r * pitch);
+    MH_ROW_STAMP(r);
+  }
   }
 #undef MH_STEP
 #undef MH_STEP_R
-#undef MH_STEP_L
+#undef MH_ISSUE_L
+#undef MH_ISSUE_LQ
+#undef MH_TAIL_L
 #undef MH_LOOKUP
 #undef MH_FINISH
 #undef MH_REFILL_C
@@ -1347,7 +1422,16 @@ __device__ __forceinline__ void small_decode(const DecodeArgs &a, const Tile &t,
 #if MH_DIAG_STAMPS && MH_DIAG_CLOCK
   unsigned long long c3 = 0;
 #endif
-  if (staged) {
+#if MH_DIAG_ROWS
+  uint32_t rowv = 0;
+#define MH_ROWS_ARG , &rowv
+#else
+#define MH_ROWS_ARG
+#endif
+  // Code layout: the staged 14-bit chain (no code over 14 bits: the bench's frames) is the
+  // fall-through behind the staging; the flat, escape and oversize flavours lie behind it, out
+  // of its fetch path.
+  if (__builtin_expect(staged, 1)) {
     span_write(t, lane, R, stage);
     wave_sync();
     MH_STAMP(3);
@@ -1355,12 +1439,12 @@ __device__ __forceinline__ void small_decode(const DecodeArgs &a, const Tile &t,
     c3 = __builtin_amdgcn_s_memtime();
 #endif
     LdsWords src{stage};
-    if (flat8)
+    if (__builtin_expect(l14 && !flat8, 1))
+      decode_block<kDelta, Small14>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid MH_ROWS_ARG);
+    else if (flat8)
       decode_block<kDelta, SmallFlat8>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
-    else if (l14)
-      decode_block<kDelta, Small14>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
     else
-      decode_block<kDelta, Small13>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid);
+      decode_block<kDelta, Small13>(src, lut, t.p, t.init, out, row0, (uint32_t)a.out_pitch, !t.valid MH_ROWS_ARG);
   } else if (flat8) {
     decode_halves<kDelta, SmallFlat8>(a, t, lane, lut, stage, out, row0, !t.valid);
   } else if (l14) {
@@ -1381,9 +1465,13 @@ __device__ __forceinline__ void small_decode(const DecodeArgs &a, const Tile &t,
   ts[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)__smid() << 32) | blockIdx.x;
   if (lane == 0 && gw < (uint32_t)kDiagWaves)
     for (int i = 0; i < kDiagSlots; ++i) g_stamps[gw * kDiagSlots + i] = ts[i];
+#if MH_DIAG_ROWS
+  if (lane < (uint32_t)kDiagRowSlots && gw < (uint32_t)kDiagWaves) g_rows[gw * kDiagRowSlots + lane] = rowv;
+#endif
 #else
   (void)gw;
 #endif
+#undef MH_ROWS_ARG
 }
 
 template <bool kDelta>
@@ -2104,6 +2192,13 @@ int mh_diag_stamps(unsigned long long *host, size_t n) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), n * sizeof(unsigned long long), 0,
                              hipMemcpyDeviceToHost) == hipSuccess ? (int)n : -1;
 }
+#if MH_DIAG_ROWS
+int mh_diag_rows(uint32_t *host, size_t n) {
+  if (n > sizeof(g_rows) / sizeof(g_rows[0])) n = sizeof(g_rows) / sizeof(g_rows[0]);
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rows), n * sizeof(uint32_t), 0, hipMemcpyDeviceToHost) == hipSuccess
+             ? (int)n : -1;
+}
+#endif
 #endif
 
 #ifdef MH_TABLE_STAMPS  // diagnostic builds: room for the table kernel's phase stamps

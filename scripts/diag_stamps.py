@@ -5,6 +5,11 @@
 Stamps (s_memrealtime, 100 MHz) per wave: 0 entry, 1 first header resolved,
 2 LUT ready, 3 first span staged, 4 first tile decoded (stores issued),
 5 loop done, 6 stores drained.
+
+--launches N stamps the last of N back-to-back launches, each on a frame set of its own
+(with --cold: all of them never decoded before, the flush in front of the first).
+--rows (MH_DIAG_ROWS build, small launches): core clocks of each of the 8 block rows of
+the chain, from the s_memtime stamps behind every row store.
 """
 import argparse
 import ctypes
@@ -34,6 +39,10 @@ ap.add_argument("--random8192", action="store_true",
                      "stamps 2 and 3 = 1, stamp 4 = first tile's codes landed and stores issued)")
 ap.add_argument("--cold", action="store_true",
                 help="stamp a launch of a second, never-decoded frame set after a 1 GiB cache flush (bench.py's cold rule)")
+ap.add_argument("--launches", type=int, default=1,
+                help="stamp the last of this many back-to-back launches, each on its own frame set")
+ap.add_argument("--rows", action="store_true",
+                help="MH_DIAG_ROWS build: core clocks per block row of the single-frame chain")
 args = ap.parse_args()
 
 lib = N.lib()
@@ -50,12 +59,21 @@ elif args.tile8192:
 else:
     efs = [mh.encode_frame(F.block_shuffle(bb, i) if i else bb) for i in range(args.batch)]
     efs2 = ([mh.encode_frame(F.block_shuffle(bb, 1000 + i)) for i in range(args.batch)] if args.cold else efs)
+# the frame sets of the launches in front of the stamped one (fresh ones when cold)
+sets_before = []
+for k in range(1, args.launches):
+    if args.cold and not (args.random8192 or args.tile8192):
+        sets_before.append([mh.encode_frame(F.block_shuffle(bb, 1000 + 100 * k + i)) for i in range(args.batch)])
+    else:
+        sets_before.append(efs)
 t1, t2 = efs[0].tables()
 tabs = D.DeviceTables.upload(t1, t2, "cuda")
 fr = D.DeviceFrames.pack(efs, "cuda")
 fr2 = D.DeviceFrames.pack(efs2, "cuda")
+frs_before = [D.DeviceFrames.pack(e, "cuda") for e in sets_before]
 out = D.decode(fr, tabs)
 out2 = torch.empty_like(out)
+outs_before = [torch.empty_like(out) for _ in frs_before]
 for _ in range(args.reps):
     D.decode(fr, tabs, out)
 if args.cold:  # evict the Infinity Cache and L2s; the stamped launch decodes frames nothing touched yet
@@ -64,6 +82,8 @@ if args.cold:  # evict the Infinity Cache and L2s; the stamped launch decodes fr
     del fa
 torch.cuda.synchronize()
 s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+for f_, o_ in zip(frs_before, outs_before):
+    D.decode(f_, tabs, o_)
 s0.record()
 D.decode(fr2, tabs, out2)
 s1.record()
@@ -89,6 +109,22 @@ if args.args:  # slot 5 = the small-launch kernels' output arguments in register
     d = (st[:, 5].astype(np.int64) - st[:, 2].astype(np.int64)) * 0.01
     print(f"lut->out args p50 {np.median(d):7.2f}  p90 {np.percentile(d, 90):7.2f}  max {d.max():7.2f}")
     st[:, 5] = st[:, 4]
+if args.rows:  # lanes 0-7: s_memtime (low word) behind each row's store; lane 8: at the chain's entry
+    if not hasattr(lib, "mh_diag_rows"):
+        sys.exit("not a MH_DIAG_ROWS build")
+    rb = (ctypes.c_uint32 * (8192 * 16))()
+    assert lib.mh_diag_rows(rb, ctypes.c_size_t(8192 * 16)) == 8192 * 16
+    rw = np.frombuffer(rb, dtype=np.uint32).reshape(-1, 16)[live].astype(np.int64)
+    rw = rw[rw[:, 8] != 0]
+    edges = np.concatenate([rw[:, 8:9], rw[:, :8]], axis=1)
+    per_row = np.diff(edges, axis=1) & 0xFFFFFFFF
+    print(f"row clocks ({len(rw)} waves), cycles per symbol (8 symbols per row):")
+    for r in range(8):
+        v = per_row[:, r] / 8.0
+        print(f"  row {r}: p10 {np.percentile(v, 10):6.1f}  p50 {np.median(v):6.1f}  p90 {np.percentile(v, 90):6.1f}  "
+              f"mean {v.mean():6.1f}")
+    tot = per_row.sum(axis=1) / 64.0
+    print(f"  all rows: p50 {np.median(tot):6.1f}  mean {tot.mean():6.1f} cycles per symbol")
 names = ["entry", "hdr", "lut", "staged", "tile0", "loop", "drain"]
 for i, nm in enumerate(names):
     v = (st[:, i].astype(np.int64) - int(t0)) * 0.01
@@ -104,6 +140,8 @@ T = lambda i: (st[:, i].astype(np.int64) - int(t0)) * 0.01
 start, fin10, end = float(np.median(T(3))), float(np.percentile(T(5), 10)), float(T(6).max())
 print(f"decomposition: start {start:.2f} us, steady {fin10 - start:.2f} us, drain {end - fin10:.2f} us "
       f"(end {end:.2f} us)")
+if args.launches > 1:
+    args.tag += f"_l{args.launches}"
 out_npz = os.path.join(ROOT, "gpurun_out", f"stamps_b{args.batch}{args.tag}{'_cold' if args.cold else ''}.npz")
 os.makedirs(os.path.dirname(out_npz), exist_ok=True)
 np.savez(out_npz, stamps=np.frombuffer(buf, dtype=np.uint64).reshape(-1, 8))
