@@ -252,7 +252,10 @@ using Lut13 = StepCfg<kLutBits, true>;  // the batch kernel's step
 // first level then decodes every window; no per-symbol escape test)
 using Lut13NoEsc = StepCfg<kLutBits, true, false>;
 // ... and for flat tables (every code the same length, e.g. uniform bytes: every
-// block the same size, so lanes sit a multiple of 128 B apart): swizzled stage
+// block the same size, so lanes sit a multiple of 128 B apart): swizzled stage.
+// Escape-free like Lut13NoEsc, so only for a length <= 13 bits: the sampled
+// longest == shortest also holds for {14: n}, {15: n}, {16: n} and {15: 1, 16: 2},
+// whose codes all live in the second level (the general step)
 using Lut13Flat = StepCfg<kLutBits, true, false, true>;
 
 #if MH_DIAG_ROWS  // lane r of *rowv: the core clock behind row r's store; lane 8: at the chain's entry
@@ -1011,9 +1014,10 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   }
   hdr_issue(a, t0, lane, hc);
   // The step flavour, from the prepared table's code lengths (kernel-uniform):
-  //   2: one code length (flat) -> escape-free step, swizzled stage
-  //   1: no code over 13 bits   -> escape-free step
-  //   0: general step (escapes), also for an in-kernel table
+  //   2: one code length (flat), <= 13 bits -> escape-free step, swizzled stage
+  //   1: no code over 13 bits               -> escape-free step
+  //   0: general step (escapes), also for an in-kernel table and for a flat table of
+  //      14- to 16-bit codes, whose every window escapes to the second level
   const uint32_t mx = a.lut ? __builtin_amdgcn_readfirstlane(lw.x) : 16u;
   const uint32_t mn = __builtin_amdgcn_readfirstlane(lw.y), f8 = __builtin_amdgcn_readfirstlane(lw.z);
   // A flat 8-bit identity table (code c = symbol c, the prepared table's flat8 word,
@@ -1036,7 +1040,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   }
 
   // the escape-free flavours need a prepared table, so a full fixed copy (>= 5 waves)
-  const uint32_t flavor = !fixed_copy ? 0u : mx == mn ? 2u : mx <= (uint32_t)kLutBits ? 1u : 0u;
+  const uint32_t flavor = !fixed_copy ? 0u : mx > (uint32_t)kLutBits ? 0u : mx == mn ? 2u : 1u;
   if (f8)
     flat8_loop<kDelta>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG);
   else if (flavor == 1)
@@ -1129,7 +1133,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   }
   if (f8)
     flat8_loop<kDelta>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG);
-  else if (mx == mn)
+  else if (mx == mn && mx <= (uint32_t)kLutBits)
     batch_loop<kDelta, Lut13Flat>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
   else if (mx <= (uint32_t)kLutBits)
     batch_loop<kDelta, Lut13NoEsc>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
@@ -1356,7 +1360,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   lds_barrier();  // the table is complete, and nobody reads the scratch in the staging windows any more
   if (hf.flat8)
     flat8_loop<kDelta>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG);
-  else if (hf.mx == hf.mn)
+  else if (hf.mx == hf.mn && hf.mx <= (uint32_t)kLutBits)
     batch_loop<kDelta, Lut13Flat>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
   else if (hf.mx <= (uint32_t)kLutBits)
     batch_loop<kDelta, Lut13NoEsc>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);

@@ -225,3 +225,220 @@ def check_containment(buf_after: np.ndarray, plan: ContainmentPlan, expected_fra
             raise AssertionError(f"wrong pixel: frame {f}, row {y}, column {x}, buffer offset {i}: "
                                  f"{int(got[f, y, x]):#04x}, expected {int(want[y, x]):#04x}; "
                                  f"{ys.size} wrong pixel(s) in this frame")
+
+
+# ---- frames under a chosen canonical header, and a zoo of headers ------------------------------
+#
+# The decoders are a function of the frame's 256 code lengths. The product's encoders only ever
+# emit Huffman-optimal lengths; encode_with_header packs a frame under ANY valid header
+# (lengths <= 16, Kraft sum <= 1), and header_zoo is a deterministic collection of such headers:
+# random complete codes, incomplete ones, hand-written extremes and headers that must be rejected.
+
+PREPARED_L13_BYTES = 18464                            # 13-bit table: 8192 first-level + 1040 second-level u16
+PREPARED_L14_BYTES = 32768                            # single-level 14-bit table
+PREPARED_WORD_OFF = PREPARED_L13_BYTES + PREPARED_L14_BYTES   # u32[4]: longest, shortest, flat8, 0
+PREPARED_BYTES = PREPARED_WORD_OFF + 16
+
+
+def encode_with_header(canon, deltas, width, height, *, no_delta=False, init_zero_delta=False):
+    """An EncodedFrame of `deltas` (block order, 64 per block, as image_from_block_deltas takes
+    them) under the canonical header `canon`, which need not be the Huffman code of the data:
+    codes from oracle.canonical_codes, packed MSB-first, the last byte zero-filled, MH_CODES_PAD
+    zero bytes behind it, one bit offset per 64 symbols. no_delta: the symbols are the pixels
+    (the image is the block merge of `deltas`); init_zero_delta: the first delta of every block
+    travels in block_init and a zero symbol takes its place. Every symbol that is encoded must
+    have a code."""
+    from oracle import oracle as O
+    from metalhuffman_amd import _native as N
+    from metalhuffman_amd.codec import EncodedFrame
+    assert width % 8 == 0 and height % 8 == 0 and not (no_delta and init_zero_delta)
+    canon = np.array(canon, np.uint8)   # a copy: the frame owns a writable header
+    nb = (width // 8) * (height // 8)
+    sym = np.array(deltas, np.uint8).reshape(nb, 64)
+    init = None
+    if init_zero_delta:
+        init = sym[:, 0].copy()
+        sym[:, 0] = 0
+    sym = sym.reshape(-1)
+    lens = canon[sym].astype(np.int64)
+    assert canon.shape == (256,) and canon.max() <= 16 and (lens > 0).all(), "a symbol without a code"
+    codes16 = O.canonical_codes(canon)[sym].astype(np.uint32)           # left-justified in 16 bits
+    start = np.concatenate([[0], np.cumsum(lens)])
+    k = np.arange(16, dtype=np.uint32)
+    bits = ((codes16[:, None] >> (15 - k)[None, :]) & 1).astype(np.uint8)
+    stream = bits[k[None, :] < lens[:, None]]                           # row-major: symbol order, MSB first
+    assert stream.size == start[-1] < 2 ** 32
+    payload = np.packbits(stream)                                       # zero-fills the last byte
+    codes = np.concatenate([payload, np.zeros(N.MH_CODES_PAD, np.uint8)])
+    flags = N.MH_FLAG_NO_DELTA if no_delta else 0
+    return EncodedFrame(width, height, canon, codes, start[:-1:64].astype(np.uint32), init, flags)
+
+
+def image_of_symbols(deltas, width, height, *, no_delta=False) -> np.ndarray:
+    """The raster a frame of encode_with_header(canon, deltas, ...) decodes to."""
+    if not no_delta:
+        return image_from_block_deltas(np.asarray(deltas, np.uint8), width, height)
+    bw, bh = width // 8, height // 8
+    return np.ascontiguousarray(np.asarray(deltas, np.uint8).reshape(bh, bw, 8, 8).transpose(0, 2, 1, 3)
+                                .reshape(height, width))
+
+
+def frame_under_header(canon, width, height, seed, *, no_delta=False, init_zero_delta=False):
+    """(EncodedFrame, image): symbols drawn uniformly from the header's used symbols; with
+    init_zero_delta every block's first delta is any byte (it travels outside the codes)."""
+    r = np.random.default_rng(seed)
+    used = np.flatnonzero(np.asarray(canon)).astype(np.uint8)
+    nb = (width // 8) * (height // 8)
+    d = r.choice(used, nb * 64)
+    if init_zero_delta:
+        d.reshape(nb, 64)[:, 0] = r.integers(0, 256, nb, dtype=np.uint8)
+    ef = encode_with_header(canon, d, width, height, no_delta=no_delta, init_zero_delta=init_zero_delta)
+    return ef, image_of_symbols(d, width, height, no_delta=no_delta)
+
+
+def kraft_sum(canon) -> int:
+    """Sum of 2^(16 - length) over the used lengths <= 16 (65536: a complete code)."""
+    c = np.asarray(canon).astype(np.int64)
+    c = c[(c > 0) & (c <= 16)]
+    return int((1 << (16 - c)).sum())
+
+
+def long_prefixes(canon) -> int:
+    """13-bit prefixes taken by codes longer than 13 bits: ceil((4 n14 + 2 n15 + n16) / 8)."""
+    c = np.asarray(canon)
+    return -(-(4 * int((c == 14).sum()) + 2 * int((c == 15).sum()) + int((c == 16).sum())) // 8)
+
+
+@dataclasses.dataclass(frozen=True)
+class ZooHeader:
+    name: str
+    kind: str                 # "random", "incomplete", "hand", "rejected"
+    canon: np.ndarray         # u8[256], read-only
+    status: int               # what the device builders report: 0, -3 (a length over 16), -5 (Kraft sum over 1)
+
+    @property
+    def longest(self) -> int:
+        return int(self.canon.max())
+
+
+def _split_lengths(r, nsym, depth, bias):
+    """Leaf depths of a random binary tree with nsym leaves, none deeper than `depth`: start
+    with one leaf and split a leaf shallower than `depth` -- the deepest such with probability
+    `bias`, else any -- until there are nsym. A full tree: the Kraft sum is exactly 1."""
+    assert 2 <= nsym <= (1 << depth)
+    count = np.zeros(depth + 1, np.int64)   # leaves per depth: which leaf of a depth splits makes no difference
+    count[0] = 1
+    for _ in range(nsym - 1):
+        ok = np.flatnonzero(count[:depth])
+        if r.random() < bias:
+            d = int(ok[-1])
+        else:
+            d = int(r.choice(ok, p=count[ok] / count[ok].sum()))
+        count[d] -= 1
+        count[d + 1] += 2
+    return np.repeat(np.arange(depth + 1, dtype=np.uint8), count)
+
+
+def _deal(lengths, perm) -> np.ndarray:
+    canon = np.zeros(256, np.uint8)
+    canon[perm[: len(lengths)]] = lengths
+    canon.setflags(write=False)
+    return canon
+
+
+HAND_HEADERS = {  # name -> {length: how many symbols}
+    "14x2": {14: 2}, "14x256": {14: 256}, "15x256": {15: 256}, "16x256": {16: 256}, "15x1_16x2": {15: 1, 16: 2},
+    "13x3": {13: 3}, "8x255": {8: 255}, "8x256": {8: 256}, "1x1": {1: 1}, "1x1_9x255": {1: 1, 9: 255},
+    "8x255_16x1": {8: 255, 16: 1}, "1x1_16x255": {1: 1, 16: 255}, "2x3_16x253": {2: 3, 16: 253},
+    "13_14_15_16x2": {13: 1, 14: 1, 15: 1, 16: 2},
+    "1to15_16x2": {**{l: 1 for l in range(1, 16)}, 16: 2},
+    "1to13_14x2": {**{l: 1 for l in range(1, 14)}, 14: 2},
+}
+ZOO_SEED = 8
+ZOO_RANDOM = 400
+_ZOO: dict = {}
+
+
+def header_zoo(seed: int = ZOO_SEED) -> list:
+    """The header zoo, the same list for the same seed: ZOO_RANDOM random complete codes
+    ("rnd<i>"), an incomplete variant of every 8th ("inc<i>": a random quarter of its symbols
+    dropped), the hand-written extremes under two dealings of the lengths to symbols ("<name>/a":
+    ascending lengths on symbols 0, 1, ...; "/b": a random permutation), and rejected headers."""
+    if seed in _ZOO:
+        return _ZOO[seed]
+    r = np.random.default_rng(seed)
+    zoo = []
+    for i in range(ZOO_RANDOM):
+        nsym = int(r.integers(2, 257))
+        depth = int(r.integers(max(1, int(np.ceil(np.log2(nsym)))), 17))
+        lengths = _split_lengths(r, nsym, depth, float(r.random()))
+        zoo.append(ZooHeader(f"rnd{i}", "random", _deal(lengths, r.permutation(256)), 0))
+    for i in range(0, ZOO_RANDOM, 8):
+        g = zoo[i].canon.copy()
+        used = np.flatnonzero(g)
+        g[r.choice(used, max(1, used.size // 4), replace=False)] = 0
+        g.setflags(write=False)
+        zoo.append(ZooHeader(f"inc{i}", "incomplete", g, 0))
+    for name, spec in HAND_HEADERS.items():
+        lengths = np.repeat(np.array(sorted(spec), np.uint8), [spec[l] for l in sorted(spec)])
+        zoo.append(ZooHeader(name + "/a", "hand", _deal(lengths, np.arange(256)), 0))
+        zoo.append(ZooHeader(name + "/b", "hand", _deal(lengths, r.permutation(256)), 0))
+
+    def rejected(name, base, changes, status):
+        g = np.array(base, np.uint8)
+        for s, l in changes.items():
+            g[s] = l
+        g.setflags(write=False)
+        zoo.append(ZooHeader(name, "rejected", g, status))
+
+    room = next(z.canon for z in zoo if z.kind == "random" and 8 <= int((z.canon > 0).sum()) <= 200)
+    free = np.flatnonzero(room == 0)
+    rejected("complete+16", room, {int(free[0]): 16}, -5)              # Kraft sum 65537
+    rejected("three_1bit", np.zeros(256), {1: 1, 2: 1, 3: 1}, -5)
+    for long in (17, 32, 128, 255):                                    # one length over 16, the rest valid
+        rejected(f"len{long}", room, {int(free[long % free.size]): long}, -3)
+    rejected("len200_oversubscribed", room, {int(free[1]): 1, int(free[2]): 200}, -3)   # too-long wins
+    _ZOO[seed] = zoo
+    return zoo
+
+
+def zoo_accepted(seed: int = ZOO_SEED) -> list:
+    return [z for z in header_zoo(seed) if z.status == 0]
+
+
+def prepared_table_reference(O, canon, status: int = 0) -> np.ndarray:
+    """u8[PREPARED_BYTES]: what the prepared table of a header must contain, stated plainly from
+    the oracle's 65,536-entry {symbol, length} table T (not from T1/T2). step(e) = ((symbol << 8)
+    - length) & 0xFFFF for a length > 0, else 0.
+      13-bit table, first level: P0 = the smallest 13-bit prefix p whose window p << 3 decodes a
+        code longer than 13 bits (8192 when there is none); entry p < P0 is step(T[p << 3]); entry
+        p >= P0 is the escape p - P0 + 1 while that is below 129, else 0.
+      second level (1040 entries): 0..7 zero; 8 + j = step(T[(P0 << 3) + j]) for
+        j < min((8192 - P0) * 8, 1024); the rest zero.
+      14-bit table: entry q = step(T[q << 2]) when that length is <= 14, else 0.
+      lengths word: [longest, shortest non-zero length over T[q << 2] (0 and 255 when there is
+        none), flat8 = 1 only for all 256 symbols at 8 bits, 0].
+    A rejected header (status != 0): all-zero tables and the word [0, 255, 0, 0]."""
+    out = np.zeros(PREPARED_BYTES, np.uint8)
+    word = out[PREPARED_WORD_OFF:].view(np.uint32)
+    if status != 0:
+        word[:] = [0, 255, 0, 0]
+        return out
+    canon = np.asarray(canon, np.uint8)
+    T = O.single_table(canon).view(np.uint16).astype(np.uint32)
+    sym, ln = T & 0xFF, T >> 8
+    step = np.where(ln > 0, ((sym << 8) - ln) & 0xFFFF, 0).astype(np.uint16)
+    p = np.arange(8192)
+    long13 = np.flatnonzero(ln[p << 3] > 13)
+    P0 = int(long13[0]) if long13.size else 8192
+    l13 = out[:PREPARED_L13_BYTES].view(np.uint16)
+    sub = p - P0 + 1
+    l13[:8192] = np.where(p < P0, step[p << 3], np.where(sub < 129, sub, 0))
+    n2 = min((8192 - P0) * 8, 1024)
+    l13[8192 + 8: 8192 + 8 + n2] = step[(P0 << 3): (P0 << 3) + n2]
+    q = np.arange(16384) << 2
+    out[PREPARED_L13_BYTES:PREPARED_WORD_OFF].view(np.uint16)[:] = np.where(ln[q] <= 14, step[q], 0)
+    seen = ln[q][ln[q] > 0]
+    word[:] = [int(seen.max()) if seen.size else 0, int(seen.min()) if seen.size else 255,
+               int((canon == 8).all()), 0]
+    return out

@@ -2,7 +2,12 @@
 building its frame's 13-bit table in LDS. The table is pinned byte for byte against
 mh_build_luts_device (mh_header_luts_device copies it out); the decodes are compared with the
 encoder inputs and the oracle's shader-semantics decode with each frame's own tables -- with
-mh_decode_frames' raster only where the docstring says so. Every case is bit-exact."""
+mh_decode_frames' raster only where the docstring says so. Every case is bit-exact.
+
+The headers here are Huffman-optimal ones (and ten of them with a quarter of their lengths zeroed).
+Valid headers that no Huffman construction emits -- all-long codes, random complete and incomplete
+codes, the extremes of the escape range -- and the comparison of each builder's table with a plain
+reference live in test_gpu_header_zoo.py; new header shapes go there, not here."""
 from __future__ import annotations
 
 import ctypes
