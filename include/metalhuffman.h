@@ -110,7 +110,15 @@ typedef struct {
  * or bring a prepared table each (mh_decode_frames, which ignores the table fields).
  * Frame f's block offsets are d_block_offsets[f*NB .. f*NB+NB) (bit offsets
  * relative to frame f's first code byte); its code bytes start at
- * d_codes + frame_code_offsets[f] (16-byte aligned). */
+ * d_codes + frame_code_offsets[f] (16-byte aligned).
+ * Every declared byte must be readable: all codes_bytes bytes at d_codes for one frame
+ * without an offset array, and for a batch every byte of every slot
+ * [frame_code_offsets[f], frame_code_offsets[f+1]) -- a decode may load anywhere inside
+ * them, not only where the frame's codes lie (lanes without a block load near byte
+ * 0xFFFFFF00 of a frame that large). Code bytes are addressed with 32 bits per frame: one
+ * frame takes codes_bytes <= 0xFFFFFFF0 (more: MH_ERR_CAPACITY); a batch slot may be any
+ * size and one over 0xFFFFFFF0 bytes is treated as 0xFFFFFFF0 bytes (bytes behind that read
+ * as zero). frame_code_offsets themselves are 64-bit: a batch may lie beyond 4 GiB. */
 typedef struct {
   const uint32_t *d_block_offsets;        /* slot [0], u32[n_frames * NB]      */
   const uint8_t *d_codes;                 /* slot [1], 16-byte aligned          */

@@ -614,7 +614,10 @@ __device__ __forceinline__ Tile hdr_resolve(const DecodeArgs &a, const TileHdr &
   t.fb32 = (uint32_t)(fbytes > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : fbytes);
   const uint32_t fbits = t.fb32 > 0x1FFFFFFFu ? 0xFFFFFFFFu : t.fb32 * 8u;
   // a frame's last block ends at most 64 x 16 bits after its start, whatever the
-  // buffer size (a reused streaming slot is larger than the frame it holds)
+  // buffer size (a reused streaming slot is larger than the frame it holds).
+  // The sum wraps for a last block at or above bit 2^32 - 1024: the end then lies below the
+  // tile's start, so the span below is "unknown" and the tile takes decode_halves, whose
+  // (end - start) wraps again to a whole window from the half's own start.
   const uint32_t end_l = (b + 1u < a.nb) ? h.nxt : min(fbits, h.off + 64u * 16u);
   const uint32_t last = min(63u, a.nb - 1u - t.b0);  // last lane holding a block
   const uint32_t sb = __builtin_amdgcn_readfirstlane(h.off);
@@ -622,7 +625,8 @@ __device__ __forceinline__ Tile hdr_resolve(const DecodeArgs &a, const TileHdr &
   t.span_end_bits = eb;
   t.start = (sb >> 3) & ~15u;
   uint32_t end = (eb >> 3) + 24u;
-  if (end > t.fb32 + 16u) end = t.fb32 + 16u;
+  // compared without the sum: fb32 + 16 wraps to 0 for a frame of 0xFFFFFFF0 bytes (end >= 24)
+  if (end - 16u > t.fb32) end = t.fb32 + 16u;
   t.span = end > t.start ? ((end - t.start + 15u) & ~15u) : 0xFFFFFFFFu;
   t.p = t.valid ? h.off - t.start * 8u : 0u;
   t.init = h.init & 0xFFu;
@@ -729,7 +733,7 @@ __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const Tile &t
     }
     const uint32_t start = (sb >> 3) & ~15u;
     uint32_t end = (eb >> 3) + 24u;
-    if (end > t.fb32 + 16u) end = t.fb32 + 16u;
+    if (end - 16u > t.fb32) end = t.fb32 + 16u;  // as hdr_resolve: no wrapping sum
     const uint32_t span = min((end - start + 15u) & ~15u, (uint32_t)kStageBytes);
     __builtin_amdgcn_s_waitcnt(0);  // rare path: drain before reusing the window
     for (uint32_t c = lane; c * 16u < span; c += 64u) {
@@ -1920,7 +1924,7 @@ __global__ void __launch_bounds__(64 * kLpWaves) mh_decode_lanepair_kernel(const
   const uint32_t eb = __builtin_amdgcn_readlane(end_l, last);
   t.start = (sb >> 3) & ~15u;
   uint32_t endb = (eb >> 3) + 24u;
-  if (endb > t.fb32 + 16u) endb = t.fb32 + 16u;
+  if (endb - 16u > t.fb32) endb = t.fb32 + 16u;  // as hdr_resolve: no wrapping sum
   t.span = endb > t.start ? min((endb - t.start + 15u) & ~15u, (uint32_t)kLpStageBytes) : 0u;
   t.p = t.valid ? off - t.start * 8u : 0u;
   t.init = init;

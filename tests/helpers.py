@@ -82,6 +82,92 @@ def shift_stream(ef, k: int):
     return dataclasses.replace(ef, codes=codes, block_offsets=(ef.block_offsets + np.uint32(k)).astype(np.uint32))
 
 
+def place_stream(ef, lead_bytes: int):
+    """The same frame with `lead_bytes` zero bytes in front of its codes and 8 * lead_bytes added
+    to every block offset -> (payload, offsets, total): the frame's own bytes (MH_CODES_PAD
+    included), which belong at [lead_bytes, total) of an otherwise zero buffer of `total` bytes,
+    and the u32 block offsets into that buffer. The lead is not materialised."""
+    lead_bytes = int(lead_bytes)
+    assert lead_bytes >= 0
+    offs = ef.block_offsets.astype(np.uint64) + np.uint64(8 * lead_bytes)
+    assert int(offs[-1]) < 2 ** 32, "block offsets are u32"
+    return ef.codes, offs.astype(np.uint32), lead_bytes + int(ef.codes.size)
+
+
+def placed_host_frame(ef, lead_bytes: int):
+    """place_stream materialised on the host: an EncodedFrame over np.zeros(total) with only the
+    tail written (the untouched lead costs no memory)."""
+    payload, offs, total = place_stream(ef, lead_bytes)
+    codes = np.zeros(total, np.uint8)
+    codes[lead_bytes:] = payload
+    return dataclasses.replace(ef, codes=codes, block_offsets=offs)
+
+
+def lead_top(ef, aligned: bool = False) -> int:
+    """The `top` placement: the largest lead at which the stream's last code bit still lies below
+    2^32 and the lead is no multiple of 16 (the first tile's 16-byte aligned span start then
+    differs from its first byte). The last block's offset lies in (2^32 - 1024, 2^32), so the
+    u32 sum offset + 1024 wraps. One kind of frame cannot have both: a last block of exactly
+    1024 bits (64 codes of 16 bits) ends below 2^32 only from offset 2^32 - 1024 down, where the
+    sum wraps to exactly 0 and the lead is a multiple of 16 when the whole frame is 16-bit codes.
+    For such a frame `top` keeps the odd lead (offset 2^32 - 1032, the largest sum that does not
+    wrap) and aligned=True gives the other half, lead % 16 == 0 at offset 2^32 - 1024."""
+    return lead_top_bits(int(ef.block_offsets[-1]), 8 * ef.payload_bytes, aligned)
+
+
+def lead_top_bits(last: int, end_bits: int, aligned: bool = False) -> int:
+    """lead_top from the last block's offset and the payload's bit count (whole bytes)."""
+    assert 0 < end_bits - last <= 1024 + 7 and end_bits % 8 == 0
+    lead = (2 ** 32 - end_bits) // 8
+    full = end_bits - last == 1024
+    if aligned:
+        assert full and lead % 16 == 0 and 8 * lead + last == 2 ** 32 - 1024
+        return lead
+    if lead % 16 == 0:
+        lead -= 1
+    assert lead % 16 != 0 and 8 * lead + end_bits <= 2 ** 32
+    if full:
+        assert 8 * lead + last == 2 ** 32 - 1032
+    else:
+        assert 2 ** 32 - 1024 < 8 * lead + last < 2 ** 32
+    return lead
+
+
+def lead_mid(ef) -> int:
+    """The `mid` placement: block offsets straddle 2^31 inside tile 0 -- the tile's first block
+    starts below the boundary and its last block (block 63, or the frame's last) at or above it."""
+    offs = ef.block_offsets.astype(np.int64)
+    t0_last = min(63, offs.size - 1)
+    lead = (2 ** 31 - int(offs[t0_last // 2 + 1])) // 8 + 1
+    placed = offs + 8 * lead
+    assert placed[0] < 2 ** 31 <= placed[t0_last] <= placed[-1] < 2 ** 32
+    return lead
+
+
+def exactly_uniform_image(width: int, height: int, seed: int, device=None):
+    """A u8 [height, width] image in which every byte value occurs equally often (+-1 when the
+    pixel count is no multiple of 256): every run of 256 pixels in raster order is the bijection
+    j -> (j * odd_r + c_r) & 0xFF of 0..255 with a run's own odd multiplier and offset. A torch
+    tensor on `device`, or (device=None) a numpy array. The counts are asserted."""
+    import torch
+    n = width * height
+    runs = -(-n // 256)
+    g = torch.Generator().manual_seed(seed)
+    odd = (torch.randint(0, 128, (runs, 1), generator=g, dtype=torch.int32) * 2 + 1).to(torch.uint8)
+    c = torch.randint(0, 256, (runs, 1), generator=g, dtype=torch.int32).to(torch.uint8)
+    dev = torch.device("cpu") if device is None else device
+    j = torch.arange(256, dtype=torch.int32).to(torch.uint8).to(dev)[None, :]
+    flat = (j * odd.to(dev) + c.to(dev)).reshape(-1)[:n]      # u8 arithmetic: modulo 256
+    assert flat.dtype == torch.uint8 and flat.numel() == n
+    counts = torch.zeros(256, dtype=torch.int64, device=dev)
+    for lo in range(0, n, 1 << 26):
+        counts += torch.bincount(flat[lo: lo + (1 << 26)].to(torch.int32), minlength=256)
+    assert int(counts.sum()) == n and int(counts.min()) >= n // 256 and int(counts.max()) <= -(-n // 256), \
+        (int(counts.min()), int(counts.max()))
+    img = flat.reshape(height, width)
+    return img if device is not None else img.numpy()
+
+
 def lane_pair_oversize_deltas(seed: int = 0) -> np.ndarray:
     """512x512 deltas whose first 32 blocks hold 249 rare symbols x 8 (15-bit codes under
     a geometric chain of 7 common symbols): that 32-block lane-pair tile spans 3,735 B,
