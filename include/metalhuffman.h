@@ -44,7 +44,9 @@ extern "C" {
 #define MH_OK 0
 #define MH_ERR_INVALID_ARG (-1)   /* NULL pointer, zero size, bad flags          */
 #define MH_ERR_DIMS (-2)          /* dims inconsistent or above the u16 limits   */
-#define MH_ERR_CODE_TOO_LONG (-3) /* Huffman depth > 16 (ref: assert codei < 16) */
+#define MH_ERR_CODE_TOO_LONG (-3) /* Huffman depth > 16 (the reference asserts codei < 16;
+                                     an encoder given MH_ENCODE_LIMIT_LENGTHS never
+                                     reports it: it limits the lengths instead)   */
 #define MH_ERR_CAPACITY (-4)      /* caller buffer too small                     */
 #define MH_ERR_TABLE (-5)         /* table2 smaller than 256 or not 256-aligned  */
 #define MH_ERR_ALIGN (-6)         /* codes not 16-byte aligned / pitch % 8 != 0  */
@@ -287,7 +289,8 @@ size_t mh_encode_workspace_bytes(uint32_t width, uint32_t height);
  * count is payload + MH_CODES_PAD zero bytes), *d_codes_len (device u64,
  * optional), d_block_offsets (u32[NB]) and, if non-NULL, d_block_init (u8[NB],
  * the IMPL_DELTAS_AND_INIT_ZERO_DELTA variant). *d_status (device int32,
- * optional) becomes MH_OK, MH_ERR_EMPTY, MH_ERR_CODE_TOO_LONG (depth > 16) or
+ * optional) becomes MH_OK, MH_ERR_EMPTY, MH_ERR_CODE_TOO_LONG (depth > 16, unless
+ * MH_ENCODE_LIMIT_LENGTHS is set: then the tree workgroup limits the lengths) or
  * MH_ERR_CAPACITY (round_up(codes_len, 4) > codes_cap, or >= 2^32 code bits);
  * on an error no code bytes or offsets are written, *d_codes_len is 0 and the
  * header's content is unspecified.
@@ -299,6 +302,15 @@ size_t mh_encode_workspace_bytes(uint32_t width, uint32_t height);
  * MH_ENCODE_WORKSPACE_ZEROED in `flags` to skip the per-call clear (one memset
  * launch, ~2 us of a ~33 us frame). */
 #define MH_ENCODE_WORKSPACE_ZEROED 0x100u
+/* Encoder-only flag (mh_encode_frame, mh_encode_frame_device[_async],
+ * mh_encode_frames_device_async; every mh_decode* refuses it): never reject a frame
+ * for its tree's depth. The reference tree is built as always; if no leaf is deeper
+ * than 16 the output is byte-identical to the unflagged call. Only a deeper tree has
+ * its lengths replaced by the optimal code of at most 16 bits
+ * (mh_code_lengths_limited(freq, 16, ...): package-merge, host and device byte for
+ * byte the same), and the status is MH_OK where it was MH_ERR_CODE_TOO_LONG. The
+ * decoders need nothing: they work from the 256 lengths alone. */
+#define MH_ENCODE_LIMIT_LENGTHS 0x200u
 int mh_encode_frame_device_async(const uint8_t *d_gray, uint32_t width, uint32_t height, uint32_t flags,
                                  uint8_t *d_canon_header, uint8_t *d_codes, uint64_t codes_cap,
                                  uint64_t *d_codes_len, uint32_t *d_block_offsets, uint8_t *d_block_init,
@@ -461,7 +473,8 @@ int mh_encode_huffman(const uint8_t *symbols, uint64_t n_symbols, uint32_t block
  * mh_codes_bound(NB*64) + 2. block_offsets: NB entries. block_init (optional,
  * NB bytes): when non-NULL, the first delta of every block is moved into it
  * and zeroed (IMPL_DELTAS_AND_INIT_ZERO_DELTA_BEFORE_HUFF_ENCODING,
- * AAPLRenderer.m:449-473). */
+ * AAPLRenderer.m:449-473). flags: MH_FLAG_NO_DELTA, MH_ENCODE_LIMIT_LENGTHS (a tree
+ * deeper than 16 gets the limited lengths instead of MH_ERR_CODE_TOO_LONG). */
 int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
                     uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
                     uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init);
@@ -516,6 +529,19 @@ int mh_parse_container_header(const uint8_t header[MH_CONTAINER_HEADER_BYTES], u
  * reference tree's tie-breaking (HuffmanEncoder.cpp:29-145). MH_ERR_EMPTY for no
  * symbols, MH_ERR_CODE_TOO_LONG past 16 bits (lengths still written). */
 int mh_code_lengths(const uint64_t freq[256], uint8_t canon_header[256]);
+
+/* Code lengths of at most max_bits bits: mh_code_lengths' where those fit, otherwise the
+ * optimal length-limited code by package-merge. Leaves are the present symbols sorted by
+ * (count, symbol); list_1 is the leaves, list_l (l = 2..max_bits) the merge of the leaves
+ * with the pairs of list_{l-1} (a trailing odd item dropped; on equal weight the leaf
+ * first, packages in order); from t = 2n - 2, for l = max_bits..1, a_l is the number of
+ * leaves among the first t items of list_l and t becomes 2 (t - a_l); the leaf of rank r
+ * gets length #{l : a_l > r}, so among equal counts the lower symbol's code is not the
+ * shorter. The result has Kraft sum 1 and the least sum of count x length of any code
+ * within max_bits. max_bits in 1..16 with 2^max_bits >= the number of present symbols,
+ * and a count total below 2^59 (weights are exact in 64 bits), else MH_ERR_INVALID_ARG;
+ * MH_ERR_EMPTY for no symbols; one symbol gets length 1. */
+int mh_code_lengths_limited(const uint64_t freq[256], uint32_t max_bits, uint8_t canon_header[256]);
 
 /* HuffmanUtil::generateLookupTable (HuffmanUtil.cpp:314-334): 65536 entries. */
 int mh_build_single_table(const uint8_t canon_header[256], mh_lookup_symbol table[65536]);

@@ -16,12 +16,14 @@ of mdejong/MetalHuffman).
   * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
 """
-from ._native import EXPORTS, LIB_PATH, MH_CODES_PAD, MH_FLAG_LANE_PAIRS, MH_FLAG_NO_DELTA, MHError, lib
-from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, decode_frame_cpu, encode_frame, merge_blocks,
-                    split_blocks)
+from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS, MH_FLAG_NO_DELTA,
+                      MHError, lib)
+from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, code_lengths_limited, decode_frame_cpu,
+                    encode_frame, merge_blocks, split_blocks)
 
 __all__ = [
     "EXPORTS", "LIB_PATH", "MH_CODES_PAD", "MH_FLAG_LANE_PAIRS", "MH_FLAG_NO_DELTA", "MHError", "lib", "BLOCK_DIM",
     "EncodedFrame", "Huffman", "block_grid", "decode_frame_cpu", "encode_frame", "merge_blocks", "split_blocks",
+    "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited",
 ]
 __version__ = "0.1.0"

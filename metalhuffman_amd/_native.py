@@ -16,6 +16,7 @@ MH_FLAG_NO_DELTA = 0x1
 MH_FLAG_LANE_PAIRS = 0x2  # lane-pair single-frame decode: diagnostic library only (diag_lanepairs())
 MH_FLAG_ANY_ORDER = 0x4  # the launch may overlap earlier work on the stream (caller guarantees independence)
 MH_ENCODE_WORKSPACE_ZEROED = 0x100  # the encoder workspace was zero-filled once (mh_encode_frame_device*)
+MH_ENCODE_LIMIT_LENGTHS = 0x200  # encoders only: a tree deeper than 16 gets package-merge lengths, not -3
 MH_CODES_PAD = 4
 MH_TABLE2_MAX_ENTRIES = 257 * 256
 MH_MAX_DIM = 65535
@@ -39,6 +40,7 @@ EXPORTS = (
     "mh_build_luts_device", "mh_decode_frames", "mh_decode_frames_shape",
     "mh_decode_headers", "mh_decode_headers_shape", "mh_header_luts_device",
     "mh_stream_create_headers", "mh_stream_submit_header", "mh_stream_slot_status",
+    "mh_code_lengths_limited",
 )
 
 
@@ -166,6 +168,7 @@ def lib() -> ctypes.CDLL:
         L.mh_stream_group_synchronize.argtypes = [_vp]
         L.mh_stream_group_destroy.argtypes = [_vp]
         L.mh_code_lengths.argtypes = [_u64p, _u8p]
+        L.mh_code_lengths_limited.argtypes = [_u64p, ctypes.c_uint32, _u8p]
         L.mh_container_header.argtypes = [ctypes.c_uint64, _u8p]
         L.mh_parse_container_header.argtypes = [_u8p, _u64p]
         L.mh_encode_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]

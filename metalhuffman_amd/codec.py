@@ -10,7 +10,8 @@ Differences from the reference, by design:
     stashing them (HuffmanUtil.cpp:87-102), and generateSplitLookupTables takes the
     canonical header explicitly;
   * errors raise MHError instead of assert() (e.g. a code deeper than 16 bits,
-    HuffmanEncoder.cpp:131);
+    HuffmanEncoder.cpp:131); encode_frame(limit_lengths=True) encodes such a frame
+    with the optimal code of at most 16 bits instead (code_lengths_limited);
   * the CPU decoders (decodeHuffmanBits*, decode_frame_cpu) are product code in the
     native library (csrc/mh_cpu.cpp, a threaded frame decoder for the reference's CPU
     path); the GPU decoder is the hot path. Neither calls the CPU restatement in
@@ -257,8 +258,25 @@ def merge_blocks(blocks: np.ndarray, width: int, height: int, block_dim: int = B
     return out
 
 
-def encode_frame(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False) -> EncodedFrame:
-    """The renderer's producer step (AAPLRenderer.m:374-688) for one 8-bit frame."""
+def code_lengths_limited(freq, max_bits: int = 16) -> np.ndarray:
+    """Code lengths (u8[256]) of at most `max_bits` bits from 256 symbol counts
+    (mh_code_lengths_limited): the reference tree's where they fit, otherwise the
+    optimal length-limited code (package-merge)."""
+    f = np.ascontiguousarray(freq, dtype=np.uint64)
+    if f.shape != (256,):
+        raise ValueError("freq must hold 256 counts")
+    lens = np.zeros(256, np.uint8)
+    N.check(N.lib().mh_code_lengths_limited(f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(max_bits),
+                                            _p(lens)), "code_lengths_limited")
+    return lens
+
+
+def encode_frame(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False,
+                 limit_lengths: bool = False) -> EncodedFrame:
+    """The renderer's producer step (AAPLRenderer.m:374-688) for one 8-bit frame.
+    limit_lengths: a frame whose Huffman tree is deeper than 16 gets the length-limited
+    code (MH_ENCODE_LIMIT_LENGTHS) instead of MHError -3; any other frame is unchanged.
+    The keyword reaches the encoder only, never the frame's `flags`."""
     gray = _u8(gray)
     if gray.ndim != 2:
         raise ValueError("expected a 2-D uint8 image")
@@ -271,7 +289,8 @@ def encode_frame(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False
     offs = np.zeros(nb, np.uint32)
     init = np.zeros(nb, np.uint8) if init_zero_delta else None
     ln = ctypes.c_uint64(0)
-    N.check(N.lib().mh_encode_frame(_p(gray), w, h, flags, _p(canon), _p(codes), cap, ctypes.byref(ln),
+    enc_flags = flags | (N.MH_ENCODE_LIMIT_LENGTHS if limit_lengths else 0)
+    N.check(N.lib().mh_encode_frame(_p(gray), w, h, enc_flags, _p(canon), _p(codes), cap, ctypes.byref(ln),
                                     _p(offs, _u32p), _p(init) if init is not None else None),
             "encode_frame")
     return EncodedFrame(w, h, canon, codes[: ln.value].copy(), offs, init, flags)

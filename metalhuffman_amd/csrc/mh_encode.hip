@@ -511,6 +511,86 @@ __device__ __forceinline__ uint32_t wait_table(const uint32_t *table, const uint
   return any_timeout ? 3u : any_bad ? 2u : 1u;
 }
 
+// MH_ENCODE_LIMIT_LENGTHS: the optimal code of at most 16 bits (package-merge in the form
+// that keeps only counts; the rule is in DESIGN.md, "Length-limited codes", and
+// mh_code_lengths_limited is its host twin, byte for byte) for a tree that came out
+// deeper. Called by all kTreeThreads threads (workgroup-uniform). lw: the n >= 2 leaf
+// weights sorted by (count, symbol). list_1 is the leaves; level l = 2..16 merges the
+// leaves with the pairs of list_{l-1}: leaf thread i binary-searches the pair sums
+// below its weight (a leaf goes first on a tie), thread 256 + j the leaves at or below
+// pair j, and each writes its weight at its merged place in the other list (the two
+// lists ping-pong; 64-bit weights as low and high words, < 2n <= 511 items, exact:
+// a package is below 16 x the symbol total). A leaf keeps its 15 package counts
+// (<= 255 each) in four registers, newest in the low byte. Backwards from t = 2n - 2:
+// leaf i is among the first t items of list_l iff i + its package count < t, a_l
+// counts those leaves (one counting barrier per level), t becomes 2 (t - a_l), and the
+// leaf of rank r gets length #{l : a_l > r}. Returns that length to thread r < n.
+__device__ __forceinline__ uint32_t limit_lengths16(const uint32_t *lw, uint32_t n, uint32_t *a_lo, uint32_t *a_hi,
+                                                    uint32_t *b_lo, uint32_t *b_hi) {
+  const uint32_t tid = threadIdx.x;
+  const bool leaf = tid < n;
+  const uint32_t w = leaf ? lw[tid] : 0u;
+  if (leaf) {
+    a_lo[tid] = w;
+    a_hi[tid] = 0;
+  }
+  uint32_t pb0 = 0, pb1 = 0, pb2 = 0, pb3 = 0;
+  uint32_t m = n;
+  uint32_t *plo = a_lo, *phi = a_hi, *qlo = b_lo, *qhi = b_hi;
+  __syncthreads();
+  for (uint32_t l = 2; l <= 16; ++l) {
+    const uint32_t np = m >> 1;  // pairs of list_{l-1}; a trailing odd item is dropped
+    const auto pair = [&](uint32_t j) {
+      return (((uint64_t)phi[2 * j] << 32) | plo[2 * j]) + (((uint64_t)phi[2 * j + 1] << 32) | plo[2 * j + 1]);
+    };
+    if (leaf) {
+      uint32_t lo = 0, hi = np;  // packages below this leaf
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pair(mid) < (uint64_t)w) lo = mid + 1;
+        else hi = mid;
+      }
+      pb3 = (pb3 << 8) | (pb2 >> 24);
+      pb2 = (pb2 << 8) | (pb1 >> 24);
+      pb1 = (pb1 << 8) | (pb0 >> 24);
+      pb0 = (pb0 << 8) | lo;
+      qlo[tid + lo] = w;  // tid + lo <= n - 1 + np <= 510
+      qhi[tid + lo] = 0;
+    } else if (tid >= 256u && tid - 256u < np) {
+      const uint32_t j = tid - 256u;
+      const uint64_t p = pair(j);
+      uint32_t lo = 0, hi = n;  // leaves at or below package j (they go first)
+      if (p >> 32) lo = n;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (lw[mid] <= (uint32_t)p) lo = mid + 1;
+        else hi = mid;
+      }
+      qlo[j + lo] = (uint32_t)p;  // j + lo <= np - 1 + n <= 510
+      qhi[j + lo] = (uint32_t)(p >> 32);
+    }
+    m = n + np;
+    uint32_t *t0 = plo, *t1 = phi;
+    plo = qlo;
+    phi = qhi;
+    qlo = t0;
+    qhi = t1;
+    __syncthreads();
+  }
+  uint32_t t = 2 * n - 2, len = 0;
+  for (uint32_t l = 16; l >= 2; --l) {
+    const uint32_t c = pb0 & 0xFFu;
+    pb0 = (pb0 >> 8) | (pb1 << 24);
+    pb1 = (pb1 >> 8) | (pb2 << 24);
+    pb2 = (pb2 >> 8) | (pb3 << 24);
+    pb3 >>= 8;
+    const uint32_t a = (uint32_t)__syncthreads_count(leaf && tid + c < t);
+    len += a > tid ? 1u : 0u;
+    t = 2 * (t - a);
+  }
+  return len + (t > tid ? 1u : 0u);  // list_1 is the leaves alone
+}
+
 // One 256-thread workgroup: the reference's Huffman tree (HuffmanEncoder.cpp:29-145)
 // from the 256 counts. The reference keeps every node in one array sorted by weight,
 // inserts at upper_bound (a new node goes after all nodes of equal weight) and merges
@@ -539,7 +619,7 @@ template <bool kFused>
 // histograms, which are left zeroed.
 __device__ __forceinline__ uint32_t tree_body(uint64_t *hist, uint8_t *canon_out, uint32_t *table, uint64_t *meta,
                                           uint64_t *codes_len_out, uint64_t codes_cap, int32_t *status,
-                                          uint64_t nsym, const uint32_t *counts = nullptr) {
+                                          uint64_t nsym, bool limit, const uint32_t *counts = nullptr) {
   constexpr uint32_t kEnd = 0xFFFFFFFFu;  // empty queue slot
   constexpr uint32_t kW32End = (1u << 22) - 1u;  // 32-bit merge keys: an empty slot's weight
   const bool k32 = nsym < (uint64_t)kW32End;
@@ -726,6 +806,13 @@ __device__ __forceinline__ uint32_t tree_body(uint64_t *hist, uint8_t *canon_out
     cur ^= 1;
     __syncthreads();
   }
+  uint32_t d = 0;  // the depth of leaf tid
+  if (n >= 2 && tid < n) d = s_par[cur][tid] == root ? s_dep[cur][tid] : 17u;
+  // MH_ENCODE_LIMIT_LENGTHS (uniform; the flag comes first, so a call without it meets no
+  // barrier here): a tree deeper than 16 gets the length-limited code, on all 16 waves;
+  // the lists take the parent and depth arrays, which are dead once d is read
+  if (limit && __syncthreads_or(d > 16))
+    d = limit_lengths16(s_lw, n, s_par[0], s_par[1], s_dep[0], s_dep[1]);
   // the rest needs one thread per symbol: the other 12 waves end here (a finished
   // wave no longer counts at the workgroup barriers below)
   if (!sym_thread) return 0u;
@@ -734,7 +821,6 @@ __device__ __forceinline__ uint32_t tree_body(uint64_t *hist, uint8_t *canon_out
   } else if (n == 1) {  // single symbol -> 1-bit code "0" (HuffmanEncoder.cpp:118-121)
     if (tid == 0) s_len[s_leaf_sym[0]] = 1;
   } else if (tid < n) {
-    const uint32_t d = s_par[cur][tid] == root ? s_dep[cur][tid] : 17u;
     if (d > 16) s_bad = (uint32_t)-MH_ERR_CODE_TOO_LONG;
     s_len[s_leaf_sym[tid]] = d;
   }
@@ -827,8 +913,9 @@ __device__ __forceinline__ uint32_t tree_body(uint64_t *hist, uint8_t *canon_out
 
 __global__ void __launch_bounds__(kTreeThreads) enc_tree_kernel(uint64_t *hist, uint8_t *canon_out,
                                                        uint32_t *table, uint64_t *meta, uint64_t *codes_len_out,
-                                                       uint64_t codes_cap, int32_t *status, uint64_t nsym) {
-  tree_body<false>(hist, canon_out, table, meta, codes_len_out, codes_cap, status, nsym);
+                                                       uint64_t codes_cap, int32_t *status, uint64_t nsym,
+                                                       uint32_t limit) {
+  tree_body<false>(hist, canon_out, table, meta, codes_len_out, codes_cap, status, nsym, limit != 0u);
 }
 
 // Block offsets, one kernel: each workgroup zeroes its share of the code words the
@@ -1222,11 +1309,11 @@ __global__ void __launch_bounds__(kCodeThreads, kCodeMinWaves) enc_code_kernel(u
                                                                 uint64_t codes_cap, int32_t *status,
                                                                 const Pixels px, const uint16_t *tile_hist,
                                                                 uint64_t nb, uint32_t ntiles, uint32_t *offsets,
-                                                                uint32_t *words) {
+                                                                uint32_t *words, uint32_t limit) {
   static_assert(kTreeThreads == kCodeThreads, "workgroup 0 runs the tree");
   if (blockIdx.x == 0) {
     MH_CODE_STAMP(0, 0)
-    tree_body<true>(hist, canon_out, table, meta, codes_len_out, codes_cap, status, nb * 64);
+    tree_body<true>(hist, canon_out, table, meta, codes_len_out, codes_cap, status, nb * 64, limit != 0u);
     MH_CODE_STAMP(0, 3)
     return;
   }
@@ -1249,7 +1336,7 @@ constexpr uint32_t kTileBatch = 16;  // tiles per wave and chunk of the tile-off
 __global__ void __launch_bounds__(kTreeThreads) enc_tree_batch_kernel(
     uint64_t *hist, uint8_t *canon, uint32_t *table, uint64_t *meta, uint64_t *codes_len, uint64_t codes_cap,
     int32_t *status, uint64_t nb, const uint16_t *tile_hist, uint32_t ncode, uint32_t *tile_off,
-    uint64_t *frame_off, uint32_t f0, uint32_t n_frames) {
+    uint64_t *frame_off, uint32_t f0, uint32_t n_frames, uint32_t limit) {
   // f0: this launch's first frame of the call (its pointers start there; frame_off is
   // the call's, indexed by call frame)
   const uint32_t f = blockIdx.x, tid = threadIdx.x;
@@ -1298,7 +1385,7 @@ __global__ void __launch_bounds__(kTreeThreads) enc_tree_batch_kernel(
   }
   const uint32_t e = tree_body<false>(nullptr, canon + (uint64_t)f * 256, table + (uint64_t)f * 256,
                                       meta + (uint64_t)f * kMetaWords, codes_len ? codes_len + f : nullptr,
-                                      codes_cap, status ? status + f : nullptr, nb * 64, s_cnt);
+                                      codes_cap, status ? status + f : nullptr, nb * 64, limit != 0u, s_cnt);
   if (tid >= 256) return;  // tree_body leaves the 256 symbol threads (4 waves)
   __shared__ uint32_t s_len[256], s_chunk[4 * kTileBatch];
   static_assert(4 * kTileBatch == 64, "one chunk total per lane of wave 0");
@@ -1677,7 +1764,7 @@ int mh_encode_frame_device_async(const uint8_t *d_gray, uint32_t width, uint32_t
                                  int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
   if (!d_gray || !d_canon_header || !d_codes || !d_block_offsets || !d_workspace)
     return MH_ERR_INVALID_ARG;
-  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED)) return MH_ERR_INVALID_ARG;
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
   if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
   if (((uintptr_t)d_codes & 3u) || ((uintptr_t)d_workspace & 255u)) return MH_ERR_ALIGN;
   const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
@@ -1702,7 +1789,8 @@ int mh_encode_frame_device_async(const uint8_t *d_gray, uint32_t width, uint32_t
   const size_t state_bytes = align256(kHistParts * 256 * 8) + align256(256 * 4) + kGen * 8;
   if (!(flags & MH_ENCODE_WORKSPACE_ZEROED) && hipMemsetAsync(w.hist, 0, state_bytes, s) != hipSuccess)
     return MH_ERR_HIP;
-  flags &= ~MH_ENCODE_WORKSPACE_ZEROED;
+  const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;  // the tree kernels' own argument
+  flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
   const uint32_t vec = (width % 8 == 0 && ((uintptr_t)d_gray & 7u) == 0) ? 1u : 0u;
   const int path = encode_kernels();
   if (ncode <= kFusedMaxTiles && path == 2) {
@@ -1713,14 +1801,14 @@ int mh_encode_frame_device_async(const uint8_t *d_gray, uint32_t width, uint32_t
     const Pixels px{d_gray, width, height, bw, vec, !(flags & MH_FLAG_NO_DELTA), d_block_init != nullptr};
     hipLaunchKernelGGL(enc_code_kernel, dim3((uint32_t)ncode + 1), dim3(kCodeThreads), 0, s, w.hist,
                        d_canon_header, w.table, w.meta, d_codes_len, codes_cap, d_status, px, w.tile_hist, nb,
-                       (uint32_t)ncode, d_block_offsets, reinterpret_cast<uint32_t *>(d_codes));
+                       (uint32_t)ncode, d_block_offsets, reinterpret_cast<uint32_t *>(d_codes), limit);
     return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
   }
   const uint32_t gsplit = (uint32_t)std::min<uint64_t>((nb + 31) / 32, kSplitWgs);
   hipLaunchKernelGGL((vec ? enc_split_kernel<true, false> : enc_split_kernel<false, false>), dim3(gsplit), dim3(256), 0,
                      s, d_gray, width, height, bw, nb, flags, w.sym, d_block_init, w.hist, nullptr, w.meta, 0u, 0ull, nullptr);
   hipLaunchKernelGGL(enc_tree_kernel, dim3(1), dim3(kTreeThreads), 0, s, w.hist, d_canon_header, w.table, w.meta,
-                     d_codes_len, codes_cap, d_status, nb * 64);
+                     d_codes_len, codes_cap, d_status, nb * 64, limit);
   hipLaunchKernelGGL(enc_scan_kernel, dim3((uint32_t)ntiles), dim3(kScanTile), 0, s, w.sym, w.table, nb, w.blen,
                      w.tsum, w.meta, reinterpret_cast<uint32_t *>(d_codes));
   hipLaunchKernelGGL(enc_pack_kernel, dim3((uint32_t)((nb + kPackBlocks - 1) / kPackBlocks)), dim3(256), 0, s, w.sym, w.table, w.blen, w.tsum, nb,
@@ -1767,7 +1855,7 @@ int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_str
                                   int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
   if (!d_gray || !d_canon_headers || !d_codes || !d_block_offsets || !d_workspace || !n_frames)
     return MH_ERR_INVALID_ARG;
-  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED)) return MH_ERR_INVALID_ARG;
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
   if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
   if (((uintptr_t)d_codes & 15u) || (codes_frame_stride & 15u) || ((uintptr_t)d_workspace & 255u))
     return MH_ERR_ALIGN;
@@ -1782,7 +1870,8 @@ int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_str
   hipStream_t s = (hipStream_t)stream;
   // every part of the workspace is written before it is read within the call (the tile
   // counts by the split, the tables and tile offsets by the trees): nothing to clear
-  flags &= ~MH_ENCODE_WORKSPACE_ZEROED;
+  const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;  // the tree kernels' own argument
+  flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
   const uint32_t vec = (width % 8 == 0 && ((uintptr_t)d_gray & 7u) == 0 && (gray_frame_stride & 7u) == 0) ? 1u : 0u;
   const Pixels px0{d_gray, width, height, bw, vec, !(flags & MH_FLAG_NO_DELTA), d_block_init != nullptr};
   // frames [f0, f0 + m): split, trees, packing on stream st
@@ -1804,7 +1893,7 @@ int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_str
     hipLaunchKernelGGL(enc_tree_batch_kernel, dim3(m), dim3(kTreeThreads), 0, st, nullptr,
                        d_canon_headers + (uint64_t)f0 * 256, table, meta, d_codes_len ? d_codes_len + f0 : nullptr,
                        codes_frame_stride, d_status ? d_status + f0 : nullptr, nb, th, (uint32_t)ncode, to,
-                       d_frame_code_offsets, f0, n_frames);
+                       d_frame_code_offsets, f0, n_frames, limit);
     Pixels px = px0;
     px.gray = gray;
     const uint32_t ncode_wg = (uint32_t)((ncode + kPackWaves - 1) / kPackWaves);

@@ -71,6 +71,58 @@ int code_lengths(const uint64_t freq[256], uint8_t lens[256]) {
   return too_long ? MH_ERR_CODE_TOO_LONG : MH_OK;
 }
 
+// Optimal code lengths of at most L bits (package-merge, the form that keeps only
+// counts; DESIGN.md "Length-limited codes" states the rule). Leaves are the n >= 2
+// present symbols sorted by (count, symbol); list_1 is the leaves; list_l is the merge
+// of the leaves with the pairs of list_{l-1} (a trailing odd item dropped), the leaf
+// first on equal weight. Backwards from t = 2n - 2 items of list_L, a_l is the number
+// of leaves among the first t items of list_l and t becomes 2 (t - a_l); the leaf of
+// rank r gets length #{l : a_l > r}. Weights are exact: a package is below L x the
+// total, and the caller bounds the total by 2^59. Needs 2^L >= n.
+void limited_lengths(const uint64_t freq[256], uint32_t L, uint8_t lens[256]) {
+  std::memset(lens, 0, 256);
+  int leaf_symbol[256];
+  uint64_t lw[256];
+  uint32_t n = 0;
+  for (int s = 0; s < 256; ++s)
+    if (freq[s]) leaf_symbol[n++] = s;
+  std::stable_sort(leaf_symbol, leaf_symbol + n, [&](int a, int b) { return freq[a] < freq[b]; });
+  for (uint32_t i = 0; i < n; ++i) lw[i] = freq[leaf_symbol[i]];
+  // per level: which items of the merged list are leaves (a list has < 2n items)
+  std::vector<uint8_t> is_leaf((size_t)(L + 1) * 512, 0);
+  uint64_t list[2][512];
+  uint32_t m = n, cur = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    list[0][i] = lw[i];
+    is_leaf[512 + i] = 1;
+  }
+  for (uint32_t l = 2; l <= L; ++l) {
+    const uint64_t *prev = list[cur];
+    uint64_t *next = list[cur ^ 1];
+    const uint32_t np = m / 2;
+    uint32_t i = 0, j = 0, k = 0;
+    while (i < n || j < np) {
+      const uint64_t p = j < np ? prev[2 * j] + prev[2 * j + 1] : 0;
+      if (i < n && (j >= np || lw[i] <= p)) {
+        is_leaf[(size_t)l * 512 + k] = 1;
+        next[k++] = lw[i++];
+      } else {
+        next[k++] = p;
+        ++j;
+      }
+    }
+    m = k;
+    cur ^= 1;
+  }
+  uint32_t t = 2 * n - 2;
+  for (uint32_t l = L; l >= 1; --l) {
+    uint32_t a = 0;
+    for (uint32_t k = 0; k < t; ++k) a += is_leaf[(size_t)l * 512 + k];
+    for (uint32_t r = 0; r < a; ++r) ++lens[leaf_symbol[r]];
+    t = 2 * (t - a);
+  }
+}
+
 // huff_util.hpp:94-193: canonical order = (length, symbol); codes count up
 // and are shifted left whenever the length grows; stored left-justified.
 void canonical_codes(const uint8_t lens[256], uint16_t codes[256]) {
@@ -115,10 +167,16 @@ struct BitWriter {
 };
 
 int encode_symbols(const uint8_t *sym, uint64_t n, uint64_t stride, uint8_t canon[256],
-                   uint8_t *codes, uint64_t codes_cap, uint64_t *codes_len, uint32_t *offsets) {
+                   uint8_t *codes, uint64_t codes_cap, uint64_t *codes_len, uint32_t *offsets,
+                   bool limit = false) {
   uint64_t freq[256] = {0};
   for (uint64_t i = 0; i < n; ++i) freq[sym[i]]++;
   int rc = code_lengths(freq, canon);
+  // MH_ENCODE_LIMIT_LENGTHS: only a tree deeper than 16 is replaced (n < 2^59 symbols)
+  if (rc == MH_ERR_CODE_TOO_LONG && limit && n < (1ull << 59)) {
+    limited_lengths(freq, 16, canon);
+    rc = MH_OK;
+  }
   if (rc != MH_OK) return rc;
   uint16_t cc[256];
   canonical_codes(canon, cc);
@@ -247,7 +305,7 @@ int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32
   }
   if (codes_cap < 2) return MH_ERR_CAPACITY;
   rc = encode_symbols(blocks.data(), blocks.size(), 64, canon_header, codes, codes_cap - 2,
-                      codes_len, block_offsets);
+                      codes_len, block_offsets, (flags & MH_ENCODE_LIMIT_LENGTHS) != 0);
   if (rc != MH_OK) return rc;
   codes[*codes_len] = 0;  // renderer read-ahead (AAPLRenderer.m:576-585)
   codes[*codes_len + 1] = 0;
@@ -277,6 +335,27 @@ int mh_parse_container_header(const uint8_t header[MH_CONTAINER_HEADER_BYTES], u
 int mh_code_lengths(const uint64_t freq[256], uint8_t canon_header[256]) {
   if (!freq || !canon_header) return MH_ERR_INVALID_ARG;
   return code_lengths(freq, canon_header);
+}
+
+int mh_code_lengths_limited(const uint64_t freq[256], uint32_t max_bits, uint8_t canon_header[256]) {
+  if (!freq || !canon_header || max_bits < 1 || max_bits > 16) return MH_ERR_INVALID_ARG;
+  uint64_t total = 0;
+  uint32_t n = 0;
+  for (int s = 0; s < 256; ++s) {
+    if (freq[s] >= (1ull << 59)) return MH_ERR_INVALID_ARG;
+    total += freq[s];  // below 2^60: no wrap
+    if (total >= (1ull << 59)) return MH_ERR_INVALID_ARG;
+    n += freq[s] != 0;
+  }
+  if (n > (1u << max_bits)) return MH_ERR_INVALID_ARG;
+  const int rc = code_lengths(freq, canon_header);
+  if (rc == MH_ERR_EMPTY || n == 1) return rc;
+  for (int s = 0; s < 256; ++s)
+    if (canon_header[s] > max_bits) {
+      limited_lengths(freq, max_bits, canon_header);
+      break;
+    }
+  return MH_OK;
 }
 
 int mh_canonical_codes(const uint8_t canon_header[256], uint16_t codes[256]) {

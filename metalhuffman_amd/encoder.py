@@ -21,6 +21,10 @@ from .codec import block_grid
 from .decoder import DeviceFrames, _dev, _stream_ptr
 
 
+def _limit(limit_lengths: bool) -> int:
+    return N.MH_ENCODE_LIMIT_LENGTHS if limit_lengths else 0
+
+
 @dataclasses.dataclass
 class DeviceEncodedFrame:
     width: int
@@ -58,7 +62,10 @@ class Encoder:
         self.cap = (self.nb * 64 * 2 + N.MH_CODES_PAD + 3) // 4 * 4 + 16
 
     def encode(self, gray: torch.Tensor, flags: int = 0, init_zero_delta: bool = False,
-               stream: Optional[torch.cuda.Stream] = None) -> DeviceEncodedFrame:
+               stream: Optional[torch.cuda.Stream] = None, limit_lengths: bool = False) -> DeviceEncodedFrame:
+        """limit_lengths (here and in encode_async): a tree deeper than 16 gets the
+        length-limited code on the device (MH_ENCODE_LIMIT_LENGTHS) instead of status -3.
+        The keyword goes to the encoder only, never into the frame's `flags`."""
         if gray.dtype != torch.uint8 or gray.shape != (self.height, self.width) or not gray.is_contiguous():
             raise ValueError(f"gray must be contiguous uint8 [{self.height}, {self.width}]")
         gray = gray.to(self.device)
@@ -70,7 +77,7 @@ class Encoder:
         base = self.workspace.data_ptr()
         aligned = (base + 255) // 256 * 256
         N.check(N.lib().mh_encode_frame_device(
-            gray.data_ptr(), self.width, self.height, flags | N.MH_ENCODE_WORKSPACE_ZEROED,
+            gray.data_ptr(), self.width, self.height, flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
             canon.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), codes.data_ptr(), self.cap,
             ctypes.byref(n), offs.data_ptr(), init.data_ptr() if init is not None else None,
             aligned, self.workspace.numel() - (aligned - base), _stream_ptr(stream, self.device)),
@@ -79,7 +86,7 @@ class Encoder:
 
     def encode_async(self, gray: torch.Tensor, flags: int = 0, init_zero_delta: bool = False,
                      stream: Optional[torch.cuda.Stream] = None,
-                     codes: Optional[torch.Tensor] = None) -> AsyncEncodedFrame:
+                     codes: Optional[torch.Tensor] = None, limit_lengths: bool = False) -> AsyncEncodedFrame:
         """Enqueue the encode on `stream` (default: the current stream) and return
         at once. `gray` must be ready on that stream (make it wait on the stream
         that produced the frame). `codes` may be a reused u8 buffer of at least the
@@ -102,7 +109,7 @@ class Encoder:
         base = self.workspace.data_ptr()
         aligned = (base + 255) // 256 * 256
         N.check(N.lib().mh_encode_frame_device_async(
-            gray.data_ptr(), self.width, self.height, flags | N.MH_ENCODE_WORKSPACE_ZEROED,
+            gray.data_ptr(), self.width, self.height, flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
             canon.data_ptr(), codes.data_ptr(),
             codes.numel(), meta.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None,
             meta.data_ptr() + 8, aligned, self.workspace.numel() - (aligned - base),
@@ -164,8 +171,10 @@ class BatchEncoder:
         self.slot = (self.nb * 64 * 2 + N.MH_CODES_PAD + 15) // 16 * 16 + 16
 
     def encode_async(self, grays: torch.Tensor, flags: int = 0, init_zero_delta: bool = False,
-                     stream: Optional[torch.cuda.Stream] = None) -> "AsyncEncodedBatch":
-        """grays: contiguous uint8 [n, H, W] on the encoder's device, ready on `stream`."""
+                     stream: Optional[torch.cuda.Stream] = None, limit_lengths: bool = False) -> "AsyncEncodedBatch":
+        """grays: contiguous uint8 [n, H, W] on the encoder's device, ready on `stream`.
+        limit_lengths: frames whose tree is deeper than 16 get the length-limited code
+        (MH_ENCODE_LIMIT_LENGTHS) instead of status -3; the batch's `flags` do not carry it."""
         if (grays.dtype != torch.uint8 or tuple(grays.shape) != (self.n, self.height, self.width)
                 or not grays.is_contiguous()):
             raise ValueError(f"grays must be contiguous uint8 [{self.n}, {self.height}, {self.width}]")
@@ -185,7 +194,7 @@ class BatchEncoder:
         aligned = (base + 255) // 256 * 256
         N.check(N.lib().mh_encode_frames_device_async(
             grays.data_ptr(), self.height * self.width, n, self.width, self.height,
-            flags | N.MH_ENCODE_WORKSPACE_ZEROED, canon.data_ptr(), cbase, self.slot, lens.data_ptr(),
+            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths), canon.data_ptr(), cbase, self.slot, lens.data_ptr(),
             fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None, status.data_ptr(),
             aligned, self.workspace.numel() - (aligned - base), _stream_ptr(stream, self.device)),
             "mh_encode_frames_device_async")
@@ -268,7 +277,8 @@ class AsyncEncodedBatch:
                                   self.block_offsets[f * nb:(f + 1) * nb], init, self.flags)
 
 
-def encode_frame_device(gray: torch.Tensor, flags: int = 0, init_zero_delta: bool = False) -> DeviceEncodedFrame:
+def encode_frame_device(gray: torch.Tensor, flags: int = 0, init_zero_delta: bool = False,
+                        limit_lengths: bool = False) -> DeviceEncodedFrame:
     """One-shot GPU encode of a [H, W] uint8 device tensor."""
     h, w = gray.shape
-    return Encoder(w, h, gray.device).encode(gray, flags, init_zero_delta)
+    return Encoder(w, h, gray.device).encode(gray, flags, init_zero_delta, limit_lengths=limit_lengths)
