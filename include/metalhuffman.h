@@ -261,6 +261,51 @@ int mh_decode_headers(const mh_frame *frame, const uint8_t *d_canon_headers,
 int mh_decode_headers_shape(const mh_frame *frame, void *stream, uint32_t *groups_per_frame,
                             uint32_t *waves_per_group);
 
+/* ---------------------------------------------------------------------- */
+/* A block-aligned region of every frame in one launch. Every block has its own bit offset,  */
+/* so the blocks [bx0, bx0 + bw) x [by0, by0 + bh) of the frame's 8x8 grid decode without the */
+/* rest of the frame and without a full-size raster: a window of a large scan, a pan of it,   */
+/* the same crop of every frame of a sequence. Not covered: regions for mh_decode_headers,    */
+/* the streams, the multi-GPU paths and mh_check; pixel-granular stores (a region is whole    */
+/* blocks; the caller views its rectangle inside the region's raster); a CPU twin; packing    */
+/* several rows of a region narrower than 64 blocks into one wave (lane utilisation is        */
+/* bw / (64 ceil(bw / 64))).                                                                  */
+typedef struct {
+  uint32_t bx0, by0, bw, bh; /* in 8x8 blocks of the frame's grid */
+} mh_region;
+
+/* mh_decode_frames for the region's blocks only. The region's pixel size is
+ *   RW = min(W, 8 (bx0 + bw)) - 8 bx0,  RH = min(H, 8 (by0 + bh)) - 8 by0.
+ * Output: frame f, region row y starts at d_out + f * out_frame_stride + y * out_pitch; 8 bw
+ * (= round_up(RW, 8)) bytes of every row y < RH are written; the rest of the pitch and rows
+ * >= RH are not touched. The written bytes equal the same bytes of the rectangle at
+ * (8 bx0, 8 by0) of the raster mh_decode_frames writes for that frame; for the region
+ * {0, 0, block_width, block_height} the two outputs are byte-identical.
+ * Tables: frame f decodes with the prepared table d_luts + f * lut_stride_bytes (from
+ * mh_prepare_lut, mh_build_tables_device or mh_build_luts_device). lut_stride_bytes == 0: one
+ * table shared by all frames (one scan, one table, many windows); any other stride is a
+ * multiple of 16 and >= mh_lut_bytes(). frame->d_table1 / d_table2 / table2_entries / d_lut are
+ * ignored. d_frame_status as in mh_decode_frames: a non-zero word means no byte of that frame's
+ * region raster is written. d_block_init works as elsewhere, indexed by the frame's block number.
+ * Checks: all before any HIP call, in mh_decode_frames' order and with its codes, RW / RH in the
+ * place of W / H in the pitch and frame stride rules (out_pitch >= RW, out_frame_stride >=
+ * out_pitch * RH); and NULL region -> MH_ERR_INVALID_ARG; bw == 0, bh == 0, bx0 + bw >
+ * block_width or by0 + bh > block_height (computed without wrapping) -> MH_ERR_DIMS, with the
+ * frame's dims; more than 2^31 - 1 tiles or workgroups -> MH_ERR_CAPACITY. flags:
+ * MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER only.
+ * One kernel launch, asynchronous on `stream`: a tile is a run of <= 64 consecutive blocks
+ * inside one block row of the region (S = ceil(bw / 64) per row, bh * S per frame), and the
+ * launch is n_frames * G workgroups of 8 waves, G = clamp(ceil(R / n_frames), 1,
+ * ceil(bh * S / 8)), R the workgroups of this kernel resident on the device at once. */
+int mh_decode_region(const mh_frame *frame, const mh_region *region, const uint16_t *d_luts,
+                     uint64_t lut_stride_bytes, const int32_t *d_frame_status, uint8_t *d_out,
+                     size_t out_pitch, size_t out_frame_stride, void *stream);
+
+/* The launch shape mh_decode_region would use on `stream`'s device (no launch): workgroups per
+ * frame (G above) and waves per workgroup. For tests and tools. */
+int mh_decode_region_shape(const mh_frame *frame, const mh_region *region, void *stream,
+                           uint32_t *groups_per_frame, uint32_t *waves_per_group);
+
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a
  * prepared table) and the 16-byte lengths word at their prepared-table offsets in

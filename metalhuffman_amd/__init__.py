@@ -10,6 +10,7 @@ of mdejong/MetalHuffman).
   * decoder.DeviceTables            T1/T2 + prepared table (uploaded, or built on the device)
   * decoder.decode_frames / DeviceTableSet   a batch with a table per frame, one launch
   * decoder.decode_headers          the same batch straight from its canonical headers (table built in-kernel)
+  * decoder.decode_region / decode_rect   a block-aligned region (a pixel rectangle) of every frame, one launch
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync

@@ -41,6 +41,7 @@ EXPORTS = (
     "mh_decode_headers", "mh_decode_headers_shape", "mh_header_luts_device",
     "mh_stream_create_headers", "mh_stream_submit_header", "mh_stream_slot_status",
     "mh_code_lengths_limited",
+    "mh_decode_region", "mh_decode_region_shape",
 )
 
 
@@ -71,6 +72,11 @@ class mh_frame(ctypes.Structure):
         ("n_frames", ctypes.c_uint32),
         ("flags", ctypes.c_uint32),
     ]
+
+
+class mh_region(ctypes.Structure):
+    _fields_ = [("bx0", ctypes.c_uint32), ("by0", ctypes.c_uint32), ("bw", ctypes.c_uint32),
+                ("bh", ctypes.c_uint32)]
 
 
 _lib = None
@@ -138,6 +144,9 @@ def lib() -> ctypes.CDLL:
         L.mh_decode_headers.argtypes = [ctypes.POINTER(mh_frame), _vp, _vp, _vp, _vp, ctypes.c_size_t,
                                         ctypes.c_size_t, _vp]
         L.mh_decode_headers_shape.argtypes = [ctypes.POINTER(mh_frame), _vp, _u32p, _u32p]
+        L.mh_decode_region.argtypes = [ctypes.POINTER(mh_frame), ctypes.POINTER(mh_region), _vp, ctypes.c_uint64, _vp,
+                                       _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
+        L.mh_decode_region_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.POINTER(mh_region), _vp, _u32p, _u32p]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]
         L.mh_stream_create_headers.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint64, ctypes.c_uint32,
                                                ctypes.POINTER(_vp), ctypes.POINTER(_vp)]

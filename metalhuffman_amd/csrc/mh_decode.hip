@@ -546,24 +546,68 @@ __device__ __forceinline__ uint32_t frame_of(const DecodeArgs &a, uint32_t tile)
   return tile / a.tiles_per_frame;
 }
 
-struct TileHdr {
+// Tile -> blocks: the mapping policy of the helpers below (a type, and for a region an object).
+// FrameMap, the default: tile t of a frame is blocks [64 t, 64 t + 64) of the frame in block
+//   order; tiles count through the batch (frame_of) and the last tile of a frame may be short.
+// RegionMap (mh_decode_region): a tile is a run of <= 64 consecutive blocks inside ONE block row
+//   of the region [bx0, bx0 + bw) x [by0, by0 + bh): S = ceil(bw / 64) tiles per row, tile t =
+//   (row r = t / S, segment s = t - r S), first block (by0 + r) * a.bw + bx0 + 64 s of the frame,
+//   min(64, bw - 64 s) live lanes, stored at region row 8 r, byte 8 (64 s + lane). Tiles are
+//   relative to the workgroup's frame `f` (a.total_tiles == a.tiles_per_frame == bh * S), and
+//   a.bw / a.nb stay the FRAME's: offsets and block_init are indexed by the frame's block number.
+struct FrameMap {
+  static constexpr bool kRegion = false;
+};
+struct RegionMap {
+  static constexpr bool kRegion = true;
+  uint32_t f, bx0, by0, bw, S;
+};
+
+struct TileHdrBase {
   uint32_t tile;      // wave-uniform; >= total_tiles: no tile
   uint32_t off;       // this lane's block start bit
   uint32_t nxt;       // next block's start bit (this lane's block end)
   uint32_t fo_lo, fo_hi;  // lanes 0/1: frame_off[f], frame_off[f+1]
   uint32_t init;      // per-block initial prev (block_init) or 0
 };
+// ... and what a map adds to it (FrameMap: nothing)
+template <class Map>
+struct TileHdrOf : TileHdrBase {};
+template <>
+struct TileHdrOf<RegionMap> : TileHdrBase {
+  uint32_t r, s;      // the tile's region row and segment (wave-uniform)
+};
+using TileHdr = TileHdrOf<FrameMap>;
 
+// tile -> (r, s). One segment per row skips the division (a uniform branch), as frame_of does
+// for one frame: it sits ahead of the wave's first HBM load.
+__device__ __forceinline__ void region_rs(const RegionMap &m, uint32_t tile, uint32_t &r, uint32_t &s) {
+  r = tile;
+  s = 0u;
+  if (m.S != 1u) {
+    r = tile / m.S;
+    s = tile - r * m.S;
+  }
+}
+
+template <class Map = FrameMap>
 __device__ __forceinline__ void hdr_issue(const DecodeArgs &a, uint32_t tile, uint32_t lane,
-                                          TileHdr &h) {
+                                          TileHdrOf<Map> &h, const Map &m = Map()) {
   // Branch-free: absent arrays (frame_off / block_init == NULL) get descriptors
   // with zero records, whose loads return 0 without touching memory; a past-the-end
   // tile reads through zero-record descriptors too. Unconditional loads keep the
   // compiler from waiting on the span prefetch to re-zero these registers.
   tile = __builtin_amdgcn_readfirstlane(tile);
   const bool live = tile < a.total_tiles;
-  const uint32_t f = live ? frame_of(a, tile) : 0u;
-  const uint32_t b = (live ? (tile - f * a.tiles_per_frame) * 64u : 0u) + lane;
+  uint32_t f, b;
+  if constexpr (Map::kRegion) {
+    region_rs(m, tile, h.r, h.s);
+    f = m.f;
+    b = (live ? (m.by0 + h.r) * a.bw + m.bx0 + 64u * h.s : 0u) + lane;
+  } else {
+    f = live ? frame_of(a, tile) : 0u;
+    b = (live ? (tile - f * a.tiles_per_frame) * 64u : 0u) + lane;
+  }
   h.tile = tile;
   const __amdgpu_buffer_rsrc_t ro = uniform_rsrc(a.offsets + (uint64_t)f * a.nb, live ? a.nb * 4u : 0u);
   h.off = __builtin_amdgcn_raw_buffer_load_b32(ro, (int)(b * 4u), 0, 0);
@@ -582,7 +626,7 @@ __device__ __forceinline__ void hdr_issue(const DecodeArgs &a, uint32_t tile, ui
 }
 
 // Everything derived from a header once its loads have landed.
-struct Tile {
+struct TileBase {
   uint32_t tile, f, b0;
   bool valid;          // this lane holds a block
   uint32_t p;          // lane's start bit relative to the staged span
@@ -593,14 +637,36 @@ struct Tile {
   uint32_t init;
   uint32_t span_end_bits;  // end bit of the tile's last block (frame relative)
 };
+template <class Map>
+struct TileOf : TileBase {};
+template <>
+struct TileOf<RegionMap> : TileBase {
+  uint32_t r, s, n;    // region row, segment, blocks in the run (1..64)
+};
+using Tile = TileOf<FrameMap>;
 
-__device__ __forceinline__ Tile hdr_resolve(const DecodeArgs &a, const TileHdr &h, uint32_t lane) {
-  Tile t;
+template <class Map = FrameMap>
+__device__ __forceinline__ TileOf<Map> hdr_resolve(const DecodeArgs &a, const TileHdrOf<Map> &h, uint32_t lane,
+                                                   const Map &m = Map()) {
+  TileOf<Map> t;
   t.tile = h.tile;
-  t.f = frame_of(a, h.tile);
-  t.b0 = (h.tile - t.f * a.tiles_per_frame) * 64u;
+  if constexpr (Map::kRegion) {
+    t.f = m.f;
+    t.r = h.r;
+    t.s = h.s;
+    t.n = min(64u, m.bw - 64u * h.s);
+    t.b0 = (m.by0 + h.r) * a.bw + m.bx0 + 64u * h.s;
+  } else {
+    t.f = frame_of(a, h.tile);
+    t.b0 = (h.tile - t.f * a.tiles_per_frame) * 64u;
+  }
   const uint32_t b = t.b0 + lane;
-  t.valid = b < a.nb;
+  // a region's lanes past the run are dead even where the frame has a block: those are real
+  // blocks to the right of the region
+  if constexpr (Map::kRegion)
+    t.valid = lane < t.n;
+  else
+    t.valid = b < a.nb;
   uint64_t fbytes = a.codes_bytes;
   t.fbeg = 0;
   if (a.frame_off) {
@@ -618,8 +684,13 @@ __device__ __forceinline__ Tile hdr_resolve(const DecodeArgs &a, const TileHdr &
   // The sum wraps for a last block at or above bit 2^32 - 1024: the end then lies below the
   // tile's start, so the span below is "unknown" and the tile takes decode_halves, whose
   // (end - start) wraps again to a whole window from the half's own start.
+  // (a region's run ends at the next block's offset too, though that block lies outside it)
   const uint32_t end_l = (b + 1u < a.nb) ? h.nxt : min(fbits, h.off + 64u * 16u);
-  const uint32_t last = min(63u, a.nb - 1u - t.b0);  // last lane holding a block
+  uint32_t last;  // last lane holding a block
+  if constexpr (Map::kRegion)
+    last = t.n - 1u;
+  else
+    last = min(63u, a.nb - 1u - t.b0);
   const uint32_t sb = __builtin_amdgcn_readfirstlane(h.off);
   const uint32_t eb = __builtin_amdgcn_readlane(end_l, last);
   t.span_end_bits = eb;
@@ -636,7 +707,7 @@ __device__ __forceinline__ Tile hdr_resolve(const DecodeArgs &a, const TileHdr &
   return t;
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t codes_rsrc(const DecodeArgs &a, const Tile &t) {
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t codes_rsrc(const DecodeArgs &a, const TileBase &t) {
   return uniform_rsrc(a.codes + t.fbeg, t.fb32);
 }
 
@@ -648,20 +719,32 @@ struct OutTile {
   __amdgpu_buffer_rsrc_t rsrc;
   uint32_t row0;
 };
-__device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const Tile &t, uint32_t lane) {
-  const uint32_t b = t.b0 + lane;
-  const uint32_t bx = b % a.bw, by = b / a.bw;
-  const uint32_t by0 = __builtin_amdgcn_readfirstlane(t.b0 / a.bw);
-  const uint64_t base = (uint64_t)by0 * 8u * a.out_pitch;
-  const uint64_t rem = a.out_frame_bytes > base ? a.out_frame_bytes - base : 0u;
-  OutTile o;
-  o.rsrc = uniform_rsrc(a.out + (uint64_t)t.f * a.out_frame_stride + base,
-                        (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
-  o.row0 = (by - by0) * 8u * (uint32_t)a.out_pitch + bx * 8u;
-  return o;
+template <class Map = FrameMap>
+__device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane) {
+  if constexpr (Map::kRegion) {
+    // based at region row 8 r and limited by RH * pitch (a.out_frame_bytes): rows >= RH are dropped
+    const uint64_t base = (uint64_t)t.r * 8u * a.out_pitch;
+    const uint64_t rem = a.out_frame_bytes > base ? a.out_frame_bytes - base : 0u;
+    OutTile o;
+    o.rsrc = uniform_rsrc(a.out + (uint64_t)t.f * a.out_frame_stride + base,
+                          (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
+    o.row0 = (64u * t.s + lane) * 8u;
+    return o;
+  } else {
+    const uint32_t b = t.b0 + lane;
+    const uint32_t bx = b % a.bw, by = b / a.bw;
+    const uint32_t by0 = __builtin_amdgcn_readfirstlane(t.b0 / a.bw);
+    const uint64_t base = (uint64_t)by0 * 8u * a.out_pitch;
+    const uint64_t rem = a.out_frame_bytes > base ? a.out_frame_bytes - base : 0u;
+    OutTile o;
+    o.rsrc = uniform_rsrc(a.out + (uint64_t)t.f * a.out_frame_stride + base,
+                          (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
+    o.row0 = (by - by0) * 8u * (uint32_t)a.out_pitch + bx * 8u;
+    return o;
+  }
 }
 
-__device__ __forceinline__ void span_issue(const DecodeArgs &a, const Tile &t, uint32_t lane,
+__device__ __forceinline__ void span_issue(const DecodeArgs &a, const TileBase &t, uint32_t lane,
                                            v4u32 (&R)[kStageChunks], bool on = true) {
   // Unconditional loads (no exec-masked branches, so the compiler can count them
   // in vmcnt); chunks past the span use an offset outside the descriptor's range,
@@ -679,7 +762,7 @@ __device__ __forceinline__ void span_issue(const DecodeArgs &a, const Tile &t, u
 }
 
 template <bool kSwz = false>
-__device__ __forceinline__ void span_write(const Tile &t, uint32_t lane, const v4u32 (&R)[kStageChunks],
+__device__ __forceinline__ void span_write(const TileBase &t, uint32_t lane, const v4u32 (&R)[kStageChunks],
                                            uint8_t *stage) {
 #pragma unroll
   for (int k = 0; k < kStageChunks; ++k) {
@@ -711,8 +794,8 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 // Oversize tile: stage + decode lanes [0,32) then [32,64), each from its own span.
-template <bool kDelta, class Cfg>
-__device__ __forceinline__ void decode_halves(const DecodeArgs &a, const Tile &t, uint32_t lane,
+template <bool kDelta, class Cfg, class Map = FrameMap>
+__device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
                                               const uint8_t *lut, uint8_t *stage,
                                               __amdgpu_buffer_rsrc_t out, uint32_t row0, bool dead) {
   const __amdgpu_buffer_rsrc_t rc = codes_rsrc(a, t);
@@ -723,7 +806,11 @@ __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const Tile &t
     const uint32_t first = h * 32u;
     const uint32_t sb = __builtin_amdgcn_readlane(my_off, first);
     // end of the half: start bit of lane first+32 (or the tile's last block end)
-    const uint32_t nblk = a.nb - t.b0;  // blocks in this tile (may be < 64)
+    uint32_t nblk;  // blocks in this tile (may be < 64)
+    if constexpr (Map::kRegion)
+      nblk = t.n;
+    else
+      nblk = a.nb - t.b0;
     if (first >= nblk) break;
     uint32_t eb;
     if (first + 32u < nblk) {
@@ -776,20 +863,20 @@ __device__ __forceinline__ uint32_t next_tile(const DecodeArgs &a, uint32_t t, u
 // LDS window once tile i has finished reading it. One instantiation per flavour, entered
 // with nothing but the first header live (a flavour branch with the first span in
 // flight spilled: 80 VGPRs + 40 B of scratch).
-template <bool kDelta, class Cfg>
+template <bool kDelta, class Cfg, class Map = FrameMap>
 __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, uint8_t *stage,
                                            const uint8_t *lut, uint32_t t0, uint32_t gstride,
-                                           const TileHdr &hc, bool synced MH_TS_PARAM) {
-  TileHdr hn;
+                                           const TileHdrOf<Map> &hc, bool synced MH_TS_PARAM, const Map &m = Map()) {
+  TileHdrOf<Map> hn;
 #if MH_DIAG_STAMPS
   bool first_tile = true;
 #endif
   v4u32 R[kStageChunks];
-  Tile cur = hdr_resolve(a, hc, lane);
+  TileOf<Map> cur = hdr_resolve(a, hc, lane, m);
   MH_STAMP(1);
   bool cur_staged = cur.tile < a.total_tiles && cur.span <= (uint32_t)kStageBytes;
   span_issue(a, cur, lane, R, cur_staged);
-  hdr_issue(a, next_tile(a, t0, gstride), lane, hn);
+  hdr_issue(a, next_tile(a, t0, gstride), lane, hn, m);
   if constexpr (Cfg::kEsc) {  // the general flavour: also an in-kernel table, or a copy loop
     if (!synced) {
       if (a.lut)
@@ -803,7 +890,7 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
   MH_STAMP(3);
   // Resolved even past the end (zero-record loads): every Tile field is defined
   // before span_issue builds a descriptor from it.
-  Tile nxt = hdr_resolve(a, hn, lane);
+  TileOf<Map> nxt = hdr_resolve(a, hn, lane, m);
 
   // Per iteration the only VMEM issued after a prefetch is the 8 unconditional row
   // stores, so every wait below is an exact vmcnt that leaves the stores in flight.
@@ -812,12 +899,12 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     const bool nxt_live = nxt.tile < a.total_tiles;
     const bool nxt_staged = nxt_live && nxt.span <= (uint32_t)kStageBytes;
     span_issue(a, nxt, lane, R, nxt_staged);  // unconditional (all out of range if not staged)
-    hdr_issue(a, next_tile(a, nxt.tile, gstride), lane, hn);
+    hdr_issue(a, next_tile(a, nxt.tile, gstride), lane, hn, m);
 
     wave_sync();  // this tile's staging writes -> reads
     {
       const bool dead = !cur.valid;
-      const OutTile ot = out_tile(a, cur, lane);
+      const OutTile ot = out_tile<Map>(a, cur, lane);
       LdsWords src{stage};
       // waves with more tiles left run first (the arbiter otherwise favours the oldest)
       set_prio(min((a.total_tiles - 1u - cur.tile) / gstride, 3u));
@@ -829,7 +916,7 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
 #endif
     wave_sync();  // this tile's reads -> next tile's staging writes
     if (nxt_staged) span_write<Cfg::kSwz>(nxt, lane, R, stage);
-    const Tile nn = hdr_resolve(a, hn, lane);
+    const TileOf<Map> nn = hdr_resolve(a, hn, lane, m);
     cur = nxt;
     cur_staged = nxt_staged;
     nxt = nn;
@@ -840,11 +927,11 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
   // Kept after the pipelined loop so its waits never merge into that loop.
   for (uint32_t t = cur.tile; t < a.total_tiles; t = next_tile(a, t, gstride)) {
     __builtin_amdgcn_s_waitcnt(0);
-    TileHdr h;
-    hdr_issue(a, t, lane, h);
-    const Tile tt = hdr_resolve(a, h, lane);
-    const OutTile ot = out_tile(a, tt, lane);
-    decode_halves<kDelta, Cfg>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid);
+    TileHdrOf<Map> h;
+    hdr_issue(a, t, lane, h, m);
+    const TileOf<Map> tt = hdr_resolve(a, h, lane, m);
+    const OutTile ot = out_tile<Map>(a, tt, lane);
+    decode_halves<kDelta, Cfg, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid);
   }
 }
 
@@ -862,7 +949,7 @@ struct Flat8Codes {
   uint32_t w[17];  // the block's 64 code bytes from the dword below its first byte
 };
 
-__device__ __forceinline__ void flat8_issue(const DecodeArgs &a, const Tile &t, Flat8Codes &c) {
+__device__ __forceinline__ void flat8_issue(const DecodeArgs &a, const TileBase &t, Flat8Codes &c) {
   // unconditional loads (a fixed count, exact vmcnt); a lane without a block reads far
   // past the frame (out of range: 0, no access)
   const __amdgpu_buffer_rsrc_t rc = codes_rsrc(a, t);
@@ -879,11 +966,12 @@ __device__ __forceinline__ void flat8_issue(const DecodeArgs &a, const Tile &t, 
   c.w[16] = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(base + 64u), 0, 0);
 }
 
-template <bool kDelta>
-__device__ __forceinline__ void flat8_block(const DecodeArgs &a, const Tile &t, uint32_t lane, const Flat8Codes &c) {
+template <bool kDelta, class Map = FrameMap>
+__device__ __forceinline__ void flat8_block(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
+                                            const Flat8Codes &c) {
   typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
   const uint32_t sb = (t.start + (t.p >> 3)) & 3u;
-  const OutTile ot = out_tile(a, t, lane);
+  const OutTile ot = out_tile<Map>(a, t, lane);
   const uint32_t rbase = (t.valid && !MH_DIAG_DROP_STORES) ? ot.row0 : 0x80000000u;
   const uint32_t pitch = (uint32_t)a.out_pitch;
   uint32_t s = t.init;  // running delta sum (byte 0)
@@ -913,15 +1001,16 @@ __device__ __forceinline__ void flat8_block(const DecodeArgs &a, const Tile &t, 
 // pipelined like batch_loop -- while a tile decodes, the next tile's codes and the one
 // after's header are in flight, all issued before this tile's row stores, so no wait
 // below is for a store.
-template <bool kDelta>
+template <bool kDelta, class Map = FrameMap>
 __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, uint8_t *stage, const uint8_t *lut,
-                                           uint32_t t0, uint32_t gstride, const TileHdr &hc MH_TS_PARAM) {
-  TileHdr h;
+                                           uint32_t t0, uint32_t gstride, const TileHdrOf<Map> &hc MH_TS_PARAM,
+                                           const Map &m = Map()) {
+  TileHdrOf<Map> h;
   Flat8Codes cc, cn;
-  Tile cur = hdr_resolve(a, hc, lane);
+  TileOf<Map> cur = hdr_resolve(a, hc, lane, m);
   MH_STAMP(1);
   flat8_issue(a, cur, cc);
-  hdr_issue(a, next_tile(a, t0, gstride), lane, h);
+  hdr_issue(a, next_tile(a, t0, gstride), lane, h, m);
 #if MH_DIAG_STAMPS
   ts[2] = ts[1];
   ts[3] = ts[1];
@@ -930,10 +1019,10 @@ __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, u
   while (cur.tile < a.total_tiles) {  // wave-uniform
     // a block off the byte grid: this tile and the rest in the slow loop below
     if (__builtin_expect(__ballot(cur.valid && ((cur.p & 7u) != 0u)) != 0, 0)) break;
-    const Tile nxt = hdr_resolve(a, h, lane);
+    const TileOf<Map> nxt = hdr_resolve(a, h, lane, m);
     flat8_issue(a, nxt, cn);
-    hdr_issue(a, next_tile(a, nxt.tile, gstride), lane, h);
-    flat8_block<kDelta>(a, cur, lane, cc);
+    hdr_issue(a, next_tile(a, nxt.tile, gstride), lane, h, m);
+    flat8_block<kDelta, Map>(a, cur, lane, cc);
 #if MH_DIAG_STAMPS
     if (first_tile) MH_STAMP(4);  // the first tile's codes landed and its stores issued
     first_tile = false;
@@ -946,11 +1035,11 @@ __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, u
   using Batch8 = StepCfg<kLutBits, true, false, false, kBatchStoreAux, false, true>;
   for (uint32_t t = cur.tile; t < a.total_tiles; t = next_tile(a, t, gstride)) {
     __builtin_amdgcn_s_waitcnt(0);
-    TileHdr hs;
-    hdr_issue(a, t, lane, hs);
-    const Tile tt = hdr_resolve(a, hs, lane);
-    const OutTile ot = out_tile(a, tt, lane);
-    decode_halves<kDelta, Batch8>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid);
+    TileHdrOf<Map> hs;
+    hdr_issue(a, t, lane, hs, m);
+    const TileOf<Map> tt = hdr_resolve(a, hs, lane, m);
+    const OutTile ot = out_tile<Map>(a, tt, lane);
+    decode_halves<kDelta, Batch8, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid);
   }
 }
 
@@ -1143,6 +1232,79 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     batch_loop<kDelta, Lut13NoEsc>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
   else
     batch_loop<kDelta, Lut13>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+}
+
+// ---- a block-aligned region of every frame (mh_decode_region) ---------------------
+// mh_decode_multitable_kernel's decomposition and prologue (workgroup g serves frame g / G as
+// slice g % G with 8 waves; status word, lengths word, table copy, first header, LDS-only
+// barrier; the flavour per workgroup) over RegionMap's tiles: runs of <= 64 blocks inside one
+// block row of the region, stored into a raster of the region's own size. Tiles are frame
+// relative (the map carries the frame), so no tile -> frame division; the tile -> (row, segment)
+// division is skipped for regions of <= 64 blocks per row. lut_stride 0: one table for all frames.
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_region_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, uint64_t p_lut_stride, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbx0, uint32_t p_rby0, const DecodeArgs a0) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t G = p_groups;
+  const uint32_t f = blockIdx.x / G, slice = blockIdx.x - f * G;
+  DecodeArgs a = a0;
+  a.offsets = p_offsets;
+  a.frame_off = p_frame_off;
+  a.block_init = p_block_init;
+  a.lut = reinterpret_cast<const uint16_t *>(p_luts + (uint64_t)f * p_lut_stride);
+  a.nb = p_nb;
+  a.tiles_per_frame = p_tiles_per_frame;
+  a.total_tiles = p_tiles_per_frame;  // frame-relative tiles: the workgroup never leaves its frame
+  constexpr uint32_t nwaves = kMaxWavesPerWG, nthreads = nwaves * 64u;
+  a.nwaves = nwaves;
+  a.grid = G;
+  const RegionMap m{f, p_rbx0, p_rby0, p_rbw, p_segs};
+  const uint32_t gstride = G * nwaves;
+  uint8_t *stage = s_stage + wave * kStageBytes;
+  const uint8_t *lut = reinterpret_cast<const uint8_t *>(s_lut);
+#if MH_DIAG_STAMPS
+  unsigned long long ts[kDiagSlots] = {};
+#endif
+  MH_STAMP(0);
+
+  const uint32_t t0 = min(slice * nwaves + wave, a.total_tiles);
+  TileHdrOf<RegionMap> hc;
+  // status word, lengths word, table, first header: vector loads, the oldest first (as above)
+  const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
+      uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
+  const v4u32 lw = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(a.lut, (uint32_t)kPreparedBytes),
+                                                         kMaxLenOff, 0, 0);
+  constexpr uint32_t kLutChunks = kLutBytes / 16, kLutPer = 4;
+  static_assert(nthreads * kLutPer >= kLutChunks, "four loads per thread cover the table");
+  v4u32 L[kLutPer];
+  {
+    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(a.lut, (uint32_t)kLutBytes);
+#pragma unroll
+    for (uint32_t k = 0; k < kLutPer; ++k)
+      L[k] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)((threadIdx.x + k * nthreads) * 16u), 0, 0);
+  }
+  hdr_issue(a, t0, lane, hc, m);
+  if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
+  const uint32_t mx = __builtin_amdgcn_readfirstlane(lw.x), mn = __builtin_amdgcn_readfirstlane(lw.y);
+  const uint32_t f8 = __builtin_amdgcn_readfirstlane(lw.z);
+  {
+    v4u32 *dstv = reinterpret_cast<v4u32 *>(s_lut);
+#pragma unroll
+    for (uint32_t k = 0; k < kLutPer; ++k)
+      if (threadIdx.x + k * nthreads < kLutChunks) dstv[threadIdx.x + k * nthreads] = L[k];
+    if (!f8) lds_barrier();  // the flat 8-bit identity table decodes without the table in LDS
+  }
+  if (f8)
+    flat8_loop<kDelta, RegionMap>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG, m);
+  else if (mx == mn && mx <= (uint32_t)kLutBits)
+    batch_loop<kDelta, Lut13Flat, RegionMap>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
+  else if (mx <= (uint32_t)kLutBits)
+    batch_loop<kDelta, Lut13NoEsc, RegionMap>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
+  else
+    batch_loop<kDelta, Lut13, RegionMap>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
 }
 
 // ---- a batch decoded straight from canonical headers (mh_decode_headers) ---------
@@ -1973,6 +2135,7 @@ struct DeviceInfo {
   int occ[2][kMaxWavesPerWG + 1] = {};
   int occ_frames[2] = {};  // mh_decode_multitable_kernel at 8 waves (raw / delta)
   int occ_headers[2] = {};  // mh_decode_headers_kernel at 8 waves (raw / delta)
+  int occ_region[2] = {};  // mh_decode_region_kernel at 8 waves (raw / delta)
 };
 DeviceInfo g_devinfo[kMaxDevices];
 
@@ -2020,6 +2183,8 @@ const DeviceInfo *device_info(hipStream_t s) {
   d.occ_frames[1] = occupancy_of(mh_decode_multitable_kernel<true>, kMaxWavesPerWG);
   d.occ_headers[0] = occupancy_of(mh_decode_headers_kernel<false>, kMaxWavesPerWG);
   d.occ_headers[1] = occupancy_of(mh_decode_headers_kernel<true>, kMaxWavesPerWG);
+  d.occ_region[0] = occupancy_of(mh_decode_region_kernel<false>, kMaxWavesPerWG);
+  d.occ_region[1] = occupancy_of(mh_decode_region_kernel<true>, kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -2089,10 +2254,15 @@ int launch(const DecodeArgs &a0, hipStream_t s, bool lane_pairs, bool any_order)
 
 // The argument checks of the decode entry points, all before any HIP call. `luts`: the
 // per-frame-table entry (mh_decode_frames), which ignores the frame's own table fields and
-// checks d_luts / lut_stride in their place, rule by rule in the same order.
+// checks d_luts / lut_stride in their place, rule by rule in the same order. `regional`: the
+// region entry (mh_decode_region), whose region is checked with the dims, whose pixel size
+// RW x RH stands where W x H does in the pitch and stride rules, and which takes a stride of 0
+// (one table for all frames).
 int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                      uint32_t allowed_flags, bool luts, const uint16_t *d_luts, uint64_t lut_stride) {
+                      uint32_t allowed_flags, bool luts, const uint16_t *d_luts, uint64_t lut_stride,
+                      bool regional = false, const mh_region *rg = nullptr) {
   if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
+  if (regional && !rg) return MH_ERR_INVALID_ARG;
   if (luts ? !d_luts : (!fr->d_table1 || !fr->d_table2)) return MH_ERR_INVALID_ARG;
   if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
   if (fr->flags & ~allowed_flags) return MH_ERR_INVALID_ARG;
@@ -2100,6 +2270,15 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
       d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
     return MH_ERR_DIMS;
+  uint64_t pw = d.width, ph = d.height;  // the raster's pixel size
+  if (regional) {
+    if (!rg->bw || !rg->bh || (uint64_t)rg->bx0 + rg->bw > d.block_width ||
+        (uint64_t)rg->by0 + rg->bh > d.block_height)
+      return MH_ERR_DIMS;
+    const uint64_t x1 = 8ull * (rg->bx0 + rg->bw), y1 = 8ull * (rg->by0 + rg->bh);
+    pw = (x1 < d.width ? x1 : d.width) - 8ull * rg->bx0;
+    ph = (y1 < d.height ? y1 : d.height) - 8ull * rg->by0;
+  }
   if (!luts && (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
                 fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
     return MH_ERR_TABLE;
@@ -2108,19 +2287,20 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
     return MH_ERR_ALIGN;
   if (luts ? (((uintptr_t)d_luts & 15u) || (lut_stride & 15u)) : (((uintptr_t)fr->d_lut & 15u) != 0))
     return MH_ERR_ALIGN;
-  if (out_pitch < d.width || out_pitch > (1u << 20) ||
-      (fr->n_frames > 1 && out_frame_stride < out_pitch * d.height))
+  if (out_pitch < pw || out_pitch > (1u << 20) || (fr->n_frames > 1 && out_frame_stride < out_pitch * ph))
     return MH_ERR_CAPACITY;
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
     return MH_ERR_CAPACITY;
-  if (luts && lut_stride < (uint64_t)kPreparedBytes) return MH_ERR_CAPACITY;  // mh_lut_bytes()
+  if (luts && lut_stride < (uint64_t)kPreparedBytes && !(regional && lut_stride == 0))
+    return MH_ERR_CAPACITY;  // mh_lut_bytes()
   return MH_OK;
 }
 
 // DecodeArgs from a checked frame (tables excepted); MH_ERR_CAPACITY past 2^31 - 1 tiles.
+// Not `frame_tiles`: the tile counts are left to the caller (region_args: a region's tiles).
 int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                     DecodeArgs &a) {
+                     DecodeArgs &a, bool frame_tiles = true) {
   const mh_dims &d = fr->dims;
   a.offsets = fr->d_block_offsets;
   a.codes = fr->d_codes;
@@ -2136,6 +2316,7 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
   a.bw = d.block_width;
   a.bh = d.block_height;
   a.nb = d.block_width * d.block_height;
+  if (!frame_tiles) return MH_OK;
   a.tiles_per_frame = (a.nb + 63) / 64;
   const uint64_t total = (uint64_t)a.tiles_per_frame * fr->n_frames;
   if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
@@ -2149,11 +2330,12 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
 // R = the workgroups resident on the device at once (CUs x the kernel's occupancy): about
 // one resident round when the frames are few, one workgroup per frame when they are many.
 // `headers`: the shape of mh_decode_headers, the same rule with its kernel's occupancy.
+// `region`: the shape of mh_decode_region, the same rule over the region's tiles.
 int frames_shape(uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s, uint32_t *groups,
-                 bool headers = false) {
+                 bool headers = false, bool region = false) {
   const DeviceInfo *di = device_info(s);
   if (!di) return MH_ERR_HIP;
-  const int occ = (headers ? di->occ_headers : di->occ_frames)[delta ? 1 : 0];
+  const int occ = (region ? di->occ_region : headers ? di->occ_headers : di->occ_frames)[delta ? 1 : 0];
   const uint64_t resident = (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)occ;
   const uint64_t want = (resident + n_frames - 1) / n_frames;
   const uint64_t most = (tiles_per_frame + (uint32_t)kMaxWavesPerWG - 1) / (uint32_t)kMaxWavesPerWG;
@@ -2184,6 +2366,36 @@ int launch_headers(const DecodeArgs &a, uint32_t n_frames, const uint8_t *header
   if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
   MH_LAUNCH(mh_decode_headers_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
             a.offsets, a.frame_off, a.block_init, headers, status, header_status, a.nb, a.tiles_per_frame, G, a);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+// A checked region's tiling: S = ceil(bw / 64) tiles per block row, bh * S tiles per frame.
+// DecodeArgs of fill_decode_args turned into the region kernel's: the raster is RH rows, the
+// tiles are the region's. MH_ERR_CAPACITY past 2^31 - 1 tiles.
+int region_args(const mh_frame *fr, const mh_region *rg, DecodeArgs &a, uint32_t *segs) {
+  const uint32_t S = (rg->bw + 63u) / 64u;
+  const uint64_t y1 = 8ull * (rg->by0 + rg->bh);
+  const uint64_t rh = (y1 < fr->dims.height ? y1 : fr->dims.height) - 8ull * rg->by0;
+  a.out_frame_bytes = rh * a.out_pitch;
+  a.tiles_per_frame = rg->bh * S;  // <= 8192 * 128
+  const uint64_t total = (uint64_t)a.tiles_per_frame * fr->n_frames;
+  if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  a.total_tiles = (uint32_t)total;
+  *segs = S;
+  return MH_OK;
+}
+
+template <bool kDelta>
+int launch_region(const DecodeArgs &a, uint32_t n_frames, const mh_region *rg, uint32_t segs, const uint8_t *luts,
+                  uint64_t lut_stride, const int32_t *status, hipStream_t s, bool any_order) {
+  uint32_t G = 0;
+  const int rc = frames_shape(n_frames, a.tiles_per_frame, kDelta, s, &G, false, true);
+  if (rc != MH_OK) return rc;
+  const uint64_t grid = (uint64_t)G * n_frames;
+  if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  MH_LAUNCH(mh_decode_region_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
+            a.offsets, a.frame_off, a.block_init, luts, status, lut_stride, a.nb, a.tiles_per_frame, G, segs,
+            rg->bw, rg->bx0, rg->by0, a);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 #endif
@@ -2330,6 +2542,46 @@ int mh_decode_headers_shape(const mh_frame *fr, void *stream, uint32_t *groups_p
   const uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
   const int rc = frames_shape(fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
                               groups_per_frame, true);
+  if (rc != MH_OK) return rc;
+  *waves_per_group = kMaxWavesPerWG;
+  return MH_OK;
+}
+
+int mh_decode_region(const mh_frame *fr, const mh_region *rg, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                     const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
+                     void *stream) {
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, true,
+                             d_luts, lut_stride_bytes, true, rg);
+  if (rc != MH_OK) return rc;
+  DecodeArgs a{};  // t1 / t2 / lut stay null: every workgroup takes its frame's table from d_luts
+  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a, false);
+  if (rc != MH_OK) return rc;
+  uint32_t segs = 0;
+  rc = region_args(fr, rg, a, &segs);
+  if (rc != MH_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
+  const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return (fr->flags & MH_FLAG_NO_DELTA)
+             ? launch_region<false>(a, fr->n_frames, rg, segs, luts, lut_stride_bytes, d_frame_status, s, ao)
+             : launch_region<true>(a, fr->n_frames, rg, segs, luts, lut_stride_bytes, d_frame_status, s, ao);
+}
+
+int mh_decode_region_shape(const mh_frame *fr, const mh_region *rg, void *stream, uint32_t *groups_per_frame,
+                           uint32_t *waves_per_group) {
+  if (!fr || !rg || !groups_per_frame || !waves_per_group || fr->n_frames == 0) return MH_ERR_INVALID_ARG;
+  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
+  const mh_dims &d = fr->dims;
+  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
+      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
+    return MH_ERR_DIMS;
+  if (!rg->bw || !rg->bh || (uint64_t)rg->bx0 + rg->bw > d.block_width ||
+      (uint64_t)rg->by0 + rg->bh > d.block_height)
+    return MH_ERR_DIMS;
+  const uint32_t tiles = rg->bh * ((rg->bw + 63u) / 64u);
+  if ((uint64_t)tiles * fr->n_frames > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  const int rc = frames_shape(fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
+                              groups_per_frame, false, true);
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
   return MH_OK;

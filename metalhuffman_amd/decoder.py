@@ -11,7 +11,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import dataclasses
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -375,6 +375,118 @@ def decode_frames(frames, table_set="cuda", out: Optional[torch.Tensor] = None,
     if rc:
         N.check(rc, "mh_decode_frames")
     return out
+
+
+class Region(NamedTuple):
+    """Blocks [bx0, bx0 + bw) x [by0, by0 + bh) of a frame's 8x8 block grid (mh_region)."""
+    bx0: int
+    by0: int
+    bw: int
+    bh: int
+
+    def pixel_size(self, width: int, height: int) -> tuple:
+        """(RW, RH): the region's pixels inside a width x height frame (the frame's right and
+        bottom edge blocks are partial)."""
+        return (min(width, 8 * (self.bx0 + self.bw)) - 8 * self.bx0,
+                min(height, 8 * (self.by0 + self.bh)) - 8 * self.by0)
+
+
+def region_of_rect(width: int, height: int, x0: int, y0: int, w: int, h: int) -> tuple:
+    """The pixel rectangle [x0, x0 + w) x [y0, y0 + h) of a width x height frame rounded out to
+    whole blocks -> (Region, dx, dy), (dx, dy) the rectangle's offset inside the region. Pure.
+    ValueError when the rectangle is empty or leaves the frame."""
+    width, height, x0, y0, w, h = (int(v) for v in (width, height, x0, y0, w, h))
+    if width < 1 or height < 1:
+        raise ValueError("an empty frame")
+    if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > width or y0 + h > height:
+        raise ValueError(f"the rectangle {w}x{h} at ({x0}, {y0}) lies outside the {width}x{height} frame")
+    bx0, by0 = x0 // 8, y0 // 8
+    return (Region(bx0, by0, (x0 + w + 7) // 8 - bx0, (y0 + h + 7) // 8 - by0), x0 - 8 * bx0, y0 - 8 * by0)
+
+
+def _region_struct(frames: DeviceFrames, region) -> "N.mh_region":
+    bx0, by0, bw, bh = (int(v) for v in region)
+    gw, gh = block_grid(frames.width, frames.height)
+    if bw < 1 or bh < 1 or bx0 < 0 or by0 < 0 or bx0 + bw > gw or by0 + bh > gh:
+        raise ValueError(f"region {(bx0, by0, bw, bh)} lies outside the {gw}x{gh} block grid")
+    return N.mh_region(bx0, by0, bw, bh)
+
+
+def decode_region_shape(frames: DeviceFrames, region, stream: Optional[torch.cuda.Stream] = None,
+                        extra_flags: int = 0) -> tuple:
+    """(workgroups per frame, waves per workgroup) decode_region would launch with
+    (mh_decode_region_shape)."""
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    rg = _region_struct(frames, region)
+    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
+    N.check(N.lib().mh_decode_region_shape(ctypes.byref(fr), ctypes.byref(rg), sp, ctypes.byref(g), ctypes.byref(w)),
+            "mh_decode_region_shape")
+    return int(g.value), int(w.value)
+
+
+def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                  skip_rejected: bool = True) -> torch.Tensor:
+    """Decode the blocks `region` = (bx0, by0, bw, bh) of every frame into out[n, RH, 8 * bw] in
+    one launch (mh_decode_region); the full W x H raster is neither written nor needed. tables: a
+    DeviceTables (its prepared table shared by all frames) or a DeviceTableSet (a table per
+    frame; with skip_rejected its status goes in as the per-frame status and a frame whose word
+    is non-zero is left untouched). out: decode()'s contract with the region's shape."""
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_region")
+    rg = _region_struct(frames, region)
+    if isinstance(tables, DeviceTables):
+        if tables.lut is None:
+            raise ValueError("decode_region needs the prepared table (DeviceTables.prepare_lut())")
+        if tables.lut.get_device() != dev_index:
+            raise ValueError(f"the table must live on cuda:{dev_index}")
+        luts, stride, status = tables.lut, 0, None
+    elif isinstance(tables, DeviceTableSet):
+        if (tables.n_tables != frames.n_frames or tables.luts.get_device() != dev_index
+                or tables.luts.dtype is not torch.uint8 or not tables.luts.is_contiguous()
+                or tables.status.get_device() != dev_index or tables.status.dtype is not torch.int32
+                or tables.status.numel() != frames.n_frames or not tables.status.is_contiguous()):
+            raise ValueError(f"the table set must hold {frames.n_frames} tables on cuda:{dev_index}")
+        luts, stride, status = tables.luts, tables.stride, tables.status if skip_rejected else None
+    else:
+        raise TypeError("decode_region takes a DeviceTables or a DeviceTableSet")
+    pitch = 8 * rg.bw
+    h = min(frames.height, 8 * (rg.by0 + rg.bh)) - 8 * rg.by0
+    if out is None:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            out = torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=frames.codes.device)
+    else:
+        sh = out.shape
+        if (out.dtype is not torch.uint8 or len(sh) < 2 or sh[-1] != pitch or sh[-2] != h
+                or out.get_device() != dev_index or not out.is_contiguous()
+                or out.numel() < frames.n_frames * h * pitch):
+            raise ValueError(f"out must be a contiguous uint8 [{frames.n_frames}, {h}, {pitch}] "
+                             f"tensor on cuda:{dev_index}")
+    if stream is not None:
+        sp = stream.cuda_stream
+    elif _raw_stream is not None:
+        sp = _raw_stream(dev_index)
+    else:
+        sp = torch.cuda.current_stream(dev_index).cuda_stream
+    rc = N.lib().mh_decode_region(ctypes.byref(fr), ctypes.byref(rg), luts.data_ptr(), stride,
+                                  status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
+                                  h * pitch, sp)
+    if rc:
+        N.check(rc, "mh_decode_region")
+    return out
+
+
+def decode_rect(frames: DeviceFrames, tables, x0: int, y0: int, w: int, h: int,
+                out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                extra_flags: int = 0, skip_rejected: bool = True) -> torch.Tensor:
+    """The pixel rectangle [x0, x0 + w) x [y0, y0 + h) of every frame: decode_region of the
+    blocks that cover it (region_of_rect), returned as the [n, h, w] view of that raster (`out`,
+    when given, has the region's shape)."""
+    region, dx, dy = region_of_rect(frames.width, frames.height, x0, y0, w, h)
+    full = decode_region(frames, tables, region, out, stream, extra_flags, skip_rejected)
+    return full.reshape(frames.n_frames, full.shape[-2], full.shape[-1])[:, dy: dy + h, dx: dx + w]
 
 
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,

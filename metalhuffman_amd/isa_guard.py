@@ -87,6 +87,25 @@ def kernels(lib_path: str) -> dict:
     return out
 
 
+def resources(lib_path: str) -> dict:
+    """kernel symbol -> {"vgpr", "sgpr", "lds", "scratch"}: the register counts, the static LDS
+    bytes and the scratch bytes of each kernel, from the same metadata notes (for the budget
+    tables in DESIGN.md)."""
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for co in _code_objects(lib_path, d):
+            notes = subprocess.run([READELF, "--notes", co], check=True, capture_output=True, text=True).stdout
+            for blk in re.split(r"\n\s+- \.", notes):
+                m = re.search(r"\.name:\s+(\S+)", blk)
+                if not m or "kernel" not in m.group(1):
+                    continue
+                get = lambda k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
+                out[m.group(1)] = {"vgpr": get("vgpr_count"), "sgpr": get("sgpr_count"),
+                                   "lds": get("group_segment_fixed_size"),
+                                   "scratch": get("private_segment_fixed_size")}
+    return out
+
+
 def check_library(lib_path: str) -> list:
     """Problems found in a linked library (empty: it passes)."""
     ks = kernels(lib_path)
