@@ -1155,158 +1155,6 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
 }
 
 #if !MH_LANE_PAIRS
-// ---- a batch with one prepared table per frame (mh_decode_frames) ----------------
-// The batch kernel's machinery with another decomposition: workgroup g serves ONE frame,
-// f = g / G, as slice j = g % G of it, so it copies frame f's table (luts + f * stride)
-// into LDS once and never crosses a frame. Wave w decodes tiles f*tpf + j*8 + w, stepping
-// by 8*G, below (f+1)*tpf: the persistent loops run on a workgroup-local DecodeArgs whose
-// total_tiles is the frame's end (frame_of's one-frame shortcut then holds for f = 0 only,
-// where it is right; every other frame divides). Always 8 waves, so four 16-byte loads per
-// thread cover the table; waves without a tile idle behind the barrier. The step flavour
-// comes from the frame's own [longest, shortest, flat8] word, per workgroup. A frame whose
-// status word is non-zero (rejected by the encoder or the table build) is left alone: the
-// workgroup returns before any store. The grid is n_frames * G, not persistent across
-// frames.
-template <bool kDelta>
-__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_multitable_kernel(
-    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
-    const int32_t *p_status, uint64_t p_lut_stride, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
-    const DecodeArgs a0) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t G = p_groups;
-  const uint32_t f = blockIdx.x / G, slice = blockIdx.x - f * G;
-  DecodeArgs a = a0;
-  a.offsets = p_offsets;
-  a.frame_off = p_frame_off;
-  a.block_init = p_block_init;
-  a.lut = reinterpret_cast<const uint16_t *>(p_luts + (uint64_t)f * p_lut_stride);
-  a.nb = p_nb;
-  a.tiles_per_frame = p_tiles_per_frame;
-  a.total_tiles = (f + 1u) * p_tiles_per_frame;  // this workgroup's tiles end with its frame
-  constexpr uint32_t nwaves = kMaxWavesPerWG, nthreads = nwaves * 64u;
-  a.nwaves = nwaves;
-  a.grid = G;
-  const uint32_t gstride = G * nwaves;
-  uint8_t *stage = s_stage + wave * kStageBytes;
-  const uint8_t *lut = reinterpret_cast<const uint8_t *>(s_lut);
-#if MH_DIAG_STAMPS
-  unsigned long long ts[kDiagSlots] = {};
-#endif
-  MH_STAMP(0);
-
-  const uint32_t t0 = min(f * p_tiles_per_frame + slice * nwaves + wave, a.total_tiles);
-  TileHdr hc;
-  // The frame's status word, then its table's lengths word, then the table: vector loads
-  // through descriptors (the status one empty without a status array), the oldest first, so
-  // each has landed by the time the table's loads have (as the batch kernel's lengths word).
-  const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
-      uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
-  const v4u32 lw = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(a.lut, (uint32_t)kPreparedBytes),
-                                                         kMaxLenOff, 0, 0);
-  constexpr uint32_t kLutChunks = kLutBytes / 16, kLutPer = 4;
-  static_assert(nthreads * kLutPer >= kLutChunks, "four loads per thread cover the table");
-  v4u32 L[kLutPer];
-  {
-    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(a.lut, (uint32_t)kLutBytes);
-#pragma unroll
-    for (uint32_t k = 0; k < kLutPer; ++k)
-      L[k] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)((threadIdx.x + k * nthreads) * 16u), 0, 0);
-  }
-  hdr_issue(a, t0, lane, hc);
-  if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
-  const uint32_t mx = __builtin_amdgcn_readfirstlane(lw.x), mn = __builtin_amdgcn_readfirstlane(lw.y);
-  const uint32_t f8 = __builtin_amdgcn_readfirstlane(lw.z);
-  {
-    v4u32 *dstv = reinterpret_cast<v4u32 *>(s_lut);
-#pragma unroll
-    for (uint32_t k = 0; k < kLutPer; ++k)
-      if (threadIdx.x + k * nthreads < kLutChunks) dstv[threadIdx.x + k * nthreads] = L[k];
-    if (!f8) lds_barrier();  // the flat 8-bit identity table decodes without the table in LDS
-  }
-  if (f8)
-    flat8_loop<kDelta>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG);
-  else if (mx == mn && mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13Flat>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
-  else if (mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13NoEsc>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
-  else
-    batch_loop<kDelta, Lut13>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
-}
-
-// ---- a block-aligned region of every frame (mh_decode_region) ---------------------
-// mh_decode_multitable_kernel's decomposition and prologue (workgroup g serves frame g / G as
-// slice g % G with 8 waves; status word, lengths word, table copy, first header, LDS-only
-// barrier; the flavour per workgroup) over RegionMap's tiles: runs of <= 64 blocks inside one
-// block row of the region, stored into a raster of the region's own size. Tiles are frame
-// relative (the map carries the frame), so no tile -> frame division; the tile -> (row, segment)
-// division is skipped for regions of <= 64 blocks per row. lut_stride 0: one table for all frames.
-template <bool kDelta>
-__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_region_kernel(
-    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
-    const int32_t *p_status, uint64_t p_lut_stride, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
-    uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbx0, uint32_t p_rby0, const DecodeArgs a0) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t G = p_groups;
-  const uint32_t f = blockIdx.x / G, slice = blockIdx.x - f * G;
-  DecodeArgs a = a0;
-  a.offsets = p_offsets;
-  a.frame_off = p_frame_off;
-  a.block_init = p_block_init;
-  a.lut = reinterpret_cast<const uint16_t *>(p_luts + (uint64_t)f * p_lut_stride);
-  a.nb = p_nb;
-  a.tiles_per_frame = p_tiles_per_frame;
-  a.total_tiles = p_tiles_per_frame;  // frame-relative tiles: the workgroup never leaves its frame
-  constexpr uint32_t nwaves = kMaxWavesPerWG, nthreads = nwaves * 64u;
-  a.nwaves = nwaves;
-  a.grid = G;
-  const RegionMap m{f, p_rbx0, p_rby0, p_rbw, p_segs};
-  const uint32_t gstride = G * nwaves;
-  uint8_t *stage = s_stage + wave * kStageBytes;
-  const uint8_t *lut = reinterpret_cast<const uint8_t *>(s_lut);
-#if MH_DIAG_STAMPS
-  unsigned long long ts[kDiagSlots] = {};
-#endif
-  MH_STAMP(0);
-
-  const uint32_t t0 = min(slice * nwaves + wave, a.total_tiles);
-  TileHdrOf<RegionMap> hc;
-  // status word, lengths word, table, first header: vector loads, the oldest first (as above)
-  const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
-      uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
-  const v4u32 lw = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(a.lut, (uint32_t)kPreparedBytes),
-                                                         kMaxLenOff, 0, 0);
-  constexpr uint32_t kLutChunks = kLutBytes / 16, kLutPer = 4;
-  static_assert(nthreads * kLutPer >= kLutChunks, "four loads per thread cover the table");
-  v4u32 L[kLutPer];
-  {
-    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(a.lut, (uint32_t)kLutBytes);
-#pragma unroll
-    for (uint32_t k = 0; k < kLutPer; ++k)
-      L[k] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)((threadIdx.x + k * nthreads) * 16u), 0, 0);
-  }
-  hdr_issue(a, t0, lane, hc, m);
-  if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
-  const uint32_t mx = __builtin_amdgcn_readfirstlane(lw.x), mn = __builtin_amdgcn_readfirstlane(lw.y);
-  const uint32_t f8 = __builtin_amdgcn_readfirstlane(lw.z);
-  {
-    v4u32 *dstv = reinterpret_cast<v4u32 *>(s_lut);
-#pragma unroll
-    for (uint32_t k = 0; k < kLutPer; ++k)
-      if (threadIdx.x + k * nthreads < kLutChunks) dstv[threadIdx.x + k * nthreads] = L[k];
-    if (!f8) lds_barrier();  // the flat 8-bit identity table decodes without the table in LDS
-  }
-  if (f8)
-    flat8_loop<kDelta, RegionMap>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG, m);
-  else if (mx == mn && mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13Flat, RegionMap>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
-  else if (mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13NoEsc, RegionMap>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
-  else
-    batch_loop<kDelta, Lut13, RegionMap>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
-}
-
 // ---- a batch decoded straight from canonical headers (mh_decode_headers) ---------
 // The 13-bit table is a pure function of the header's 256 code lengths, so a workgroup
 // builds it in LDS itself: no table launch, no prepared buffer, no trip of the table
@@ -1477,28 +1325,110 @@ __device__ __forceinline__ HeaderFacts header_build(uint32_t L, uint16_t *lut, H
   return hf;
 }
 
-// mh_decode_multitable_kernel with another prologue: the workgroup loads frame f's 256 code
-// lengths (and its first tile header), builds the table in LDS (header_build) and takes the
-// step flavour from the facts the builder returns. Slice 0 of every frame that is not skipped
-// by its status word writes the header's verdict; a rejected header returns before any store
-// to the raster.
-template <bool kDelta>
-__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_headers_kernel(
-    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_headers,
-    const int32_t *p_status, int32_t *p_header_status, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
-    const DecodeArgs a0) {
+// ---- one frame slice per workgroup (mh_decode_frames / _region / _headers) --------
+// The batch kernel's machinery with another decomposition, shared by three entries:
+// workgroup g serves ONE frame, f = g / G, as slice j = g % G of it, so it brings frame f's
+// table into LDS once and never crosses a frame. Wave w decodes the frame's tiles j*8 + w,
+// stepping by 8*G: the persistent loops run on a workgroup-local DecodeArgs whose total_tiles
+// is the workgroup's last tile + 1. Always 8 waves; waves without a tile idle behind the
+// barrier. The step flavour comes from the frame's own [longest, shortest, flat8] facts, per
+// workgroup. A frame whose status word is non-zero (rejected by the encoder or the table
+// build) is left alone: the workgroup returns before any store. The grid is n_frames * G, not
+// persistent across frames (DESIGN.md sections 3b-3d).
+//
+// Two things vary. The tile map:
+//   FrameMap:  tiles count through the batch, f*tpf + j*8 + w below (f+1)*tpf (frame_of's
+//              one-frame shortcut then holds for f = 0 only, where it is right; every other
+//              frame divides).
+//   RegionMap: runs of <= 64 blocks inside one block row of the region, stored into a raster of
+//              the region's own size. Tiles are frame relative (the map carries the frame), so no
+//              tile -> frame division; the tile -> (row, segment) division is skipped for regions
+//              of <= 64 blocks per row.
+// And where the 13-bit table comes from (a table source: `lut_of`, `issue`, `into_lds`):
+//   PreparedTable: frame f's prepared table at luts + f * stride (stride 0: one table for all
+//              frames), copied by four 16-byte loads per thread.
+//   HeaderTable: built in LDS from frame f's 256 code lengths (header_build); slice 0 of every
+//              frame that is not skipped by its status word writes the header's verdict, and a
+//              rejected header returns before any store to the raster.
+// Every load of the prologue is a vector load through a descriptor, issued oldest first: the
+// status word (empty descriptor without a status array), the source's loads, the first tile
+// header. So each has landed by the time the table's loads have (as the batch kernel's lengths
+// word), and the barrier behind the table is LDS-only: no wave waits there for another wave's
+// (HBM, cold) header.
+struct TableFacts {
+  uint32_t mx, mn, flat8;  // the prepared table's lengths word (mh_lut.hpp)
+};
+
+struct PreparedTable {
+  const uint8_t *luts;
+  uint64_t stride;
+  static constexpr uint32_t kLutChunks = kLutBytes / 16, kLutPer = 4, kThreads = 64u * kMaxWavesPerWG;
+  static_assert(kThreads * kLutPer >= kLutChunks, "four loads per thread cover the table");
+  struct Loads {
+    v4u32 lw, L[kLutPer];
+  };
+  __device__ __forceinline__ const uint16_t *lut_of(uint32_t f) const {
+    return reinterpret_cast<const uint16_t *>(luts + (uint64_t)f * stride);
+  }
+  // the table's lengths word, then the table (from a.lut: the pointer is formed once, ahead of the status load)
+  __device__ __forceinline__ void issue(const DecodeArgs &a, uint32_t, Loads &ld) const {
+    ld.lw = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(a.lut, (uint32_t)kPreparedBytes), kMaxLenOff, 0, 0);
+    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(a.lut, (uint32_t)kLutBytes);
+#pragma unroll
+    for (uint32_t k = 0; k < kLutPer; ++k)
+      ld.L[k] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)((threadIdx.x + k * kThreads) * 16u), 0, 0);
+  }
+  __device__ __forceinline__ bool into_lds(const Loads &ld, uint32_t, uint32_t, TableFacts &tf) const {
+    tf.mx = __builtin_amdgcn_readfirstlane(ld.lw.x);
+    tf.mn = __builtin_amdgcn_readfirstlane(ld.lw.y);
+    tf.flat8 = __builtin_amdgcn_readfirstlane(ld.lw.z);
+    v4u32 *dstv = reinterpret_cast<v4u32 *>(s_lut);
+#pragma unroll
+    for (uint32_t k = 0; k < kLutPer; ++k)
+      if (threadIdx.x + k * kThreads < kLutChunks) dstv[threadIdx.x + k * kThreads] = ld.L[k];
+    if (!tf.flat8) lds_barrier();  // the flat 8-bit identity table decodes without the table in LDS
+    return true;
+  }
+};
+
+struct HeaderTable {
+  const uint8_t *headers;
+  int32_t *verdict;
+  struct Loads {
+    uint32_t L;
+  };
+  __device__ __forceinline__ const uint16_t *lut_of(uint32_t) const { return nullptr; }
+  // the frame's code lengths (threads past 255 read out of range: 0)
+  __device__ __forceinline__ void issue(const DecodeArgs &, uint32_t f, Loads &ld) const {
+    ld.L = __builtin_amdgcn_raw_buffer_load_b8(uniform_rsrc(headers + (uint64_t)f * 256u, 256u), (int)threadIdx.x,
+                                               0, 0) & 0xFFu;
+  }
+  __device__ __forceinline__ bool into_lds(const Loads &ld, uint32_t f, uint32_t slice, TableFacts &tf) const {
+    const HeaderFacts hf = header_build(ld.L, s_lut, reinterpret_cast<HeaderScratch *>(s_stage), threadIdx.x, true);
+    if (verdict && slice == 0 && threadIdx.x == 0) verdict[f] = hf.status;
+    if (hf.status != MH_OK) return false;  // workgroup-uniform: a rejected header, no store to the raster
+    lds_barrier();  // the table is complete, and nobody reads the scratch in the staging windows any more
+    tf = TableFacts{hf.mx, hf.mn, hf.flat8};
+    return true;
+  }
+};
+
+template <bool kDelta, class Map, class Src>
+__device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_t *p_offsets,
+                                             const uint64_t *p_frame_off, const uint8_t *p_block_init,
+                                             const int32_t *p_status, uint32_t p_nb, uint32_t p_tiles_per_frame,
+                                             uint32_t G, uint32_t f, uint32_t slice, const Src &src, const Map &m) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t G = p_groups;
-  const uint32_t f = blockIdx.x / G, slice = blockIdx.x - f * G;
   DecodeArgs a = a0;
   a.offsets = p_offsets;
   a.frame_off = p_frame_off;
   a.block_init = p_block_init;
-  a.lut = nullptr;
+  a.lut = src.lut_of(f);
   a.nb = p_nb;
   a.tiles_per_frame = p_tiles_per_frame;
-  a.total_tiles = (f + 1u) * p_tiles_per_frame;  // this workgroup's tiles end with its frame
+  // this workgroup's tiles end with its frame
+  a.total_tiles = Map::kRegion ? p_tiles_per_frame : (f + 1u) * p_tiles_per_frame;
   constexpr uint32_t nwaves = kMaxWavesPerWG;
   a.nwaves = nwaves;
   a.grid = G;
@@ -1510,28 +1440,56 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
 #endif
   MH_STAMP(0);
 
-  const uint32_t t0 = min(f * p_tiles_per_frame + slice * nwaves + wave, a.total_tiles);
-  TileHdr hc;
-  // the frame's status word, its code lengths (threads past 255 read out of range: 0), then the
-  // first tile header: vector loads, the oldest first
+  const uint32_t t0 = min((Map::kRegion ? 0u : f * p_tiles_per_frame) + slice * nwaves + wave, a.total_tiles);
+  TileHdrOf<Map> hc;
   const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
       uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
-  const uint32_t L = __builtin_amdgcn_raw_buffer_load_b8(uniform_rsrc(p_headers + (uint64_t)f * 256u, 256u),
-                                                         (int)threadIdx.x, 0, 0) & 0xFFu;
-  hdr_issue(a, t0, lane, hc);
+  typename Src::Loads ld;
+  src.issue(a, f, ld);
+  hdr_issue<Map>(a, t0, lane, hc, m);
   if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
-  const HeaderFacts hf = header_build(L, s_lut, reinterpret_cast<HeaderScratch *>(s_stage), threadIdx.x, true);
-  if (p_header_status && slice == 0 && threadIdx.x == 0) p_header_status[f] = hf.status;
-  if (hf.status != MH_OK) return;  // workgroup-uniform: a rejected header, no store to the raster
-  lds_barrier();  // the table is complete, and nobody reads the scratch in the staging windows any more
-  if (hf.flat8)
-    flat8_loop<kDelta>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG);
-  else if (hf.mx == hf.mn && hf.mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13Flat>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
-  else if (hf.mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13NoEsc>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+  TableFacts tf;
+  if (!src.into_lds(ld, f, slice, tf)) return;
+  if (tf.flat8)
+    flat8_loop<kDelta, Map>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG, m);
+  else if (tf.mx == tf.mn && tf.mx <= (uint32_t)kLutBits)
+    batch_loop<kDelta, Lut13Flat, Map>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
+  else if (tf.mx <= (uint32_t)kLutBits)
+    batch_loop<kDelta, Lut13NoEsc, Map>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
   else
-    batch_loop<kDelta, Lut13>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG);
+    batch_loop<kDelta, Lut13, Map>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
+}
+
+// The three entries: names, launch bounds and argument order are the ABI of the launchers, the
+// ISA guard and the diagnostic scripts; the leading 16 arguments are preloaded into SGPRs.
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_multitable_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, uint64_t p_lut_stride, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    const DecodeArgs a0) {
+  const uint32_t f = blockIdx.x / p_groups, slice = blockIdx.x - f * p_groups;
+  slice_decode<kDelta>(a0, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
+                       PreparedTable{p_luts, p_lut_stride}, FrameMap{});
+}
+
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_region_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, uint64_t p_lut_stride, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbx0, uint32_t p_rby0, const DecodeArgs a0) {
+  const uint32_t f = blockIdx.x / p_groups, slice = blockIdx.x - f * p_groups;
+  slice_decode<kDelta>(a0, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
+                       PreparedTable{p_luts, p_lut_stride}, RegionMap{f, p_rbx0, p_rby0, p_rbw, p_segs});
+}
+
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_headers_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_headers,
+    const int32_t *p_status, int32_t *p_header_status, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    const DecodeArgs a0) {
+  const uint32_t f = blockIdx.x / p_groups, slice = blockIdx.x - f * p_groups;
+  slice_decode<kDelta>(a0, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
+                       HeaderTable{p_headers, p_header_status}, FrameMap{});
 }
 
 // mh_header_luts_device: header_build's table and facts copied out at their prepared-table
@@ -2129,13 +2087,13 @@ __global__ void __launch_bounds__(64 * kLpWaves) mh_decode_lanepair_kernel(const
 // is shared between devices or written by concurrent callers (the reference keeps
 // its tables in module statics, Shared/HuffmanUtil.cpp:87-102).
 constexpr int kMaxDevices = 64;
+// The kernels that decode one frame slice per workgroup (slice_decode), by entry point.
+enum SliceKernel { kSliceFrames, kSliceHeaders, kSliceRegion, kSliceKernels };
 struct DeviceInfo {
   std::mutex m;
   std::atomic<int> cus{0};  // nonzero once the entry is complete
   int occ[2][kMaxWavesPerWG + 1] = {};
-  int occ_frames[2] = {};  // mh_decode_multitable_kernel at 8 waves (raw / delta)
-  int occ_headers[2] = {};  // mh_decode_headers_kernel at 8 waves (raw / delta)
-  int occ_region[2] = {};  // mh_decode_region_kernel at 8 waves (raw / delta)
+  int occ_slice[kSliceKernels][2] = {};  // the frame-slice kernels at 8 waves (raw / delta)
 };
 DeviceInfo g_devinfo[kMaxDevices];
 
@@ -2179,12 +2137,12 @@ const DeviceInfo *device_info(hipStream_t s) {
     d.occ[1][nw] = occupancy_query<true>(nw);
   }
 #if !MH_LANE_PAIRS
-  d.occ_frames[0] = occupancy_of(mh_decode_multitable_kernel<false>, kMaxWavesPerWG);
-  d.occ_frames[1] = occupancy_of(mh_decode_multitable_kernel<true>, kMaxWavesPerWG);
-  d.occ_headers[0] = occupancy_of(mh_decode_headers_kernel<false>, kMaxWavesPerWG);
-  d.occ_headers[1] = occupancy_of(mh_decode_headers_kernel<true>, kMaxWavesPerWG);
-  d.occ_region[0] = occupancy_of(mh_decode_region_kernel<false>, kMaxWavesPerWG);
-  d.occ_region[1] = occupancy_of(mh_decode_region_kernel<true>, kMaxWavesPerWG);
+  d.occ_slice[kSliceFrames][0] = occupancy_of(mh_decode_multitable_kernel<false>, kMaxWavesPerWG);
+  d.occ_slice[kSliceFrames][1] = occupancy_of(mh_decode_multitable_kernel<true>, kMaxWavesPerWG);
+  d.occ_slice[kSliceHeaders][0] = occupancy_of(mh_decode_headers_kernel<false>, kMaxWavesPerWG);
+  d.occ_slice[kSliceHeaders][1] = occupancy_of(mh_decode_headers_kernel<true>, kMaxWavesPerWG);
+  d.occ_slice[kSliceRegion][0] = occupancy_of(mh_decode_region_kernel<false>, kMaxWavesPerWG);
+  d.occ_slice[kSliceRegion][1] = occupancy_of(mh_decode_region_kernel<true>, kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -2252,55 +2210,86 @@ int launch(const DecodeArgs &a0, hipStream_t s, bool lane_pairs, bool any_order)
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 
-// The argument checks of the decode entry points, all before any HIP call. `luts`: the
-// per-frame-table entry (mh_decode_frames), which ignores the frame's own table fields and
-// checks d_luts / lut_stride in their place, rule by rule in the same order. `regional`: the
-// region entry (mh_decode_region), whose region is checked with the dims, whose pixel size
-// RW x RH stands where W x H does in the pitch and stride rules, and which takes a stride of 0
-// (one table for all frames).
+bool dims_ok(const mh_dims &d) {
+  return d.width && d.height && d.width <= MH_MAX_DIM && d.height <= MH_MAX_DIM &&
+         d.block_width == (d.width + 7) / 8 && d.block_height == (d.height + 7) / 8;
+}
+
+// A region's raster and tiling: pixel size pw x ph (the frame's edge clips the last blocks),
+// S = ceil(bw / 64) tiles per block row, bh * S tiles per frame (<= 8192 * 128).
+// false: the region is empty or leaves the frame (`d` has passed dims_ok).
+struct RegionExtent {
+  uint64_t pw, ph;
+  uint32_t segs, tiles;
+};
+bool region_extent(const mh_dims &d, const mh_region *rg, RegionExtent &e) {
+  if (!rg->bw || !rg->bh || (uint64_t)rg->bx0 + rg->bw > d.block_width ||
+      (uint64_t)rg->by0 + rg->bh > d.block_height)
+    return false;
+  const uint64_t x1 = 8ull * (rg->bx0 + rg->bw), y1 = 8ull * (rg->by0 + rg->bh);
+  e.pw = (x1 < d.width ? x1 : d.width) - 8ull * rg->bx0;
+  e.ph = (y1 < d.height ? y1 : d.height) - 8ull * rg->by0;
+  e.segs = (rg->bw + 63u) / 64u;
+  e.tiles = rg->bh * e.segs;
+  return true;
+}
+
+// Where an entry point's Huffman tables come from, and so which table rules it checks.
+struct TableRule {
+  enum Kind {
+    kInFrame,   // mh_decode: the frame's own table1 / table2 (+ optional d_lut)
+    kPrepared,  // mh_decode_frames: prepared tables at `ptr`, `stride` bytes apart
+    kHeaders,   // mh_decode_headers: canonical headers at `ptr`, no alignment or stride rule
+    kRegion,    // mh_decode_region: kPrepared over region `rg`; stride 0 is one table for all frames
+  } kind;
+  const void *ptr = nullptr;
+  uint64_t stride = 0;
+  const mh_region *rg = nullptr;
+};
+
+// The argument checks of the decode entry points, all before any HIP call. Every entry runs
+// the same rules in the same order; the frame's own table fields count only for kInFrame, and
+// the other kinds check `ptr` / `stride` in their place, rule by rule. A region is checked with
+// the dims, and its pixel size (*re) stands where W x H does in the pitch and stride rules.
 int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                      uint32_t allowed_flags, bool luts, const uint16_t *d_luts, uint64_t lut_stride,
-                      bool regional = false, const mh_region *rg = nullptr) {
+                      uint32_t allowed_flags, const TableRule &tr, RegionExtent *re = nullptr) {
+  const bool in_frame = tr.kind == TableRule::kInFrame, regional = tr.kind == TableRule::kRegion;
+  const bool prepared = tr.kind == TableRule::kPrepared || regional;
   if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
-  if (regional && !rg) return MH_ERR_INVALID_ARG;
-  if (luts ? !d_luts : (!fr->d_table1 || !fr->d_table2)) return MH_ERR_INVALID_ARG;
+  if (regional && !tr.rg) return MH_ERR_INVALID_ARG;
+  if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !tr.ptr) return MH_ERR_INVALID_ARG;
   if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
   if (fr->flags & ~allowed_flags) return MH_ERR_INVALID_ARG;
   const mh_dims &d = fr->dims;
-  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
-      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
-    return MH_ERR_DIMS;
+  if (!dims_ok(d)) return MH_ERR_DIMS;
   uint64_t pw = d.width, ph = d.height;  // the raster's pixel size
   if (regional) {
-    if (!rg->bw || !rg->bh || (uint64_t)rg->bx0 + rg->bw > d.block_width ||
-        (uint64_t)rg->by0 + rg->bh > d.block_height)
-      return MH_ERR_DIMS;
-    const uint64_t x1 = 8ull * (rg->bx0 + rg->bw), y1 = 8ull * (rg->by0 + rg->bh);
-    pw = (x1 < d.width ? x1 : d.width) - 8ull * rg->bx0;
-    ph = (y1 < d.height ? y1 : d.height) - 8ull * rg->by0;
+    if (!region_extent(d, tr.rg, *re)) return MH_ERR_DIMS;
+    pw = re->pw;
+    ph = re->ph;
   }
-  if (!luts && (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
-                fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
+  if (in_frame && (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
+                   fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
     return MH_ERR_TABLE;
   if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & 7u) || ((uintptr_t)d_out & 7u) ||
       (fr->n_frames > 1 && (out_frame_stride & 7u)))
     return MH_ERR_ALIGN;
-  if (luts ? (((uintptr_t)d_luts & 15u) || (lut_stride & 15u)) : (((uintptr_t)fr->d_lut & 15u) != 0))
+  if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)tr.ptr & 15u) || (tr.stride & 15u))))
     return MH_ERR_ALIGN;
   if (out_pitch < pw || out_pitch > (1u << 20) || (fr->n_frames > 1 && out_frame_stride < out_pitch * ph))
     return MH_ERR_CAPACITY;
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
     return MH_ERR_CAPACITY;
-  if (luts && lut_stride < (uint64_t)kPreparedBytes && !(regional && lut_stride == 0))
+  if (prepared && tr.stride < (uint64_t)kPreparedBytes && !(regional && tr.stride == 0))
     return MH_ERR_CAPACITY;  // mh_lut_bytes()
   return MH_OK;
 }
 
 // DecodeArgs from a checked frame (tables excepted); MH_ERR_CAPACITY past 2^31 - 1 tiles.
-// Not `frame_tiles`: the tile counts are left to the caller (region_args: a region's tiles).
+// With `re` the raster and the tiles are the region's, not the frame's.
 int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                     DecodeArgs &a, bool frame_tiles = true) {
+                     DecodeArgs &a, const RegionExtent *re = nullptr) {
   const mh_dims &d = fr->dims;
   a.offsets = fr->d_block_offsets;
   a.codes = fr->d_codes;
@@ -2310,14 +2299,13 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
   a.out = d_out;
   a.out_pitch = out_pitch;
   a.out_frame_stride = out_frame_stride;
-  a.out_frame_bytes = (uint64_t)d.height * out_pitch;
+  a.out_frame_bytes = (re ? re->ph : (uint64_t)d.height) * out_pitch;
   a.w = d.width;
   a.h = d.height;
   a.bw = d.block_width;
   a.bh = d.block_height;
   a.nb = d.block_width * d.block_height;
-  if (!frame_tiles) return MH_OK;
-  a.tiles_per_frame = (a.nb + 63) / 64;
+  a.tiles_per_frame = re ? re->tiles : (a.nb + 63) / 64;
   const uint64_t total = (uint64_t)a.tiles_per_frame * fr->n_frames;
   if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
   a.total_tiles = (uint32_t)total;
@@ -2325,78 +2313,59 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
 }
 
 #if !MH_LANE_PAIRS
-// mh_decode_frames' launch shape: G workgroups of 8 waves per frame,
+// The frame-slice kernels' launch shape: G workgroups of 8 waves per frame,
 //   G = clamp(ceil(R / n_frames), 1, ceil(tiles_per_frame / 8)),
 // R = the workgroups resident on the device at once (CUs x the kernel's occupancy): about
 // one resident round when the frames are few, one workgroup per frame when they are many.
-// `headers`: the shape of mh_decode_headers, the same rule with its kernel's occupancy.
-// `region`: the shape of mh_decode_region, the same rule over the region's tiles.
-int frames_shape(uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s, uint32_t *groups,
-                 bool headers = false, bool region = false) {
+// One rule for the three kernels, each with its own occupancy and (a region) its own tiles.
+int slice_shape(SliceKernel k, uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s,
+                uint32_t *groups) {
   const DeviceInfo *di = device_info(s);
   if (!di) return MH_ERR_HIP;
-  const int occ = (region ? di->occ_region : headers ? di->occ_headers : di->occ_frames)[delta ? 1 : 0];
-  const uint64_t resident = (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)occ;
+  const uint64_t resident =
+      (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)di->occ_slice[k][delta ? 1 : 0];
   const uint64_t want = (resident + n_frames - 1) / n_frames;
   const uint64_t most = (tiles_per_frame + (uint32_t)kMaxWavesPerWG - 1) / (uint32_t)kMaxWavesPerWG;
   *groups = (uint32_t)(want < 1 ? 1 : want > most ? most : want);
   return MH_OK;
 }
 
-template <bool kDelta>
-int launch_frames(const DecodeArgs &a, uint32_t n_frames, const uint8_t *luts, uint64_t lut_stride,
-                  const int32_t *status, hipStream_t s, bool any_order) {
+// One launch of a frame-slice kernel. The kernels' argument lists differ only in the table
+// arguments on either side of `status` (prepared tables: luts, stride; headers: headers, verdict)
+// and in the region's scalars (`tail`), which follow the group count.
+template <class Kernel, class Table, class TableAux, class... Tail>
+int launch_slices(Kernel kernel, SliceKernel k, bool delta, const DecodeArgs &a, uint32_t n_frames, hipStream_t s,
+                  bool any_order, Table table, const int32_t *status, TableAux aux, Tail... tail) {
   uint32_t G = 0;
-  const int rc = frames_shape(n_frames, a.tiles_per_frame, kDelta, s, &G);
+  const int rc = slice_shape(k, n_frames, a.tiles_per_frame, delta, s, &G);
   if (rc != MH_OK) return rc;
   const uint64_t grid = (uint64_t)G * n_frames;
   if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  MH_LAUNCH(mh_decode_multitable_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
-            a.offsets, a.frame_off, a.block_init, luts, status, lut_stride, a.nb, a.tiles_per_frame, G, a);
+  MH_LAUNCH(kernel, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order, a.offsets, a.frame_off,
+            a.block_init, table, status, aux, a.nb, a.tiles_per_frame, G, tail..., a);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 
-template <bool kDelta>
-int launch_headers(const DecodeArgs &a, uint32_t n_frames, const uint8_t *headers, const int32_t *status,
-                   int32_t *header_status, hipStream_t s, bool any_order) {
-  uint32_t G = 0;
-  const int rc = frames_shape(n_frames, a.tiles_per_frame, kDelta, s, &G, true);
+// mh_decode_{frames,headers,region}_shape: slice_shape for a frame description (`rg`: kSliceRegion only).
+int slice_shape_entry(SliceKernel k, const mh_frame *fr, const mh_region *rg, void *stream,
+                      uint32_t *groups_per_frame, uint32_t *waves_per_group) {
+  if (!fr || (k == kSliceRegion && !rg) || !groups_per_frame || !waves_per_group || fr->n_frames == 0)
+    return MH_ERR_INVALID_ARG;
+  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
+  const mh_dims &d = fr->dims;
+  if (!dims_ok(d)) return MH_ERR_DIMS;
+  uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
+  if (k == kSliceRegion) {
+    RegionExtent re;
+    if (!region_extent(d, rg, re)) return MH_ERR_DIMS;
+    tiles = re.tiles;
+    if ((uint64_t)tiles * fr->n_frames > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  }
+  const int rc = slice_shape(k, fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
+                             groups_per_frame);
   if (rc != MH_OK) return rc;
-  const uint64_t grid = (uint64_t)G * n_frames;
-  if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  MH_LAUNCH(mh_decode_headers_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
-            a.offsets, a.frame_off, a.block_init, headers, status, header_status, a.nb, a.tiles_per_frame, G, a);
-  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
-}
-
-// A checked region's tiling: S = ceil(bw / 64) tiles per block row, bh * S tiles per frame.
-// DecodeArgs of fill_decode_args turned into the region kernel's: the raster is RH rows, the
-// tiles are the region's. MH_ERR_CAPACITY past 2^31 - 1 tiles.
-int region_args(const mh_frame *fr, const mh_region *rg, DecodeArgs &a, uint32_t *segs) {
-  const uint32_t S = (rg->bw + 63u) / 64u;
-  const uint64_t y1 = 8ull * (rg->by0 + rg->bh);
-  const uint64_t rh = (y1 < fr->dims.height ? y1 : fr->dims.height) - 8ull * rg->by0;
-  a.out_frame_bytes = rh * a.out_pitch;
-  a.tiles_per_frame = rg->bh * S;  // <= 8192 * 128
-  const uint64_t total = (uint64_t)a.tiles_per_frame * fr->n_frames;
-  if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  a.total_tiles = (uint32_t)total;
-  *segs = S;
+  *waves_per_group = kMaxWavesPerWG;
   return MH_OK;
-}
-
-template <bool kDelta>
-int launch_region(const DecodeArgs &a, uint32_t n_frames, const mh_region *rg, uint32_t segs, const uint8_t *luts,
-                  uint64_t lut_stride, const int32_t *status, hipStream_t s, bool any_order) {
-  uint32_t G = 0;
-  const int rc = frames_shape(n_frames, a.tiles_per_frame, kDelta, s, &G, false, true);
-  if (rc != MH_OK) return rc;
-  const uint64_t grid = (uint64_t)G * n_frames;
-  if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  MH_LAUNCH(mh_decode_region_kernel<kDelta>, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order,
-            a.offsets, a.frame_off, a.block_init, luts, status, lut_stride, a.nb, a.tiles_per_frame, G, segs,
-            rg->bw, rg->bx0, rg->by0, a);
-  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 #endif
 
@@ -2462,7 +2431,7 @@ int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_f
   // MH_FLAG_LANE_PAIRS: honoured by the diagnostic library only; the product library accepts
   // it (callers built against round-4 libraries pass it) and decodes with the default kernels
   int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride,
-                             MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER | MH_FLAG_LANE_PAIRS, false, nullptr, 0);
+                             MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER | MH_FLAG_LANE_PAIRS, {TableRule::kInFrame});
   if (rc != MH_OK) return rc;
   DecodeArgs a{};
   a.t1 = reinterpret_cast<const uint16_t *>(fr->d_table1);
@@ -2478,113 +2447,68 @@ int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_f
 }
 
 #if !MH_LANE_PAIRS
+// The three frame-slice entries: t1 / t2 / lut of DecodeArgs stay null, every workgroup takes
+// its frame's table from d_luts or builds it from the frame's header.
 int mh_decode_frames(const mh_frame *fr, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                      const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                      void *stream) {
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, true,
-                             d_luts, lut_stride_bytes);
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
+                             {TableRule::kPrepared, d_luts, lut_stride_bytes});
   if (rc != MH_OK) return rc;
-  DecodeArgs a{};  // t1 / t2 / lut stay null: every workgroup takes its frame's table from d_luts
+  DecodeArgs a{};
   rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
   if (rc != MH_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
   const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
-  const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return (fr->flags & MH_FLAG_NO_DELTA)
-             ? launch_frames<false>(a, fr->n_frames, luts, lut_stride_bytes, d_frame_status, s, ao)
-             : launch_frames<true>(a, fr->n_frames, luts, lut_stride_bytes, d_frame_status, s, ao);
+  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return launch_slices(delta ? mh_decode_multitable_kernel<true> : mh_decode_multitable_kernel<false>, kSliceFrames,
+                       delta, a, fr->n_frames, (hipStream_t)stream, ao, luts, d_frame_status, lut_stride_bytes);
 }
 
 int mh_decode_frames_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame,
                            uint32_t *waves_per_group) {
-  if (!fr || !groups_per_frame || !waves_per_group || fr->n_frames == 0) return MH_ERR_INVALID_ARG;
-  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
-  const mh_dims &d = fr->dims;
-  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
-      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
-    return MH_ERR_DIMS;
-  const uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
-  const int rc = frames_shape(fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
-                              groups_per_frame);
-  if (rc != MH_OK) return rc;
-  *waves_per_group = kMaxWavesPerWG;
-  return MH_OK;
+  return slice_shape_entry(kSliceFrames, fr, nullptr, stream, groups_per_frame, waves_per_group);
 }
 
 int mh_decode_headers(const mh_frame *fr, const uint8_t *d_canon_headers, const int32_t *d_frame_status,
                       int32_t *d_header_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                       void *stream) {
   if (d_header_status && d_header_status == d_frame_status) return MH_ERR_INVALID_ARG;
-  // mh_decode_frames' checks in its order; the headers stand where d_luts does (NULL ->
-  // MH_ERR_INVALID_ARG) and have no alignment or stride rule of their own
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, true,
-                             d_canon_headers ? reinterpret_cast<const uint16_t *>(uintptr_t{16}) : nullptr,
-                             (uint64_t)kPreparedBytes);
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
+                             {TableRule::kHeaders, d_canon_headers});
   if (rc != MH_OK) return rc;
-  DecodeArgs a{};  // t1 / t2 / lut stay null: every workgroup builds its frame's table from the header
+  DecodeArgs a{};
   rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
   if (rc != MH_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return (fr->flags & MH_FLAG_NO_DELTA)
-             ? launch_headers<false>(a, fr->n_frames, d_canon_headers, d_frame_status, d_header_status, s, ao)
-             : launch_headers<true>(a, fr->n_frames, d_canon_headers, d_frame_status, d_header_status, s, ao);
+  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return launch_slices(delta ? mh_decode_headers_kernel<true> : mh_decode_headers_kernel<false>, kSliceHeaders, delta,
+                       a, fr->n_frames, (hipStream_t)stream, ao, d_canon_headers, d_frame_status, d_header_status);
 }
 
 int mh_decode_headers_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame,
                             uint32_t *waves_per_group) {
-  if (!fr || !groups_per_frame || !waves_per_group || fr->n_frames == 0) return MH_ERR_INVALID_ARG;
-  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
-  const mh_dims &d = fr->dims;
-  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
-      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
-    return MH_ERR_DIMS;
-  const uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
-  const int rc = frames_shape(fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
-                              groups_per_frame, true);
-  if (rc != MH_OK) return rc;
-  *waves_per_group = kMaxWavesPerWG;
-  return MH_OK;
+  return slice_shape_entry(kSliceHeaders, fr, nullptr, stream, groups_per_frame, waves_per_group);
 }
 
 int mh_decode_region(const mh_frame *fr, const mh_region *rg, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                      const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                      void *stream) {
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, true,
-                             d_luts, lut_stride_bytes, true, rg);
+  RegionExtent re;
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
+                             {TableRule::kRegion, d_luts, lut_stride_bytes, rg}, &re);
   if (rc != MH_OK) return rc;
-  DecodeArgs a{};  // t1 / t2 / lut stay null: every workgroup takes its frame's table from d_luts
-  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a, false);
+  DecodeArgs a{};
+  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a, &re);
   if (rc != MH_OK) return rc;
-  uint32_t segs = 0;
-  rc = region_args(fr, rg, a, &segs);
-  if (rc != MH_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
   const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
-  const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return (fr->flags & MH_FLAG_NO_DELTA)
-             ? launch_region<false>(a, fr->n_frames, rg, segs, luts, lut_stride_bytes, d_frame_status, s, ao)
-             : launch_region<true>(a, fr->n_frames, rg, segs, luts, lut_stride_bytes, d_frame_status, s, ao);
+  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return launch_slices(delta ? mh_decode_region_kernel<true> : mh_decode_region_kernel<false>, kSliceRegion, delta, a,
+                       fr->n_frames, (hipStream_t)stream, ao, luts, d_frame_status, lut_stride_bytes, re.segs, rg->bw,
+                       rg->bx0, rg->by0);
 }
 
 int mh_decode_region_shape(const mh_frame *fr, const mh_region *rg, void *stream, uint32_t *groups_per_frame,
                            uint32_t *waves_per_group) {
-  if (!fr || !rg || !groups_per_frame || !waves_per_group || fr->n_frames == 0) return MH_ERR_INVALID_ARG;
-  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
-  const mh_dims &d = fr->dims;
-  if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
-      d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)
-    return MH_ERR_DIMS;
-  if (!rg->bw || !rg->bh || (uint64_t)rg->bx0 + rg->bw > d.block_width ||
-      (uint64_t)rg->by0 + rg->bh > d.block_height)
-    return MH_ERR_DIMS;
-  const uint32_t tiles = rg->bh * ((rg->bw + 63u) / 64u);
-  if ((uint64_t)tiles * fr->n_frames > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  const int rc = frames_shape(fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
-                              groups_per_frame, false, true);
-  if (rc != MH_OK) return rc;
-  *waves_per_group = kMaxWavesPerWG;
-  return MH_OK;
+  return slice_shape_entry(kSliceRegion, fr, rg, stream, groups_per_frame, waves_per_group);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

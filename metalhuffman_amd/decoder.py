@@ -314,16 +314,54 @@ def _frames_entry(frames: DeviceFrames, extra_flags: int = 0):
     return fr, cache[3]
 
 
+def _out_raster(frames: DeviceFrames, out: Optional[torch.Tensor], h: int, pitch: int, dev_index: int,
+                stream: Optional[torch.cuda.Stream]) -> torch.Tensor:
+    """decode()'s `out` contract for a raster of h rows: allocated (on `stream`) when None,
+    validated otherwise."""
+    if out is None:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=frames.codes.device)
+    sh = out.shape
+    if (out.dtype is not torch.uint8 or len(sh) < 2 or sh[-1] != pitch or sh[-2] != h
+            or out.get_device() != dev_index or not out.is_contiguous()
+            or out.numel() < frames.n_frames * h * pitch):
+        raise ValueError(f"out must be a contiguous uint8 [{frames.n_frames}, {h}, {pitch}] "
+                         f"tensor on cuda:{dev_index}")
+    return out
+
+
+def _raw_stream_ptr(stream: Optional[torch.cuda.Stream], dev_index: int) -> int:
+    if stream is not None:
+        return stream.cuda_stream
+    if _raw_stream is not None:
+        return _raw_stream(dev_index)
+    return torch.cuda.current_stream(dev_index).cuda_stream
+
+
+def _check_table_set(ts: DeviceTableSet, frames: DeviceFrames, dev_index: int) -> None:
+    if (ts.n_tables != frames.n_frames or ts.luts.get_device() != dev_index
+            or ts.luts.dtype is not torch.uint8 or not ts.luts.is_contiguous()
+            or ts.status.get_device() != dev_index or ts.status.dtype is not torch.int32
+            or ts.status.numel() != frames.n_frames or not ts.status.is_contiguous()):
+        raise ValueError(f"the table set must hold {frames.n_frames} tables on cuda:{dev_index}")
+
+
+def _slice_shape(entry: str, frames: DeviceFrames, stream: Optional[torch.cuda.Stream], extra_flags: int,
+                 region=None) -> tuple:
+    """(workgroups per frame, waves per workgroup) from the C entry `entry` (mh_decode_*_shape)."""
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    rg = () if region is None else (ctypes.byref(_region_struct(frames, region)),)
+    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
+    N.check(getattr(N.lib(), entry)(ctypes.byref(fr), *rg, sp, ctypes.byref(g), ctypes.byref(w)), entry)
+    return int(g.value), int(w.value)
+
+
 def decode_frames_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
                         extra_flags: int = 0) -> tuple:
     """(workgroups per frame, waves per workgroup) decode_frames would launch with
     (mh_decode_frames_shape)."""
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
-    N.check(N.lib().mh_decode_frames_shape(ctypes.byref(fr), sp, ctypes.byref(g), ctypes.byref(w)),
-            "mh_decode_frames_shape")
-    return int(g.value), int(w.value)
+    return _slice_shape("mh_decode_frames_shape", frames, stream, extra_flags)
 
 
 def decode_frames(frames, table_set="cuda", out: Optional[torch.Tensor] = None,
@@ -346,29 +384,11 @@ def decode_frames(frames, table_set="cuda", out: Optional[torch.Tensor] = None,
     fr, dev_index = _frames_entry(frames, extra_flags)
     if fr.flags & N.MH_FLAG_LANE_PAIRS:
         raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_frames")
-    if (table_set.n_tables != frames.n_frames or table_set.luts.get_device() != dev_index
-            or table_set.luts.dtype is not torch.uint8 or not table_set.luts.is_contiguous()
-            or table_set.status.get_device() != dev_index or table_set.status.dtype is not torch.int32
-            or table_set.status.numel() != frames.n_frames or not table_set.status.is_contiguous()):
-        raise ValueError(f"the table set must hold {frames.n_frames} tables on cuda:{dev_index}")
+    _check_table_set(table_set, frames, dev_index)
     pitch = (frames.width + 7) // 8 * 8
     h = frames.height
-    if out is None:
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            out = torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=frames.codes.device)
-    else:
-        sh = out.shape
-        if (out.dtype is not torch.uint8 or len(sh) < 2 or sh[-1] != pitch or sh[-2] != h
-                or out.get_device() != dev_index or not out.is_contiguous()
-                or out.numel() < frames.n_frames * h * pitch):
-            raise ValueError(f"out must be a contiguous uint8 [{frames.n_frames}, {h}, {pitch}] "
-                             f"tensor on cuda:{dev_index}")
-    if stream is not None:
-        sp = stream.cuda_stream
-    elif _raw_stream is not None:
-        sp = _raw_stream(dev_index)
-    else:
-        sp = torch.cuda.current_stream(dev_index).cuda_stream
+    out = _out_raster(frames, out, h, pitch, dev_index, stream)
+    sp = _raw_stream_ptr(stream, dev_index)
     rc = N.lib().mh_decode_frames(ctypes.byref(fr), table_set.luts.data_ptr(), table_set.stride,
                                   table_set.status.data_ptr() if skip_rejected else None, out.data_ptr(), pitch,
                                   h * pitch, sp)
@@ -416,13 +436,7 @@ def decode_region_shape(frames: DeviceFrames, region, stream: Optional[torch.cud
                         extra_flags: int = 0) -> tuple:
     """(workgroups per frame, waves per workgroup) decode_region would launch with
     (mh_decode_region_shape)."""
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    rg = _region_struct(frames, region)
-    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
-    N.check(N.lib().mh_decode_region_shape(ctypes.byref(fr), ctypes.byref(rg), sp, ctypes.byref(g), ctypes.byref(w)),
-            "mh_decode_region_shape")
-    return int(g.value), int(w.value)
+    return _slice_shape("mh_decode_region_shape", frames, stream, extra_flags, region)
 
 
 def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tensor] = None,
@@ -444,32 +458,14 @@ def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tens
             raise ValueError(f"the table must live on cuda:{dev_index}")
         luts, stride, status = tables.lut, 0, None
     elif isinstance(tables, DeviceTableSet):
-        if (tables.n_tables != frames.n_frames or tables.luts.get_device() != dev_index
-                or tables.luts.dtype is not torch.uint8 or not tables.luts.is_contiguous()
-                or tables.status.get_device() != dev_index or tables.status.dtype is not torch.int32
-                or tables.status.numel() != frames.n_frames or not tables.status.is_contiguous()):
-            raise ValueError(f"the table set must hold {frames.n_frames} tables on cuda:{dev_index}")
+        _check_table_set(tables, frames, dev_index)
         luts, stride, status = tables.luts, tables.stride, tables.status if skip_rejected else None
     else:
         raise TypeError("decode_region takes a DeviceTables or a DeviceTableSet")
     pitch = 8 * rg.bw
     h = min(frames.height, 8 * (rg.by0 + rg.bh)) - 8 * rg.by0
-    if out is None:
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            out = torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=frames.codes.device)
-    else:
-        sh = out.shape
-        if (out.dtype is not torch.uint8 or len(sh) < 2 or sh[-1] != pitch or sh[-2] != h
-                or out.get_device() != dev_index or not out.is_contiguous()
-                or out.numel() < frames.n_frames * h * pitch):
-            raise ValueError(f"out must be a contiguous uint8 [{frames.n_frames}, {h}, {pitch}] "
-                             f"tensor on cuda:{dev_index}")
-    if stream is not None:
-        sp = stream.cuda_stream
-    elif _raw_stream is not None:
-        sp = _raw_stream(dev_index)
-    else:
-        sp = torch.cuda.current_stream(dev_index).cuda_stream
+    out = _out_raster(frames, out, h, pitch, dev_index, stream)
+    sp = _raw_stream_ptr(stream, dev_index)
     rc = N.lib().mh_decode_region(ctypes.byref(fr), ctypes.byref(rg), luts.data_ptr(), stride,
                                   status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
                                   h * pitch, sp)
@@ -493,12 +489,7 @@ def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Strea
                          extra_flags: int = 0) -> tuple:
     """(workgroups per frame, waves per workgroup) decode_headers would launch with
     (mh_decode_headers_shape)."""
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
-    N.check(N.lib().mh_decode_headers_shape(ctypes.byref(fr), sp, ctypes.byref(g), ctypes.byref(w)),
-            "mh_decode_headers_shape")
-    return int(g.value), int(w.value)
+    return _slice_shape("mh_decode_headers_shape", frames, stream, extra_flags)
 
 
 def decode_headers(frames: DeviceFrames, canons, out: Optional[torch.Tensor] = None,
@@ -527,22 +518,8 @@ def decode_headers(frames: DeviceFrames, canons, out: Optional[torch.Tensor] = N
             raise ValueError(f"{name} must be a contiguous int32 [{frames.n_frames}] tensor on cuda:{dev_index}")
     pitch = (frames.width + 7) // 8 * 8
     h = frames.height
-    if out is None:
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            out = torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=dev)
-    else:
-        sh = out.shape
-        if (out.dtype is not torch.uint8 or len(sh) < 2 or sh[-1] != pitch or sh[-2] != h
-                or out.get_device() != dev_index or not out.is_contiguous()
-                or out.numel() < frames.n_frames * h * pitch):
-            raise ValueError(f"out must be a contiguous uint8 [{frames.n_frames}, {h}, {pitch}] "
-                             f"tensor on cuda:{dev_index}")
-    if stream is not None:
-        sp = stream.cuda_stream
-    elif _raw_stream is not None:
-        sp = _raw_stream(dev_index)
-    else:
-        sp = torch.cuda.current_stream(dev_index).cuda_stream
+    out = _out_raster(frames, out, h, pitch, dev_index, stream)
+    sp = _raw_stream_ptr(stream, dev_index)
     rc = N.lib().mh_decode_headers(ctypes.byref(fr), hdr.data_ptr(),
                                    frame_status.data_ptr() if frame_status is not None else None,
                                    header_status.data_ptr() if header_status is not None else None,
