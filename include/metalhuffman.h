@@ -306,6 +306,52 @@ int mh_decode_region(const mh_frame *frame, const mh_region *region, const uint1
 int mh_decode_region_shape(const mh_frame *frame, const mh_region *region, void *stream,
                            uint32_t *groups_per_frame, uint32_t *waves_per_group);
 
+/* ---------------------------------------------------------------------- */
+/* A region at 1/2, 1/4 or 1/8 scale in one launch: an overview of a large scan, a thumbnail  */
+/* strip of a sequence, a pyramid level. One lane decodes one 8x8 block, and a 2x2, 4x4 or    */
+/* 8x8 box never crosses a block, so the decoder averages in registers and stores 1/4, 1/16   */
+/* or 1/64 of the raster; no full-size raster exists. Not covered: scaling for mh_decode,     */
+/* mh_decode_frames and mh_decode_headers (the whole frame is the full region); the streams;  */
+/* the multi-GPU paths; scales other than 2, 4 and 8; any filter other than the box.          */
+
+/* mh_decode_region at scale s = 2^log2_scale; c = 8 >> log2_scale is the number of output
+ * bytes per block and output row. With RW / RH mh_decode_region's, the scaled size is
+ *   SW = ceil(RW / s),  SH = ceil(RH / s).
+ * Output: frame f, output row Y starts at d_out + f * out_frame_stride + Y * out_pitch; bw * c
+ * (= round_up(SW, c)) bytes of every row Y < SH are written and nothing else is touched.
+ * Pixel (X, Y), X < SW: over the region pixels (x, y) with s X <= x < min(s (X + 1), RW) and
+ * s Y <= y < min(s (Y + 1), RH) -- n of them, of sum S in the raster mh_decode_region writes --
+ * the byte is floor((2 S + n) / (2 n)): the mean of the cell's pixels INSIDE the frame, halves
+ * rounded up. An edge block's padding never enters S or n. Bytes at X >= SW (cells of a
+ * right-edge block wholly outside the frame) are written as 0. A region starts on a block and s
+ * divides 8, so cells are those of the whole frame's grid: a scaled region is the matching
+ * rectangle of the scaled whole frame.
+ * log2_scale == 0 is mh_decode_region (same checks, same kernel, same bytes); 1, 2, 3 are
+ * kernels of their own; > 3 -> MH_ERR_INVALID_ARG, reported where a bad flag is.
+ * Tables, d_frame_status, d_block_init and flags: mh_decode_region's.
+ * Checks: all before any HIP call, in mh_decode_region's order and with its codes, with SW / SH
+ * in the place of RW / RH (out_pitch >= SW, out_frame_stride >= out_pitch * SH) and c in the
+ * place of 8 in the alignment rules (d_out, out_pitch and, for n_frames > 1, out_frame_stride
+ * are multiples of c; at log2_scale 3 any pitch is legal).
+ * One kernel launch, asynchronous; tiles and the launch-shape rule are mh_decode_region's, with
+ * this kernel's own occupancy. */
+int mh_decode_region_scaled(const mh_frame *frame, const mh_region *region, uint32_t log2_scale,
+                            const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                            const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch,
+                            size_t out_frame_stride, void *stream);
+
+/* The launch shape mh_decode_region_scaled would use (no launch), as mh_decode_region_shape. */
+int mh_decode_region_scaled_shape(const mh_frame *frame, const mh_region *region, uint32_t log2_scale,
+                                  void *stream, uint32_t *groups_per_frame, uint32_t *waves_per_group);
+
+/* The CPU twin of that output stage: the same definition applied to a width x height raster in
+ * host memory (rows `pitch` bytes apart), writing ceil(width / s) x ceil(height / s) bytes into
+ * `out` (rows `out_pitch` apart) and nothing else. log2_scale 0..3; 0 copies.
+ * MH_ERR_INVALID_ARG: a NULL pointer, a zero size, log2_scale > 3; MH_ERR_CAPACITY: pitch <
+ * width or out_pitch < ceil(width / s). */
+int mh_box_reduce(const uint8_t *raster, uint32_t width, uint32_t height, size_t pitch,
+                  uint32_t log2_scale, uint8_t *out, size_t out_pitch);
+
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a
  * prepared table) and the 16-byte lengths word at their prepared-table offsets in

@@ -11,6 +11,8 @@ of mdejong/MetalHuffman).
   * decoder.decode_frames / DeviceTableSet   a batch with a table per frame, one launch
   * decoder.decode_headers          the same batch straight from its canonical headers (table built in-kernel)
   * decoder.decode_region / decode_rect   a block-aligned region (a pixel rectangle) of every frame, one launch
+  * decoder.decode_region_scaled / decode_scaled   a region (the frame) at 1/2, 1/4 or 1/8 scale, one launch:
+                                    box means taken in the decoder's registers; codec.box_reduce is the CPU twin
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync
@@ -19,12 +21,12 @@ of mdejong/MetalHuffman).
 """
 from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS, MH_FLAG_NO_DELTA,
                       MHError, lib)
-from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, code_lengths_limited, decode_frame_cpu,
-                    encode_frame, merge_blocks, split_blocks)
+from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, code_lengths_limited,
+                    decode_frame_cpu, encode_frame, merge_blocks, split_blocks)
 
 __all__ = [
     "EXPORTS", "LIB_PATH", "MH_CODES_PAD", "MH_FLAG_LANE_PAIRS", "MH_FLAG_NO_DELTA", "MHError", "lib", "BLOCK_DIM",
     "EncodedFrame", "Huffman", "block_grid", "decode_frame_cpu", "encode_frame", "merge_blocks", "split_blocks",
-    "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited",
+    "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce",
 ]
 __version__ = "0.1.0"

@@ -42,6 +42,7 @@ EXPORTS = (
     "mh_stream_create_headers", "mh_stream_submit_header", "mh_stream_slot_status",
     "mh_code_lengths_limited",
     "mh_decode_region", "mh_decode_region_shape",
+    "mh_decode_region_scaled", "mh_decode_region_scaled_shape", "mh_box_reduce",
 )
 
 
@@ -147,6 +148,12 @@ def lib() -> ctypes.CDLL:
         L.mh_decode_region.argtypes = [ctypes.POINTER(mh_frame), ctypes.POINTER(mh_region), _vp, ctypes.c_uint64, _vp,
                                        _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
         L.mh_decode_region_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.POINTER(mh_region), _vp, _u32p, _u32p]
+        L.mh_decode_region_scaled.argtypes = [ctypes.POINTER(mh_frame), ctypes.POINTER(mh_region), ctypes.c_uint32,
+                                              _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
+        L.mh_decode_region_scaled_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.POINTER(mh_region),
+                                                    ctypes.c_uint32, _vp, _u32p, _u32p]
+        L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
+                                    ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]
         L.mh_stream_create_headers.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint64, ctypes.c_uint32,
                                                ctypes.POINTER(_vp), ctypes.POINTER(_vp)]

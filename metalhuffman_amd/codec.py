@@ -308,3 +308,20 @@ def decode_frame_cpu(ef: EncodedFrame, threads: int = 1) -> np.ndarray:
                                         ef.height, ef.flags, _p(out), ef.width, int(threads)),
             "mh_decode_frame_cpu")
     return out
+
+
+def box_reduce(img: np.ndarray, log2_scale: int) -> np.ndarray:
+    """The H x W image at scale s = 2^log2_scale (0..3) -> u8[ceil(H / s), ceil(W / s)]: every
+    s x s cell's mean over its pixels inside the image, halves rounded up (mh_box_reduce, the CPU
+    twin of decode_region_scaled's output stage)."""
+    img = _u8(img)
+    if img.ndim != 2 or img.size == 0:
+        raise ValueError("expected a non-empty 2-D uint8 image")
+    k = int(log2_scale)
+    if k != log2_scale or not 0 <= k <= 3:
+        raise ValueError(f"log2_scale must be 0, 1, 2 or 3, not {log2_scale!r}")
+    h, w = img.shape
+    s = 1 << k
+    out = np.empty(((h + s - 1) // s, (w + s - 1) // s), np.uint8)
+    N.check(N.lib().mh_box_reduce(_p(img), w, h, w, k, _p(out), out.shape[1]), "mh_box_reduce")
+    return out

@@ -24,6 +24,7 @@
 #include <pthread.h>
 
 #include "../../include/metalhuffman.h"
+#include "mh_box.hpp"
 
 namespace {
 
@@ -353,6 +354,27 @@ int mh_decode_frame_cpu(const uint32_t *block_offsets, const uint8_t *codes, uin
     Pool::get().run(nt, nt, job);
   } catch (...) {
     return MH_ERR_CAPACITY;  // no exception crosses the C ABI
+  }
+  return MH_OK;
+}
+
+// The CPU twin of mh_decode_region_scaled's output stage: every s x s cell's in-frame mean,
+// rounded by the function the kernels round an edge cell with (mh_box.hpp).
+int mh_box_reduce(const uint8_t *raster, uint32_t width, uint32_t height, size_t pitch, uint32_t log2_scale,
+                  uint8_t *out, size_t out_pitch) {
+  if (!raster || !out || !width || !height || log2_scale > 3) return MH_ERR_INVALID_ARG;
+  const uint32_t s = 1u << log2_scale;
+  const uint32_t sw = (width + s - 1) >> log2_scale, sh = (height + s - 1) >> log2_scale;
+  if (pitch < width || out_pitch < sw) return MH_ERR_CAPACITY;
+  for (uint32_t Y = 0; Y < sh; ++Y) {
+    const uint32_t nh = std::min(s, height - Y * s);
+    for (uint32_t X = 0; X < sw; ++X) {
+      const uint32_t nw = std::min(s, width - X * s);
+      uint32_t sum = 0;
+      for (uint32_t y = 0; y < nh; ++y)
+        for (uint32_t x = 0; x < nw; ++x) sum += raster[(size_t)(Y * s + y) * pitch + X * s + x];
+      out[(size_t)Y * out_pitch + X] = (uint8_t)mh_box_round(sum, nw * nh);
+    }
   }
   return MH_OK;
 }

@@ -29,6 +29,7 @@
 #include <mutex>
 
 #include "../../include/metalhuffman.h"
+#include "mh_box.hpp"
 #include "mh_lut.hpp"
 
 namespace {
@@ -260,12 +261,118 @@ using Lut13Flat = StepCfg<kLutBits, true, false, true>;
 
 #if MH_DIAG_ROWS  // lane r of *rowv: the core clock behind row r's store; lane 8: at the chain's entry
 #define MH_ROWS_PARAM , uint32_t *rowv = nullptr
+#define MH_ROWS_NONE , nullptr  // a caller that names the output stage behind it
 #define MH_ROW_STAMP(r) \
   if (rowv) *rowv = (threadIdx.x & 63u) == (r) ? (uint32_t)__builtin_amdgcn_s_memtime() : *rowv
 #else
 #define MH_ROWS_PARAM
+#define MH_ROWS_NONE
 #define MH_ROW_STAMP(r) ((void)0)
 #endif
+
+// The output stage of a block row. decode_block and flat8_block finish every row of a block as
+// two packed words (byte i of o0 = pixel i, of o1 = pixel 4 + i); what becomes of them is a policy.
+//   StoreRows, the default: one 8-byte store per row at `off` -- a frame's or a region's raster.
+//   BoxRows<k> (mh_decode_region_scaled, k = 1..3): the block's s x s cells, s = 2^k, averaged
+//     over their IN-FRAME pixels, c = 8 >> k bytes per output row in one b32 / b16 / b8 store at
+//     rbase + (r >> k) * pitch (the lanes of a wave write 64 c contiguous bytes).
+//     Straight-line code, no branch and no select inside the decode chain: the chain leaves no
+//     SGPRs for either (every live comparison result is a pair of them; a wave-uniform "edge
+//     tile" branch per row or per rounding point cost the kernels 5 to 27 SGPR spills).
+//     Columns: each word passes a v_perm_b32 whose per-lane selectors (sel0 / sel1, once per
+//       tile) turn the bytes outside the frame into 0 -- all identity but in the frame's
+//       right-edge block. Rows: a row at or below the frame's bottom takes the all-zero selector
+//       (a scalar select and v_max_u32: identity selectors are below 0x0C0C0C0C as words).
+//     Sums: s = 2 keeps SWAR 16-bit pair sums, s = 4 and 8 a byte sum per word (v_sad_u8 against 0).
+//     Rounding, s = 2: a cell has 4, 2, 1 or 0 pixels, and the mean of 2 (1) pixels is the mean of
+//       the 4 with each counted twice (four times). So the selectors REPLICATE a lone last
+//       column into its neighbour, a lone last row is doubled by a scalar shift, and every cell
+//       rounds by (sum + 2) >> 2 -- exact, no division.
+//     Rounding, s = 4 and 8: a cell has n = nw * nh pixels, any of 0..s^2, and takes
+//       mh_box_round (mh_box.hpp; a 24-bit division, 2 and 1 per output row); nw is counted from
+//       the selectors, nh is scalar. n = 0 -- a cell wholly outside the frame -- gives byte 0.
+//     Dead lanes and rows >= SH store outside the descriptor as everywhere (OutTile).
+typedef unsigned int v2u32_t __attribute__((ext_vector_type(2)));
+struct StoreRows {
+  static constexpr int kLog2 = 0;
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t, uint32_t o0, uint32_t o1, uint32_t off,
+                                      uint32_t, uint32_t) {
+    v2u32_t v;
+    v.x = o0;
+    v.y = o1;
+    __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)off, 0, kAux);
+  }
+  // (the byte loops hold the row as a vector already)
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t, v2u32_t v, uint32_t off, uint32_t,
+                                      uint32_t) {
+    __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)off, 0, kAux);
+  }
+};
+
+template <int kLog2_>
+struct BoxRows {
+  static constexpr int kLog2 = kLog2_;
+  static_assert(kLog2 >= 1 && kLog2 <= 3, "cells of 2, 4 or 8 pixels");
+  static constexpr uint32_t kZeroSel = 0x0C0C0C0Cu;  // v_perm_b32: every byte the constant 0
+  uint32_t ch;          // in-frame rows of the tile's block row, 1..8 (wave-uniform)
+  uint32_t sel0, sel1;  // per lane: byte selectors of o0 / o1 (rows_of)
+  uint32_t a0 = 0, a1 = 0;  // k = 1: 16-bit sums of cells 0,1 / 2,3; k = 2: of cell 0 / 1; k = 3: a0 alone
+  // in-frame columns among the four of a word, from its selector (0x0C has bit 3, 0..3 have not)
+  static __device__ __forceinline__ uint32_t live_cols(uint32_t sel) { return 4u - (uint32_t)__popc(sel & 0x08080808u); }
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t r, uint32_t o0, uint32_t o1, uint32_t,
+                                      uint32_t rbase, uint32_t pitch) {
+    constexpr uint32_t s = 1u << kLog2;
+    const uint32_t dead = r >= ch ? kZeroSel : 0u;  // scalar
+    o0 = __builtin_amdgcn_perm(0u, o0, max(sel0, dead));
+    o1 = __builtin_amdgcn_perm(0u, o1, max(sel1, dead));
+    if constexpr (kLog2 == 1) {
+      a0 += (o0 & 0x00FF00FFu) + ((o0 >> 8) & 0x00FF00FFu);
+      a1 += (o1 & 0x00FF00FFu) + ((o1 >> 8) & 0x00FF00FFu);
+    } else if constexpr (kLog2 == 2) {
+      a0 = __builtin_amdgcn_sad_u8(o0, 0u, a0);
+      a1 = __builtin_amdgcn_sad_u8(o1, 0u, a1);
+    } else {
+      a0 = __builtin_amdgcn_sad_u8(o0, 0u, __builtin_amdgcn_sad_u8(o1, 0u, a0));
+    }
+    // the row is summed HERE, as a store would have consumed it here: left to the scheduler, the
+    // sums of a row sink towards the rounding and the rows' symbols stay live (1/8 scale, raw
+    // pixels, general step: 80 VGPRs and 12 bytes of scratch)
+    if constexpr (kLog2 == 3)
+      asm volatile("" : "+v"(a0));
+    else
+      asm volatile("" : "+v"(a0), "+v"(a1));
+    if ((r & (s - 1u)) != s - 1u) return;
+    const uint32_t Y = r >> kLog2;
+    uint32_t v;
+    if constexpr (kLog2 == 1) {
+      const uint32_t twice = r == ch ? 1u : 0u;  // scalar: row r - 1 is the frame's last, alone in its cell
+      v = __builtin_amdgcn_perm((((a1 << twice) + 0x00020002u) >> 2) & 0x00FF00FFu,
+                                (((a0 << twice) + 0x00020002u) >> 2) & 0x00FF00FFu, 0x06040200u);
+    } else {
+      const uint32_t nh = mh_box_cell_live(ch, Y, kLog2);  // scalar
+      if constexpr (kLog2 == 2)
+        v = mh_box_round(a0, nh * live_cols(sel0)) | (mh_box_round(a1, nh * live_cols(sel1)) << 8);
+      else
+        v = mh_box_round(a0, nh * (live_cols(sel0) + live_cols(sel1)));
+    }
+    const int off = (int)(rbase + Y * pitch);
+    if constexpr (kLog2 == 1)
+      __builtin_amdgcn_raw_buffer_store_b32(v, out, off, 0, kAux);
+    else if constexpr (kLog2 == 2)
+      __builtin_amdgcn_raw_buffer_store_b16((unsigned short)v, out, off, 0, kAux);
+    else
+      __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, out, off, 0, kAux);
+    a0 = a1 = 0u;
+  }
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t r, v2u32_t v, uint32_t off, uint32_t rbase,
+                                      uint32_t pitch) {
+    row<kAux>(out, r, v.x, v.y, off, rbase, pitch);
+  }
+};
 
 // One lane decodes one 8x8 block: 64 serial steps of AAPLShaders.metal:241-268
 // (cursor advance + delta fold); each finished 8-pixel block row is stored at once.
@@ -278,10 +385,11 @@ using Lut13Flat = StepCfg<kLutBits, true, false, true>;
 // at bits 1..kBits, i.e. the byte address of their u16 table entry; one add of the
 // entry's step word then advances sh and prev together (the low byte stays in
 // [kCur - 63, kCur], so it never borrows from prev).
-template <bool kDelta, class Cfg, class Src>
+template <bool kDelta, class Cfg, class Src, class Out = StoreRows>
 __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut, uint32_t p,
                                              uint32_t prev, __amdgpu_buffer_rsrc_t out,
-                                             uint32_t row0, uint32_t pitch, bool dead MH_ROWS_PARAM) {
+                                             uint32_t row0, uint32_t pitch, bool dead MH_ROWS_PARAM,
+                                             Out sink = Out()) {
   if constexpr (Cfg::kFlat8) {
     // 64 one-byte codes from bit p of the staged (big-endian word) span: 17 words, each
     // output word a 64-bit funnel shift (any bit alignment); code c is symbol c
@@ -316,7 +424,7 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
         v.x = bswap32(c[0]);
         v.y = bswap32(c[1]);
       }
-      __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)(rbase + r * pitch), 0, Cfg::kAux);
+      sink.template row<Cfg::kAux>(out, r, v, rbase + r * pitch, rbase, pitch);
     }
     return;
   }
@@ -434,12 +542,9 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
   // block and rows below the frame use offsets outside the descriptor's range,
   // which the hardware drops. A right-edge block writes its 8 bytes into the
   // row's pitch padding (pitch >= round_up(W, 8)).
-  typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
-  const auto store_row = [&](uint32_t o0, uint32_t o1, uint32_t off) {
-    v2u32 v;
-    v.x = o0;
-    v.y = o1;
-    __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)off, 0, Cfg::kAux);
+  // (StoreRows; another output stage takes the row number and works out its own offset)
+  const auto store_row = [&](uint32_t r, uint32_t o0, uint32_t o1, uint32_t off) {
+    sink.template row<Cfg::kAux>(out, r, o0, o1, off, rbase, pitch);
   };
   MH_ROW_STAMP(8);
   if constexpr (Cfg::kLazy) {
@@ -486,7 +591,7 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
         } else {
           MH_ISSUE_L();
         }
-        store_row(o0, o1, off);
+        store_row(r + q, o0, o1, off);
         off += pitch;
         MH_ROW_STAMP(r + q);
       }
@@ -511,7 +616,7 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
     MH_STEP_R(2, o1);
     MH_STEP(3, o1);
     if (kDelta) o1 = pack_prev4(sv[0], sv[1], sv[2], sv[3]);
-    store_row(o0, o1, rbase + r * pitch);
+    store_row(r, o0, o1, rbase + r * pitch);
     MH_ROW_STAMP(r);
   }
   }
@@ -561,6 +666,9 @@ struct FrameMap {
 struct RegionMap {
   static constexpr bool kRegion = true;
   uint32_t f, bx0, by0, bw, S;
+  // BoxRows only: the frame's pixels from the region's origin on, (W - 8 bx0) | (H - 8 by0) << 16
+  // (both <= 65535) -- one SGPR for a tile's edge facts, where W, H and the origin would be four
+  uint32_t rem = 0;
 };
 
 struct TileHdrBase {
@@ -719,16 +827,20 @@ struct OutTile {
   __amdgpu_buffer_rsrc_t rsrc;
   uint32_t row0;
 };
-template <class Map = FrameMap>
+template <class Map = FrameMap, int kLog2 = 0>
 __device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane) {
+  static_assert(Map::kRegion || kLog2 == 0, "only a region is decoded at a reduced scale");
   if constexpr (Map::kRegion) {
-    // based at region row 8 r and limited by RH * pitch (a.out_frame_bytes): rows >= RH are dropped
-    const uint64_t base = (uint64_t)t.r * 8u * a.out_pitch;
+    // based at region row 8 r and limited by RH * pitch (a.out_frame_bytes): rows >= RH are dropped.
+    // At scale 2^kLog2 a block row is c = 8 >> kLog2 output rows of c bytes per block, and the
+    // limit is SH * pitch.
+    constexpr uint32_t c = 8u >> kLog2;
+    const uint64_t base = (uint64_t)t.r * c * a.out_pitch;
     const uint64_t rem = a.out_frame_bytes > base ? a.out_frame_bytes - base : 0u;
     OutTile o;
     o.rsrc = uniform_rsrc(a.out + (uint64_t)t.f * a.out_frame_stride + base,
                           (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
-    o.row0 = (64u * t.s + lane) * 8u;
+    o.row0 = (64u * t.s + lane) * c;
     return o;
   } else {
     const uint32_t b = t.b0 + lane;
@@ -740,6 +852,30 @@ __device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Ma
     o.rsrc = uniform_rsrc(a.out + (uint64_t)t.f * a.out_frame_stride + base,
                           (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
     o.row0 = (by - by0) * 8u * (uint32_t)a.out_pitch + bx * 8u;
+    return o;
+  }
+}
+
+// A tile's output stage (StoreRows / BoxRows above). StoreRows has no state. BoxRows takes the
+// tile's edge facts: how many rows of its block row lie inside the frame (a region tile lies in
+// one block row, so this is wave-uniform) and the lane's column selectors.
+template <class Out, class Map>
+__device__ __forceinline__ Out rows_of(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane, const Map &m) {
+  if constexpr (Out::kLog2 == 0) {
+    return Out();
+  } else {
+    static_assert(Map::kRegion, "only a region is decoded at a reduced scale");
+    Out o;
+    const uint32_t cols = (m.rem & 0xFFFFu) - 512u * t.s;  // in-frame columns from the tile's first block on
+    o.ch = __builtin_amdgcn_readfirstlane(min(8u, (m.rem >> 16) - 8u * t.r));
+    const uint32_t cw = (uint32_t)min(max((int)cols - 8 * (int)lane, 0), 8);  // 0: a dead lane past the frame
+    // byte i of a word keeps selector i while its column is inside the frame, else the constant 0;
+    // at scale 2 a last column alone in its cell (cw odd) is copied into its neighbour
+    const uint64_t keep = cw >= 8u ? ~0ull : (1ull << (8u * cw)) - 1ull;
+    uint64_t sel = (0x0302010003020100ull & keep) | (0x0C0C0C0C0C0C0C0Cull & ~keep);
+    if (Out::kLog2 == 1 && (cw & 1u)) sel = (sel & ~(0xFFull << (8u * cw))) | ((uint64_t)((cw - 1u) & 3u) << (8u * cw));
+    o.sel0 = (uint32_t)sel;
+    o.sel1 = (uint32_t)(sel >> 32);
     return o;
   }
 }
@@ -794,10 +930,10 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 // Oversize tile: stage + decode lanes [0,32) then [32,64), each from its own span.
-template <bool kDelta, class Cfg, class Map = FrameMap>
+template <bool kDelta, class Cfg, class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
                                               const uint8_t *lut, uint8_t *stage,
-                                              __amdgpu_buffer_rsrc_t out, uint32_t row0, bool dead) {
+                                              __amdgpu_buffer_rsrc_t out, uint32_t row0, bool dead, Out sink = Out()) {
   const __amdgpu_buffer_rsrc_t rc = codes_rsrc(a, t);
   const uint32_t my_off = t.p + t.start * 8u;  // lane's absolute start bit
   const uint32_t fbits = t.fb32 > 0x1FFFFFFFu ? 0xFFFFFFFFu : t.fb32 * 8u;
@@ -835,7 +971,7 @@ __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<
     if (lane >= first && lane < first + 32u) {
       LdsWords src{stage};
       decode_block<kDelta, Cfg>(src, lut, t.valid ? my_off - start * 8u : 0u, t.init, out, row0,
-                                (uint32_t)a.out_pitch, dead);
+                                (uint32_t)a.out_pitch, dead MH_ROWS_NONE, sink);  // (a lane decodes in one half only)
     }
     wave_sync();
   }
@@ -863,7 +999,7 @@ __device__ __forceinline__ uint32_t next_tile(const DecodeArgs &a, uint32_t t, u
 // LDS window once tile i has finished reading it. One instantiation per flavour, entered
 // with nothing but the first header live (a flavour branch with the first span in
 // flight spilled: 80 VGPRs + 40 B of scratch).
-template <bool kDelta, class Cfg, class Map = FrameMap>
+template <bool kDelta, class Cfg, class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, uint8_t *stage,
                                            const uint8_t *lut, uint32_t t0, uint32_t gstride,
                                            const TileHdrOf<Map> &hc, bool synced MH_TS_PARAM, const Map &m = Map()) {
@@ -904,11 +1040,12 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     wave_sync();  // this tile's staging writes -> reads
     {
       const bool dead = !cur.valid;
-      const OutTile ot = out_tile<Map>(a, cur, lane);
+      const OutTile ot = out_tile<Map, Out::kLog2>(a, cur, lane);
       LdsWords src{stage};
       // waves with more tiles left run first (the arbiter otherwise favours the oldest)
       set_prio(min((a.total_tiles - 1u - cur.tile) / gstride, 3u));
-      decode_block<kDelta, Cfg>(src, lut, cur.p, cur.init, ot.rsrc, ot.row0, (uint32_t)a.out_pitch, dead);
+      decode_block<kDelta, Cfg>(src, lut, cur.p, cur.init, ot.rsrc, ot.row0, (uint32_t)a.out_pitch, dead MH_ROWS_NONE,
+                                rows_of<Out>(a, cur, lane, m));
     }
 #if MH_DIAG_STAMPS
     if (first_tile) MH_STAMP(4);
@@ -930,8 +1067,8 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     TileHdrOf<Map> h;
     hdr_issue(a, t, lane, h, m);
     const TileOf<Map> tt = hdr_resolve(a, h, lane, m);
-    const OutTile ot = out_tile<Map>(a, tt, lane);
-    decode_halves<kDelta, Cfg, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid);
+    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane);
+    decode_halves<kDelta, Cfg, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid, rows_of<Out>(a, tt, lane, m));
   }
 }
 
@@ -966,12 +1103,12 @@ __device__ __forceinline__ void flat8_issue(const DecodeArgs &a, const TileBase 
   c.w[16] = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(base + 64u), 0, 0);
 }
 
-template <bool kDelta, class Map = FrameMap>
+template <bool kDelta, class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ void flat8_block(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
-                                            const Flat8Codes &c) {
+                                            const Flat8Codes &c, Out sink = Out()) {
   typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
   const uint32_t sb = (t.start + (t.p >> 3)) & 3u;
-  const OutTile ot = out_tile<Map>(a, t, lane);
+  const OutTile ot = out_tile<Map, Out::kLog2>(a, t, lane);
   const uint32_t rbase = (t.valid && !MH_DIAG_DROP_STORES) ? ot.row0 : 0x80000000u;
   const uint32_t pitch = (uint32_t)a.out_pitch;
   uint32_t s = t.init;  // running delta sum (byte 0)
@@ -993,7 +1130,7 @@ __device__ __forceinline__ void flat8_block(const DecodeArgs &a, const TileOf<Ma
       v.x = c0;
       v.y = c1;
     }
-    __builtin_amdgcn_raw_buffer_store_b64(v, ot.rsrc, (int)(rbase + r * pitch), 0, kBatchStoreAux);
+    sink.template row<kBatchStoreAux>(ot.rsrc, r, v, rbase + r * pitch, rbase, pitch);
   }
 }
 
@@ -1001,7 +1138,7 @@ __device__ __forceinline__ void flat8_block(const DecodeArgs &a, const TileOf<Ma
 // pipelined like batch_loop -- while a tile decodes, the next tile's codes and the one
 // after's header are in flight, all issued before this tile's row stores, so no wait
 // below is for a store.
-template <bool kDelta, class Map = FrameMap>
+template <bool kDelta, class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, uint8_t *stage, const uint8_t *lut,
                                            uint32_t t0, uint32_t gstride, const TileHdrOf<Map> &hc MH_TS_PARAM,
                                            const Map &m = Map()) {
@@ -1022,7 +1159,7 @@ __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, u
     const TileOf<Map> nxt = hdr_resolve(a, h, lane, m);
     flat8_issue(a, nxt, cn);
     hdr_issue(a, next_tile(a, nxt.tile, gstride), lane, h, m);
-    flat8_block<kDelta, Map>(a, cur, lane, cc);
+    flat8_block<kDelta, Map>(a, cur, lane, cc, rows_of<Out>(a, cur, lane, m));
 #if MH_DIAG_STAMPS
     if (first_tile) MH_STAMP(4);  // the first tile's codes landed and its stores issued
     first_tile = false;
@@ -1038,8 +1175,9 @@ __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, u
     TileHdrOf<Map> hs;
     hdr_issue(a, t, lane, hs, m);
     const TileOf<Map> tt = hdr_resolve(a, hs, lane, m);
-    const OutTile ot = out_tile<Map>(a, tt, lane);
-    decode_halves<kDelta, Batch8, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid);
+    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane);
+    decode_halves<kDelta, Batch8, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid,
+                                       rows_of<Out>(a, tt, lane, m));
   }
 }
 
@@ -1413,7 +1551,7 @@ struct HeaderTable {
   }
 };
 
-template <bool kDelta, class Map, class Src>
+template <bool kDelta, class Out = StoreRows, class Map, class Src>
 __device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_t *p_offsets,
                                              const uint64_t *p_frame_off, const uint8_t *p_block_init,
                                              const int32_t *p_status, uint32_t p_nb, uint32_t p_tiles_per_frame,
@@ -1451,13 +1589,13 @@ __device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_
   TableFacts tf;
   if (!src.into_lds(ld, f, slice, tf)) return;
   if (tf.flat8)
-    flat8_loop<kDelta, Map>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG, m);
+    flat8_loop<kDelta, Map, Out>(a, lane, stage, lut, t0, gstride, hc MH_TS_ARG, m);
   else if (tf.mx == tf.mn && tf.mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13Flat, Map>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
+    batch_loop<kDelta, Lut13Flat, Map, Out>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
   else if (tf.mx <= (uint32_t)kLutBits)
-    batch_loop<kDelta, Lut13NoEsc, Map>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
+    batch_loop<kDelta, Lut13NoEsc, Map, Out>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
   else
-    batch_loop<kDelta, Lut13, Map>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
+    batch_loop<kDelta, Lut13, Map, Out>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
 }
 
 // The three entries: names, launch bounds and argument order are the ABI of the launchers, the
@@ -1480,6 +1618,19 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   const uint32_t f = blockIdx.x / p_groups, slice = blockIdx.x - f * p_groups;
   slice_decode<kDelta>(a0, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
                        PreparedTable{p_luts, p_lut_stride}, RegionMap{f, p_rbx0, p_rby0, p_rbw, p_segs});
+}
+
+// ... and the region at scale 2^kLog2 (kLog2 = 1..3): the region kernel with the BoxRows output stage
+template <bool kDelta, int kLog2>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_region_scaled_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, uint64_t p_lut_stride, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbx0, uint32_t p_rby0, const DecodeArgs a0) {
+  const uint32_t f = blockIdx.x / p_groups, slice = blockIdx.x - f * p_groups;
+  slice_decode<kDelta, BoxRows<kLog2>>(a0, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame,
+                                       p_groups, f, slice, PreparedTable{p_luts, p_lut_stride},
+                                       RegionMap{f, p_rbx0, p_rby0, p_rbw, p_segs,
+                                                 (a0.w - 8u * p_rbx0) | ((a0.h - 8u * p_rby0) << 16)});
 }
 
 template <bool kDelta>
@@ -2088,7 +2239,8 @@ __global__ void __launch_bounds__(64 * kLpWaves) mh_decode_lanepair_kernel(const
 // its tables in module statics, Shared/HuffmanUtil.cpp:87-102).
 constexpr int kMaxDevices = 64;
 // The kernels that decode one frame slice per workgroup (slice_decode), by entry point.
-enum SliceKernel { kSliceFrames, kSliceHeaders, kSliceRegion, kSliceKernels };
+// (kSliceScaled + k - 1: the region kernel at scale 2^k, k = 1..3)
+enum SliceKernel { kSliceFrames, kSliceHeaders, kSliceRegion, kSliceScaled, kSliceKernels = kSliceScaled + 3 };
 struct DeviceInfo {
   std::mutex m;
   std::atomic<int> cus{0};  // nonzero once the entry is complete
@@ -2143,6 +2295,12 @@ const DeviceInfo *device_info(hipStream_t s) {
   d.occ_slice[kSliceHeaders][1] = occupancy_of(mh_decode_headers_kernel<true>, kMaxWavesPerWG);
   d.occ_slice[kSliceRegion][0] = occupancy_of(mh_decode_region_kernel<false>, kMaxWavesPerWG);
   d.occ_slice[kSliceRegion][1] = occupancy_of(mh_decode_region_kernel<true>, kMaxWavesPerWG);
+  d.occ_slice[kSliceScaled + 0][0] = occupancy_of(mh_decode_region_scaled_kernel<false, 1>, kMaxWavesPerWG);
+  d.occ_slice[kSliceScaled + 0][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 1>, kMaxWavesPerWG);
+  d.occ_slice[kSliceScaled + 1][0] = occupancy_of(mh_decode_region_scaled_kernel<false, 2>, kMaxWavesPerWG);
+  d.occ_slice[kSliceScaled + 1][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 2>, kMaxWavesPerWG);
+  d.occ_slice[kSliceScaled + 2][0] = occupancy_of(mh_decode_region_scaled_kernel<false, 3>, kMaxWavesPerWG);
+  d.occ_slice[kSliceScaled + 2][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 3>, kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -2251,8 +2409,12 @@ struct TableRule {
 // the same rules in the same order; the frame's own table fields count only for kInFrame, and
 // the other kinds check `ptr` / `stride` in their place, rule by rule. A region is checked with
 // the dims, and its pixel size (*re) stands where W x H does in the pitch and stride rules.
+// A region at scale 2^log2_scale (mh_decode_region_scaled): a scale above 3 is reported where a bad
+// flag is, the scaled size SW x SH (written back to *re) stands where the region's does, and
+// c = 8 >> log2_scale where 8 does in the raster's alignment rules.
 int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                      uint32_t allowed_flags, const TableRule &tr, RegionExtent *re = nullptr) {
+                      uint32_t allowed_flags, const TableRule &tr, RegionExtent *re = nullptr,
+                      uint32_t log2_scale = 0) {
   const bool in_frame = tr.kind == TableRule::kInFrame, regional = tr.kind == TableRule::kRegion;
   const bool prepared = tr.kind == TableRule::kPrepared || regional;
   if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
@@ -2260,19 +2422,22 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !tr.ptr) return MH_ERR_INVALID_ARG;
   if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
   if (fr->flags & ~allowed_flags) return MH_ERR_INVALID_ARG;
+  if (log2_scale > 3u) return MH_ERR_INVALID_ARG;
   const mh_dims &d = fr->dims;
   if (!dims_ok(d)) return MH_ERR_DIMS;
   uint64_t pw = d.width, ph = d.height;  // the raster's pixel size
   if (regional) {
     if (!region_extent(d, tr.rg, *re)) return MH_ERR_DIMS;
-    pw = re->pw;
-    ph = re->ph;
+    const uint64_t s = 1ull << log2_scale;
+    pw = re->pw = (re->pw + s - 1) >> log2_scale;
+    ph = re->ph = (re->ph + s - 1) >> log2_scale;
   }
+  const uint64_t am = (8u >> log2_scale) - 1u;  // the row store's width - 1
   if (in_frame && (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
                    fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
     return MH_ERR_TABLE;
-  if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & 7u) || ((uintptr_t)d_out & 7u) ||
-      (fr->n_frames > 1 && (out_frame_stride & 7u)))
+  if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & am) || ((uintptr_t)d_out & am) ||
+      (fr->n_frames > 1 && (out_frame_stride & am)))
     return MH_ERR_ALIGN;
   if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)tr.ptr & 15u) || (tr.stride & 15u))))
     return MH_ERR_ALIGN;
@@ -2346,16 +2511,19 @@ int launch_slices(Kernel kernel, SliceKernel k, bool delta, const DecodeArgs &a,
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 
-// mh_decode_{frames,headers,region}_shape: slice_shape for a frame description (`rg`: kSliceRegion only).
+// mh_decode_{frames,headers,region,region_scaled}_shape: slice_shape for a frame description (`rg`:
+// kSliceRegion only; with a log2_scale of 1..3 the region kernel of that scale stands for it).
 int slice_shape_entry(SliceKernel k, const mh_frame *fr, const mh_region *rg, void *stream,
-                      uint32_t *groups_per_frame, uint32_t *waves_per_group) {
-  if (!fr || (k == kSliceRegion && !rg) || !groups_per_frame || !waves_per_group || fr->n_frames == 0)
+                      uint32_t *groups_per_frame, uint32_t *waves_per_group, uint32_t log2_scale = 0) {
+  if (!fr || (k >= kSliceRegion && !rg) || !groups_per_frame || !waves_per_group || fr->n_frames == 0)
     return MH_ERR_INVALID_ARG;
   if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
+  if (log2_scale > 3u) return MH_ERR_INVALID_ARG;
+  if (log2_scale) k = (SliceKernel)(kSliceScaled + log2_scale - 1u);
   const mh_dims &d = fr->dims;
   if (!dims_ok(d)) return MH_ERR_DIMS;
   uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
-  if (k == kSliceRegion) {
+  if (k >= kSliceRegion) {
     RegionExtent re;
     if (!region_extent(d, rg, re)) return MH_ERR_DIMS;
     tiles = re.tiles;
@@ -2509,6 +2677,38 @@ int mh_decode_region(const mh_frame *fr, const mh_region *rg, const uint16_t *d_
 int mh_decode_region_shape(const mh_frame *fr, const mh_region *rg, void *stream, uint32_t *groups_per_frame,
                            uint32_t *waves_per_group) {
   return slice_shape_entry(kSliceRegion, fr, rg, stream, groups_per_frame, waves_per_group);
+}
+
+// The region at scale 2^log2_scale: scale 1 is mh_decode_region itself; 2, 4 and 8 are the region
+// kernel with the box-filter output stage (BoxRows), same tiles and launch-shape rule.
+int mh_decode_region_scaled(const mh_frame *fr, const mh_region *rg, uint32_t log2_scale, const uint16_t *d_luts,
+                            uint64_t lut_stride_bytes, const int32_t *d_frame_status, uint8_t *d_out,
+                            size_t out_pitch, size_t out_frame_stride, void *stream) {
+  if (log2_scale == 0)
+    return mh_decode_region(fr, rg, d_luts, lut_stride_bytes, d_frame_status, d_out, out_pitch, out_frame_stride,
+                            stream);
+  RegionExtent re;
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
+                             {TableRule::kRegion, d_luts, lut_stride_bytes, rg}, &re, log2_scale);
+  if (rc != MH_OK) return rc;
+  DecodeArgs a{};
+  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a, &re);  // re.ph = SH: the descriptor's limit
+  if (rc != MH_OK) return rc;
+  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
+  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  const SliceKernel k = (SliceKernel)(kSliceScaled + log2_scale - 1u);
+#define MH_SCALED(K)                                                                                              \
+  launch_slices(delta ? mh_decode_region_scaled_kernel<true, K> : mh_decode_region_scaled_kernel<false, K>, k, delta, \
+                a, fr->n_frames, (hipStream_t)stream, ao, luts, d_frame_status, lut_stride_bytes, re.segs, rg->bw, \
+                rg->bx0, rg->by0)
+  return log2_scale == 1 ? MH_SCALED(1) : log2_scale == 2 ? MH_SCALED(2) : MH_SCALED(3);
+#undef MH_SCALED
+}
+
+int mh_decode_region_scaled_shape(const mh_frame *fr, const mh_region *rg, uint32_t log2_scale, void *stream,
+                                  uint32_t *groups_per_frame, uint32_t *waves_per_group) {
+  // (scale 1: the region kernel's shape; a bad scale is reported where a bad flag is)
+  return slice_shape_entry(kSliceRegion, fr, rg, stream, groups_per_frame, waves_per_group, log2_scale);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

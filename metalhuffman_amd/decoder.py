@@ -410,6 +410,12 @@ class Region(NamedTuple):
         return (min(width, 8 * (self.bx0 + self.bw)) - 8 * self.bx0,
                 min(height, 8 * (self.by0 + self.bh)) - 8 * self.by0)
 
+    def scaled_size(self, width: int, height: int, log2_scale: int) -> tuple:
+        """(SW, SH): the region's size at scale 2^log2_scale, ceil(RW / s) x ceil(RH / s)."""
+        s = 1 << _log2_scale(log2_scale)
+        rw, rh = self.pixel_size(width, height)
+        return (rw + s - 1) // s, (rh + s - 1) // s
+
 
 def region_of_rect(width: int, height: int, x0: int, y0: int, w: int, h: int) -> tuple:
     """The pixel rectangle [x0, x0 + w) x [y0, y0 + h) of a width x height frame rounded out to
@@ -439,6 +445,20 @@ def decode_region_shape(frames: DeviceFrames, region, stream: Optional[torch.cud
     return _slice_shape("mh_decode_region_shape", frames, stream, extra_flags, region)
 
 
+def _region_tables(who: str, frames: DeviceFrames, tables, dev_index: int, skip_rejected: bool) -> tuple:
+    """decode_region's table argument -> (luts, stride, status or None)."""
+    if isinstance(tables, DeviceTables):
+        if tables.lut is None:
+            raise ValueError(f"{who} needs the prepared table (DeviceTables.prepare_lut())")
+        if tables.lut.get_device() != dev_index:
+            raise ValueError(f"the table must live on cuda:{dev_index}")
+        return tables.lut, 0, None
+    if isinstance(tables, DeviceTableSet):
+        _check_table_set(tables, frames, dev_index)
+        return tables.luts, tables.stride, tables.status if skip_rejected else None
+    raise TypeError(f"{who} takes a DeviceTables or a DeviceTableSet")
+
+
 def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tensor] = None,
                   stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
                   skip_rejected: bool = True) -> torch.Tensor:
@@ -451,17 +471,7 @@ def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tens
     if fr.flags & N.MH_FLAG_LANE_PAIRS:
         raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_region")
     rg = _region_struct(frames, region)
-    if isinstance(tables, DeviceTables):
-        if tables.lut is None:
-            raise ValueError("decode_region needs the prepared table (DeviceTables.prepare_lut())")
-        if tables.lut.get_device() != dev_index:
-            raise ValueError(f"the table must live on cuda:{dev_index}")
-        luts, stride, status = tables.lut, 0, None
-    elif isinstance(tables, DeviceTableSet):
-        _check_table_set(tables, frames, dev_index)
-        luts, stride, status = tables.luts, tables.stride, tables.status if skip_rejected else None
-    else:
-        raise TypeError("decode_region takes a DeviceTables or a DeviceTableSet")
+    luts, stride, status = _region_tables("decode_region", frames, tables, dev_index, skip_rejected)
     pitch = 8 * rg.bw
     h = min(frames.height, 8 * (rg.by0 + rg.bh)) - 8 * rg.by0
     out = _out_raster(frames, out, h, pitch, dev_index, stream)
@@ -472,6 +482,66 @@ def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tens
     if rc:
         N.check(rc, "mh_decode_region")
     return out
+
+
+def _log2_scale(log2_scale) -> int:
+    k = int(log2_scale)
+    if k != log2_scale or not 0 <= k <= 3:
+        raise ValueError(f"log2_scale must be 0, 1, 2 or 3 (scale 1, 1/2, 1/4, 1/8), not {log2_scale!r}")
+    return k
+
+
+def decode_region_scaled_shape(frames: DeviceFrames, region, log2_scale: int,
+                               stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
+    """(workgroups per frame, waves per workgroup) decode_region_scaled would launch with
+    (mh_decode_region_scaled_shape)."""
+    k = _log2_scale(log2_scale)
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    rg = _region_struct(frames, region)
+    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
+    N.check(N.lib().mh_decode_region_scaled_shape(ctypes.byref(fr), ctypes.byref(rg), k, sp, ctypes.byref(g),
+                                                  ctypes.byref(w)), "mh_decode_region_scaled_shape")
+    return int(g.value), int(w.value)
+
+
+def decode_region_scaled(frames: DeviceFrames, tables, region, log2_scale: int, out: Optional[torch.Tensor] = None,
+                         stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                         skip_rejected: bool = True) -> torch.Tensor:
+    """decode_region at scale s = 2^log2_scale (0..3) in one launch (mh_decode_region_scaled): every
+    s x s cell of the region becomes the mean of its pixels inside the frame, halves rounded up,
+    and no full-size raster exists. -> out[n, SH, bw * c], c = 8 >> log2_scale, whose first SW
+    columns are the picture ((SW, SH) = Region.scaled_size; the columns beyond, cells of a
+    right-edge block outside the frame, are 0). tables, out and skip_rejected: decode_region's.
+    log2_scale 0 is decode_region."""
+    k = _log2_scale(log2_scale)
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_region_scaled")
+    rg = _region_struct(frames, region)
+    luts, stride, status = _region_tables("decode_region_scaled", frames, tables, dev_index, skip_rejected)
+    pitch = (8 >> k) * rg.bw
+    h = Region(rg.bx0, rg.by0, rg.bw, rg.bh).scaled_size(frames.width, frames.height, k)[1]
+    out = _out_raster(frames, out, h, pitch, dev_index, stream)
+    sp = _raw_stream_ptr(stream, dev_index)
+    rc = N.lib().mh_decode_region_scaled(ctypes.byref(fr), ctypes.byref(rg), k, luts.data_ptr(), stride,
+                                         status.data_ptr() if status is not None else None, out.data_ptr(),
+                                         pitch, h * pitch, sp)
+    if rc:
+        N.check(rc, "mh_decode_region_scaled")
+    return out
+
+
+def decode_scaled(frames: DeviceFrames, tables, log2_scale: int, out: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                  skip_rejected: bool = True) -> torch.Tensor:
+    """The whole frame at scale 2^log2_scale: decode_region_scaled of the full block grid, returned
+    as its [n, ceil(H / s), ceil(W / s)] view (`out`, when given, has the region's shape)."""
+    gw, gh = block_grid(frames.width, frames.height)
+    region = Region(0, 0, gw, gh)
+    full = decode_region_scaled(frames, tables, region, log2_scale, out, stream, extra_flags, skip_rejected)
+    sw, sh = region.scaled_size(frames.width, frames.height, log2_scale)
+    return full.reshape(frames.n_frames, full.shape[-2], full.shape[-1])[:, :sh, :sw]
 
 
 def decode_rect(frames: DeviceFrames, tables, x0: int, y0: int, w: int, h: int,
