@@ -352,6 +352,60 @@ int mh_decode_region_scaled_shape(const mh_frame *frame, const mh_region *region
 int mh_box_reduce(const uint8_t *raster, uint32_t width, uint32_t height, size_t pitch,
                   uint32_t log2_scale, uint8_t *out, size_t out_pitch);
 
+/* ---------------------------------------------------------------------- */
+/* A list of windows in one launch: rectangles of one size in blocks, each with its own frame   */
+/* and origin -- random crops of a set of scans, the tiles a viewer's cache misses after a     */
+/* jump, a tracked box that moves from frame to frame. mh_decode_region decodes the SAME        */
+/* rectangle of every frame; N rectangles took N launches of it. Not covered: windows at a     */
+/* reduced scale; windows for mh_decode_headers, the streams, the multi-GPU paths and mh_check; */
+/* windows of different sizes in one launch; packing several rows of a window narrower than 64  */
+/* blocks into one wave (lane utilisation is bw / (64 ceil(bw / 64)), as for a region);         */
+/* pixel-granular stores; a CPU twin.                                                           */
+typedef struct {
+  uint32_t frame, bx0, by0, reserved; /* 16 bytes; reserved must be 0 */
+} mh_window;
+
+/* Window p = d_windows[p] is the blocks [bx0, bx0 + bw) x [by0, by0 + bh) of frame `frame`; its
+ * pixel size RW_p x RH_p is mh_decode_region's RW x RH for that rectangle.
+ * d_windows is a DEVICE array of n_windows descriptors, 16-byte aligned (a sampler on the GPU can
+ * write it; the host never reads it). Windows may overlap, repeat and name frames in any order.
+ * Output: window p, row y starts at d_out + p * out_window_stride + y * out_pitch; 8 bw bytes of
+ * every row y < RH_p are written; nothing else is touched, in that slot or outside it (rows
+ * >= RH_p of a window at the frame's bottom edge keep what they held). The written bytes equal the
+ * same bytes of the rectangle at (8 bx0, 8 by0) of the raster mh_decode_frames writes for that frame.
+ * Tables, lut_stride_bytes == 0, d_block_init and flags: mh_decode_region's. d_frame_status
+ * (optional, device int32[n_frames]) is indexed by the window's FRAME: a non-zero word means no
+ * byte of any window of that frame is written.
+ * Windows are validated on the device, by the workgroups that serve them and from the descriptor
+ * alone: frame >= n_frames, bx0 + bw > block_width, by0 + bh > block_height (compared without
+ * wrapping: bx0 = 0xFFFFFFFF is rejected) or reserved != 0 reject the window. A rejected window
+ * loads nothing through its descriptor and writes no byte of the raster; the others are decoded.
+ * d_window_status (optional output, device int32[n_windows], must not alias d_frame_status ->
+ * MH_ERR_INVALID_ARG), written by one workgroup of window p: MH_ERR_DIMS for a rejected window;
+ * else its frame's status word when that is non-zero (the slot is then untouched, as above); else
+ * MH_OK.
+ * Checks: all before any HIP call, in mh_decode_region's order and with its codes, with n_windows
+ * rasters of 8 bw x 8 bh in the place of n_frames rasters of RW x RH, and: NULL d_windows or
+ * n_windows == 0 -> MH_ERR_INVALID_ARG; bw == 0, bh == 0, bw > block_width or bh > block_height ->
+ * MH_ERR_DIMS; d_windows not 16-byte aligned -> MH_ERR_ALIGN; out_pitch < 8 bw (the full block
+ * width: windows differ in RW) or, for n_windows > 1, out_window_stride < out_pitch * 8 bh ->
+ * MH_ERR_CAPACITY (the window stride is a multiple of 8 as the frame stride is, for n_windows > 1);
+ * n_windows * bh * S tiles or the grid above 2^31 - 1 -> MH_ERR_CAPACITY. flags: MH_FLAG_NO_DELTA |
+ * MH_FLAG_ANY_ORDER only.
+ * One kernel launch, asynchronous on `stream`: tiles are mh_decode_region's (S = ceil(bw / 64) per
+ * block row, bh * S per window), and the launch is n_windows * G workgroups of 8 waves, workgroup g
+ * serving window g / G, G = clamp(ceil(R / n_windows), 1, ceil(bh * S / 8)), R the workgroups of this
+ * kernel resident on the device at once. */
+int mh_decode_windows(const mh_frame *frame, const mh_window *d_windows, uint32_t n_windows,
+                      uint32_t bw, uint32_t bh, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                      const int32_t *d_frame_status, int32_t *d_window_status, uint8_t *d_out,
+                      size_t out_pitch, size_t out_window_stride, void *stream);
+
+/* The launch shape mh_decode_windows would use on `stream`'s device (no launch): workgroups per
+ * window (G above) and waves per workgroup. For tests and tools. */
+int mh_decode_windows_shape(const mh_frame *frame, uint32_t n_windows, uint32_t bw, uint32_t bh,
+                            void *stream, uint32_t *groups_per_window, uint32_t *waves_per_group);
+
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a
  * prepared table) and the 16-byte lengths word at their prepared-table offsets in

@@ -13,6 +13,8 @@ of mdejong/MetalHuffman).
   * decoder.decode_region / decode_rect   a block-aligned region (a pixel rectangle) of every frame, one launch
   * decoder.decode_region_scaled / decode_scaled   a region (the frame) at 1/2, 1/4 or 1/8 scale, one launch:
                                     box means taken in the decoder's registers; codec.box_reduce is the CPU twin
+  * decoder.decode_windows / windows_of_rects   a list of windows of one size, each with its own frame and
+                                    origin (random crops, a viewer's missing tiles, a moving box), one launch
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync

@@ -43,6 +43,7 @@ EXPORTS = (
     "mh_code_lengths_limited",
     "mh_decode_region", "mh_decode_region_shape",
     "mh_decode_region_scaled", "mh_decode_region_scaled_shape", "mh_box_reduce",
+    "mh_decode_windows", "mh_decode_windows_shape",
 )
 
 
@@ -78,6 +79,11 @@ class mh_frame(ctypes.Structure):
 class mh_region(ctypes.Structure):
     _fields_ = [("bx0", ctypes.c_uint32), ("by0", ctypes.c_uint32), ("bw", ctypes.c_uint32),
                 ("bh", ctypes.c_uint32)]
+
+
+class mh_window(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_uint32), ("bx0", ctypes.c_uint32), ("by0", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 _lib = None
@@ -152,6 +158,11 @@ def lib() -> ctypes.CDLL:
                                               _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
         L.mh_decode_region_scaled_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.POINTER(mh_region),
                                                     ctypes.c_uint32, _vp, _u32p, _u32p]
+        L.mh_decode_windows.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                        ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_size_t,
+                                        ctypes.c_size_t, _vp]
+        L.mh_decode_windows_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_uint32, _vp, _u32p, _u32p]
         L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
                                     ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]

@@ -660,8 +660,13 @@ __device__ __forceinline__ uint32_t frame_of(const DecodeArgs &a, uint32_t tile)
 //   min(64, bw - 64 s) live lanes, stored at region row 8 r, byte 8 (64 s + lane). Tiles are
 //   relative to the workgroup's frame `f` (a.total_tiles == a.tiles_per_frame == bh * S), and
 //   a.bw / a.nb stay the FRAME's: offsets and block_init are indexed by the frame's block number.
+// WindowMap (mh_decode_windows): a RegionMap whose frame and origin come from the workgroup's window
+//   descriptor, and whose raster slot is the window's index `slot`, not the frame: `f` addresses
+//   what is read (offsets, codes, block_init), raster_slot() what is written. Its report() writes
+//   the window's status word (slice_decode calls every map's; the others report nothing).
 struct FrameMap {
   static constexpr bool kRegion = false;
+  __device__ __forceinline__ void report(uint32_t, uint32_t) const {}
 };
 struct RegionMap {
   static constexpr bool kRegion = true;
@@ -669,6 +674,17 @@ struct RegionMap {
   // BoxRows only: the frame's pixels from the region's origin on, (W - 8 bx0) | (H - 8 by0) << 16
   // (both <= 65535) -- one SGPR for a tile's edge facts, where W, H and the origin would be four
   uint32_t rem = 0;
+  __device__ __forceinline__ uint32_t raster_slot() const { return f; }
+  __device__ __forceinline__ void report(uint32_t, uint32_t) const {}
+};
+struct WindowMap : RegionMap {
+  uint32_t slot;
+  int32_t *wstatus;  // d_window_status or null
+  __device__ __forceinline__ uint32_t raster_slot() const { return slot; }
+  // the window's status word = its frame's (0: MH_OK), written by one thread of slice 0 with a vector store
+  __device__ __forceinline__ void report(uint32_t frame_status, uint32_t slice) const {
+    if (wstatus && slice == 0 && threadIdx.x == 0) wstatus[slot] = (int32_t)frame_status;
+  }
 };
 
 struct TileHdrBase {
@@ -685,6 +701,8 @@ template <>
 struct TileHdrOf<RegionMap> : TileHdrBase {
   uint32_t r, s;      // the tile's region row and segment (wave-uniform)
 };
+template <>
+struct TileHdrOf<WindowMap> : TileHdrOf<RegionMap> {};
 using TileHdr = TileHdrOf<FrameMap>;
 
 // tile -> (r, s). One segment per row skips the division (a uniform branch), as frame_of does
@@ -735,7 +753,7 @@ __device__ __forceinline__ void hdr_issue(const DecodeArgs &a, uint32_t tile, ui
 
 // Everything derived from a header once its loads have landed.
 struct TileBase {
-  uint32_t tile, f, b0;
+  uint32_t tile, f, b0;  // f: the raster slot (the frame; a window's index under WindowMap)
   bool valid;          // this lane holds a block
   uint32_t p;          // lane's start bit relative to the staged span
   uint32_t start;      // span start byte (16-aligned, frame relative)
@@ -751,6 +769,8 @@ template <>
 struct TileOf<RegionMap> : TileBase {
   uint32_t r, s, n;    // region row, segment, blocks in the run (1..64)
 };
+template <>
+struct TileOf<WindowMap> : TileOf<RegionMap> {};
 using Tile = TileOf<FrameMap>;
 
 template <class Map = FrameMap>
@@ -759,7 +779,7 @@ __device__ __forceinline__ TileOf<Map> hdr_resolve(const DecodeArgs &a, const Ti
   TileOf<Map> t;
   t.tile = h.tile;
   if constexpr (Map::kRegion) {
-    t.f = m.f;
+    t.f = m.raster_slot();
     t.r = h.r;
     t.s = h.s;
     t.n = min(64u, m.bw - 64u * h.s);
@@ -831,7 +851,8 @@ template <class Map = FrameMap, int kLog2 = 0>
 __device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane) {
   static_assert(Map::kRegion || kLog2 == 0, "only a region is decoded at a reduced scale");
   if constexpr (Map::kRegion) {
-    // based at region row 8 r and limited by RH * pitch (a.out_frame_bytes): rows >= RH are dropped.
+    // based at region row 8 r of the raster slot t.f (the frame; a window's index) and limited by
+    // RH * pitch (a.out_frame_bytes): rows >= RH are dropped.
     // At scale 2^kLog2 a block row is c = 8 >> kLog2 output rows of c bytes per block, and the
     // limit is SH * pitch.
     constexpr uint32_t c = 8u >> kLog2;
@@ -1482,6 +1503,9 @@ __device__ __forceinline__ HeaderFacts header_build(uint32_t L, uint16_t *lut, H
 //              the region's own size. Tiles are frame relative (the map carries the frame), so no
 //              tile -> frame division; the tile -> (row, segment) division is skipped for regions
 //              of <= 64 blocks per row.
+//   WindowMap: a RegionMap per workgroup (mh_decode_windows): frame and origin from the window's
+//              descriptor, the raster slot the window's index; behind the status load it writes the
+//              window's status word (the frame's), so a skipped frame's windows carry it.
 // And where the 13-bit table comes from (a table source: `lut_of`, `issue`, `into_lds`):
 //   PreparedTable: frame f's prepared table at luts + f * stride (stride 0: one table for all
 //              frames), copied by four 16-byte loads per thread.
@@ -1585,7 +1609,9 @@ __device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_
   typename Src::Loads ld;
   src.issue(a, f, ld);
   hdr_issue<Map>(a, t0, lane, hc, m);
-  if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
+  const uint32_t st = __builtin_amdgcn_readfirstlane(stv);
+  m.report(st, slice);  // WindowMap: the window's status word
+  if (st != 0u) return;  // workgroup-uniform: a skipped frame, nothing stored
   TableFacts tf;
   if (!src.into_lds(ld, f, slice, tf)) return;
   if (tf.flat8)
@@ -1631,6 +1657,37 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
                                        p_groups, f, slice, PreparedTable{p_luts, p_lut_stride},
                                        RegionMap{f, p_rbx0, p_rby0, p_rbw, p_segs,
                                                  (a0.w - 8u * p_rbx0) | ((a0.h - 8u * p_rby0) << 16)});
+}
+
+// mh_decode_windows: workgroup g serves window g / G, whose frame and origin it reads from the
+// window's 16-byte descriptor -- one load per workgroup, the one dependent trip ahead of
+// slice_decode's prologue. The workgroup judges the descriptor by itself, before anything is
+// addressed through it: a window that names no frame, leaves the block grid or has a non-zero
+// reserved word returns here, having loaded and stored nothing but its status word. The origin is
+// compared with the last one that fits, p_max_bx0 = block_width - bw and p_max_by0 = block_height -
+// bh from the host (which has checked bw <= block_width and bh <= block_height), so no sum of
+// descriptor values is formed and nothing wraps; the limits arrive with the other scalars, ahead
+// of the descriptor. a0.out_frame_stride is the window stride; the workgroup's own row limit
+// RH_p * pitch replaces a0.out_frame_bytes.
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_windows_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const mh_window *p_windows, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbh, uint32_t p_nframes, uint32_t p_max_bx0, uint32_t p_max_by0,
+    uint64_t p_lut_stride, int32_t *p_wstatus, const DecodeArgs a0) {
+  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
+  const v4u32 wd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_windows + p, 16u), 0, 0, 0);
+  const uint32_t f = __builtin_amdgcn_readfirstlane(wd.x), bx0 = __builtin_amdgcn_readfirstlane(wd.y);
+  const uint32_t by0 = __builtin_amdgcn_readfirstlane(wd.z), reserved = __builtin_amdgcn_readfirstlane(wd.w);
+  if ((f >= p_nframes) | (bx0 > p_max_bx0) | (by0 > p_max_by0) | (reserved != 0u)) {  // workgroup-uniform
+    if (p_wstatus && slice == 0 && threadIdx.x == 0) p_wstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  DecodeArgs aw = a0;
+  aw.out_frame_bytes = (uint64_t)(min(a0.h, 8u * (by0 + p_rbh)) - 8u * by0) * a0.out_pitch;
+  slice_decode<kDelta>(aw, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
+                       PreparedTable{p_luts, p_lut_stride},
+                       WindowMap{{f, bx0, by0, p_rbw, p_segs}, p, p_wstatus});
 }
 
 template <bool kDelta>
@@ -2240,7 +2297,14 @@ __global__ void __launch_bounds__(64 * kLpWaves) mh_decode_lanepair_kernel(const
 constexpr int kMaxDevices = 64;
 // The kernels that decode one frame slice per workgroup (slice_decode), by entry point.
 // (kSliceScaled + k - 1: the region kernel at scale 2^k, k = 1..3)
-enum SliceKernel { kSliceFrames, kSliceHeaders, kSliceRegion, kSliceScaled, kSliceKernels = kSliceScaled + 3 };
+enum SliceKernel {
+  kSliceFrames,
+  kSliceHeaders,
+  kSliceRegion,
+  kSliceScaled,
+  kSliceWindows = kSliceScaled + 3,
+  kSliceKernels
+};
 struct DeviceInfo {
   std::mutex m;
   std::atomic<int> cus{0};  // nonzero once the entry is complete
@@ -2301,6 +2365,8 @@ const DeviceInfo *device_info(hipStream_t s) {
   d.occ_slice[kSliceScaled + 1][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 2>, kMaxWavesPerWG);
   d.occ_slice[kSliceScaled + 2][0] = occupancy_of(mh_decode_region_scaled_kernel<false, 3>, kMaxWavesPerWG);
   d.occ_slice[kSliceScaled + 2][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 3>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindows][0] = occupancy_of(mh_decode_windows_kernel<false>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindows][1] = occupancy_of(mh_decode_windows_kernel<true>, kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -2399,10 +2465,14 @@ struct TableRule {
     kPrepared,  // mh_decode_frames: prepared tables at `ptr`, `stride` bytes apart
     kHeaders,   // mh_decode_headers: canonical headers at `ptr`, no alignment or stride rule
     kRegion,    // mh_decode_region: kPrepared over region `rg`; stride 0 is one table for all frames
+    kWindows,   // mh_decode_windows: kRegion with rg = {0, 0, bw, bh}, the windows' size, and
+                // n_windows rasters of 8 bw x 8 bh, described by the device array `windows`
   } kind;
   const void *ptr = nullptr;
   uint64_t stride = 0;
   const mh_region *rg = nullptr;
+  const void *windows = nullptr;
+  uint32_t n_windows = 0;
 };
 
 // The argument checks of the decode entry points, all before any HIP call. Every entry runs
@@ -2412,13 +2482,20 @@ struct TableRule {
 // A region at scale 2^log2_scale (mh_decode_region_scaled): a scale above 3 is reported where a bad
 // flag is, the scaled size SW x SH (written back to *re) stands where the region's does, and
 // c = 8 >> log2_scale where 8 does in the raster's alignment rules.
+// Windows (mh_decode_windows): the region's rules for rg = {0, 0, bw, bh} -- so a size that is
+// empty or exceeds the grid is MH_ERR_DIMS -- with n_windows rasters of the full 8 bw x 8 bh in the
+// place of n_frames rasters of RW x RH (windows differ in RW / RH; `out_frame_stride` is the window
+// stride), and the descriptor array checked where the tables are.
 int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                       uint32_t allowed_flags, const TableRule &tr, RegionExtent *re = nullptr,
                       uint32_t log2_scale = 0) {
-  const bool in_frame = tr.kind == TableRule::kInFrame, regional = tr.kind == TableRule::kRegion;
+  const bool in_frame = tr.kind == TableRule::kInFrame, windowed = tr.kind == TableRule::kWindows;
+  const bool regional = tr.kind == TableRule::kRegion || windowed;
   const bool prepared = tr.kind == TableRule::kPrepared || regional;
   if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
   if (regional && !tr.rg) return MH_ERR_INVALID_ARG;
+  if (windowed && (!tr.windows || tr.n_windows == 0)) return MH_ERR_INVALID_ARG;
+  const uint32_t n_rasters = windowed ? tr.n_windows : fr->n_frames;
   if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !tr.ptr) return MH_ERR_INVALID_ARG;
   if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
   if (fr->flags & ~allowed_flags) return MH_ERR_INVALID_ARG;
@@ -2428,6 +2505,10 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   uint64_t pw = d.width, ph = d.height;  // the raster's pixel size
   if (regional) {
     if (!region_extent(d, tr.rg, *re)) return MH_ERR_DIMS;
+    if (windowed) {
+      re->pw = 8ull * tr.rg->bw;
+      re->ph = 8ull * tr.rg->bh;
+    }
     const uint64_t s = 1ull << log2_scale;
     pw = re->pw = (re->pw + s - 1) >> log2_scale;
     ph = re->ph = (re->ph + s - 1) >> log2_scale;
@@ -2437,11 +2518,12 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
                    fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
     return MH_ERR_TABLE;
   if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & am) || ((uintptr_t)d_out & am) ||
-      (fr->n_frames > 1 && (out_frame_stride & am)))
+      (n_rasters > 1 && (out_frame_stride & am)))
     return MH_ERR_ALIGN;
+  if (windowed && ((uintptr_t)tr.windows & 15u)) return MH_ERR_ALIGN;
   if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)tr.ptr & 15u) || (tr.stride & 15u))))
     return MH_ERR_ALIGN;
-  if (out_pitch < pw || out_pitch > (1u << 20) || (fr->n_frames > 1 && out_frame_stride < out_pitch * ph))
+  if (out_pitch < pw || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * ph))
     return MH_ERR_CAPACITY;
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
@@ -2452,9 +2534,10 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
 }
 
 // DecodeArgs from a checked frame (tables excepted); MH_ERR_CAPACITY past 2^31 - 1 tiles.
-// With `re` the raster and the tiles are the region's, not the frame's.
+// With `re` the raster and the tiles are the region's, not the frame's; with n_windows there are
+// that many rasters, not n_frames.
 int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                     DecodeArgs &a, const RegionExtent *re = nullptr) {
+                     DecodeArgs &a, const RegionExtent *re = nullptr, uint32_t n_windows = 0) {
   const mh_dims &d = fr->dims;
   a.offsets = fr->d_block_offsets;
   a.codes = fr->d_codes;
@@ -2471,7 +2554,7 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
   a.bh = d.block_height;
   a.nb = d.block_width * d.block_height;
   a.tiles_per_frame = re ? re->tiles : (a.nb + 63) / 64;
-  const uint64_t total = (uint64_t)a.tiles_per_frame * fr->n_frames;
+  const uint64_t total = (uint64_t)a.tiles_per_frame * (n_windows ? n_windows : fr->n_frames);
   if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
   a.total_tiles = (uint32_t)total;
   return MH_OK;
@@ -2496,8 +2579,10 @@ int slice_shape(SliceKernel k, uint32_t n_frames, uint32_t tiles_per_frame, bool
 }
 
 // One launch of a frame-slice kernel. The kernels' argument lists differ only in the table
-// arguments on either side of `status` (prepared tables: luts, stride; headers: headers, verdict)
-// and in the region's scalars (`tail`), which follow the group count.
+// arguments on either side of `status` (prepared tables: luts, stride; headers: headers, verdict;
+// windows: luts, the descriptor array) and in the region's or the windows' scalars (`tail`), which
+// follow the group count. `n_frames` is the number of units the grid is cut into: the windows, for
+// mh_decode_windows.
 template <class Kernel, class Table, class TableAux, class... Tail>
 int launch_slices(Kernel kernel, SliceKernel k, bool delta, const DecodeArgs &a, uint32_t n_frames, hipStream_t s,
                   bool any_order, Table table, const int32_t *status, TableAux aux, Tail... tail) {
@@ -2513,10 +2598,14 @@ int launch_slices(Kernel kernel, SliceKernel k, bool delta, const DecodeArgs &a,
 
 // mh_decode_{frames,headers,region,region_scaled}_shape: slice_shape for a frame description (`rg`:
 // kSliceRegion only; with a log2_scale of 1..3 the region kernel of that scale stands for it).
+// kSliceWindows: rg = {0, 0, bw, bh} and n_windows units in the place of n_frames.
 int slice_shape_entry(SliceKernel k, const mh_frame *fr, const mh_region *rg, void *stream,
-                      uint32_t *groups_per_frame, uint32_t *waves_per_group, uint32_t log2_scale = 0) {
+                      uint32_t *groups_per_frame, uint32_t *waves_per_group, uint32_t log2_scale = 0,
+                      uint32_t n_windows = 0) {
   if (!fr || (k >= kSliceRegion && !rg) || !groups_per_frame || !waves_per_group || fr->n_frames == 0)
     return MH_ERR_INVALID_ARG;
+  if (k == kSliceWindows && n_windows == 0) return MH_ERR_INVALID_ARG;
+  const uint32_t n_units = k == kSliceWindows ? n_windows : fr->n_frames;
   if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
   if (log2_scale > 3u) return MH_ERR_INVALID_ARG;
   if (log2_scale) k = (SliceKernel)(kSliceScaled + log2_scale - 1u);
@@ -2527,9 +2616,9 @@ int slice_shape_entry(SliceKernel k, const mh_frame *fr, const mh_region *rg, vo
     RegionExtent re;
     if (!region_extent(d, rg, re)) return MH_ERR_DIMS;
     tiles = re.tiles;
-    if ((uint64_t)tiles * fr->n_frames > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+    if ((uint64_t)tiles * n_units > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
   }
-  const int rc = slice_shape(k, fr->n_frames, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
+  const int rc = slice_shape(k, n_units, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
                              groups_per_frame);
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
@@ -2709,6 +2798,38 @@ int mh_decode_region_scaled_shape(const mh_frame *fr, const mh_region *rg, uint3
                                   uint32_t *groups_per_frame, uint32_t *waves_per_group) {
   // (scale 1: the region kernel's shape; a bad scale is reported where a bad flag is)
   return slice_shape_entry(kSliceRegion, fr, rg, stream, groups_per_frame, waves_per_group, log2_scale);
+}
+
+// A list of windows of one size, each with its own frame and origin: the region kernel's body with
+// a map read from the window's descriptor (WindowMap); n_windows stands where n_frames does in the
+// launch-shape rule and the grid.
+int mh_decode_windows(const mh_frame *fr, const mh_window *d_windows, uint32_t n_windows, uint32_t bw, uint32_t bh,
+                      const uint16_t *d_luts, uint64_t lut_stride_bytes, const int32_t *d_frame_status,
+                      int32_t *d_window_status, uint8_t *d_out, size_t out_pitch, size_t out_window_stride,
+                      void *stream) {
+  if (d_window_status && d_window_status == d_frame_status) return MH_ERR_INVALID_ARG;
+  const mh_region size = {0u, 0u, bw, bh};
+  TableRule tr{TableRule::kWindows, d_luts, lut_stride_bytes, &size};
+  tr.windows = d_windows;
+  tr.n_windows = n_windows;
+  RegionExtent re;
+  int rc = check_decode_args(fr, d_out, out_pitch, out_window_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, tr, &re);
+  if (rc != MH_OK) return rc;
+  DecodeArgs a{};
+  rc = fill_decode_args(fr, d_out, out_pitch, out_window_stride, a, &re, n_windows);
+  if (rc != MH_OK) return rc;
+  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
+  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return launch_slices(delta ? mh_decode_windows_kernel<true> : mh_decode_windows_kernel<false>, kSliceWindows, delta,
+                       a, n_windows, (hipStream_t)stream, ao, luts, d_frame_status, d_windows, re.segs, bw, bh,
+                       fr->n_frames, fr->dims.block_width - bw, fr->dims.block_height - bh, lut_stride_bytes,
+                       d_window_status);
+}
+
+int mh_decode_windows_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh, void *stream,
+                            uint32_t *groups_per_window, uint32_t *waves_per_group) {
+  const mh_region size = {0u, 0u, bw, bh};
+  return slice_shape_entry(kSliceWindows, fr, &size, stream, groups_per_window, waves_per_group, 0, n_windows);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

@@ -555,6 +555,147 @@ def decode_rect(frames: DeviceFrames, tables, x0: int, y0: int, w: int, h: int,
     return full.reshape(frames.n_frames, full.shape[-2], full.shape[-1])[:, dy: dy + h, dx: dx + w]
 
 
+def windows_of_rects(width: int, height: int, frame_idx, x0, y0, w: int, h: int) -> tuple:
+    """n pixel rectangles of ONE size w x h, rectangle i at (x0[i], y0[i]) of frame frame_idx[i]
+    (arrays of one length) of width x height frames -> (windows int64[n, 3] of (frame, bx0, by0),
+    (bw, bh), dx[n], dy[n]) for decode_windows: rectangle i is out[i, dy[i]: dy[i] + h, dx[i]: dx[i] + w].
+    Every window starts at its rectangle's block (region_of_rect's rounding), and (bw, bh) is the
+    smallest block size that holds every rectangle at its own sub-block offset (dx, dy). Pure.
+    ValueError when a rectangle is empty or leaves the frame, or when a window grown to (bw, bh)
+    leaves the block grid."""
+    width, height, w, h = (int(v) for v in (width, height, w, h))
+    if width < 1 or height < 1:
+        raise ValueError("an empty frame")
+    f, x0, y0 = (np.atleast_1d(np.asarray(v)).astype(np.int64) for v in (frame_idx, x0, y0))
+    if not (f.ndim == x0.ndim == y0.ndim == 1 and f.size == x0.size == y0.size and f.size >= 1):
+        raise ValueError("frame_idx, x0 and y0 are arrays of one length >= 1")
+    bad = (x0 < 0) | (y0 < 0) | (x0 + w > width) | (y0 + h > height) | (f < 0)
+    if w < 1 or h < 1 or bad.any():
+        i = int(np.flatnonzero(bad)[0]) if bad.any() else 0
+        raise ValueError(f"rectangle {i}: {w}x{h} at ({int(x0[i])}, {int(y0[i])}) of frame {int(f[i])} lies outside "
+                         f"the {width}x{height} frame")
+    bx0, by0 = x0 // 8, y0 // 8
+    bw = int(((x0 + w + 7) // 8 - bx0).max())
+    bh = int(((y0 + h + 7) // 8 - by0).max())
+    gw, gh = block_grid(width, height)
+    out = (bx0 + bw > gw) | (by0 + bh > gh)
+    if out.any():
+        i = int(np.flatnonzero(out)[0])
+        raise ValueError(f"rectangle {i}: its window of {bw}x{bh} blocks at block ({int(bx0[i])}, {int(by0[i])}) "
+                         f"leaves the {gw}x{gh} block grid")
+    return np.stack([f, bx0, by0], axis=1), (bw, bh), x0 - 8 * bx0, y0 - 8 * by0
+
+
+def _window_size(frames: DeviceFrames, size) -> tuple:
+    bw, bh = (int(v) for v in size)
+    gw, gh = block_grid(frames.width, frames.height)
+    if bw < 1 or bh < 1 or bw > gw or bh > gh:
+        raise ValueError(f"a window of {bw}x{bh} blocks does not fit the {gw}x{gh} block grid")
+    return bw, bh
+
+
+def _host_windows(frames: DeviceFrames, windows, bw: int, bh: int):
+    """decode_windows' `windows` checked on the host: a device tensor's type and shape only (it is
+    not read: no host sync, the kernel validates it) -> None; a host sequence against the frames
+    and the block grid (ValueError) -> its int32 [n, 4] descriptor array."""
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        dev = frames.codes.device
+        if (windows.device != dev or windows.dtype is not torch.int32 or windows.dim() != 2
+                or windows.shape[1] not in (3, 4) or windows.shape[0] < 1):
+            raise ValueError(f"a device windows tensor is int32 [n, 3] or [n, 4] on {dev}")
+        return None
+    w = np.asarray(windows.numpy() if isinstance(windows, torch.Tensor) else windows)
+    if w.ndim != 2 or w.shape[1] != 3 or w.shape[0] < 1 or w.dtype.kind not in "iu":
+        raise ValueError("windows is a sequence of (frame, bx0, by0) integers")
+    w = w.astype(np.int64)
+    gw, gh = block_grid(frames.width, frames.height)
+    bad = ((w < 0).any(axis=1) | (w[:, 0] >= frames.n_frames) | (w[:, 1] + bw > gw) | (w[:, 2] + bh > gh))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"window {i} = {tuple(int(v) for v in w[i])} of {bw}x{bh} blocks lies outside the "
+                         f"{frames.n_frames} frames of {gw}x{gh} blocks")
+    full = np.zeros((w.shape[0], 4), np.int32)
+    full[:, :3] = w
+    return full
+
+
+def _windows_tensor(frames: DeviceFrames, windows, host) -> torch.Tensor:
+    """The int32 [n, 4] descriptor array on the frames' device, 16-byte aligned: the upload of a
+    checked host list (_host_windows), or the caller's device tensor -- as it is when it is [n, 4],
+    contiguous and aligned."""
+    if host is not None:
+        return torch.from_numpy(host).to(frames.codes.device)
+    if windows.shape[1] == 3:
+        windows = torch.nn.functional.pad(windows, (0, 1))
+    if not windows.is_contiguous() or windows.data_ptr() % 16:
+        windows = windows.clone(memory_format=torch.contiguous_format)
+    return windows
+
+
+def decode_windows_shape(frames: DeviceFrames, n_windows: int, size,
+                         stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
+    """(workgroups per window, waves per workgroup) decode_windows would launch n_windows windows
+    of size = (bw, bh) blocks with (mh_decode_windows_shape)."""
+    bw, bh = _window_size(frames, size)
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    if int(n_windows) < 1:
+        raise ValueError("no windows")
+    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
+    N.check(N.lib().mh_decode_windows_shape(ctypes.byref(fr), int(n_windows), bw, bh, sp, ctypes.byref(g),
+                                            ctypes.byref(w)), "mh_decode_windows_shape")
+    return int(g.value), int(w.value)
+
+
+def decode_windows(frames: DeviceFrames, tables, windows, size, out: Optional[torch.Tensor] = None,
+                   status=None, stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                   skip_rejected: bool = True):
+    """Decode a list of windows of one size = (bw, bh) in blocks, window p the blocks
+    [bx0, bx0 + bw) x [by0, by0 + bh) of frame `frame`, into out[n_windows, 8 * bh, 8 * bw] in one
+    launch (mh_decode_windows). Windows may overlap, repeat and name frames in any order.
+    windows: an int32 tensor [n, 3] or [n, 4] of (frame, bx0, by0[, 0]) on the frames' device -- used as
+    it is when [n, 4], contiguous and 16-byte aligned, never read on the host (no sync): the kernel
+    validates every window and rejects, with status MH_ERR_DIMS and an untouched slot, one that
+    names no frame or leaves the block grid -- or a host sequence / array of (frame, bx0, by0),
+    validated here (ValueError) and uploaded.
+    out: a contiguous uint8 [n, 8 * bh, 8 * bw] tensor on the frames' device; None allocates a
+    ZERO-FILLED one, because the rows >= RH_p of a window at the frame's bottom edge (and a rejected
+    or skipped window's whole slot) are never written. The first RW_p columns of a row are the picture.
+    status: None; True to get (out, int32[n] per-window status); or an int32[n] device tensor that
+    receives it (out is returned): MH_ERR_DIMS for a rejected window, the frame's non-zero status
+    word for a window of a skipped frame, else 0.
+    tables, extra_flags, skip_rejected: decode_region's (the table set's status is per frame)."""
+    bw, bh = _window_size(frames, size)
+    host = _host_windows(frames, windows, bw, bh)
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_windows")
+    luts, stride, fstatus = _region_tables("decode_windows", frames, tables, dev_index, skip_rejected)
+    dev = frames.codes.device
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        wins = _windows_tensor(frames, windows, host)  # (an upload or a padded copy belongs to `stream`)
+        n = int(wins.shape[0])
+        shape = (n, 8 * bh, 8 * bw)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.uint8, device=dev)
+        wstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
+    if (out.dtype is not torch.uint8 or tuple(out.shape) != shape or out.get_device() != dev_index
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on cuda:{dev_index}")
+    if wstatus is not None and (not isinstance(wstatus, torch.Tensor) or wstatus.dtype is not torch.int32
+                                or wstatus.numel() != n or wstatus.get_device() != dev_index
+                                or not wstatus.is_contiguous()):
+        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
+    sp = _raw_stream_ptr(stream, dev_index)
+    rc = N.lib().mh_decode_windows(ctypes.byref(fr), wins.data_ptr(), n, bw, bh, luts.data_ptr(), stride,
+                                   fstatus.data_ptr() if fstatus is not None else None,
+                                   wstatus.data_ptr() if wstatus is not None else None, out.data_ptr(), 8 * bw,
+                                   8 * bh * 8 * bw, sp)
+    if rc:
+        N.check(rc, "mh_decode_windows")
+    return (out, wstatus) if status is True else out
+
+
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
                          extra_flags: int = 0) -> tuple:
     """(workgroups per frame, waves per workgroup) decode_headers would launch with
