@@ -356,8 +356,9 @@ int mh_box_reduce(const uint8_t *raster, uint32_t width, uint32_t height, size_t
 /* A list of windows in one launch: rectangles of one size in blocks, each with its own frame   */
 /* and origin -- random crops of a set of scans, the tiles a viewer's cache misses after a     */
 /* jump, a tracked box that moves from frame to frame. mh_decode_region decodes the SAME        */
-/* rectangle of every frame; N rectangles took N launches of it. Not covered: windows at a     */
-/* reduced scale; windows for mh_decode_headers, the streams, the multi-GPU paths and mh_check; */
+/* rectangle of every frame; N rectangles took N launches of it. Windows at a reduced scale:  */
+/* mh_decode_windows_scaled below. Not covered: windows for mh_decode_headers, the streams, the */
+/* multi-GPU paths and mh_check;                                                                */
 /* windows of different sizes in one launch; packing several rows of a window narrower than 64  */
 /* blocks into one wave (lane utilisation is bw / (64 ceil(bw / 64)), as for a region);         */
 /* pixel-granular stores; a CPU twin.                                                           */
@@ -405,6 +406,42 @@ int mh_decode_windows(const mh_frame *frame, const mh_window *d_windows, uint32_
  * window (G above) and waves per workgroup. For tests and tools. */
 int mh_decode_windows_shape(const mh_frame *frame, uint32_t n_windows, uint32_t bw, uint32_t bh,
                             void *stream, uint32_t *groups_per_window, uint32_t *waves_per_group);
+
+/* ---------------------------------------------------------------------- */
+/* A list of windows at 1/2, 1/4 or 1/8 scale in one launch: the tiles a viewer's cache misses  */
+/* at pyramid level k, one crop per scan of a thumbnail sheet, multi-scale random crops.        */
+/* Not covered: a scale per window; windows clipped at the grid's edge; and what                */
+/* mh_decode_windows and mh_decode_region_scaled leave out.                                     */
+
+/* mh_decode_windows at scale s = 2^log2_scale; c = 8 >> log2_scale. Window p is
+ * mh_decode_windows' window p, of pixel size RW_p x RH_p; its scaled size is
+ *   SW_p = ceil(RW_p / s),  SH_p = ceil(RH_p / s).
+ * Output: window p, output row Y starts at d_out + p * out_window_stride + Y * out_pitch; bw * c
+ * bytes of every row Y < SH_p are written, those at X >= SW_p as 0; nothing else is touched, in
+ * that slot or outside it. Pixel (X, Y), X < SW_p, is mh_decode_region_scaled's: the mean of the
+ * cell's pixels inside the frame, floor((2 S + n) / (2 n)). The written bytes equal those
+ * mh_decode_region_scaled writes for the region {bx0, by0, bw, bh} of that frame.
+ * log2_scale == 0 is mh_decode_windows (same checks, same kernel, same bytes); 1, 2, 3 are kernels
+ * of their own; > 3 -> MH_ERR_INVALID_ARG, reported where a bad flag is.
+ * d_windows, tables, d_frame_status, d_window_status, the validation of a window on the device and
+ * flags: mh_decode_windows'.
+ * Checks: all before any HIP call, in mh_decode_windows' order and with its codes, with n_windows
+ * rasters of c bw x c bh in the place of 8 bw x 8 bh (out_pitch >= c bw; for n_windows > 1,
+ * out_window_stride >= out_pitch * c bh) and c in the place of 8 in the alignment rules (d_out,
+ * out_pitch and, for n_windows > 1, out_window_stride are multiples of c; at log2_scale 3 any
+ * value is legal).
+ * One kernel launch, asynchronous; tiles and the launch-shape rule are mh_decode_windows', with
+ * this kernel's own occupancy. */
+int mh_decode_windows_scaled(const mh_frame *frame, const mh_window *d_windows, uint32_t n_windows,
+                             uint32_t bw, uint32_t bh, uint32_t log2_scale,
+                             const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                             const int32_t *d_frame_status, int32_t *d_window_status,
+                             uint8_t *d_out, size_t out_pitch, size_t out_window_stride, void *stream);
+
+/* The launch shape mh_decode_windows_scaled would use (no launch), as mh_decode_windows_shape. */
+int mh_decode_windows_scaled_shape(const mh_frame *frame, uint32_t n_windows, uint32_t bw, uint32_t bh,
+                                   uint32_t log2_scale, void *stream,
+                                   uint32_t *groups_per_window, uint32_t *waves_per_group);
 
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a

@@ -15,6 +15,8 @@ of mdejong/MetalHuffman).
                                     box means taken in the decoder's registers; codec.box_reduce is the CPU twin
   * decoder.decode_windows / windows_of_rects   a list of windows of one size, each with its own frame and
                                     origin (random crops, a viewer's missing tiles, a moving box), one launch
+  * decoder.decode_windows_scaled   the same list at 1/2, 1/4 or 1/8 scale (a viewer's missing tiles at a pyramid
+                                    level, a thumbnail sheet, multi-scale crops), one launch
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync

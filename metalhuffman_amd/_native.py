@@ -44,6 +44,7 @@ EXPORTS = (
     "mh_decode_region", "mh_decode_region_shape",
     "mh_decode_region_scaled", "mh_decode_region_scaled_shape", "mh_box_reduce",
     "mh_decode_windows", "mh_decode_windows_shape",
+    "mh_decode_windows_scaled", "mh_decode_windows_scaled_shape",
 )
 
 
@@ -163,6 +164,11 @@ def lib() -> ctypes.CDLL:
                                         ctypes.c_size_t, _vp]
         L.mh_decode_windows_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
                                               ctypes.c_uint32, _vp, _u32p, _u32p]
+        L.mh_decode_windows_scaled.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_uint32, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                               ctypes.c_size_t, ctypes.c_size_t, _vp]
+        L.mh_decode_windows_scaled_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
+                                                     ctypes.c_uint32, ctypes.c_uint32, _vp, _u32p, _u32p]
         L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
                                     ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]

@@ -1690,6 +1690,37 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
                        WindowMap{{f, bx0, by0, p_rbw, p_segs}, p, p_wstatus});
 }
 
+// ... and the windows at scale 2^kLog2 (kLog2 = 1..3): the same descriptor trip and the same verdict
+// ahead of the same body with the BoxRows output stage. The window's edge word `rem` and its row
+// limit SH_p * pitch are formed behind the verdict, from the accepted origin only. The scaled
+// body has no SGPR to spare for the slot index (raw pixels at 1/4 scale spilled with it), so the
+// slot is folded into the raster's base here and the window stride is 0 from then on:
+// raster_slot() * 0 is no instruction, and `p` lives no longer than report().
+template <bool kDelta, int kLog2>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_windows_scaled_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const mh_window *p_windows, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbh, uint32_t p_nframes, uint32_t p_max_bx0, uint32_t p_max_by0,
+    uint64_t p_lut_stride, int32_t *p_wstatus, const DecodeArgs a0) {
+  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
+  const v4u32 wd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_windows + p, 16u), 0, 0, 0);
+  const uint32_t f = __builtin_amdgcn_readfirstlane(wd.x), bx0 = __builtin_amdgcn_readfirstlane(wd.y);
+  const uint32_t by0 = __builtin_amdgcn_readfirstlane(wd.z), reserved = __builtin_amdgcn_readfirstlane(wd.w);
+  if ((f >= p_nframes) | (bx0 > p_max_bx0) | (by0 > p_max_by0) | (reserved != 0u)) {  // workgroup-uniform
+    if (p_wstatus && slice == 0 && threadIdx.x == 0) p_wstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  constexpr uint32_t s = 1u << kLog2;
+  DecodeArgs aw = a0;
+  aw.out = a0.out + (uint64_t)p * a0.out_frame_stride;
+  aw.out_frame_stride = 0;
+  aw.out_frame_bytes = (uint64_t)((min(a0.h, 8u * (by0 + p_rbh)) - 8u * by0 + s - 1u) >> kLog2) * a0.out_pitch;
+  slice_decode<kDelta, BoxRows<kLog2>>(
+      aw, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
+      PreparedTable{p_luts, p_lut_stride},
+      WindowMap{{f, bx0, by0, p_rbw, p_segs, (a0.w - 8u * bx0) | ((a0.h - 8u * by0) << 16)}, p, p_wstatus});
+}
+
 template <bool kDelta>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_headers_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_headers,
@@ -2303,7 +2334,8 @@ enum SliceKernel {
   kSliceRegion,
   kSliceScaled,
   kSliceWindows = kSliceScaled + 3,
-  kSliceKernels
+  kSliceWindowsScaled,  // + k - 1: the windows kernel at scale 2^k
+  kSliceKernels = kSliceWindowsScaled + 3
 };
 struct DeviceInfo {
   std::mutex m;
@@ -2367,6 +2399,12 @@ const DeviceInfo *device_info(hipStream_t s) {
   d.occ_slice[kSliceScaled + 2][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 3>, kMaxWavesPerWG);
   d.occ_slice[kSliceWindows][0] = occupancy_of(mh_decode_windows_kernel<false>, kMaxWavesPerWG);
   d.occ_slice[kSliceWindows][1] = occupancy_of(mh_decode_windows_kernel<true>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindowsScaled + 0][0] = occupancy_of(mh_decode_windows_scaled_kernel<false, 1>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindowsScaled + 0][1] = occupancy_of(mh_decode_windows_scaled_kernel<true, 1>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindowsScaled + 1][0] = occupancy_of(mh_decode_windows_scaled_kernel<false, 2>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindowsScaled + 1][1] = occupancy_of(mh_decode_windows_scaled_kernel<true, 2>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindowsScaled + 2][0] = occupancy_of(mh_decode_windows_scaled_kernel<false, 3>, kMaxWavesPerWG);
+  d.occ_slice[kSliceWindowsScaled + 2][1] = occupancy_of(mh_decode_windows_scaled_kernel<true, 3>, kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -2485,7 +2523,8 @@ struct TableRule {
 // Windows (mh_decode_windows): the region's rules for rg = {0, 0, bw, bh} -- so a size that is
 // empty or exceeds the grid is MH_ERR_DIMS -- with n_windows rasters of the full 8 bw x 8 bh in the
 // place of n_frames rasters of RW x RH (windows differ in RW / RH; `out_frame_stride` is the window
-// stride), and the descriptor array checked where the tables are.
+// stride), and the descriptor array checked where the tables are. At scale 2^log2_scale
+// (mh_decode_windows_scaled) the rasters are c bw x c bh and c stands where 8 does, as for a region.
 int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                       uint32_t allowed_flags, const TableRule &tr, RegionExtent *re = nullptr,
                       uint32_t log2_scale = 0) {
@@ -2598,7 +2637,8 @@ int launch_slices(Kernel kernel, SliceKernel k, bool delta, const DecodeArgs &a,
 
 // mh_decode_{frames,headers,region,region_scaled}_shape: slice_shape for a frame description (`rg`:
 // kSliceRegion only; with a log2_scale of 1..3 the region kernel of that scale stands for it).
-// kSliceWindows: rg = {0, 0, bw, bh} and n_windows units in the place of n_frames.
+// kSliceWindows: rg = {0, 0, bw, bh} and n_windows units in the place of n_frames; with a
+// log2_scale of 1..3 the windows kernel of that scale stands for it.
 int slice_shape_entry(SliceKernel k, const mh_frame *fr, const mh_region *rg, void *stream,
                       uint32_t *groups_per_frame, uint32_t *waves_per_group, uint32_t log2_scale = 0,
                       uint32_t n_windows = 0) {
@@ -2608,7 +2648,7 @@ int slice_shape_entry(SliceKernel k, const mh_frame *fr, const mh_region *rg, vo
   const uint32_t n_units = k == kSliceWindows ? n_windows : fr->n_frames;
   if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
   if (log2_scale > 3u) return MH_ERR_INVALID_ARG;
-  if (log2_scale) k = (SliceKernel)(kSliceScaled + log2_scale - 1u);
+  if (log2_scale) k = (SliceKernel)((k == kSliceWindows ? kSliceWindowsScaled : kSliceScaled) + log2_scale - 1u);
   const mh_dims &d = fr->dims;
   if (!dims_ok(d)) return MH_ERR_DIMS;
   uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
@@ -2830,6 +2870,47 @@ int mh_decode_windows_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw,
                             uint32_t *groups_per_window, uint32_t *waves_per_group) {
   const mh_region size = {0u, 0u, bw, bh};
   return slice_shape_entry(kSliceWindows, fr, &size, stream, groups_per_window, waves_per_group, 0, n_windows);
+}
+
+// The windows at scale 2^log2_scale: scale 1 is mh_decode_windows itself; 2, 4 and 8 are the windows
+// kernel with the box-filter output stage, every slot a raster of c bw x c bh (c = 8 >> log2_scale).
+int mh_decode_windows_scaled(const mh_frame *fr, const mh_window *d_windows, uint32_t n_windows, uint32_t bw,
+                             uint32_t bh, uint32_t log2_scale, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                             const int32_t *d_frame_status, int32_t *d_window_status, uint8_t *d_out,
+                             size_t out_pitch, size_t out_window_stride, void *stream) {
+  if (log2_scale == 0)
+    return mh_decode_windows(fr, d_windows, n_windows, bw, bh, d_luts, lut_stride_bytes, d_frame_status,
+                             d_window_status, d_out, out_pitch, out_window_stride, stream);
+  if (d_window_status && d_window_status == d_frame_status) return MH_ERR_INVALID_ARG;
+  const mh_region size = {0u, 0u, bw, bh};
+  TableRule tr{TableRule::kWindows, d_luts, lut_stride_bytes, &size};
+  tr.windows = d_windows;
+  tr.n_windows = n_windows;
+  RegionExtent re;
+  int rc = check_decode_args(fr, d_out, out_pitch, out_window_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, tr, &re,
+                             log2_scale);
+  if (rc != MH_OK) return rc;
+  DecodeArgs a{};
+  rc = fill_decode_args(fr, d_out, out_pitch, out_window_stride, a, &re, n_windows);
+  if (rc != MH_OK) return rc;
+  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
+  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  const SliceKernel k = (SliceKernel)(kSliceWindowsScaled + log2_scale - 1u);
+#define MH_SCALED(K)                                                                                                \
+  launch_slices(delta ? mh_decode_windows_scaled_kernel<true, K> : mh_decode_windows_scaled_kernel<false, K>, k,    \
+                delta, a, n_windows, (hipStream_t)stream, ao, luts, d_frame_status, d_windows, re.segs, bw, bh,      \
+                fr->n_frames, fr->dims.block_width - bw, fr->dims.block_height - bh, lut_stride_bytes,              \
+                d_window_status)
+  return log2_scale == 1 ? MH_SCALED(1) : log2_scale == 2 ? MH_SCALED(2) : MH_SCALED(3);
+#undef MH_SCALED
+}
+
+int mh_decode_windows_scaled_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh,
+                                   uint32_t log2_scale, void *stream, uint32_t *groups_per_window,
+                                   uint32_t *waves_per_group) {
+  const mh_region size = {0u, 0u, bw, bh};
+  return slice_shape_entry(kSliceWindows, fr, &size, stream, groups_per_window, waves_per_group, log2_scale,
+                           n_windows);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

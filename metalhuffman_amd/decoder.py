@@ -647,6 +647,44 @@ def decode_windows_shape(frames: DeviceFrames, n_windows: int, size,
     return int(g.value), int(w.value)
 
 
+def _decode_windows(who: str, k: int, frames: DeviceFrames, tables, windows, size, out, status, stream,
+                    extra_flags: int, skip_rejected: bool):
+    """decode_windows (k = 0) and decode_windows_scaled: the arguments checked, the descriptor array and
+    the default rasters made, one launch."""
+    bw, bh = _window_size(frames, size)
+    c = 8 >> k
+    host = _host_windows(frames, windows, bw, bh)
+    fr, dev_index = _frames_entry(frames, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
+    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
+    dev = frames.codes.device
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        wins = _windows_tensor(frames, windows, host)  # (an upload or a padded copy belongs to `stream`)
+        n = int(wins.shape[0])
+        shape = (n, c * bh, c * bw)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.uint8, device=dev)
+        wstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
+    if (out.dtype is not torch.uint8 or tuple(out.shape) != shape or out.get_device() != dev_index
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on cuda:{dev_index}")
+    if wstatus is not None and (not isinstance(wstatus, torch.Tensor) or wstatus.dtype is not torch.int32
+                                or wstatus.numel() != n or wstatus.get_device() != dev_index
+                                or not wstatus.is_contiguous()):
+        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
+    sp = _raw_stream_ptr(stream, dev_index)
+    tail = (luts.data_ptr(), stride, fstatus.data_ptr() if fstatus is not None else None,
+            wstatus.data_ptr() if wstatus is not None else None, out.data_ptr(), c * bw, c * bh * c * bw, sp)
+    if k:
+        rc = N.lib().mh_decode_windows_scaled(ctypes.byref(fr), wins.data_ptr(), n, bw, bh, k, *tail)
+    else:
+        rc = N.lib().mh_decode_windows(ctypes.byref(fr), wins.data_ptr(), n, bw, bh, *tail)
+    if rc:
+        N.check(rc, "mh_decode_windows_scaled" if k else "mh_decode_windows")
+    return (out, wstatus) if status is True else out
+
+
 def decode_windows(frames: DeviceFrames, tables, windows, size, out: Optional[torch.Tensor] = None,
                    status=None, stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
                    skip_rejected: bool = True):
@@ -665,35 +703,45 @@ def decode_windows(frames: DeviceFrames, tables, windows, size, out: Optional[to
     receives it (out is returned): MH_ERR_DIMS for a rejected window, the frame's non-zero status
     word for a window of a skipped frame, else 0.
     tables, extra_flags, skip_rejected: decode_region's (the table set's status is per frame)."""
+    return _decode_windows("decode_windows", 0, frames, tables, windows, size, out, status, stream, extra_flags,
+                           skip_rejected)
+
+
+def decode_windows_scaled_shape(frames: DeviceFrames, n_windows: int, size, log2_scale: int,
+                                stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
+    """(workgroups per window, waves per workgroup) decode_windows_scaled would launch n_windows
+    windows of size = (bw, bh) blocks with, at scale 2^log2_scale (mh_decode_windows_scaled_shape)."""
+    k = _log2_scale(log2_scale)
     bw, bh = _window_size(frames, size)
-    host = _host_windows(frames, windows, bw, bh)
     fr, dev_index = _frames_entry(frames, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_windows")
-    luts, stride, fstatus = _region_tables("decode_windows", frames, tables, dev_index, skip_rejected)
-    dev = frames.codes.device
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        wins = _windows_tensor(frames, windows, host)  # (an upload or a padded copy belongs to `stream`)
-        n = int(wins.shape[0])
-        shape = (n, 8 * bh, 8 * bw)
-        if out is None:
-            out = torch.zeros(shape, dtype=torch.uint8, device=dev)
-        wstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
-    if (out.dtype is not torch.uint8 or tuple(out.shape) != shape or out.get_device() != dev_index
-            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on cuda:{dev_index}")
-    if wstatus is not None and (not isinstance(wstatus, torch.Tensor) or wstatus.dtype is not torch.int32
-                                or wstatus.numel() != n or wstatus.get_device() != dev_index
-                                or not wstatus.is_contiguous()):
-        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
-    sp = _raw_stream_ptr(stream, dev_index)
-    rc = N.lib().mh_decode_windows(ctypes.byref(fr), wins.data_ptr(), n, bw, bh, luts.data_ptr(), stride,
-                                   fstatus.data_ptr() if fstatus is not None else None,
-                                   wstatus.data_ptr() if wstatus is not None else None, out.data_ptr(), 8 * bw,
-                                   8 * bh * 8 * bw, sp)
-    if rc:
-        N.check(rc, "mh_decode_windows")
-    return (out, wstatus) if status is True else out
+    if int(n_windows) < 1:
+        raise ValueError("no windows")
+    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
+    N.check(N.lib().mh_decode_windows_scaled_shape(ctypes.byref(fr), int(n_windows), bw, bh, k, sp, ctypes.byref(g),
+                                                   ctypes.byref(w)), "mh_decode_windows_scaled_shape")
+    return int(g.value), int(w.value)
+
+
+def decode_windows_scaled(frames: DeviceFrames, tables, windows, size, log2_scale: int,
+                          out: Optional[torch.Tensor] = None, status=None,
+                          stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                          skip_rejected: bool = True):
+    """decode_windows at scale s = 2^log2_scale (0..3) in one launch (mh_decode_windows_scaled): every
+    s x s cell of a window becomes the mean of its pixels inside the frame, halves rounded up, as in
+    decode_region_scaled, and no full-size raster exists. -> out[n_windows, bh * c, bw * c],
+    c = 8 >> log2_scale. Window p's picture is its first SH_p rows and SW_p columns, (SW_p, SH_p) =
+    Region(bx0, by0, bw, bh).scaled_size; the columns beyond SW_p in those rows are 0, and rows
+    >= SH_p (and a rejected or skipped window's whole slot) are never written, so out = None
+    allocates a ZERO-FILLED raster as decode_windows does.
+    Rectangle i of windows_of_rects lies at out[i, dy[i] // s: (dy[i] + h) // s, dx[i] // s:
+    (dx[i] + w) // s] -- exactly only when dx[i], dy[i], w and h are multiples of s: the cells are
+    those of the frame's grid, and a cell the rectangle covers in part averages pixels outside it.
+    windows, size, status, tables, extra_flags, skip_rejected: decode_windows'. log2_scale 0 is
+    decode_windows."""
+    k = _log2_scale(log2_scale)
+    return _decode_windows("decode_windows_scaled", k, frames, tables, windows, size, out, status, stream,
+                           extra_flags, skip_rejected)
 
 
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
