@@ -205,7 +205,9 @@ int mh_build_tables_device(const uint8_t *d_canon_header, mh_lookup_symbol *d_ta
 /* streams such frames from host memory. Not covered: mh_check with per-frame  */
 /* tables, stream groups and the multi-GPU paths with per-frame tables, and an */
 /* in-kernel table build from T1/T2 for mh_decode_frames (it needs prepared    */
-/* tables).                                                                    */
+/* tables). A batch of different frames that should decode under ONE table     */
+/* (mh_decode, the fastest route) is encoded by                                */
+/* mh_encode_frames_shared_device_async instead.                               */
 
 /* n prepared tables (mh_prepare_lut's buffer) from n 256-byte canonical headers in ONE
  * launch: header i at d_canon_headers + 256 i -> d_luts + i * lut_stride_bytes, byte-identical
@@ -536,6 +538,71 @@ int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_str
                                   uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
                                   int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Device workspace mh_encode_frames_shared_device_async needs for n_frames frames of
+ * width x height (mh_encode_frames_workspace_bytes' plus the one table's state). */
+size_t mh_encode_frames_shared_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_frames);
+
+/* Batched GPU encode under ONE Huffman table: the producer of what mh_decode, the
+ * table-mode streams and the multi-GPU paths consume (n frames, one 256-byte canonical
+ * header). Two modes:
+ *   built (d_canon_in == NULL): one histogram over all n frames' symbols, one tree, one
+ *     header -- mh_code_lengths of the summed histogram (the reference tree and its
+ *     tie-breaking) or, with MH_ENCODE_LIMIT_LENGTHS and a tree deeper than 16,
+ *     mh_code_lengths_limited(sum, 16, ...) -- written to d_canon_header (required);
+ *   supplied (d_canon_in != NULL, device u8[256]): no histogram reduction and no tree; the
+ *     caller's lengths are validated and turned into mh_canonical_codes' codes (a header
+ *     fixed for a sequence, an earlier batch's, one broadcast to several GPUs before they
+ *     encode). d_canon_header is then optional and receives a copy (it may alias
+ *     d_canon_in). MH_ENCODE_LIMIT_LENGTHS is ignored.
+ * Every frame is packed with that header's codes. Frame layout, slots (16-byte aligned,
+ * the slot size is the capacity), d_frame_code_offsets, d_block_init, alignment and the
+ * argument checks and their order are mh_encode_frames_device_async's, plus: NULL
+ * d_canon_in AND NULL d_canon_header -> MH_ERR_INVALID_ARG (with the other NULL checks);
+ * built mode with n_frames * NB * 64 >= 2^32 symbols -> MH_ERR_CAPACITY (ahead of the
+ * workspace check; the tree's node weights are 32-bit: 1,365 frames of 2048 x 1536 fit).
+ * The batch's total code bits are not limited; one frame's are (u32 block offsets). All
+ * checks come before any HIP call. flags: MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED |
+ * MH_ENCODE_LIMIT_LENGTHS.
+ * *d_header_status (device int32, optional), the header's verdict: MH_OK;
+ * MH_ERR_CODE_TOO_LONG (the built tree is deeper than 16 without MH_ENCODE_LIMIT_LENGTHS,
+ * or a supplied length is over 16); MH_ERR_TABLE (a supplied header whose Kraft sum
+ * exceeds 1). A supplied header with a Kraft sum under 1 -- an incomplete code, e.g. one
+ * symbol of length 1 -- is valid, as it is for every decoder here.
+ * d_status[f] (device int32[n_frames], optional), first match: the header's verdict when
+ * that is not MH_OK (every frame); MH_ERR_TABLE when frame f contains a symbol to which
+ * the header gives length 0 (supplied mode only); MH_ERR_CAPACITY when
+ * round_up(codes_len, 4) > codes_frame_stride or the frame alone has >= 2^32 code bits;
+ * MH_OK. A rejected frame writes no code byte and no block offset, its d_codes_len[f] is
+ * 0 and it does not disturb the other frames; its d_block_init slice is UNSPECIFIED (the
+ * split writes it before the verdict exists). On a rejected header in built mode the
+ * content of d_canon_header is unspecified, as in the other encoders.
+ * For every accepted frame, the codes (payload + MH_CODES_PAD zero bytes), d_codes_len[f]
+ * and the block offsets are byte for byte mh_encode_frame_with_header's for that frame and
+ * header.
+ * Launches, whatever n_frames: five kernels in built mode (tiled split, histogram
+ * reduction over frames, one tree workgroup, one plan workgroup per frame, packing), four
+ * in supplied mode (split, header -> code table, plan, packing); the split and the packer
+ * are mh_encode_frames_device_async's. d_workspace: 256-byte aligned,
+ * mh_encode_frames_shared_workspace_bytes(), any content: built mode clears the batch
+ * histogram (16 KB, one memset ahead of the kernels) unless MH_ENCODE_WORKSPACE_ZEROED
+ * says the caller zero-filled the workspace once before its first use -- every call
+ * leaves the histogram zeroed, as mh_encode_frame_device_async does. Asynchronous on
+ * `stream`, no host synchronisation; the return value covers argument checks and
+ * launches. The outputs go to mh_build_tables_device (d_canon_header) and mh_decode
+ * without touching the host. */
+int mh_encode_frames_shared_device_async(
+    const uint8_t *d_gray, uint64_t gray_frame_stride, uint32_t n_frames,
+    uint32_t width, uint32_t height, uint32_t flags,
+    const uint8_t *d_canon_in,     /* device u8[256], or NULL = build the header from the batch */
+    uint8_t *d_canon_header,       /* device u8[256] out: the header the frames were encoded with;
+                                      required when d_canon_in is NULL, optional (a copy; may alias
+                                      d_canon_in) otherwise */
+    uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
+    uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
+    int32_t *d_status,             /* optional, int32[n_frames] */
+    int32_t *d_header_status,      /* optional, one int32: the header's verdict */
+    void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------- */
 /* Streaming from host memory (BASELINE config 5; the reference's per-frame  */
 /* command buffer, AAPLRenderer.m:1178-1921).                               */
@@ -587,7 +654,9 @@ int mh_stream_destroy(mh_stream *s);
  * stores nothing into the rasters. mh_stream_output / slot_stream / compute_stream / wait / slot_time / device /
  * synchronize / destroy work on such a stream unchanged; mh_stream_submit returns
  * MH_ERR_INVALID_ARG on it, as mh_stream_submit_header does on a table-mode stream. Stream
- * groups stay table-mode only. */
+ * groups stay table-mode only. (Frames that are to share ONE table -- the table-mode stream,
+ * mh_decode, the stream groups -- come from mh_encode_frames_shared_device_async or
+ * mh_encode_frame_with_header.) */
 int mh_stream_create_headers(const mh_frame *proto, uint64_t codes_capacity, uint32_t n_slots,
                              uint8_t *const *d_outputs, mh_stream **out);
 /* mh_stream_submit with the frame's header (256 host bytes; same capacity and init-byte
@@ -660,6 +729,25 @@ int mh_encode_huffman(const uint8_t *symbols, uint64_t n_symbols, uint32_t block
 int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
                     uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
                     uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init);
+
+/* Adds the symbol counts of one frame -- what mh_encode_frame would encode: split, per-block
+ * deltas unless MH_FLAG_NO_DELTA, first delta zeroed when with_block_init -- into freq[256]
+ * (a second call adds to the first). A host user builds a shared header as
+ * mh_frame_histogram over the frames, then mh_code_lengths[_limited]. */
+int mh_frame_histogram(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                       int with_block_init, uint64_t freq[256]);
+
+/* mh_encode_frame under the caller's header instead of the frame's own tree: the host twin
+ * of mh_encode_frames_shared_device_async, frame by frame. The status is the header's
+ * verdict (MH_ERR_CODE_TOO_LONG for a length over 16, MH_ERR_TABLE for a Kraft sum over 1;
+ * an incomplete code is valid), then MH_ERR_TABLE when the frame contains a symbol of
+ * length 0 in the header, then MH_ERR_CAPACITY (codes_len > codes_cap, or >= 2^32 code
+ * bits). Nothing is written on an error. Given the frame's own header, the output equals
+ * mh_encode_frame's byte for byte. flags: MH_FLAG_NO_DELTA (MH_ENCODE_LIMIT_LENGTHS is
+ * accepted and ignored). */
+int mh_encode_frame_with_header(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                                const uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
+                                uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init);
 
 /* huff_util.hpp:94-193 huff_generate_canonical_codes: left-justified u16 codes. */
 int mh_canonical_codes(const uint8_t canon_header[256], uint16_t codes[256]);

@@ -19,18 +19,21 @@ of mdejong/MetalHuffman).
                                     level, a thumbnail sheet, multi-scale crops), one launch
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
-                                    n tables -> decode on one stream, no host sync
+                                    n tables -> decode on one stream, no host sync;
+                                    encode_shared_async: the batch under ONE table (built from the summed
+                                    histogram, or a supplied header) for decoder.decode;
+                                    codec.shared_header / encode_frame(header=) are the CPU twins
   * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
 """
 from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS, MH_FLAG_NO_DELTA,
                       MHError, lib)
 from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, code_lengths_limited,
-                    decode_frame_cpu, encode_frame, merge_blocks, split_blocks)
+                    decode_frame_cpu, encode_frame, frame_histogram, merge_blocks, shared_header, split_blocks)
 
 __all__ = [
     "EXPORTS", "LIB_PATH", "MH_CODES_PAD", "MH_FLAG_LANE_PAIRS", "MH_FLAG_NO_DELTA", "MHError", "lib", "BLOCK_DIM",
     "EncodedFrame", "Huffman", "block_grid", "decode_frame_cpu", "encode_frame", "merge_blocks", "split_blocks",
-    "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce",
+    "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
 ]
 __version__ = "0.1.0"

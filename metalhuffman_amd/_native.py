@@ -45,6 +45,8 @@ EXPORTS = (
     "mh_decode_region_scaled", "mh_decode_region_scaled_shape", "mh_box_reduce",
     "mh_decode_windows", "mh_decode_windows_shape",
     "mh_decode_windows_scaled", "mh_decode_windows_scaled_shape",
+    "mh_encode_frames_shared_workspace_bytes", "mh_encode_frames_shared_device_async",
+    "mh_frame_histogram", "mh_encode_frame_with_header",
 )
 
 
@@ -217,6 +219,16 @@ def lib() -> ctypes.CDLL:
         L.mh_encode_frames_device_async.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                     ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64,
                                                     _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+        L.mh_encode_frames_shared_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        L.mh_encode_frames_shared_workspace_bytes.restype = ctypes.c_size_t
+        L.mh_encode_frames_shared_device_async.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                           ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
+                                                           ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                           ctypes.c_size_t, _vp]
+        L.mh_frame_histogram.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                         _u64p]
+        L.mh_encode_frame_with_header.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p,
+                                                  _u8p, ctypes.c_uint64, _u64p, _u32p, _u8p]
         L.mh_split_blocks.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_uint8, _u8p, ctypes.c_size_t]
         L.mh_merge_blocks.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p,

@@ -271,12 +271,45 @@ def code_lengths_limited(freq, max_bits: int = 16) -> np.ndarray:
     return lens
 
 
+def frame_histogram(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False) -> np.ndarray:
+    """uint64[256]: the counts of the symbols encode_frame would encode for this frame
+    (mh_frame_histogram: split, per-block deltas unless MH_FLAG_NO_DELTA, the first delta
+    of every block zeroed with init_zero_delta)."""
+    gray = _u8(gray)
+    if gray.ndim != 2:
+        raise ValueError("expected a 2-D uint8 image")
+    h, w = gray.shape
+    freq = np.zeros(256, np.uint64)
+    N.check(N.lib().mh_frame_histogram(_p(gray), w, h, flags, 1 if init_zero_delta else 0,
+                                       freq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))), "frame_histogram")
+    return freq
+
+
+def shared_header(grays, flags: int = 0, init_zero_delta: bool = False, limit_lengths: bool = False) -> np.ndarray:
+    """One canonical header (u8[256]) for all of `grays` (2-D uint8 images of any sizes):
+    the reference tree of their summed symbol counts (mh_code_lengths), or with
+    limit_lengths the code of at most 16 bits where that tree is deeper
+    (mh_code_lengths_limited). What BatchEncoder.encode_shared_async builds on the device."""
+    freq = np.zeros(256, np.uint64)
+    for g in grays:
+        freq += frame_histogram(g, flags, init_zero_delta)
+    if limit_lengths:
+        return code_lengths_limited(freq, 16)
+    lens = np.zeros(256, np.uint8)
+    N.check(N.lib().mh_code_lengths(freq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _p(lens)), "shared_header")
+    return lens
+
+
 def encode_frame(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False,
-                 limit_lengths: bool = False) -> EncodedFrame:
+                 limit_lengths: bool = False, header=None) -> EncodedFrame:
     """The renderer's producer step (AAPLRenderer.m:374-688) for one 8-bit frame.
     limit_lengths: a frame whose Huffman tree is deeper than 16 gets the length-limited
     code (MH_ENCODE_LIMIT_LENGTHS) instead of MHError -3; any other frame is unchanged.
-    The keyword reaches the encoder only, never the frame's `flags`."""
+    The keyword reaches the encoder only, never the frame's `flags`.
+    header (u8[256], optional): encode under this canonical header instead of the frame's
+    own tree (mh_encode_frame_with_header; e.g. shared_header of a batch). The returned
+    frame's `canon` is that header; MHError -3 / -5 for a header that is no code, -5 when
+    the frame holds a symbol the header has no code for. limit_lengths is then unused."""
     gray = _u8(gray)
     if gray.ndim != 2:
         raise ValueError("expected a 2-D uint8 image")
@@ -284,11 +317,20 @@ def encode_frame(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False
     bw, bh = block_grid(w, h)
     nb = bw * bh
     cap = int(N.lib().mh_codes_bound(nb * 64)) + 2
-    canon = np.zeros(256, np.uint8)
     codes = np.zeros(cap, np.uint8)
     offs = np.zeros(nb, np.uint32)
     init = np.zeros(nb, np.uint8) if init_zero_delta else None
     ln = ctypes.c_uint64(0)
+    if header is not None:
+        canon = _u8(header).copy()
+        if canon.shape != (256,):
+            raise ValueError("header must hold 256 code lengths")
+        N.check(N.lib().mh_encode_frame_with_header(_p(gray), w, h, flags, _p(canon), _p(codes), cap,
+                                                    ctypes.byref(ln), _p(offs, _u32p),
+                                                    _p(init) if init is not None else None),
+                "encode_frame_with_header")
+        return EncodedFrame(w, h, canon, codes[: ln.value].copy(), offs, init, flags)
+    canon = np.zeros(256, np.uint8)
     enc_flags = flags | (N.MH_ENCODE_LIMIT_LENGTHS if limit_lengths else 0)
     N.check(N.lib().mh_encode_frame(_p(gray), w, h, enc_flags, _p(canon), _p(codes), cap, ctypes.byref(ln),
                                     _p(offs, _u32p), _p(init) if init is not None else None),

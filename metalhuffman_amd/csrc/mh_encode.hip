@@ -15,6 +15,10 @@
 // Frames of <= kFusedMaxTiles tiles: two launches, enc_split_kernel (tiled) and
 // enc_code_kernel (workgroup 0 = tree, the others = offsets + packing of one tile each).
 // Larger frames: enc_split_kernel, enc_tree_kernel, enc_scan_kernel, enc_pack_kernel.
+// Batches: mh_encode_frames_device_async (a tree per frame, three launches) and
+// mh_encode_frames_shared_device_async (ONE table for the batch, built from the summed
+// histogram -- five launches -- or supplied as 256 code lengths -- four; see "batched
+// frames under ONE table" below).
 // mh_encode_frame_device_async never synchronises (header, code bytes and status are
 // written to device memory); mh_encode_frame_device runs it and synchronises once at
 // the end to return the header and the byte count on the host.
@@ -617,9 +621,14 @@ template <bool kFused>
 // counts (optional): the 256 symbol counts already in LDS (the batched path sums its
 // tile counts itself); otherwise they are the sum of hist's kHistParts partial
 // histograms, which are left zeroed.
+// frame_caps = false (the shared-table batch, whose counts are a whole batch's): no
+// MH_ERR_CAPACITY verdict -- the 2^32 bit limit and codes_cap are per-frame rules, which
+// enc_plan_shared_kernel applies to each frame's own bits. Weights stay u32, so such a
+// caller keeps nsym <= 2^32 (every non-root weight is below the symbol total).
 __device__ __forceinline__ uint32_t tree_body(uint64_t *hist, uint8_t *canon_out, uint32_t *table, uint64_t *meta,
                                           uint64_t *codes_len_out, uint64_t codes_cap, int32_t *status,
-                                          uint64_t nsym, bool limit, const uint32_t *counts = nullptr) {
+                                          uint64_t nsym, bool limit, const uint32_t *counts = nullptr,
+                                          bool frame_caps = true) {
   constexpr uint32_t kEnd = 0xFFFFFFFFu;  // empty queue slot
   constexpr uint32_t kW32End = (1u << 22) - 1u;  // 32-bit merge keys: an empty slot's weight
   const bool k32 = nsym < (uint64_t)kW32End;
@@ -870,7 +879,7 @@ __device__ __forceinline__ uint32_t tree_body(uint64_t *hist, uint8_t *canon_out
     const uint64_t total = s_total;
     const uint64_t len = (total + 7) / 8 + MH_CODES_PAD;  // + encoder's 2 and renderer's 2 zero bytes
     uint32_t bad = s_bad;
-    if (!bad && (total >= (1ull << 32) || ((len + 3) & ~3ull) > codes_cap)) bad = (uint32_t)-MH_ERR_CAPACITY;
+    if (!bad && frame_caps && (total >= (1ull << 32) || ((len + 3) & ~3ull) > codes_cap)) bad = (uint32_t)-MH_ERR_CAPACITY;
     s_bad2 = bad;
     s_len_bytes = len;
   }
@@ -1333,73 +1342,59 @@ constexpr uint32_t kMetaWords = 32;  // per-frame meta slots (>= kGen + 1)
 static_assert(kMetaWords >= kGen + 1, "meta slots");
 constexpr uint32_t kTileBatch = 16;  // tiles per wave and chunk of the tile-offset pass
 
-__global__ void __launch_bounds__(kTreeThreads) enc_tree_batch_kernel(
-    uint64_t *hist, uint8_t *canon, uint32_t *table, uint64_t *meta, uint64_t *codes_len, uint64_t codes_cap,
-    int32_t *status, uint64_t nb, const uint16_t *tile_hist, uint32_t ncode, uint32_t *tile_off,
-    uint64_t *frame_off, uint32_t f0, uint32_t n_frames, uint32_t limit) {
-  // f0: this launch's first frame of the call (its pointers start there; frame_off is
-  // the call's, indexed by call frame)
-  const uint32_t f = blockIdx.x, tid = threadIdx.x;
-  if (frame_off && tid == 0) {  // optional: the decoder's frame_code_offsets for fixed slots
-    frame_off[f0 + f] = (uint64_t)(f0 + f) * codes_cap;
-    if (f0 + f + 1 == n_frames) frame_off[n_frames] = (uint64_t)n_frames * codes_cap;
-  }
-  // the frame's symbol counts: the sum of its tile counts (wave w: tiles w, w + 16, ...,
-  // 24 8-byte loads in flight per lane, lane l: symbols 4l..4l+3), no global atomics
-  __shared__ uint32_t s_part[kCodeWaves][256], s_cnt[256];
-  {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    const uint2 *th = reinterpret_cast<const uint2 *>(tile_hist + (uint64_t)f * ncode * 256);
-    uint32_t acc[4] = {0, 0, 0, 0};
-    // 24 tiles per wave in flight (a 2048x1536 frame's 384 tiles in one round trip),
-    // unconditional buffer loads (tiles past the frame read zero)
-    constexpr uint32_t kDepth = 24;
-    const __amdgpu_buffer_rsrc_t rth = enc_rsrc(th, (uint64_t)ncode * 512u);
-    for (uint32_t t0 = wave; t0 < ncode; t0 += kCodeWaves * kDepth) {
-      uint2 v[kDepth];
+// The frame's symbol counts into s_cnt[256]: the sum of its tile counts th (wave w: tiles
+// w, w + 16, ..., 24 8-byte loads in flight per lane, lane l: symbols 4l..4l+3), no global
+// atomics. Called by all kTreeThreads threads of a workgroup; ends with a barrier.
+__device__ __forceinline__ void frame_symbol_counts(const uint16_t *th, uint32_t ncode, uint32_t *s_cnt) {
+  __shared__ uint32_t s_part[kCodeWaves][256];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t acc[4] = {0, 0, 0, 0};
+  // 24 tiles per wave in flight (a 2048x1536 frame's 384 tiles in one round trip),
+  // unconditional buffer loads (tiles past the frame read zero)
+  constexpr uint32_t kDepth = 24;
+  const __amdgpu_buffer_rsrc_t rth = enc_rsrc(th, (uint64_t)ncode * 512u);
+  for (uint32_t t0 = wave; t0 < ncode; t0 += kCodeWaves * kDepth) {
+    uint2 v[kDepth];
 #pragma unroll
-      for (uint32_t k = 0; k < kDepth; ++k) {
-        const uint32_t t = t0 + kCodeWaves * k;
-        typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
-        const v2u32 x = __builtin_amdgcn_raw_buffer_load_b64(rth, (int)(t < ncode ? t * 512u + lane * 8u : kOob), 0, 0);
-        v[k] = make_uint2(x.x, x.y);
-      }
-#pragma unroll
-      for (uint32_t k = 0; k < kDepth; ++k) {
-        acc[0] += v[k].x & 0xFFFFu;
-        acc[1] += v[k].x >> 16;
-        acc[2] += v[k].y & 0xFFFFu;
-        acc[3] += v[k].y >> 16;
-      }
+    for (uint32_t k = 0; k < kDepth; ++k) {
+      const uint32_t t = t0 + kCodeWaves * k;
+      typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
+      const v2u32 x = __builtin_amdgcn_raw_buffer_load_b64(rth, (int)(t < ncode ? t * 512u + lane * 8u : kOob), 0, 0);
+      v[k] = make_uint2(x.x, x.y);
     }
 #pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) s_part[wave][4 * lane + j] = acc[j];
-    lds_barrier();
-    if (tid < 256) {
-      uint32_t c = 0;
-#pragma unroll
-      for (uint32_t w = 0; w < kCodeWaves; ++w) c += s_part[w][tid];
-      s_cnt[tid] = c;
+    for (uint32_t k = 0; k < kDepth; ++k) {
+      acc[0] += v[k].x & 0xFFFFu;
+      acc[1] += v[k].x >> 16;
+      acc[2] += v[k].y & 0xFFFFu;
+      acc[3] += v[k].y >> 16;
     }
-    lds_barrier();
   }
-  const uint32_t e = tree_body<false>(nullptr, canon + (uint64_t)f * 256, table + (uint64_t)f * 256,
-                                      meta + (uint64_t)f * kMetaWords, codes_len ? codes_len + f : nullptr,
-                                      codes_cap, status ? status + f : nullptr, nb * 64, limit != 0u, s_cnt);
-  if (tid >= 256) return;  // tree_body leaves the 256 symbol threads (4 waves)
-  __shared__ uint32_t s_len[256], s_chunk[4 * kTileBatch];
-  static_assert(4 * kTileBatch == 64, "one chunk total per lane of wave 0");
-  s_len[tid] = e & 0x1Fu;
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) s_part[wave][4 * lane + j] = acc[j];
   lds_barrier();
-  if (e & 0x80u) return;  // rejected frame (uniform): the pack kernel writes nothing
-  // Tile offsets: wave w reduces tiles c + w * kTileBatch + [0, kTileBatch) of each chunk
-  // of 4 * kTileBatch = 64 tiles (lane l: symbols 4l..4l+3 of a tile, one 8-byte load),
-  // the next chunk's loads in flight while one is reduced; wave 0 scans the chunk's
-  // totals (one per lane) with a running carry. Loads and stores are unconditional
-  // buffer operations (out of range past the frame), so vmcnt counts them exactly.
-  const uint32_t lane = tid & 63u, wave = tid >> 6;
-  const __amdgpu_buffer_rsrc_t rth = enc_rsrc(tile_hist + (uint64_t)f * ncode * 256, (uint64_t)ncode * 512u);
-  uint32_t *to = tile_off + (uint64_t)f * (ncode + 1);
+  if (tid < 256) {
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kCodeWaves; ++w) c += s_part[w][tid];
+    s_cnt[tid] = c;
+  }
+  lds_barrier();
+}
+
+// The frame's tile bit offsets to[0 .. ncode] (to[ncode]: the frame's bits) from its tile
+// counts th and the code lengths s_len[256] (LDS), by the 256 symbol threads (4 waves):
+// wave w reduces tiles c + w * kTileBatch + [0, kTileBatch) of each chunk of
+// 4 * kTileBatch = 64 tiles (lane l: symbols 4l..4l+3 of a tile, one 8-byte load), the
+// next chunk's loads in flight while one is reduced; wave 0 scans the chunk's totals (one
+// per lane) with a running carry. Loads and stores are unconditional buffer operations
+// (out of range past the frame), so vmcnt counts them exactly.
+__device__ __forceinline__ void frame_tile_offsets(const uint16_t *th, uint32_t ncode, uint32_t *to,
+                                                   const uint32_t *s_len) {
+  __shared__ uint32_t s_chunk[4 * kTileBatch];
+  static_assert(4 * kTileBatch == 64, "one chunk total per lane of wave 0");
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const __amdgpu_buffer_rsrc_t rth = enc_rsrc(th, (uint64_t)ncode * 512u);
   const __amdgpu_buffer_rsrc_t rto = enc_rsrc(to, (uint64_t)(ncode + 1) * 4u);
   const uint32_t l0 = s_len[4 * lane], l1 = s_len[4 * lane + 1], l2 = s_len[4 * lane + 2], l3 = s_len[4 * lane + 3];
   typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
@@ -1435,6 +1430,201 @@ __global__ void __launch_bounds__(kTreeThreads) enc_tree_batch_kernel(
     for (uint32_t k = 0; k < kTileBatch; ++k) v[k] = nv[k];
   }
   if (tid == 0) to[ncode] = carry;
+}
+
+__global__ void __launch_bounds__(kTreeThreads) enc_tree_batch_kernel(
+    uint64_t *hist, uint8_t *canon, uint32_t *table, uint64_t *meta, uint64_t *codes_len, uint64_t codes_cap,
+    int32_t *status, uint64_t nb, const uint16_t *tile_hist, uint32_t ncode, uint32_t *tile_off,
+    uint64_t *frame_off, uint32_t f0, uint32_t n_frames, uint32_t limit) {
+  // f0: this launch's first frame of the call (its pointers start there; frame_off is
+  // the call's, indexed by call frame)
+  const uint32_t f = blockIdx.x, tid = threadIdx.x;
+  if (frame_off && tid == 0) {  // optional: the decoder's frame_code_offsets for fixed slots
+    frame_off[f0 + f] = (uint64_t)(f0 + f) * codes_cap;
+    if (f0 + f + 1 == n_frames) frame_off[n_frames] = (uint64_t)n_frames * codes_cap;
+  }
+  __shared__ uint32_t s_cnt[256];
+  frame_symbol_counts(tile_hist + (uint64_t)f * ncode * 256, ncode, s_cnt);
+  const uint32_t e = tree_body<false>(nullptr, canon + (uint64_t)f * 256, table + (uint64_t)f * 256,
+                                      meta + (uint64_t)f * kMetaWords, codes_len ? codes_len + f : nullptr,
+                                      codes_cap, status ? status + f : nullptr, nb * 64, limit != 0u, s_cnt);
+  if (tid >= 256) return;  // tree_body leaves the 256 symbol threads (4 waves)
+  __shared__ uint32_t s_len[256];
+  s_len[tid] = e & 0x1Fu;
+  lds_barrier();
+  if (e & 0x80u) return;  // rejected frame (uniform): the pack kernel writes nothing
+  frame_tile_offsets(tile_hist + (uint64_t)f * ncode * 256, ncode, tile_off + (uint64_t)f * (ncode + 1), s_len);
+}
+
+// ---- batched frames under ONE table: mh_encode_frames_shared_device_async ------------
+// The split and the packer of the batched path, unchanged, with the table work between
+// them done once for the batch instead of once per frame. Built mode, five launches
+// whatever n: enc_split_kernel (tiled), enc_hist_reduce_kernel (the frames' tile counts
+// into the kHistParts 64-bit partial histograms), enc_tree_shared_kernel (one workgroup:
+// tree_body over the batch's counts -> the header and the shared code table),
+// enc_plan_shared_kernel (one workgroup per frame: its counts, verdict, bits, table copy
+// and tile offsets under the shared lengths), enc_pack_wave_kernel. Supplied mode, four:
+// enc_header_table_kernel (the caller's lengths -> verdict and canonical codes) takes the
+// place of the reduction and the tree. Without MH_ENCODE_WORKSPACE_ZEROED, built mode
+// clears the 16 KB of partial histograms first (one memset, as mh_encode_frame_device_async).
+constexpr uint32_t kVerdict = 2;  // shared meta[] slot: the header's verdict (int32)
+constexpr uint32_t kReduceDepth = 24;                 // tile loads in flight per lane
+constexpr uint32_t kReduceTiles = 4 * kReduceDepth;   // tiles per reduction workgroup (4 waves)
+
+// Workgroup f * nchunk + c: tiles [c * kReduceTiles, + kReduceTiles) of frame f, summed
+// per symbol (wave w: tiles w, w + 4, ...; lane l: symbols 4l..4l+3, one round trip of
+// unconditional buffer loads, zero past the frame) and added to one of the kHistParts
+// partial histograms: one 64-bit atomic per used bin and workgroup. A workgroup's sum is
+// below 2^21 (kReduceTiles x kBatchTile x 64); the batch's is 64-bit.
+__global__ void __launch_bounds__(256) enc_hist_reduce_kernel(const uint16_t *tile_hist, uint32_t ncode,
+                                                              uint32_t nchunk, uint64_t *hist) {
+  __shared__ uint32_t s_part[4][256];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t f = blockIdx.x / nchunk, c = blockIdx.x - f * nchunk;
+  const __amdgpu_buffer_rsrc_t rth = enc_rsrc(tile_hist + (uint64_t)f * ncode * 256, (uint64_t)ncode * 512u);
+  typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
+  v2u32 v[kReduceDepth];
+#pragma unroll
+  for (uint32_t k = 0; k < kReduceDepth; ++k) {
+    const uint32_t t = c * kReduceTiles + wave + 4u * k;
+    v[k] = __builtin_amdgcn_raw_buffer_load_b64(rth, (int)(t < ncode ? t * 512u + lane * 8u : kOob), 0, 0);
+  }
+  uint32_t acc[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (uint32_t k = 0; k < kReduceDepth; ++k) {
+    acc[0] += v[k].x & 0xFFFFu;
+    acc[1] += v[k].x >> 16;
+    acc[2] += v[k].y & 0xFFFFu;
+    acc[3] += v[k].y >> 16;
+  }
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) s_part[wave][4 * lane + j] = acc[j];
+  lds_barrier();
+  const uint32_t n = s_part[0][tid] + s_part[1][tid] + s_part[2][tid] + s_part[3][tid];
+  if (n) atomicAdd((unsigned long long *)&hist[(blockIdx.x % kHistParts) * 256 + tid], (unsigned long long)n);
+}
+
+// The batch's tree: tree_body over the partial histograms (left zeroed), nsym the batch's
+// symbol count. Writes the header, the shared table, meta[1] (the header is usable) and
+// meta[kVerdict] (MH_OK or MH_ERR_CODE_TOO_LONG; the capacity rules are per frame).
+__global__ void __launch_bounds__(kTreeThreads) enc_tree_shared_kernel(uint64_t *hist, uint8_t *canon_out,
+                                                                       uint32_t *table, uint64_t *meta,
+                                                                       uint64_t nsym, uint32_t limit) {
+  tree_body<false>(hist, canon_out, table, meta, nullptr, 0, reinterpret_cast<int32_t *>(&meta[kVerdict]), nsym,
+                   limit != 0u, nullptr, false);
+}
+
+// A caller's header (supplied mode), one workgroup of 256 threads, thread s = symbol s:
+// MH_ERR_CODE_TOO_LONG for a length over 16, MH_ERR_TABLE for a Kraft sum over 1 (an
+// incomplete code is valid, as for the decoders' table builds); then the canonical codes
+// (huff_util.hpp:94-193, mh_canonical_codes) as tree_body computes them -- a ballot per
+// length for the counts and each symbol's rank among equal lengths, the first code of
+// each length in closed form -- in the packer's table words (code_lj16 << 16 | length).
+// canon_out (optional) gets a copy of the lengths; it may be canon_in (each thread reads
+// its byte before writing it).
+__global__ void __launch_bounds__(256) enc_header_table_kernel(const uint8_t *canon_in, uint8_t *canon_out,
+                                                               uint32_t *table, uint64_t *meta) {
+  __shared__ uint32_t s_wcnt[4][17], s_first[17], s_kraft[4], s_long[4];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t L = canon_in[tid];
+  const uint64_t below = (1ull << lane) - 1ull;
+  uint32_t in_wave = 0;
+  for (uint32_t l = 1; l <= 16; ++l) {
+    const uint64_t m = __ballot(L == l);
+    if (L == l) in_wave = (uint32_t)__popcll(m & below);
+    if (lane == 0) s_wcnt[wave][l] = (uint32_t)__popcll(m);
+  }
+  uint32_t kraft = L && L <= 16 ? 1u << (16u - L) : 0u;  // in units of 2^-16; <= 2^16 per symbol, 2^24 in all
+  for (int o = 32; o; o >>= 1) kraft += __shfl_xor(kraft, o);
+  const uint64_t too_long = __ballot(L > 16);
+  if (lane == 0) {
+    s_kraft[wave] = kraft;
+    s_long[wave] = too_long ? 1u : 0u;
+  }
+  __syncthreads();
+  if (tid < 64) {
+    // first[l] = sum over j < l of count[j] << (l - j): see tree_body
+    const uint32_t ln = (tid & 15u) + 1u;
+    const uint32_t cnt = tid < 16 ? s_wcnt[0][ln] + s_wcnt[1][ln] + s_wcnt[2][ln] + s_wcnt[3][ln] : 0u;
+    const uint32_t v = cnt << (16 - ln);
+    uint32_t incl = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 16; d <<= 1) {
+      const uint32_t y = __shfl_up(incl, d);
+      if (tid >= d) incl += y;
+    }
+    if (tid < 16) s_first[ln] = (incl - v) >> (16 - ln);
+  }
+  __syncthreads();
+  const int32_t verdict = (s_long[0] | s_long[1] | s_long[2] | s_long[3]) ? MH_ERR_CODE_TOO_LONG
+                          : s_kraft[0] + s_kraft[1] + s_kraft[2] + s_kraft[3] > 0x10000u ? MH_ERR_TABLE
+                                                                                         : MH_OK;
+  uint32_t e = 0;
+  if (verdict == MH_OK && L) {
+    uint32_t rank = in_wave;  // symbols of the same length before this one
+    for (uint32_t w = 0; w < wave; ++w) rank += s_wcnt[w][L];
+    e = ((((s_first[L] + rank) << (16 - L)) & 0xFFFFu) << 16) | L;
+  }
+  table[tid] = e;
+  if (canon_out) canon_out[tid] = (uint8_t)L;
+  if (tid == 0) {
+    meta[1] = verdict == MH_OK ? 1 : 0;
+    *reinterpret_cast<int32_t *>(&meta[kVerdict]) = verdict;
+  }
+}
+
+// Workgroup f: frame f's plan under the shared table -- what enc_tree_batch_kernel does
+// after its tree. The frame's symbol counts from its tile counts; its verdict (the
+// header's when that is not MH_OK, MH_ERR_TABLE for a symbol the header has no code for,
+// MH_ERR_CAPACITY for >= 2^32 code bits or round_up(codes_len, 4) > codes_cap); its bits,
+// codes_len and meta; the shared table copied into the frame's slot (the packer reads
+// table[f * 256 + sym]); the tile bit offsets; the decoder's frame offsets. Frame 0 also
+// hands out the header's verdict.
+__global__ void __launch_bounds__(kTreeThreads) enc_plan_shared_kernel(
+    const uint32_t *shared_table, const uint64_t *shared_meta, uint32_t *table, uint64_t *meta, uint64_t *codes_len,
+    uint64_t codes_cap, int32_t *status, int32_t *header_status, uint64_t nb, const uint16_t *tile_hist,
+    uint32_t ncode, uint32_t *tile_off, uint64_t *frame_off, uint32_t n_frames) {
+  const uint32_t f = blockIdx.x, tid = threadIdx.x;
+  __shared__ uint32_t s_cnt[256], s_len[256], s_miss;
+  __shared__ unsigned long long s_total;
+  const int32_t verdict = *reinterpret_cast<const int32_t *>(&shared_meta[kVerdict]);
+  if (tid == 0) {
+    s_miss = 0;
+    s_total = 0;
+    if (frame_off) {
+      frame_off[f] = (uint64_t)f * codes_cap;
+      if (f + 1 == n_frames) frame_off[n_frames] = (uint64_t)n_frames * codes_cap;
+    }
+    if (header_status && f == 0) *header_status = verdict;
+  }
+  frame_symbol_counts(tile_hist + (uint64_t)f * ncode * 256, ncode, s_cnt);
+  if (tid >= 256) return;  // one thread per symbol from here (4 waves; a finished wave leaves the barriers)
+  const uint32_t e = shared_table[tid], L = e & 0x1Fu, cnt = s_cnt[tid];
+  table[(uint64_t)f * 256 + tid] = e;
+  s_len[tid] = L;
+  if (cnt && !L) s_miss = 1;  // a symbol of this frame without a code
+  uint64_t bits = (uint64_t)cnt * L;
+  for (int o = 32; o; o >>= 1) bits += __shfl_xor(bits, o);
+  if ((tid & 63u) == 0) atomicAdd(&s_total, (unsigned long long)bits);
+  lds_barrier();
+  const uint64_t total = s_total;
+  const uint64_t len = (total + 7) / 8 + MH_CODES_PAD;
+  int32_t st = verdict;
+  if (st == MH_OK) {
+    // a frame of 2^32 symbols (65,535 x 65,535 padded) has >= 2^32 bits, and its u32 counts may have wrapped
+    if (s_miss) st = MH_ERR_TABLE;
+    else if (nb >= (1ull << 26) || total >= (1ull << 32) || ((len + 3) & ~3ull) > codes_cap) st = MH_ERR_CAPACITY;
+  }
+  if (tid == 0) {
+    uint64_t *m = meta + (uint64_t)f * kMetaWords;
+    m[0] = st == MH_OK ? len : 0;
+    m[1] = st == MH_OK ? 1 : 0;
+    m[kTotalBits] = total;
+    if (codes_len) codes_len[f] = st == MH_OK ? len : 0;
+    if (status) status[f] = st;
+  }
+  if (st != MH_OK) return;  // rejected frame (uniform): the pack kernel writes nothing
+  frame_tile_offsets(tile_hist + (uint64_t)f * ncode * 256, ncode, tile_off + (uint64_t)f * (ncode + 1), s_len);
 }
 
 // Wave packing: each wave packs one tile alone, sixteen blocks per step (64 lanes: lane
@@ -1709,6 +1899,24 @@ uint64_t carve_batch(uint8_t *base, uint64_t nb, uint32_t n, BatchWorkspace *w) 
   return o;
 }
 
+struct SharedWorkspace {  // the batched path's parts, then the one table's
+  BatchWorkspace b;
+  uint64_t *hist;    // kHistParts x 256 partial counts of the whole batch: zero between calls
+  uint32_t *table;   // the shared code table, 256 words
+  uint64_t *meta;    // kMetaWords: [1] the header is usable, [kVerdict] its verdict
+};
+
+uint64_t carve_shared(uint8_t *base, uint64_t nb, uint32_t n, SharedWorkspace *w) {
+  uint64_t o = carve_batch(base, nb, n, w ? &w->b : nullptr);
+  if (w) w->hist = reinterpret_cast<uint64_t *>(base + o);
+  o += align256(kHistParts * 256 * 8);
+  if (w) w->table = reinterpret_cast<uint32_t *>(base + o);
+  o += align256(256 * 4);
+  if (w) w->meta = reinterpret_cast<uint64_t *>(base + o);
+  o += align256(kMetaWords * 8);
+  return o;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1907,6 +2115,71 @@ int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_str
   // (trees beside another sub-batch's split / packing) measured slower, and the packer's
   // pixel re-reads did not drop (profiles/r04_v4_encoder_batch_ab.txt).
   sub_batch(s, 0, n_frames);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+size_t mh_encode_frames_shared_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_frames) {
+  const uint64_t nb = (uint64_t)((width + 7) / 8) * ((height + 7) / 8);
+  return (size_t)carve_shared(nullptr, nb, n_frames, nullptr);
+}
+
+int mh_encode_frames_shared_device_async(const uint8_t *d_gray, uint64_t gray_frame_stride, uint32_t n_frames,
+                                         uint32_t width, uint32_t height, uint32_t flags,
+                                         const uint8_t *d_canon_in, uint8_t *d_canon_header, uint8_t *d_codes,
+                                         uint64_t codes_frame_stride, uint64_t *d_codes_len,
+                                         uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets,
+                                         uint8_t *d_block_init, int32_t *d_status, int32_t *d_header_status,
+                                         void *d_workspace, size_t workspace_bytes, void *stream) {
+  // the checks of mh_encode_frames_device_async, in its order; every one before any HIP call
+  if (!d_gray || (!d_canon_in && !d_canon_header) || !d_codes || !d_block_offsets || !d_workspace || !n_frames)
+    return MH_ERR_INVALID_ARG;
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
+  if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
+  if (((uintptr_t)d_codes & 15u) || (codes_frame_stride & 15u) || ((uintptr_t)d_workspace & 255u))
+    return MH_ERR_ALIGN;
+  if (gray_frame_stride < (uint64_t)width * height && n_frames > 1) return MH_ERR_CAPACITY;
+  const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
+  const uint64_t nb = (uint64_t)bw * bh;
+  const uint64_t ncode = (nb + kBatchTile - 1) / kBatchTile;
+  if (ncode * n_frames > 0x7FFFFFFFull || n_frames > 0x7FFFFFFFu) return MH_ERR_CAPACITY;
+  // built mode: the tree's node weights are u32 (tree_body), so the batch holds fewer than
+  // 2^32 symbols (1,365 frames of 2048 x 1536); its bit total has no such limit
+  const uint64_t nsym = (uint64_t)n_frames * nb * 64;  // < 2^31 x 2^26 x 2^6
+  if (!d_canon_in && nsym >= (1ull << 32)) return MH_ERR_CAPACITY;
+  if (workspace_bytes < mh_encode_frames_shared_workspace_bytes(width, height, n_frames)) return MH_ERR_CAPACITY;
+  SharedWorkspace w;
+  carve_shared(static_cast<uint8_t *>(d_workspace), nb, n_frames, &w);
+  hipStream_t s = (hipStream_t)stream;
+  // only the partial histograms carry state from call to call (the tree leaves them zeroed)
+  if (!d_canon_in && !(flags & MH_ENCODE_WORKSPACE_ZEROED) &&
+      hipMemsetAsync(w.hist, 0, kHistParts * 256 * 8, s) != hipSuccess)
+    return MH_ERR_HIP;
+  const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;
+  flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
+  const uint32_t vec = (width % 8 == 0 && ((uintptr_t)d_gray & 7u) == 0 && (gray_frame_stride & 7u) == 0) ? 1u : 0u;
+  const Pixels px{d_gray, width, height, bw, vec, !(flags & MH_FLAG_NO_DELTA), d_block_init != nullptr};
+  // the split and the packer: mh_encode_frames_device_async's launches
+  hipLaunchKernelGGL((vec ? enc_split_kernel<true, true, kBatchTile> : enc_split_kernel<false, true, kBatchTile>),
+                     dim3((uint32_t)(ncode * n_frames)), dim3(256), 0, s, d_gray, width, height, bw, nb, flags, nullptr,
+                     d_block_init, nullptr, w.b.tile_hist, nullptr, (uint32_t)ncode, gray_frame_stride, w.b.tile_tail);
+  if (d_canon_in) {
+    hipLaunchKernelGGL(enc_header_table_kernel, dim3(1), dim3(256), 0, s, d_canon_in, d_canon_header, w.table, w.meta);
+  } else {
+    const uint32_t nchunk = (uint32_t)((ncode + kReduceTiles - 1) / kReduceTiles);
+    hipLaunchKernelGGL(enc_hist_reduce_kernel, dim3(nchunk * n_frames), dim3(256), 0, s, w.b.tile_hist, (uint32_t)ncode,
+                       nchunk, w.hist);
+    hipLaunchKernelGGL(enc_tree_shared_kernel, dim3(1), dim3(kTreeThreads), 0, s, w.hist, d_canon_header, w.table,
+                       w.meta, nsym, limit);
+  }
+  hipLaunchKernelGGL(enc_plan_shared_kernel, dim3(n_frames), dim3(kTreeThreads), 0, s, w.table, w.meta, w.b.table,
+                     w.b.meta, d_codes_len, codes_frame_stride, d_status, d_header_status, nb, w.b.tile_hist,
+                     (uint32_t)ncode, w.b.tile_off, d_frame_code_offsets, n_frames);
+  const uint32_t ncode_wg = (uint32_t)((ncode + kPackWaves - 1) / kPackWaves);
+  hipLaunchKernelGGL((!vec ? enc_pack_wave_kernel<false, false>
+                           : bw % 2 ? enc_pack_wave_kernel<true, false> : enc_pack_wave_kernel<true, true>),
+                     dim3(ncode_wg * n_frames), dim3(kPackWaves * 64), 0, s, px, gray_frame_stride, nb, (uint32_t)ncode,
+                     w.b.table, w.b.meta, w.b.tile_off, d_block_offsets, d_codes, codes_frame_stride, ncode_wg,
+                     w.b.tile_tail);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 

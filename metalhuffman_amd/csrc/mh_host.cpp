@@ -313,6 +313,84 @@ int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32
   return MH_OK;
 }
 
+// The symbols mh_encode_frame encodes for one frame: zero-padded 8x8 blocks, per-block
+// deltas unless MH_FLAG_NO_DELTA, the first delta moved into init[b] and zeroed when the
+// format has init bytes (init: nb bytes or NULL; all zero under MH_FLAG_NO_DELTA).
+static int frame_symbols(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                         std::vector<uint8_t> &blocks, uint8_t *init) {
+  const uint64_t nb = (uint64_t)((width + 7) / 8) * ((height + 7) / 8);
+  blocks.resize(nb * 64);
+  const int rc = mh_split_blocks(gray, width, height, 8, 0, blocks.data(), blocks.size());
+  if (rc != MH_OK) return rc;
+  if (!(flags & MH_FLAG_NO_DELTA)) {
+    for (uint64_t b = 0; b < nb; ++b) {
+      uint8_t *blk = blocks.data() + b * 64;
+      mh_encode_signed_byte_deltas(blk, blk, 64);
+      if (init) {
+        init[b] = blk[0];
+        blk[0] = 0;
+      }
+    }
+  } else if (init) {
+    std::memset(init, 0, nb);
+  }
+  return MH_OK;
+}
+
+int mh_frame_histogram(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                       int with_block_init, uint64_t freq[256]) {
+  if (!gray || !freq) return MH_ERR_INVALID_ARG;
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
+  if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
+  std::vector<uint8_t> blocks, init;
+  if (with_block_init) init.resize((size_t)((width + 7) / 8) * ((height + 7) / 8));
+  const int rc = frame_symbols(gray, width, height, flags, blocks, with_block_init ? init.data() : nullptr);
+  if (rc != MH_OK) return rc;
+  for (const uint8_t s : blocks) freq[s]++;
+  return MH_OK;
+}
+
+int mh_encode_frame_with_header(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                                const uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
+                                uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init) {
+  if (!gray || !canon_header || !codes || !codes_len || !block_offsets) return MH_ERR_INVALID_ARG;
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
+  if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
+  // the header's verdict: a length over 16, then a Kraft sum over 1 (in units of 2^-16)
+  uint64_t kraft = 0;
+  for (int s = 0; s < 256; ++s) {
+    if (canon_header[s] > 16) return MH_ERR_CODE_TOO_LONG;
+    if (canon_header[s]) kraft += 1ull << (16 - canon_header[s]);
+  }
+  if (kraft > (1ull << 16)) return MH_ERR_TABLE;
+  const uint64_t nb = (uint64_t)((width + 7) / 8) * ((height + 7) / 8);
+  std::vector<uint8_t> blocks, init(block_init ? nb : 0);
+  const int rc = frame_symbols(gray, width, height, flags, blocks, block_init ? init.data() : nullptr);
+  if (rc != MH_OK) return rc;
+  uint64_t freq[256] = {0};
+  for (const uint8_t s : blocks) freq[s]++;
+  uint64_t total_bits = 0;
+  for (int s = 0; s < 256; ++s) {
+    if (freq[s] && !canon_header[s]) return MH_ERR_TABLE;  // a symbol the header has no code for
+    total_bits += freq[s] * canon_header[s];
+  }
+  if (total_bits >= (1ull << 32)) return MH_ERR_CAPACITY;  // u32 block offsets
+  const uint64_t len = (total_bits + 7) / 8 + MH_CODES_PAD;
+  if (len > codes_cap) return MH_ERR_CAPACITY;
+  uint16_t cc[256];
+  canonical_codes(canon_header, cc);
+  BitWriter bw(codes);
+  for (uint64_t i = 0; i < blocks.size(); ++i) {
+    if (i % 64 == 0) block_offsets[i / 64] = (uint32_t)bw.nbits;
+    bw.put(cc[blocks[i]], canon_header[blocks[i]]);
+  }
+  bw.flush();
+  for (int k = 0; k < MH_CODES_PAD; ++k) codes[bw.nbytes++] = 0;
+  *codes_len = bw.nbytes;
+  if (block_init) std::memcpy(block_init, init.data(), nb);
+  return MH_OK;
+}
+
 int mh_container_header(uint64_t n_symbols, uint8_t header[MH_CONTAINER_HEADER_BYTES]) {
   if (!header) return MH_ERR_INVALID_ARG;
   if (n_symbols > 0xFFFFFFFFull) return MH_ERR_CAPACITY;

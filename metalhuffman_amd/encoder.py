@@ -165,7 +165,9 @@ class BatchEncoder:
         self.width, self.height, self.n = width, height, n_frames
         bw, bh = block_grid(width, height)
         self.nb = bw * bh
-        ws = int(N.lib().mh_encode_frames_workspace_bytes(width, height, n_frames))
+        # one workspace for both entry points: whichever needs more
+        ws = max(int(N.lib().mh_encode_frames_workspace_bytes(width, height, n_frames)),
+                 int(N.lib().mh_encode_frames_shared_workspace_bytes(width, height, n_frames)))
         # zero-filled once: every call leaves the histograms zeroed (MH_ENCODE_WORKSPACE_ZEROED)
         self.workspace = torch.zeros(ws + 256, dtype=torch.uint8, device=self.device)
         self.slot = (self.nb * 64 * 2 + N.MH_CODES_PAD + 15) // 16 * 16 + 16
@@ -202,6 +204,54 @@ class BatchEncoder:
         return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status, offs,
                                  init, flags)
 
+    def encode_shared_async(self, grays: torch.Tensor, header=None, flags: int = 0, init_zero_delta: bool = False,
+                            stream: Optional[torch.cuda.Stream] = None,
+                            limit_lengths: bool = False) -> "AsyncEncodedBatch":
+        """All frames under ONE Huffman table (mh_encode_frames_shared_device_async): what
+        decoder.decode, the table-mode streams and the multi-GPU paths consume.
+        header=None builds the table from the batch's summed histogram (codec.shared_header
+        of the frames; limit_lengths as in encode_async); otherwise `header` -- 256 code
+        lengths, a device tensor or a host array -- is validated and used as it is (a header
+        fixed for a sequence, an earlier batch's, one broadcast before encoding). The result
+        is marked `shared`: `canon` is the one header (u8[256] on the device),
+        `header_status` its verdict (int32[1] on the device), `status` the per-frame words
+        (-5 for a frame that holds a symbol the header has no code for)."""
+        if (grays.dtype != torch.uint8 or tuple(grays.shape) != (self.n, self.height, self.width)
+                or not grays.is_contiguous()):
+            raise ValueError(f"grays must be contiguous uint8 [{self.n}, {self.height}, {self.width}]")
+        if grays.device != self.device:
+            raise ValueError("grays must live on the encoder's device")
+        n = self.n
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=self.device)
+            offs = torch.empty(n * self.nb, dtype=torch.int32, device=self.device)
+            init = torch.empty(n * self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
+            canon = torch.empty(256, dtype=torch.uint8, device=self.device)
+            lens = torch.empty(n, dtype=torch.int64, device=self.device)
+            fco = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            status = torch.empty(n + 1, dtype=torch.int32, device=self.device)  # [n]: the header's verdict
+            canon_in = None
+            if header is not None:
+                if isinstance(header, torch.Tensor):
+                    canon_in = header.to(self.device, torch.uint8).contiguous()
+                else:
+                    canon_in = torch.from_numpy(np.ascontiguousarray(header, np.uint8)).to(self.device)
+                if canon_in.numel() != 256:
+                    raise ValueError("header must hold 256 code lengths")
+        cbase = (codes.data_ptr() + 15) // 16 * 16
+        base = self.workspace.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        N.check(N.lib().mh_encode_frames_shared_device_async(
+            grays.data_ptr(), self.height * self.width, n, self.width, self.height,
+            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
+            canon_in.data_ptr() if canon_in is not None else None, canon.data_ptr(), cbase, self.slot,
+            lens.data_ptr(), fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None,
+            status.data_ptr(), status.data_ptr() + 4 * n, aligned, self.workspace.numel() - (aligned - base),
+            _stream_ptr(stream, self.device)), "mh_encode_frames_shared_device_async")
+        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
+        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status[:n], offs,
+                                 init, flags, True, status[n:])
+
 
 @dataclasses.dataclass
 class AsyncEncodedBatch:
@@ -223,6 +273,8 @@ class AsyncEncodedBatch:
     block_offsets: torch.Tensor       # int32 view of u32[n * NB]
     block_init: Optional[torch.Tensor]
     flags: int
+    shared: bool = False              # encode_shared_async: ONE table; canon is then u8[256]
+    header_status: Optional[torch.Tensor] = None  # shared: int32[1] on the device, the header's verdict
 
     def frames(self, check: bool = True) -> DeviceFrames:
         """All slots as one DeviceFrames batch: for decoder.decode_frames with table_set()
@@ -239,18 +291,30 @@ class AsyncEncodedBatch:
             st = self.status.cpu()
             bad = [i for i in range(self.n_frames) if int(st[i])]
             if bad:
-                raise N.MHError(int(st[bad[0]]), f"mh_encode_frames_device_async: frame(s) {bad[:8]} rejected")
+                what = "mh_encode_frames_shared_device_async" if self.shared else "mh_encode_frames_device_async"
+                raise N.MHError(int(st[bad[0]]), f"{what}: frame(s) {bad[:8]} rejected")
             payload = int(self.codes_len.sum().item()) - self.n_frames * N.MH_CODES_PAD
         else:
             payload = int(self.codes.numel()) - self.n_frames * N.MH_CODES_PAD
         return DeviceFrames(self.width, self.height, self.n_frames, self.block_offsets, self.codes,
                             self.frame_code_offsets, self.block_init, self.flags, payload)
 
+    def tables(self, prepare_lut: bool = True, stream: Optional[torch.cuda.Stream] = None):
+        """A shared batch's one table: T1/T2 (+ the prepared table) built on the device from
+        the device header (DeviceTables.from_canonical_header); asynchronous."""
+        if not self.shared:
+            raise ValueError("a batch with a table per frame has no single table: use table_set()")
+        from .decoder import DeviceTables
+        return DeviceTables.from_canonical_header(self.canon, self.canon.device, prepare_lut, stream)
+
     def table_set(self, stream: Optional[torch.cuda.Stream] = None):
         """One prepared table per frame, built on the device from the device headers in one
         launch (mh_build_luts_device); asynchronous. Its status is the encoder's word where
         the encoder rejected the frame (the header of such a frame is unspecified), else the
-        table build's -- combined on the device, so decode() skips exactly those frames."""
+        table build's -- combined on the device, so decode() skips exactly those frames.
+        A shared batch has one table: ValueError, use tables()."""
+        if self.shared:
+            raise ValueError("a shared batch has one table: use tables(), not table_set()")
         from .decoder import DeviceTableSet
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             ts = DeviceTableSet.from_canonical_headers(self.canon, self.canon.device, stream)
@@ -261,7 +325,19 @@ class AsyncEncodedBatch:
         """encode batch -> n tables -> decode batch on one stream, no host synchronisation:
         returns the raster [n, H, pitch] (decode()'s `out` contract). A rejected frame is skipped
         on the device (its raster keeps what `out` held); the tables stay in `self.tables`, whose
-        check_status() synchronises and names such frames."""
+        check_status() synchronises and names such frames.
+
+        A shared batch (encode_shared_async) decodes through decoder.decode (mh_decode) with
+        its one table, built on the device on the same stream. mh_decode cannot skip single
+        frames, so this path does NOT stay asynchronous: it calls frames(check=True), which
+        synchronises once and raises MHError if any frame (or the header) was rejected; the
+        table build and the decode follow. A pipeline that must not synchronise checks
+        `status` itself and calls decoder.decode(frames(check=False), tables(stream=...))."""
+        if self.shared:
+            from .decoder import decode
+            fr = self.frames(check=True)
+            self.shared_tables = self.tables(stream=stream)
+            return decode(fr, self.shared_tables, out=out, stream=stream)
         from .decoder import decode_frames
         self.tables = self.table_set(stream)
         return decode_frames(self.frames(check=False), self.tables, out=out, stream=stream)
@@ -272,7 +348,8 @@ class AsyncEncodedBatch:
         N.check(st, "mh_encode_frames_device_async")
         nb = self.block_offsets.numel() // self.n_frames
         init = self.block_init[f * nb:(f + 1) * nb] if self.block_init is not None else None
-        return DeviceEncodedFrame(self.width, self.height, self.canon[f].cpu().numpy(),
+        canon = self.canon if self.shared else self.canon[f]
+        return DeviceEncodedFrame(self.width, self.height, canon.cpu().numpy(),
                                   self.codes[f * self.slot: f * self.slot + n],
                                   self.block_offsets[f * nb:(f + 1) * nb], init, self.flags)
 
