@@ -1484,8 +1484,8 @@ __device__ __forceinline__ HeaderFacts header_build(uint32_t L, uint16_t *lut, H
   return hf;
 }
 
-// ---- one frame slice per workgroup (mh_decode_frames / _region / _headers) --------
-// The batch kernel's machinery with another decomposition, shared by three entries:
+// ---- one frame slice per workgroup (mh_decode_frames / _headers / _region* / _windows*) --------
+// The batch kernel's machinery with another decomposition, shared by six entries:
 // workgroup g serves ONE frame, f = g / G, as slice j = g % G of it, so it brings frame f's
 // table into LDS once and never crosses a frame. Wave w decodes the frame's tiles j*8 + w,
 // stepping by 8*G: the persistent loops run on a workgroup-local DecodeArgs whose total_tiles
@@ -1624,8 +1624,9 @@ __device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_
     batch_loop<kDelta, Lut13, Map, Out>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
 }
 
-// The three entries: names, launch bounds and argument order are the ABI of the launchers, the
-// ISA guard and the diagnostic scripts; the leading 16 arguments are preloaded into SGPRs.
+// The six kernels (ten with the scales, each in a raw and a delta instantiation: the rows of
+// kSliceTable): names, launch bounds and argument order are the ABI of the launchers, the ISA
+// guard and the diagnostic scripts; the leading 16 arguments are preloaded into SGPRs.
 template <bool kDelta>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_multitable_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
@@ -2326,17 +2327,47 @@ __global__ void __launch_bounds__(64 * kLpWaves) mh_decode_lanepair_kernel(const
 // is shared between devices or written by concurrent callers (the reference keeps
 // its tables in module statics, Shared/HuffmanUtil.cpp:87-102).
 constexpr int kMaxDevices = 64;
-// The kernels that decode one frame slice per workgroup (slice_decode), by entry point.
-// (kSliceScaled + k - 1: the region kernel at scale 2^k, k = 1..3)
+// The kernels that decode one frame slice per workgroup (slice_decode): a SliceKernel is a row of
+// kSliceTable, its family's first row + log2_scale (the region and the windows kernels exist at
+// scale 2^0..2^3; scale 0 is the unscaled kernel).
+constexpr int kSliceScales = 4;
 enum SliceKernel {
   kSliceFrames,
   kSliceHeaders,
   kSliceRegion,
-  kSliceScaled,
-  kSliceWindows = kSliceScaled + 3,
-  kSliceWindowsScaled,  // + k - 1: the windows kernel at scale 2^k
-  kSliceKernels = kSliceWindowsScaled + 3
+  kSliceWindows = kSliceRegion + kSliceScales,
+  kSliceKernels = kSliceWindows + kSliceScales
 };
+#if !MH_LANE_PAIRS
+// One row per kernel, [kDelta]: the row device_info() queries the occupancy of is the row
+// launch_slices() launches. Kernels with one argument list share a pointer type; a row keeps its
+// pair under one common function-pointer type, and launch_slices<Fn> casts back to the family's.
+using FramesFn = decltype(&mh_decode_multitable_kernel<false>);
+using HeadersFn = decltype(&mh_decode_headers_kernel<false>);
+using RegionFn = decltype(&mh_decode_region_kernel<false>);    // = mh_decode_region_scaled_kernel<_, 1..3>
+using WindowsFn = decltype(&mh_decode_windows_kernel<false>);  // = mh_decode_windows_scaled_kernel<_, 1..3>
+using AnyKernel = void (*)();
+struct SliceRow {
+  AnyKernel fn[2];
+};
+template <class Fn>
+SliceRow slice_row(Fn raw, Fn delta) {
+  return {{reinterpret_cast<AnyKernel>(raw), reinterpret_cast<AnyKernel>(delta)}};
+}
+const SliceRow kSliceTable[] = {
+    slice_row<FramesFn>(mh_decode_multitable_kernel<false>, mh_decode_multitable_kernel<true>),
+    slice_row<HeadersFn>(mh_decode_headers_kernel<false>, mh_decode_headers_kernel<true>),
+    slice_row<RegionFn>(mh_decode_region_kernel<false>, mh_decode_region_kernel<true>),
+    slice_row<RegionFn>(mh_decode_region_scaled_kernel<false, 1>, mh_decode_region_scaled_kernel<true, 1>),
+    slice_row<RegionFn>(mh_decode_region_scaled_kernel<false, 2>, mh_decode_region_scaled_kernel<true, 2>),
+    slice_row<RegionFn>(mh_decode_region_scaled_kernel<false, 3>, mh_decode_region_scaled_kernel<true, 3>),
+    slice_row<WindowsFn>(mh_decode_windows_kernel<false>, mh_decode_windows_kernel<true>),
+    slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 1>, mh_decode_windows_scaled_kernel<true, 1>),
+    slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 2>, mh_decode_windows_scaled_kernel<true, 2>),
+    slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 3>, mh_decode_windows_scaled_kernel<true, 3>),
+};
+static_assert(sizeof(kSliceTable) / sizeof(kSliceTable[0]) == kSliceKernels, "one row per SliceKernel");
+#endif
 struct DeviceInfo {
   std::mutex m;
   std::atomic<int> cus{0};  // nonzero once the entry is complete
@@ -2385,26 +2416,9 @@ const DeviceInfo *device_info(hipStream_t s) {
     d.occ[1][nw] = occupancy_query<true>(nw);
   }
 #if !MH_LANE_PAIRS
-  d.occ_slice[kSliceFrames][0] = occupancy_of(mh_decode_multitable_kernel<false>, kMaxWavesPerWG);
-  d.occ_slice[kSliceFrames][1] = occupancy_of(mh_decode_multitable_kernel<true>, kMaxWavesPerWG);
-  d.occ_slice[kSliceHeaders][0] = occupancy_of(mh_decode_headers_kernel<false>, kMaxWavesPerWG);
-  d.occ_slice[kSliceHeaders][1] = occupancy_of(mh_decode_headers_kernel<true>, kMaxWavesPerWG);
-  d.occ_slice[kSliceRegion][0] = occupancy_of(mh_decode_region_kernel<false>, kMaxWavesPerWG);
-  d.occ_slice[kSliceRegion][1] = occupancy_of(mh_decode_region_kernel<true>, kMaxWavesPerWG);
-  d.occ_slice[kSliceScaled + 0][0] = occupancy_of(mh_decode_region_scaled_kernel<false, 1>, kMaxWavesPerWG);
-  d.occ_slice[kSliceScaled + 0][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 1>, kMaxWavesPerWG);
-  d.occ_slice[kSliceScaled + 1][0] = occupancy_of(mh_decode_region_scaled_kernel<false, 2>, kMaxWavesPerWG);
-  d.occ_slice[kSliceScaled + 1][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 2>, kMaxWavesPerWG);
-  d.occ_slice[kSliceScaled + 2][0] = occupancy_of(mh_decode_region_scaled_kernel<false, 3>, kMaxWavesPerWG);
-  d.occ_slice[kSliceScaled + 2][1] = occupancy_of(mh_decode_region_scaled_kernel<true, 3>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindows][0] = occupancy_of(mh_decode_windows_kernel<false>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindows][1] = occupancy_of(mh_decode_windows_kernel<true>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindowsScaled + 0][0] = occupancy_of(mh_decode_windows_scaled_kernel<false, 1>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindowsScaled + 0][1] = occupancy_of(mh_decode_windows_scaled_kernel<true, 1>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindowsScaled + 1][0] = occupancy_of(mh_decode_windows_scaled_kernel<false, 2>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindowsScaled + 1][1] = occupancy_of(mh_decode_windows_scaled_kernel<true, 2>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindowsScaled + 2][0] = occupancy_of(mh_decode_windows_scaled_kernel<false, 3>, kMaxWavesPerWG);
-  d.occ_slice[kSliceWindowsScaled + 2][1] = occupancy_of(mh_decode_windows_scaled_kernel<true, 3>, kMaxWavesPerWG);
+  for (int k = 0; k < kSliceKernels; ++k)
+    for (int delta = 0; delta < 2; ++delta)
+      d.occ_slice[k][delta] = occupancy_of(kSliceTable[k].fn[delta], kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -2477,7 +2491,7 @@ bool dims_ok(const mh_dims &d) {
          d.block_width == (d.width + 7) / 8 && d.block_height == (d.height + 7) / 8;
 }
 
-// A region's raster and tiling: pixel size pw x ph (the frame's edge clips the last blocks),
+// A raster and its tiling. A region's: pixel size pw x ph (the frame's edge clips the last blocks),
 // S = ceil(bw / 64) tiles per block row, bh * S tiles per frame (<= 8192 * 128).
 // false: the region is empty or leaves the frame (`d` has passed dims_ok).
 struct RegionExtent {
@@ -2496,87 +2510,105 @@ bool region_extent(const mh_dims &d, const mh_region *rg, RegionExtent &e) {
   return true;
 }
 
-// Where an entry point's Huffman tables come from, and so which table rules it checks.
-struct TableRule {
+// One decode call, as every entry point describes it to the helpers below: where its Huffman tables
+// come from (and so which table rules it checks), which part of the frames it decodes at which scale
+// and, once call_geometry() has passed, the rasters and tiles that makes.
+struct DecodeCall {
   enum Kind {
     kInFrame,   // mh_decode: the frame's own table1 / table2 (+ optional d_lut)
     kPrepared,  // mh_decode_frames: prepared tables at `ptr`, `stride` bytes apart
     kHeaders,   // mh_decode_headers: canonical headers at `ptr`, no alignment or stride rule
-    kRegion,    // mh_decode_region: kPrepared over region `rg`; stride 0 is one table for all frames
-    kWindows,   // mh_decode_windows: kRegion with rg = {0, 0, bw, bh}, the windows' size, and
-                // n_windows rasters of 8 bw x 8 bh, described by the device array `windows`
+    kRegion,    // mh_decode_region[_scaled]: kPrepared over region `rg` at scale 2^log2_scale; stride 0
+                // is one table for all frames
+    kWindows,   // mh_decode_windows[_scaled]: kRegion with rg = {0, 0, bw, bh}, the windows' size, and
+                // n_windows rasters, described by the device array `windows`
   } kind;
   const void *ptr = nullptr;
   uint64_t stride = 0;
   const mh_region *rg = nullptr;
+  uint32_t log2_scale = 0;  // 0: the unscaled kernel (c = 8, s = 1 in the rules below)
   const void *windows = nullptr;
   uint32_t n_windows = 0;
+  uint32_t allowed_flags = MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER;
+  // call_geometry()'s results: one raster's pixel size and tiles (segs: a region's only), and the
+  // number of rasters, which is the number of units the grid is cut into
+  RegionExtent re = {};
+  uint32_t n_units = 0;
+  bool windowed() const { return kind == kWindows; }
+  bool regional() const { return kind == kRegion || kind == kWindows; }
 };
+
+// The rules that the decode entries and the *_shape entries share, in their one order: flags, the
+// scale (a scale above 3 is reported where a bad flag is), dims, the region. A region's pixel size
+// RW x RH -- for windows the full 8 bw x 8 bh: windows differ in RW / RH, and a size that is empty
+// or exceeds the grid is MH_ERR_DIMS -- becomes SW x SH = ceil(RW / s) x ceil(RH / s) at scale s.
+int call_geometry(const mh_frame *fr, DecodeCall &c) {
+  if (fr->flags & ~c.allowed_flags) return MH_ERR_INVALID_ARG;
+  if (c.log2_scale > 3u) return MH_ERR_INVALID_ARG;
+  const mh_dims &d = fr->dims;
+  if (!dims_ok(d)) return MH_ERR_DIMS;
+  c.n_units = c.windowed() ? c.n_windows : fr->n_frames;
+  if (!c.regional()) {
+    c.re = {d.width, d.height, 0u, (d.block_width * d.block_height + 63) / 64};
+    return MH_OK;
+  }
+  if (!region_extent(d, c.rg, c.re)) return MH_ERR_DIMS;
+  if (c.windowed()) {
+    c.re.pw = 8ull * c.rg->bw;
+    c.re.ph = 8ull * c.rg->bh;
+  }
+  const uint64_t s = 1ull << c.log2_scale;
+  c.re.pw = (c.re.pw + s - 1) >> c.log2_scale;
+  c.re.ph = (c.re.ph + s - 1) >> c.log2_scale;
+  return MH_OK;
+}
+
+// The tile cap: a launch addresses at most 2^31 - 1 tiles.
+bool tiles_fit(const DecodeCall &c) { return (uint64_t)c.re.tiles * c.n_units <= 0x7FFFFFFFull; }
 
 // The argument checks of the decode entry points, all before any HIP call. Every entry runs
 // the same rules in the same order; the frame's own table fields count only for kInFrame, and
 // the other kinds check `ptr` / `stride` in their place, rule by rule. A region is checked with
-// the dims, and its pixel size (*re) stands where W x H does in the pitch and stride rules.
-// A region at scale 2^log2_scale (mh_decode_region_scaled): a scale above 3 is reported where a bad
-// flag is, the scaled size SW x SH (written back to *re) stands where the region's does, and
-// c = 8 >> log2_scale where 8 does in the raster's alignment rules.
-// Windows (mh_decode_windows): the region's rules for rg = {0, 0, bw, bh} -- so a size that is
-// empty or exceeds the grid is MH_ERR_DIMS -- with n_windows rasters of the full 8 bw x 8 bh in the
-// place of n_frames rasters of RW x RH (windows differ in RW / RH; `out_frame_stride` is the window
-// stride), and the descriptor array checked where the tables are. At scale 2^log2_scale
-// (mh_decode_windows_scaled) the rasters are c bw x c bh and c stands where 8 does, as for a region.
+// the dims (call_geometry), and its raster's size stands where W x H does in the pitch and stride
+// rules; at scale 2^log2_scale c = 8 >> log2_scale stands where 8 does in the raster's alignment
+// rules. Windows: n_windows rasters in the place of n_frames (`out_frame_stride` is the window
+// stride), and the descriptor array checked where the tables are.
 int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                      uint32_t allowed_flags, const TableRule &tr, RegionExtent *re = nullptr,
-                      uint32_t log2_scale = 0) {
-  const bool in_frame = tr.kind == TableRule::kInFrame, windowed = tr.kind == TableRule::kWindows;
-  const bool regional = tr.kind == TableRule::kRegion || windowed;
-  const bool prepared = tr.kind == TableRule::kPrepared || regional;
+                      DecodeCall &c) {
+  const bool in_frame = c.kind == DecodeCall::kInFrame, windowed = c.windowed(), regional = c.regional();
+  const bool prepared = c.kind == DecodeCall::kPrepared || regional;
   if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
-  if (regional && !tr.rg) return MH_ERR_INVALID_ARG;
-  if (windowed && (!tr.windows || tr.n_windows == 0)) return MH_ERR_INVALID_ARG;
-  const uint32_t n_rasters = windowed ? tr.n_windows : fr->n_frames;
-  if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !tr.ptr) return MH_ERR_INVALID_ARG;
+  if (regional && !c.rg) return MH_ERR_INVALID_ARG;
+  if (windowed && (!c.windows || c.n_windows == 0)) return MH_ERR_INVALID_ARG;
+  if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !c.ptr) return MH_ERR_INVALID_ARG;
   if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
-  if (fr->flags & ~allowed_flags) return MH_ERR_INVALID_ARG;
-  if (log2_scale > 3u) return MH_ERR_INVALID_ARG;
-  const mh_dims &d = fr->dims;
-  if (!dims_ok(d)) return MH_ERR_DIMS;
-  uint64_t pw = d.width, ph = d.height;  // the raster's pixel size
-  if (regional) {
-    if (!region_extent(d, tr.rg, *re)) return MH_ERR_DIMS;
-    if (windowed) {
-      re->pw = 8ull * tr.rg->bw;
-      re->ph = 8ull * tr.rg->bh;
-    }
-    const uint64_t s = 1ull << log2_scale;
-    pw = re->pw = (re->pw + s - 1) >> log2_scale;
-    ph = re->ph = (re->ph + s - 1) >> log2_scale;
-  }
-  const uint64_t am = (8u >> log2_scale) - 1u;  // the row store's width - 1
+  const int rc = call_geometry(fr, c);
+  if (rc != MH_OK) return rc;
+  const uint32_t n_rasters = c.n_units;
+  const uint64_t am = (8u >> c.log2_scale) - 1u;  // the row store's width - 1
   if (in_frame && (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
                    fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
     return MH_ERR_TABLE;
   if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & am) || ((uintptr_t)d_out & am) ||
       (n_rasters > 1 && (out_frame_stride & am)))
     return MH_ERR_ALIGN;
-  if (windowed && ((uintptr_t)tr.windows & 15u)) return MH_ERR_ALIGN;
-  if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)tr.ptr & 15u) || (tr.stride & 15u))))
+  if (windowed && ((uintptr_t)c.windows & 15u)) return MH_ERR_ALIGN;
+  if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)c.ptr & 15u) || (c.stride & 15u))))
     return MH_ERR_ALIGN;
-  if (out_pitch < pw || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * ph))
+  if (out_pitch < c.re.pw || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * c.re.ph))
     return MH_ERR_CAPACITY;
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
     return MH_ERR_CAPACITY;
-  if (prepared && tr.stride < (uint64_t)kPreparedBytes && !(regional && tr.stride == 0))
+  if (prepared && c.stride < (uint64_t)kPreparedBytes && !(regional && c.stride == 0))
     return MH_ERR_CAPACITY;  // mh_lut_bytes()
   return MH_OK;
 }
 
-// DecodeArgs from a checked frame (tables excepted); MH_ERR_CAPACITY past 2^31 - 1 tiles.
-// With `re` the raster and the tiles are the region's, not the frame's; with n_windows there are
-// that many rasters, not n_frames.
+// DecodeArgs from a checked call (tables excepted): the raster and the tiles are c.re's, and there
+// are c.n_units rasters. MH_ERR_CAPACITY past the tile cap.
 int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
-                     DecodeArgs &a, const RegionExtent *re = nullptr, uint32_t n_windows = 0) {
+                     DecodeArgs &a, const DecodeCall &c) {
   const mh_dims &d = fr->dims;
   a.offsets = fr->d_block_offsets;
   a.codes = fr->d_codes;
@@ -2586,16 +2618,15 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
   a.out = d_out;
   a.out_pitch = out_pitch;
   a.out_frame_stride = out_frame_stride;
-  a.out_frame_bytes = (re ? re->ph : (uint64_t)d.height) * out_pitch;
+  a.out_frame_bytes = c.re.ph * out_pitch;
   a.w = d.width;
   a.h = d.height;
   a.bw = d.block_width;
   a.bh = d.block_height;
   a.nb = d.block_width * d.block_height;
-  a.tiles_per_frame = re ? re->tiles : (a.nb + 63) / 64;
-  const uint64_t total = (uint64_t)a.tiles_per_frame * (n_windows ? n_windows : fr->n_frames);
-  if (total > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  a.total_tiles = (uint32_t)total;
+  a.tiles_per_frame = c.re.tiles;
+  if (!tiles_fit(c)) return MH_ERR_CAPACITY;
+  a.total_tiles = a.tiles_per_frame * c.n_units;
   return MH_OK;
 }
 
@@ -2604,7 +2635,7 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
 //   G = clamp(ceil(R / n_frames), 1, ceil(tiles_per_frame / 8)),
 // R = the workgroups resident on the device at once (CUs x the kernel's occupancy): about
 // one resident round when the frames are few, one workgroup per frame when they are many.
-// One rule for the three kernels, each with its own occupancy and (a region) its own tiles.
+// One rule for every row of kSliceTable, each with its own occupancy and (a region, windows) its own tiles.
 int slice_shape(SliceKernel k, uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s,
                 uint32_t *groups) {
   const DeviceInfo *di = device_info(s);
@@ -2617,49 +2648,59 @@ int slice_shape(SliceKernel k, uint32_t n_frames, uint32_t tiles_per_frame, bool
   return MH_OK;
 }
 
-// One launch of a frame-slice kernel. The kernels' argument lists differ only in the table
-// arguments on either side of `status` (prepared tables: luts, stride; headers: headers, verdict;
-// windows: luts, the descriptor array) and in the region's or the windows' scalars (`tail`), which
-// follow the group count. `n_frames` is the number of units the grid is cut into: the windows, for
-// mh_decode_windows.
-template <class Kernel, class Table, class TableAux, class... Tail>
-int launch_slices(Kernel kernel, SliceKernel k, bool delta, const DecodeArgs &a, uint32_t n_frames, hipStream_t s,
-                  bool any_order, Table table, const int32_t *status, TableAux aux, Tail... tail) {
-  uint32_t G = 0;
-  const int rc = slice_shape(k, n_frames, a.tiles_per_frame, delta, s, &G);
+// What every frame-slice entry does ahead of its launch: the checks, then DecodeArgs (t1 / t2 / lut
+// stay null: every workgroup takes its frame's table from the table array or builds it from the
+// frame's header) and the two decode flags. The raster and the tiling are left in c.re.
+struct SliceArgs {
+  DecodeArgs a;
+  bool delta, any_order;
+};
+int slice_prologue(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_stride, DecodeCall &c,
+                   SliceArgs &p) {
+  int rc = check_decode_args(fr, d_out, out_pitch, out_stride, c);
   if (rc != MH_OK) return rc;
-  const uint64_t grid = (uint64_t)G * n_frames;
+  p.a = DecodeArgs{};
+  rc = fill_decode_args(fr, d_out, out_pitch, out_stride, p.a, c);
+  p.delta = !(fr->flags & MH_FLAG_NO_DELTA);
+  p.any_order = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  return rc;
+}
+
+// One launch of a frame-slice kernel: row `family` + c.log2_scale of kSliceTable, whose kernels are
+// of type Fn. The kernels' argument lists differ only in the table arguments on either side of
+// `status` (prepared tables: luts, stride; headers: headers, verdict; windows: luts, the descriptor
+// array) and in the region's or the windows' scalars (`tail`), which follow the group count. The
+// grid is cut into c.n_units units: the frames, or the windows.
+template <class Fn, class Table, class TableAux, class... Tail>
+int launch_slices(SliceKernel family, const DecodeCall &c, const SliceArgs &p, void *stream, Table table,
+                  const int32_t *status, TableAux aux, Tail... tail) {
+  const SliceKernel k = (SliceKernel)(family + c.log2_scale);
+  const DecodeArgs &a = p.a;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t G = 0;
+  const int rc = slice_shape(k, c.n_units, a.tiles_per_frame, p.delta, s, &G);
+  if (rc != MH_OK) return rc;
+  const uint64_t grid = (uint64_t)G * c.n_units;
   if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  MH_LAUNCH(kernel, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, any_order, a.offsets, a.frame_off,
+  const Fn kernel = reinterpret_cast<Fn>(kSliceTable[k].fn[p.delta ? 1 : 0]);
+  MH_LAUNCH(kernel, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, p.any_order, a.offsets, a.frame_off,
             a.block_init, table, status, aux, a.nb, a.tiles_per_frame, G, tail..., a);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 
-// mh_decode_{frames,headers,region,region_scaled}_shape: slice_shape for a frame description (`rg`:
-// kSliceRegion only; with a log2_scale of 1..3 the region kernel of that scale stands for it).
-// kSliceWindows: rg = {0, 0, bw, bh} and n_windows units in the place of n_frames; with a
-// log2_scale of 1..3 the windows kernel of that scale stands for it.
-int slice_shape_entry(SliceKernel k, const mh_frame *fr, const mh_region *rg, void *stream,
-                      uint32_t *groups_per_frame, uint32_t *waves_per_group, uint32_t log2_scale = 0,
-                      uint32_t n_windows = 0) {
-  if (!fr || (k >= kSliceRegion && !rg) || !groups_per_frame || !waves_per_group || fr->n_frames == 0)
+// mh_decode_*_shape: slice_shape for a frame description, the units and the tiles counted by the
+// decode entries' own rules (call_geometry). The tile cap is reported for a region or windows only,
+// as it always was: the whole-frame entries leave it to the decode call.
+int slice_shape_entry(SliceKernel family, const mh_frame *fr, DecodeCall c, void *stream,
+                      uint32_t *groups_per_unit, uint32_t *waves_per_group) {
+  if (!fr || (c.regional() && !c.rg) || !groups_per_unit || !waves_per_group || fr->n_frames == 0)
     return MH_ERR_INVALID_ARG;
-  if (k == kSliceWindows && n_windows == 0) return MH_ERR_INVALID_ARG;
-  const uint32_t n_units = k == kSliceWindows ? n_windows : fr->n_frames;
-  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
-  if (log2_scale > 3u) return MH_ERR_INVALID_ARG;
-  if (log2_scale) k = (SliceKernel)((k == kSliceWindows ? kSliceWindowsScaled : kSliceScaled) + log2_scale - 1u);
-  const mh_dims &d = fr->dims;
-  if (!dims_ok(d)) return MH_ERR_DIMS;
-  uint32_t tiles = (d.block_width * d.block_height + 63) / 64;
-  if (k >= kSliceRegion) {
-    RegionExtent re;
-    if (!region_extent(d, rg, re)) return MH_ERR_DIMS;
-    tiles = re.tiles;
-    if ((uint64_t)tiles * n_units > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
-  }
-  const int rc = slice_shape(k, n_units, tiles, !(fr->flags & MH_FLAG_NO_DELTA), (hipStream_t)stream,
-                             groups_per_frame);
+  if (c.windowed() && c.n_windows == 0) return MH_ERR_INVALID_ARG;
+  int rc = call_geometry(fr, c);
+  if (rc != MH_OK) return rc;
+  if (c.regional() && !tiles_fit(c)) return MH_ERR_CAPACITY;
+  rc = slice_shape((SliceKernel)(family + c.log2_scale), c.n_units, c.re.tiles, !(fr->flags & MH_FLAG_NO_DELTA),
+                   (hipStream_t)stream, groups_per_unit);
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
   return MH_OK;
@@ -2727,15 +2768,16 @@ int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_f
 #endif
   // MH_FLAG_LANE_PAIRS: honoured by the diagnostic library only; the product library accepts
   // it (callers built against round-4 libraries pass it) and decodes with the default kernels
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride,
-                             MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER | MH_FLAG_LANE_PAIRS, {TableRule::kInFrame});
+  DecodeCall c{DecodeCall::kInFrame};
+  c.allowed_flags |= MH_FLAG_LANE_PAIRS;
+  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, c);
   if (rc != MH_OK) return rc;
   DecodeArgs a{};
   a.t1 = reinterpret_cast<const uint16_t *>(fr->d_table1);
   a.t2 = reinterpret_cast<const uint16_t *>(fr->d_table2);
   a.lut = fr->d_lut;
   a.t2_entries = fr->table2_entries;
-  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
+  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a, c);
   if (rc != MH_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const bool lp = (fr->flags & MH_FLAG_LANE_PAIRS) != 0;
@@ -2744,173 +2786,111 @@ int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_f
 }
 
 #if !MH_LANE_PAIRS
-// The three frame-slice entries: t1 / t2 / lut of DecodeArgs stay null, every workgroup takes
-// its frame's table from d_luts or builds it from the frame's header.
+// The frame-slice entries. Each is its DecodeCall, the prologue and one launch of its row of
+// kSliceTable with its own trailing scalars; each *_shape twin is the same call without tables.
 int mh_decode_frames(const mh_frame *fr, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                      const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                      void *stream) {
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
-                             {TableRule::kPrepared, d_luts, lut_stride_bytes});
+  DecodeCall c{DecodeCall::kPrepared, d_luts, lut_stride_bytes};
+  SliceArgs p;
+  const int rc = slice_prologue(fr, d_out, out_pitch, out_frame_stride, c, p);
   if (rc != MH_OK) return rc;
-  DecodeArgs a{};
-  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
-  if (rc != MH_OK) return rc;
-  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
-  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return launch_slices(delta ? mh_decode_multitable_kernel<true> : mh_decode_multitable_kernel<false>, kSliceFrames,
-                       delta, a, fr->n_frames, (hipStream_t)stream, ao, luts, d_frame_status, lut_stride_bytes);
+  return launch_slices<FramesFn>(kSliceFrames, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
+                                 d_frame_status, lut_stride_bytes);
 }
 
 int mh_decode_frames_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame,
                            uint32_t *waves_per_group) {
-  return slice_shape_entry(kSliceFrames, fr, nullptr, stream, groups_per_frame, waves_per_group);
+  return slice_shape_entry(kSliceFrames, fr, {DecodeCall::kPrepared}, stream, groups_per_frame, waves_per_group);
 }
 
 int mh_decode_headers(const mh_frame *fr, const uint8_t *d_canon_headers, const int32_t *d_frame_status,
                       int32_t *d_header_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                       void *stream) {
   if (d_header_status && d_header_status == d_frame_status) return MH_ERR_INVALID_ARG;
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
-                             {TableRule::kHeaders, d_canon_headers});
+  DecodeCall c{DecodeCall::kHeaders, d_canon_headers};
+  SliceArgs p;
+  const int rc = slice_prologue(fr, d_out, out_pitch, out_frame_stride, c, p);
   if (rc != MH_OK) return rc;
-  DecodeArgs a{};
-  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a);
-  if (rc != MH_OK) return rc;
-  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return launch_slices(delta ? mh_decode_headers_kernel<true> : mh_decode_headers_kernel<false>, kSliceHeaders, delta,
-                       a, fr->n_frames, (hipStream_t)stream, ao, d_canon_headers, d_frame_status, d_header_status);
+  return launch_slices<HeadersFn>(kSliceHeaders, c, p, stream, d_canon_headers, d_frame_status, d_header_status);
 }
 
 int mh_decode_headers_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame,
                             uint32_t *waves_per_group) {
-  return slice_shape_entry(kSliceHeaders, fr, nullptr, stream, groups_per_frame, waves_per_group);
+  return slice_shape_entry(kSliceHeaders, fr, {DecodeCall::kHeaders}, stream, groups_per_frame, waves_per_group);
+}
+
+// The region at scale 2^log2_scale, same tiles and launch-shape rule at every scale: 0 is the region
+// kernel itself (mh_decode_region); 1..3 are the region kernel with the box-filter output stage (BoxRows).
+int mh_decode_region_scaled(const mh_frame *fr, const mh_region *rg, uint32_t log2_scale, const uint16_t *d_luts,
+                            uint64_t lut_stride_bytes, const int32_t *d_frame_status, uint8_t *d_out,
+                            size_t out_pitch, size_t out_frame_stride, void *stream) {
+  DecodeCall c{DecodeCall::kRegion, d_luts, lut_stride_bytes, rg, log2_scale};
+  SliceArgs p;
+  const int rc = slice_prologue(fr, d_out, out_pitch, out_frame_stride, c, p);  // c.re.ph = SH: the descriptor's limit
+  if (rc != MH_OK) return rc;
+  return launch_slices<RegionFn>(kSliceRegion, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
+                                 d_frame_status, lut_stride_bytes, c.re.segs, rg->bw, rg->bx0, rg->by0);
 }
 
 int mh_decode_region(const mh_frame *fr, const mh_region *rg, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                      const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                      void *stream) {
-  RegionExtent re;
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
-                             {TableRule::kRegion, d_luts, lut_stride_bytes, rg}, &re);
-  if (rc != MH_OK) return rc;
-  DecodeArgs a{};
-  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a, &re);
-  if (rc != MH_OK) return rc;
-  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
-  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return launch_slices(delta ? mh_decode_region_kernel<true> : mh_decode_region_kernel<false>, kSliceRegion, delta, a,
-                       fr->n_frames, (hipStream_t)stream, ao, luts, d_frame_status, lut_stride_bytes, re.segs, rg->bw,
-                       rg->bx0, rg->by0);
-}
-
-int mh_decode_region_shape(const mh_frame *fr, const mh_region *rg, void *stream, uint32_t *groups_per_frame,
-                           uint32_t *waves_per_group) {
-  return slice_shape_entry(kSliceRegion, fr, rg, stream, groups_per_frame, waves_per_group);
-}
-
-// The region at scale 2^log2_scale: scale 1 is mh_decode_region itself; 2, 4 and 8 are the region
-// kernel with the box-filter output stage (BoxRows), same tiles and launch-shape rule.
-int mh_decode_region_scaled(const mh_frame *fr, const mh_region *rg, uint32_t log2_scale, const uint16_t *d_luts,
-                            uint64_t lut_stride_bytes, const int32_t *d_frame_status, uint8_t *d_out,
-                            size_t out_pitch, size_t out_frame_stride, void *stream) {
-  if (log2_scale == 0)
-    return mh_decode_region(fr, rg, d_luts, lut_stride_bytes, d_frame_status, d_out, out_pitch, out_frame_stride,
-                            stream);
-  RegionExtent re;
-  int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER,
-                             {TableRule::kRegion, d_luts, lut_stride_bytes, rg}, &re, log2_scale);
-  if (rc != MH_OK) return rc;
-  DecodeArgs a{};
-  rc = fill_decode_args(fr, d_out, out_pitch, out_frame_stride, a, &re);  // re.ph = SH: the descriptor's limit
-  if (rc != MH_OK) return rc;
-  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
-  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  const SliceKernel k = (SliceKernel)(kSliceScaled + log2_scale - 1u);
-#define MH_SCALED(K)                                                                                              \
-  launch_slices(delta ? mh_decode_region_scaled_kernel<true, K> : mh_decode_region_scaled_kernel<false, K>, k, delta, \
-                a, fr->n_frames, (hipStream_t)stream, ao, luts, d_frame_status, lut_stride_bytes, re.segs, rg->bw, \
-                rg->bx0, rg->by0)
-  return log2_scale == 1 ? MH_SCALED(1) : log2_scale == 2 ? MH_SCALED(2) : MH_SCALED(3);
-#undef MH_SCALED
+  return mh_decode_region_scaled(fr, rg, 0, d_luts, lut_stride_bytes, d_frame_status, d_out, out_pitch,
+                                 out_frame_stride, stream);
 }
 
 int mh_decode_region_scaled_shape(const mh_frame *fr, const mh_region *rg, uint32_t log2_scale, void *stream,
                                   uint32_t *groups_per_frame, uint32_t *waves_per_group) {
-  // (scale 1: the region kernel's shape; a bad scale is reported where a bad flag is)
-  return slice_shape_entry(kSliceRegion, fr, rg, stream, groups_per_frame, waves_per_group, log2_scale);
+  return slice_shape_entry(kSliceRegion, fr, {DecodeCall::kRegion, nullptr, 0, rg, log2_scale}, stream,
+                           groups_per_frame, waves_per_group);
 }
 
-// A list of windows of one size, each with its own frame and origin: the region kernel's body with
-// a map read from the window's descriptor (WindowMap); n_windows stands where n_frames does in the
-// launch-shape rule and the grid.
-int mh_decode_windows(const mh_frame *fr, const mh_window *d_windows, uint32_t n_windows, uint32_t bw, uint32_t bh,
-                      const uint16_t *d_luts, uint64_t lut_stride_bytes, const int32_t *d_frame_status,
-                      int32_t *d_window_status, uint8_t *d_out, size_t out_pitch, size_t out_window_stride,
-                      void *stream) {
-  if (d_window_status && d_window_status == d_frame_status) return MH_ERR_INVALID_ARG;
-  const mh_region size = {0u, 0u, bw, bh};
-  TableRule tr{TableRule::kWindows, d_luts, lut_stride_bytes, &size};
-  tr.windows = d_windows;
-  tr.n_windows = n_windows;
-  RegionExtent re;
-  int rc = check_decode_args(fr, d_out, out_pitch, out_window_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, tr, &re);
-  if (rc != MH_OK) return rc;
-  DecodeArgs a{};
-  rc = fill_decode_args(fr, d_out, out_pitch, out_window_stride, a, &re, n_windows);
-  if (rc != MH_OK) return rc;
-  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
-  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return launch_slices(delta ? mh_decode_windows_kernel<true> : mh_decode_windows_kernel<false>, kSliceWindows, delta,
-                       a, n_windows, (hipStream_t)stream, ao, luts, d_frame_status, d_windows, re.segs, bw, bh,
-                       fr->n_frames, fr->dims.block_width - bw, fr->dims.block_height - bh, lut_stride_bytes,
-                       d_window_status);
+int mh_decode_region_shape(const mh_frame *fr, const mh_region *rg, void *stream, uint32_t *groups_per_frame,
+                           uint32_t *waves_per_group) {
+  return mh_decode_region_scaled_shape(fr, rg, 0, stream, groups_per_frame, waves_per_group);
 }
 
-int mh_decode_windows_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh, void *stream,
-                            uint32_t *groups_per_window, uint32_t *waves_per_group) {
-  const mh_region size = {0u, 0u, bw, bh};
-  return slice_shape_entry(kSliceWindows, fr, &size, stream, groups_per_window, waves_per_group, 0, n_windows);
-}
-
-// The windows at scale 2^log2_scale: scale 1 is mh_decode_windows itself; 2, 4 and 8 are the windows
-// kernel with the box-filter output stage, every slot a raster of c bw x c bh (c = 8 >> log2_scale).
+// A list of windows of one size, each with its own frame and origin, at scale 2^log2_scale: the
+// region kernel's body with a map read from the window's descriptor (WindowMap); n_windows stands
+// where n_frames does in the launch-shape rule and the grid. Scale 0 is the windows kernel itself
+// (mh_decode_windows); 1..3 are the windows kernel with the box-filter output stage, every slot a
+// raster of c bw x c bh (c = 8 >> log2_scale).
 int mh_decode_windows_scaled(const mh_frame *fr, const mh_window *d_windows, uint32_t n_windows, uint32_t bw,
                              uint32_t bh, uint32_t log2_scale, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                              const int32_t *d_frame_status, int32_t *d_window_status, uint8_t *d_out,
                              size_t out_pitch, size_t out_window_stride, void *stream) {
-  if (log2_scale == 0)
-    return mh_decode_windows(fr, d_windows, n_windows, bw, bh, d_luts, lut_stride_bytes, d_frame_status,
-                             d_window_status, d_out, out_pitch, out_window_stride, stream);
   if (d_window_status && d_window_status == d_frame_status) return MH_ERR_INVALID_ARG;
   const mh_region size = {0u, 0u, bw, bh};
-  TableRule tr{TableRule::kWindows, d_luts, lut_stride_bytes, &size};
-  tr.windows = d_windows;
-  tr.n_windows = n_windows;
-  RegionExtent re;
-  int rc = check_decode_args(fr, d_out, out_pitch, out_window_stride, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER, tr, &re,
-                             log2_scale);
+  DecodeCall c{DecodeCall::kWindows, d_luts, lut_stride_bytes, &size, log2_scale, d_windows, n_windows};
+  SliceArgs p;
+  const int rc = slice_prologue(fr, d_out, out_pitch, out_window_stride, c, p);
   if (rc != MH_OK) return rc;
-  DecodeArgs a{};
-  rc = fill_decode_args(fr, d_out, out_pitch, out_window_stride, a, &re, n_windows);
-  if (rc != MH_OK) return rc;
-  const uint8_t *luts = reinterpret_cast<const uint8_t *>(d_luts);
-  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  const SliceKernel k = (SliceKernel)(kSliceWindowsScaled + log2_scale - 1u);
-#define MH_SCALED(K)                                                                                                \
-  launch_slices(delta ? mh_decode_windows_scaled_kernel<true, K> : mh_decode_windows_scaled_kernel<false, K>, k,    \
-                delta, a, n_windows, (hipStream_t)stream, ao, luts, d_frame_status, d_windows, re.segs, bw, bh,      \
-                fr->n_frames, fr->dims.block_width - bw, fr->dims.block_height - bh, lut_stride_bytes,              \
-                d_window_status)
-  return log2_scale == 1 ? MH_SCALED(1) : log2_scale == 2 ? MH_SCALED(2) : MH_SCALED(3);
-#undef MH_SCALED
+  return launch_slices<WindowsFn>(kSliceWindows, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
+                                  d_frame_status, d_windows, c.re.segs, bw, bh, fr->n_frames,
+                                  fr->dims.block_width - bw, fr->dims.block_height - bh, lut_stride_bytes,
+                                  d_window_status);
+}
+
+int mh_decode_windows(const mh_frame *fr, const mh_window *d_windows, uint32_t n_windows, uint32_t bw, uint32_t bh,
+                      const uint16_t *d_luts, uint64_t lut_stride_bytes, const int32_t *d_frame_status,
+                      int32_t *d_window_status, uint8_t *d_out, size_t out_pitch, size_t out_window_stride,
+                      void *stream) {
+  return mh_decode_windows_scaled(fr, d_windows, n_windows, bw, bh, 0, d_luts, lut_stride_bytes, d_frame_status,
+                                  d_window_status, d_out, out_pitch, out_window_stride, stream);
 }
 
 int mh_decode_windows_scaled_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh,
                                    uint32_t log2_scale, void *stream, uint32_t *groups_per_window,
                                    uint32_t *waves_per_group) {
   const mh_region size = {0u, 0u, bw, bh};
-  return slice_shape_entry(kSliceWindows, fr, &size, stream, groups_per_window, waves_per_group, log2_scale,
-                           n_windows);
+  return slice_shape_entry(kSliceWindows, fr, {DecodeCall::kWindows, nullptr, 0, &size, log2_scale, nullptr, n_windows},
+                           stream, groups_per_window, waves_per_group);
+}
+
+int mh_decode_windows_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh, void *stream,
+                            uint32_t *groups_per_window, uint32_t *waves_per_group) {
+  return mh_decode_windows_scaled_shape(fr, n_windows, bw, bh, 0, stream, groups_per_window, waves_per_group);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

@@ -36,6 +36,14 @@ def _stream_ptr(stream: Optional[torch.cuda.Stream], device: torch.device) -> in
     return int(s.cuda_stream)
 
 
+def _header_tensor(canon, dev: torch.device, convert: bool = True) -> torch.Tensor:
+    """Canonical headers -> a u8 tensor on `dev`: a host array is uploaded; a tensor is moved, cast
+    and made contiguous, or (convert=False) left as it is for the caller to judge."""
+    if isinstance(canon, torch.Tensor):
+        return canon.to(dev, torch.uint8).contiguous() if convert else canon
+    return torch.from_numpy(np.ascontiguousarray(canon, np.uint8)).to(dev)
+
+
 @dataclasses.dataclass
 class DeviceTables:
     """T1/T2 (+ the derived LDS table) resident on one device."""
@@ -66,10 +74,7 @@ class DeviceTables:
         T2 keeps its full MH_TABLE2_MAX_ENTRIES capacity (zero past the used
         subtables). Asynchronous; check_status() syncs and raises on a bad header."""
         dev = _dev(device)
-        if isinstance(canon, torch.Tensor):
-            hdr = canon.to(dev, torch.uint8).contiguous()
-        else:
-            hdr = torch.from_numpy(np.ascontiguousarray(canon, np.uint8)).to(dev)
+        hdr = _header_tensor(canon, dev)
         if hdr.numel() != 256:
             raise ValueError("the canonical header has 256 entries")
         d1 = torch.empty(512, dtype=torch.uint8, device=dev)
@@ -126,10 +131,7 @@ class DeviceTableSet:
         (u8[n, 256], tensor or array) in one launch (mh_build_luts_device). Asynchronous;
         check_status() syncs and raises when a header was rejected."""
         dev = _dev(device)
-        if isinstance(canon, torch.Tensor):
-            hdr = canon.to(dev, torch.uint8).contiguous()
-        else:
-            hdr = torch.from_numpy(np.ascontiguousarray(canon, np.uint8)).to(dev)
+        hdr = _header_tensor(canon, dev)
         if hdr.dim() != 2 or hdr.shape[1] != 256 or hdr.shape[0] < 1:
             raise ValueError("canonical headers are u8[n, 256]")
         n = int(hdr.shape[0])
@@ -202,31 +204,37 @@ class DeviceFrames:
                    sum(f.payload_bytes for f in frames))
 
 
-def _frame_entry(frames: DeviceFrames, tables: DeviceTables, extra_flags: int = 0):
+def _frame_entry(frames: DeviceFrames, tables: Optional[DeviceTables], extra_flags: int = 0):
     """(mh_frame, device index) for (frames, tables), extra_flags ORed into the frames'
     flags. Filling a ctypes struct field by field costs ~5.5 us of Python -- more than
     the 5.3 us decode of a 2048x1536 frame -- so the structs are kept on `frames` and
     reused while the buffers and sizes they were built from are the same objects (the
     buffer tensors are the renderer's MTLBuffers: allocated once, never re-seated in
     place; the cache holds references to them, so their ids cannot be reused). The
-    device check runs when an entry is built. Callers never modify the struct."""
-    refs = (frames.block_offsets, frames.codes, frames.frame_code_offsets, frames.block_init,
-            tables.table1, tables.table2, tables.lut)
-    key = (id(refs[0]), id(refs[1]), id(refs[2]), id(refs[3]), id(refs[4]), id(refs[5]), id(refs[6]),
+    device check runs when an entry is built. Callers never modify the struct.
+    tables None: the struct of the frame-slice entries (mh_decode_frames, ...), whose table
+    fields stay NULL; those structs have a cache of their own beside the first."""
+    if tables is not None:
+        slot, t1, t2, lut = "_fr_cache", tables.table1, tables.table2, tables.lut
+    else:
+        slot, t1, t2, lut = "_frs_cache", None, None, None
+    refs = (frames.block_offsets, frames.codes, frames.frame_code_offsets, frames.block_init, t1, t2, lut)
+    key = (id(refs[0]), id(refs[1]), id(refs[2]), id(refs[3]), id(t1), id(t2), id(lut),
            frames.width, frames.height, frames.n_frames, frames.flags)
-    cache = frames.__dict__.get("_fr_cache")
+    cache = frames.__dict__.get(slot)
     if cache is None or cache[0] != key:
         dev = frames.codes.device
         if dev.type != "cuda" or any(t is not None and t.device != dev for t in refs):
-            raise ValueError("tables and frames must live on the same HIP device")
+            raise ValueError("tables and frames must live on the same HIP device" if tables is not None
+                             else "the frames' buffers must live on one HIP device")
         cache = (key, refs, {}, dev.index)
-        frames.__dict__["_fr_cache"] = cache
+        frames.__dict__[slot] = cache
     fr = cache[2].get(extra_flags)
     if fr is None:
         bw, bh = block_grid(frames.width, frames.height)
         ptr = [t.data_ptr() if t is not None else None for t in refs]
         fr = N.mh_frame(ptr[0], ptr[1], frames.codes.numel(), ptr[2], ptr[4], ptr[5],
-                        tables.table2_entries, ptr[6], ptr[3],
+                        tables.table2_entries if tables is not None else 0, ptr[6], ptr[3],
                         N.mh_dims(frames.width, frames.height, bw, bh), frames.n_frames,
                         frames.flags | extra_flags)
         cache[2][extra_flags] = fr
@@ -291,27 +299,7 @@ def check(frames: DeviceFrames, tables: DeviceTables,
 
 
 def _frames_entry(frames: DeviceFrames, extra_flags: int = 0):
-    """(mh_frame, device index) for mh_decode_frames: the table fields stay NULL. Cached on
-    `frames` like _frame_entry's structs."""
-    refs = (frames.block_offsets, frames.codes, frames.frame_code_offsets, frames.block_init)
-    key = (id(refs[0]), id(refs[1]), id(refs[2]), id(refs[3]), frames.width, frames.height, frames.n_frames,
-           frames.flags)
-    cache = frames.__dict__.get("_frs_cache")
-    if cache is None or cache[0] != key:
-        dev = frames.codes.device
-        if dev.type != "cuda" or any(t is not None and t.device != dev for t in refs):
-            raise ValueError("the frames' buffers must live on one HIP device")
-        cache = (key, refs, {}, dev.index)
-        frames.__dict__["_frs_cache"] = cache
-    fr = cache[2].get(extra_flags)
-    if fr is None:
-        bw, bh = block_grid(frames.width, frames.height)
-        ptr = [t.data_ptr() if t is not None else None for t in refs]
-        fr = N.mh_frame(ptr[0], ptr[1], frames.codes.numel(), ptr[2], None, None, 0, None, ptr[3],
-                        N.mh_dims(frames.width, frames.height, bw, bh), frames.n_frames,
-                        frames.flags | extra_flags)
-        cache[2][extra_flags] = fr
-    return fr, cache[3]
+    return _frame_entry(frames, None, extra_flags)
 
 
 def _out_raster(frames: DeviceFrames, out: Optional[torch.Tensor], h: int, pitch: int, dev_index: int,
@@ -347,13 +335,23 @@ def _check_table_set(ts: DeviceTableSet, frames: DeviceFrames, dev_index: int) -
 
 
 def _slice_shape(entry: str, frames: DeviceFrames, stream: Optional[torch.cuda.Stream], extra_flags: int,
-                 region=None) -> tuple:
-    """(workgroups per frame, waves per workgroup) from the C entry `entry` (mh_decode_*_shape)."""
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    rg = () if region is None else (ctypes.byref(_region_struct(frames, region)),)
+                 region=None, windows=None, log2_scale=None) -> tuple:
+    """(workgroups per frame or window, waves per workgroup) from the C entry `entry`
+    (mh_decode_*_shape). Between the frame and the stream the entry takes `region`, or
+    windows = (n_windows, (bw, bh)), and then `log2_scale` -- each when given."""
+    scale = () if log2_scale is None else (_log2_scale(log2_scale),)
+    size = () if windows is None else _window_size(frames, windows[1])
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    what = ()
+    if windows is not None:
+        if int(windows[0]) < 1:
+            raise ValueError("no windows")
+        what = (int(windows[0]), *size)
+    elif region is not None:
+        what = (ctypes.byref(_region_struct(frames, region)),)
     g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
-    N.check(getattr(N.lib(), entry)(ctypes.byref(fr), *rg, sp, ctypes.byref(g), ctypes.byref(w)), entry)
+    N.check(getattr(N.lib(), entry)(ctypes.byref(fr), *what, *scale, _raw_stream_ptr(stream, dev_index),
+                                    ctypes.byref(g), ctypes.byref(w)), entry)
     return int(g.value), int(w.value)
 
 
@@ -381,7 +379,7 @@ def decode_frames(frames, table_set="cuda", out: Optional[torch.Tensor] = None,
         return _decode_frames_host(frames, table_set)
     if not isinstance(table_set, DeviceTableSet):
         raise TypeError("decode_frames(DeviceFrames, ...) takes a DeviceTableSet")
-    fr, dev_index = _frames_entry(frames, extra_flags)
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
     if fr.flags & N.MH_FLAG_LANE_PAIRS:
         raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_frames")
     _check_table_set(table_set, frames, dev_index)
@@ -459,6 +457,31 @@ def _region_tables(who: str, frames: DeviceFrames, tables, dev_index: int, skip_
     raise TypeError(f"{who} takes a DeviceTables or a DeviceTableSet")
 
 
+def _decode_region(who: str, k: Optional[int], frames: DeviceFrames, tables, region, out, stream,
+                   extra_flags: int, skip_rejected: bool) -> torch.Tensor:
+    """decode_region (k None: the C entry takes no scale) and decode_region_scaled: the arguments
+    checked, the default raster made, one launch."""
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
+    rg = _region_struct(frames, region)
+    luts, stride, status = _region_tables(who, frames, tables, dev_index, skip_rejected)
+    k0 = k or 0
+    pitch = (8 >> k0) * rg.bw
+    h = (min(frames.height, 8 * (rg.by0 + rg.bh)) - 8 * rg.by0 + (1 << k0) - 1) >> k0  # RH, or SH = ceil(RH / s)
+    out = _out_raster(frames, out, h, pitch, dev_index, stream)
+    sp = _raw_stream_ptr(stream, dev_index)
+    tail = (luts.data_ptr(), stride, status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
+            h * pitch, sp)
+    if k is None:
+        rc = N.lib().mh_decode_region(ctypes.byref(fr), ctypes.byref(rg), *tail)
+    else:
+        rc = N.lib().mh_decode_region_scaled(ctypes.byref(fr), ctypes.byref(rg), k, *tail)
+    if rc:
+        N.check(rc, "mh_" + who)
+    return out
+
+
 def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tensor] = None,
                   stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
                   skip_rejected: bool = True) -> torch.Tensor:
@@ -467,21 +490,7 @@ def decode_region(frames: DeviceFrames, tables, region, out: Optional[torch.Tens
     DeviceTables (its prepared table shared by all frames) or a DeviceTableSet (a table per
     frame; with skip_rejected its status goes in as the per-frame status and a frame whose word
     is non-zero is left untouched). out: decode()'s contract with the region's shape."""
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_region")
-    rg = _region_struct(frames, region)
-    luts, stride, status = _region_tables("decode_region", frames, tables, dev_index, skip_rejected)
-    pitch = 8 * rg.bw
-    h = min(frames.height, 8 * (rg.by0 + rg.bh)) - 8 * rg.by0
-    out = _out_raster(frames, out, h, pitch, dev_index, stream)
-    sp = _raw_stream_ptr(stream, dev_index)
-    rc = N.lib().mh_decode_region(ctypes.byref(fr), ctypes.byref(rg), luts.data_ptr(), stride,
-                                  status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
-                                  h * pitch, sp)
-    if rc:
-        N.check(rc, "mh_decode_region")
-    return out
+    return _decode_region("decode_region", None, frames, tables, region, out, stream, extra_flags, skip_rejected)
 
 
 def _log2_scale(log2_scale) -> int:
@@ -495,14 +504,7 @@ def decode_region_scaled_shape(frames: DeviceFrames, region, log2_scale: int,
                                stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
     """(workgroups per frame, waves per workgroup) decode_region_scaled would launch with
     (mh_decode_region_scaled_shape)."""
-    k = _log2_scale(log2_scale)
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    rg = _region_struct(frames, region)
-    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
-    N.check(N.lib().mh_decode_region_scaled_shape(ctypes.byref(fr), ctypes.byref(rg), k, sp, ctypes.byref(g),
-                                                  ctypes.byref(w)), "mh_decode_region_scaled_shape")
-    return int(g.value), int(w.value)
+    return _slice_shape("mh_decode_region_scaled_shape", frames, stream, extra_flags, region, log2_scale=log2_scale)
 
 
 def decode_region_scaled(frames: DeviceFrames, tables, region, log2_scale: int, out: Optional[torch.Tensor] = None,
@@ -514,22 +516,8 @@ def decode_region_scaled(frames: DeviceFrames, tables, region, log2_scale: int, 
     columns are the picture ((SW, SH) = Region.scaled_size; the columns beyond, cells of a
     right-edge block outside the frame, are 0). tables, out and skip_rejected: decode_region's.
     log2_scale 0 is decode_region."""
-    k = _log2_scale(log2_scale)
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_region_scaled")
-    rg = _region_struct(frames, region)
-    luts, stride, status = _region_tables("decode_region_scaled", frames, tables, dev_index, skip_rejected)
-    pitch = (8 >> k) * rg.bw
-    h = Region(rg.bx0, rg.by0, rg.bw, rg.bh).scaled_size(frames.width, frames.height, k)[1]
-    out = _out_raster(frames, out, h, pitch, dev_index, stream)
-    sp = _raw_stream_ptr(stream, dev_index)
-    rc = N.lib().mh_decode_region_scaled(ctypes.byref(fr), ctypes.byref(rg), k, luts.data_ptr(), stride,
-                                         status.data_ptr() if status is not None else None, out.data_ptr(),
-                                         pitch, h * pitch, sp)
-    if rc:
-        N.check(rc, "mh_decode_region_scaled")
-    return out
+    return _decode_region("decode_region_scaled", _log2_scale(log2_scale), frames, tables, region, out, stream,
+                          extra_flags, skip_rejected)
 
 
 def decode_scaled(frames: DeviceFrames, tables, log2_scale: int, out: Optional[torch.Tensor] = None,
@@ -636,15 +624,7 @@ def decode_windows_shape(frames: DeviceFrames, n_windows: int, size,
                          stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
     """(workgroups per window, waves per workgroup) decode_windows would launch n_windows windows
     of size = (bw, bh) blocks with (mh_decode_windows_shape)."""
-    bw, bh = _window_size(frames, size)
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    if int(n_windows) < 1:
-        raise ValueError("no windows")
-    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
-    N.check(N.lib().mh_decode_windows_shape(ctypes.byref(fr), int(n_windows), bw, bh, sp, ctypes.byref(g),
-                                            ctypes.byref(w)), "mh_decode_windows_shape")
-    return int(g.value), int(w.value)
+    return _slice_shape("mh_decode_windows_shape", frames, stream, extra_flags, windows=(n_windows, size))
 
 
 def _decode_windows(who: str, k: int, frames: DeviceFrames, tables, windows, size, out, status, stream,
@@ -654,7 +634,7 @@ def _decode_windows(who: str, k: int, frames: DeviceFrames, tables, windows, siz
     bw, bh = _window_size(frames, size)
     c = 8 >> k
     host = _host_windows(frames, windows, bw, bh)
-    fr, dev_index = _frames_entry(frames, extra_flags)
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
     if fr.flags & N.MH_FLAG_LANE_PAIRS:
         raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
     luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
@@ -711,16 +691,8 @@ def decode_windows_scaled_shape(frames: DeviceFrames, n_windows: int, size, log2
                                 stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
     """(workgroups per window, waves per workgroup) decode_windows_scaled would launch n_windows
     windows of size = (bw, bh) blocks with, at scale 2^log2_scale (mh_decode_windows_scaled_shape)."""
-    k = _log2_scale(log2_scale)
-    bw, bh = _window_size(frames, size)
-    fr, dev_index = _frames_entry(frames, extra_flags)
-    if int(n_windows) < 1:
-        raise ValueError("no windows")
-    g, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    sp = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev_index).cuda_stream
-    N.check(N.lib().mh_decode_windows_scaled_shape(ctypes.byref(fr), int(n_windows), bw, bh, k, sp, ctypes.byref(g),
-                                                   ctypes.byref(w)), "mh_decode_windows_scaled_shape")
-    return int(g.value), int(w.value)
+    return _slice_shape("mh_decode_windows_scaled_shape", frames, stream, extra_flags, windows=(n_windows, size),
+                        log2_scale=log2_scale)
 
 
 def decode_windows_scaled(frames: DeviceFrames, tables, windows, size, log2_scale: int,
@@ -760,14 +732,11 @@ def decode_headers(frames: DeviceFrames, canons, out: Optional[torch.Tensor] = N
     non-zero word skips the frame. header_status (optional int32[n] on the device, not the same
     tensor): receives each decoded frame's verdict, 0, -3 or -5; a rejected frame's raster is
     left untouched. Returns the device raster out[n, H, pitch] (decode()'s `out` contract)."""
-    fr, dev_index = _frames_entry(frames, extra_flags)
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
     if fr.flags & N.MH_FLAG_LANE_PAIRS:
         raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_headers")
     dev = frames.codes.device
-    if isinstance(canons, torch.Tensor):
-        hdr = canons
-    else:
-        hdr = torch.from_numpy(np.ascontiguousarray(canons, np.uint8)).to(dev)
+    hdr = _header_tensor(canons, dev, convert=False)
     if (hdr.dtype is not torch.uint8 or hdr.dim() != 2 or tuple(hdr.shape) != (frames.n_frames, 256)
             or hdr.get_device() != dev_index or not hdr.is_contiguous()):
         raise ValueError(f"canons must be a contiguous uint8 [{frames.n_frames}, 256] tensor on cuda:{dev_index}")

@@ -15,10 +15,12 @@ tests/test_isa.py applies the same checks to the product and diagnostic librarie
 """
 from __future__ import annotations
 
+import argparse
 import os
 import re
 import shutil
 import subprocess
+import sys
 import tempfile
 
 LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin")
@@ -70,9 +72,37 @@ def disasm(lib_path: str) -> str:
                                         text=True).stdout for co in _code_objects(lib_path, d))
 
 
-def kernels(lib_path: str) -> dict:
-    """kernel symbol -> (private_segment_fixed_size, vgpr_spill_count, sgpr_spill_count,
-    vgpr_count), from the code objects' metadata notes."""
+def listings_of(disasm_text: str) -> dict:
+    """kernel symbol -> its instructions as text lines, from llvm-objdump -d output: no addresses,
+    no raw encodings and no trailing comments (objdump prints all three behind `//`), so two builds
+    whose code moved but did not change compare equal."""
+    out, cur = {}, None
+    for line in disasm_text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+            continue
+        ins = " ".join(line.split("//", 1)[0].split())
+        if cur is not None and ins and line[:1].isspace():
+            cur.append(ins)
+    return out
+
+
+def listings(lib_path: str) -> dict:
+    """listings_of the gfx950 code objects of a linked library."""
+    return listings_of(disasm(lib_path))
+
+
+def compare(old_lib: str, new_lib: str) -> tuple:
+    """(symbols only in old, symbols only in new, symbols in both whose listings differ, symbols equal)."""
+    old, new = listings(old_lib), listings(new_lib)
+    both = sorted(old.keys() & new.keys())
+    return (sorted(old.keys() - new.keys()), sorted(new.keys() - old.keys()),
+            [k for k in both if old[k] != new[k]], [k for k in both if old[k] == new[k]])
+
+
+def _metadata(lib_path: str, fields) -> dict:
+    """kernel symbol -> the integer metadata `fields` of its note, in that order."""
     out = {}
     with tempfile.TemporaryDirectory() as d:
         for co in _code_objects(lib_path, d):
@@ -81,29 +111,22 @@ def kernels(lib_path: str) -> dict:
                 m = re.search(r"\.name:\s+(\S+)", blk)
                 if not m or "kernel" not in m.group(1):
                     continue
-                get = lambda k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                out[m.group(1)] = (get("private_segment_fixed_size"), get("vgpr_spill_count"),
-                                   get("sgpr_spill_count"), get("vgpr_count"))
+                out[m.group(1)] = tuple(int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1)) for k in fields)
     return out
+
+
+def kernels(lib_path: str) -> dict:
+    """kernel symbol -> (private_segment_fixed_size, vgpr_spill_count, sgpr_spill_count,
+    vgpr_count), from the code objects' metadata notes."""
+    return _metadata(lib_path, ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count"))
 
 
 def resources(lib_path: str) -> dict:
     """kernel symbol -> {"vgpr", "sgpr", "lds", "scratch"}: the register counts, the static LDS
     bytes and the scratch bytes of each kernel, from the same metadata notes (for the budget
     tables in DESIGN.md)."""
-    out = {}
-    with tempfile.TemporaryDirectory() as d:
-        for co in _code_objects(lib_path, d):
-            notes = subprocess.run([READELF, "--notes", co], check=True, capture_output=True, text=True).stdout
-            for blk in re.split(r"\n\s+- \.", notes):
-                m = re.search(r"\.name:\s+(\S+)", blk)
-                if not m or "kernel" not in m.group(1):
-                    continue
-                get = lambda k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                out[m.group(1)] = {"vgpr": get("vgpr_count"), "sgpr": get("sgpr_count"),
-                                   "lds": get("group_segment_fixed_size"),
-                                   "scratch": get("private_segment_fixed_size")}
-    return out
+    fields = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
+    return {k: dict(zip(("vgpr", "sgpr", "lds", "scratch"), v)) for k, v in _metadata(lib_path, fields).items()}
 
 
 def check_library(lib_path: str) -> list:
@@ -114,3 +137,23 @@ def check_library(lib_path: str) -> list:
     problems += [f"{k}: 64-bit shift amount in the last allocated VGPR: {ins}"
                  for k, ins in high_reg_shifts(disasm(lib_path), {k: v[3] for k, v in ks.items()})]
     return problems
+
+
+def main(argv=None) -> int:
+    """python -m metalhuffman_amd.isa_guard OLD.so NEW.so: the kernel symbols only in one library and
+    those whose instruction lists differ; exit status 0 when there are none."""
+    ap = argparse.ArgumentParser(description=main.__doc__)
+    ap.add_argument("old")
+    ap.add_argument("new")
+    args = ap.parse_args(argv)
+    only_old, only_new, differ, equal = compare(args.old, args.new)
+    for title, names in ((f"only in {args.old}", only_old), (f"only in {args.new}", only_new),
+                         ("instruction lists differ", differ)):
+        for k in names:
+            print(f"{title}: {k}")
+    print(f"kernels equal {len(equal)}, different {len(differ)}, only old {len(only_old)}, only new {len(only_new)}")
+    return 1 if only_old or only_new or differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

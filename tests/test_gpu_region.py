@@ -172,6 +172,55 @@ def test_decode_rect_view(mh, oracle, device):
         D.decode_region(fr, D.DeviceTables(tabs.table1, tabs.table2, None), D.Region(0, 0, 1, 1))
 
 
+@pytest.mark.parametrize("flavour", ["general", "no_delta"])
+@pytest.mark.parametrize("n", [1, 3])
+def test_scale_zero_is_the_unscaled_entry(mh, oracle, device, n, flavour):
+    """The six frame-slice entries are rows of one kernel table, and scale 0 of a region or of windows
+    is the unscaled kernel: the same launch shape and the same bytes from either entry. Every shape
+    entry at every scale reports 8 waves and 1 <= G <= ceil(tiles / 8), tiles counted as the decode
+    entries count them: ceil(NB / 64) of a frame, bh * ceil(bw / 64) of a region or a window."""
+    import torch
+    from metalhuffman_amd import decoder as D
+    frames = R.frame_set(mh, oracle, flavour)[:n]
+    assert bool(frames[0][0].flags & mh.MH_FLAG_NO_DELTA) == (flavour == "no_delta")
+    fr, tabs = R.upload(device, _efs(frames))
+    assert fr.n_frames == n and (fr.frame_code_offsets is None) == (n == 1)
+
+    def ok(shape, tiles):
+        G, waves = shape
+        assert waves == 8 and 1 <= G <= -(-tiles // 8), (shape, tiles)
+
+    ok(D.decode_frames_shape(fr), -(-R.NB // 64))
+    ok(D.decode_headers_shape(fr), -(-R.NB // 64))
+    n_windows = 2
+    for name in ("full", "w65"):
+        rg = D.Region(*REGIONS[name])
+        size = (rg.bw, rg.bh)
+        tiles = rg.bh * -(-rg.bw // 64)
+        assert D.decode_region_shape(fr, rg) == D.decode_region_scaled_shape(fr, rg, 0)
+        assert D.decode_windows_shape(fr, n_windows, size) == D.decode_windows_scaled_shape(fr, n_windows, size, 0)
+        ok(D.decode_region_shape(fr, rg), tiles)
+        ok(D.decode_windows_shape(fr, n_windows, size), tiles)
+        for k in range(4):
+            ok(D.decode_region_scaled_shape(fr, rg, k), tiles)
+            ok(D.decode_windows_scaled_shape(fr, n_windows, size, k), tiles)
+
+    region = REGIONS["w65"]
+    got = R.decode_region_host(device, fr, tabs, region)
+    R.check_region(got, region, _wants(frames))
+    out0 = torch.full(got.shape, R.FILL, dtype=torch.uint8, device=device)
+    D.decode_region_scaled(fr, tabs, D.Region(*region), 0, out=out0)
+    windows = [(0, 3, 2), (n - 1, 10, 4)]
+    size = (region[2], region[3])
+    w_plain = D.decode_windows(fr, tabs, windows, size)
+    w_zero = D.decode_windows_scaled(fr, tabs, windows, size, 0)
+    torch.cuda.synchronize(device)
+    assert np.array_equal(out0.cpu().numpy(), got)
+    assert tuple(w_plain.shape) == (2, 8 * size[1], 8 * size[0])
+    assert np.array_equal(w_zero.cpu().numpy(), w_plain.cpu().numpy())
+    assert np.array_equal(w_plain[0].cpu().numpy(), got[0])  # window 0 is w65 of frame 0, no edge block in it
+
+
 # ---- 5. the pipelined loop -------------------------------------------------------------------------
 
 def test_pipelined_loop_many_frames(mh, oracle, device):

@@ -40,6 +40,37 @@ def test_high_reg_shift_checker():
     assert [b[0] for b in bad] == ["k80", "k72"], bad
 
 
+_LISTING = ("lib.so.0.hipv4-amdgcn-amd-amdhsa--gfx950:\tfile format elf64-amdgpu\n\n"
+            "Disassembly of section .text:\n\n"
+            "{a0:016x} <k_one>:\n"
+            "\ts_load_dwordx2 s[2:3], s[0:1], 0x0                         // {a0:012X}: C0060080 00000000\n"
+            "\ts_cbranch_vccnz 23                                         // {a1:012X}: BF870017 <k_one+0x64>\n"
+            "\tv_add_u32_e32 v{r}, v1, v2                                   // {a2:012X}: 68020501\n"
+            "\n"
+            "{b0:016x} <k_two>:\n"
+            "\ts_endpgm                                                   // {b0:012X}: BF810000\n")
+
+
+def _listing(base, r=1):
+    return _LISTING.format(a0=base, a1=base + 8, a2=base + 12, b0=base + 0x100, r=r)
+
+
+def test_listings_drop_addresses_and_encodings():
+    """Two listings that differ only in where the code lies compare equal, symbol by symbol."""
+    from metalhuffman_amd.isa_guard import listings_of
+    a, b = listings_of(_listing(0x1900)), listings_of(_listing(0x3700))
+    assert a == b
+    assert a == {"k_one": ["s_load_dwordx2 s[2:3], s[0:1], 0x0", "s_cbranch_vccnz 23", "v_add_u32_e32 v1, v1, v2"],
+                 "k_two": ["s_endpgm"]}
+
+
+def test_listings_keep_register_numbers():
+    """One register number apart is a different listing, for that kernel only."""
+    from metalhuffman_amd.isa_guard import listings_of
+    a, b = listings_of(_listing(0x1900)), listings_of(_listing(0x1900, r=3))
+    assert a["k_one"] != b["k_one"] and a["k_two"] == b["k_two"]
+
+
 def _disasm(lib_path):
     return _tools().disasm(lib_path)
 
