@@ -269,7 +269,7 @@ int mh_decode_headers_shape(const mh_frame *frame, void *stream, uint32_t *group
 /* rest of the frame and without a full-size raster: a window of a large scan, a pan of it,   */
 /* the same crop of every frame of a sequence. Not covered: regions for mh_decode_headers,    */
 /* the streams, the multi-GPU paths and mh_check; pixel-granular stores (a region is whole    */
-/* blocks; the caller views its rectangle inside the region's raster); a CPU twin; packing    */
+/* blocks; rectangles at pixel origins are mh_decode_crops below); a CPU twin; packing        */
 /* several rows of a region narrower than 64 blocks into one wave (lane utilisation is        */
 /* bw / (64 ceil(bw / 64))).                                                                  */
 typedef struct {
@@ -363,7 +363,8 @@ int mh_box_reduce(const uint8_t *raster, uint32_t width, uint32_t height, size_t
 /* multi-GPU paths and mh_check;                                                                */
 /* windows of different sizes in one launch; packing several rows of a window narrower than 64  */
 /* blocks into one wave (lane utilisation is bw / (64 ceil(bw / 64)), as for a region);         */
-/* pixel-granular stores; a CPU twin.                                                           */
+/* pixel-granular stores (windows are whole blocks; mh_decode_crops below takes pixel origins);  */
+/* a CPU twin.                                                                                  */
 typedef struct {
   uint32_t frame, bx0, by0, reserved; /* 16 bytes; reserved must be 0 */
 } mh_window;
@@ -444,6 +445,64 @@ int mh_decode_windows_scaled(const mh_frame *frame, const mh_window *d_windows, 
 int mh_decode_windows_scaled_shape(const mh_frame *frame, uint32_t n_windows, uint32_t bw, uint32_t bh,
                                    uint32_t log2_scale, void *stream,
                                    uint32_t *groups_per_window, uint32_t *waves_per_group);
+
+/* ---------------------------------------------------------------------- */
+/* A list of crops at PIXEL origins in one launch: rectangles of one size in pixels, each with   */
+/* its own frame and origin, every one stored densely from its own byte 0 -- a batch of random   */
+/* crops as one [n, h, w] array, a tracked box that moves by pixels. mh_decode_windows stops at  */
+/* the block grid: its caller decoded windows one block larger and viewed rectangle i at its own */
+/* (dx, dy) inside slot i, which is no array. Here the decoder moves every row onto the crop's   */
+/* byte grid in registers, at the moment it stores it; no intermediate raster exists.            */
+/* Not covered: crops at a reduced scale; crops of different sizes in one launch; flips; crops   */
+/* for mh_decode_headers, the streams, the multi-GPU paths and mh_check; stores of exactly w     */
+/* bytes (a row is written in whole 8-byte words); a CPU twin.                                   */
+typedef struct {
+  uint32_t frame, x0, y0, reserved; /* 16 bytes; pixels; reserved must be 0 */
+} mh_crop;
+
+/* Crop p = d_crops[p] is the pixels [x0, x0 + w) x [y0, y0 + h) of frame `frame`. A crop lies
+ * wholly inside the declared W x H: there is no clipping.
+ * d_crops is a DEVICE array of n_crops descriptors, 16-byte aligned (a sampler on the GPU can
+ * write it; the host never reads it). Crops may overlap, repeat and name frames in any order.
+ * Output: crop p, row y starts at d_out + p * out_crop_stride + y * out_pitch; round_up(w, 8)
+ * bytes of every row y < h are written. The first w of them are the bytes at (x0 + x, y0 + y) of
+ * the raster mh_decode_frames writes for that frame; bytes w .. round_up(w, 8) - 1 are
+ * unspecified (as the columns past RW of a region are). Nothing else is touched, in that slot or
+ * outside it. For w a multiple of 8 and out_pitch == w the slots are dense rasters.
+ * Tables, lut_stride_bytes == 0, d_block_init, d_frame_status (indexed by the crop's FRAME) and
+ * flags (MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER only): mh_decode_windows'.
+ * Crops are validated on the device as windows are, by the workgroups that serve them and from
+ * the descriptor alone, before anything is addressed through it: frame >= n_frames, x0 > W - w,
+ * y0 > H - h or reserved != 0 reject the crop. The two limits come from the host, so no sum of
+ * descriptor values is formed: x0 = 0xFFFFFFFF is rejected. A rejected crop loads nothing through
+ * its descriptor and writes no byte of the raster; the others are decoded.
+ * d_crop_status (optional output, device int32[n_crops], must not alias d_frame_status ->
+ * MH_ERR_INVALID_ARG) has d_window_status' semantics and precedence: MH_ERR_DIMS for a rejected
+ * crop; else its frame's status word when that is non-zero (the slot is then untouched); else MH_OK.
+ * Checks: all before any HIP call, in mh_decode_windows' order and with its codes, with n_crops
+ * rasters of w x h in the place of n_windows rasters of 8 bw x 8 bh: d_out, out_pitch and, for
+ * n_crops > 1, out_crop_stride are multiples of 8 (MH_ERR_ALIGN); out_pitch >= w and, for n_crops
+ * > 1, out_crop_stride >= out_pitch * h (MH_ERR_CAPACITY) -- a pitch that is a multiple of 8 and
+ * >= w holds the round_up(w, 8) written bytes; NULL d_crops or n_crops == 0 -> MH_ERR_INVALID_ARG;
+ * w == 0, h == 0, w > W or h > H -> MH_ERR_DIMS; d_crops not 16-byte aligned -> MH_ERR_ALIGN;
+ * n_crops * CBH * S tiles or the grid above 2^31 - 1 -> MH_ERR_CAPACITY.
+ * One kernel launch, asynchronous on `stream`. Tiles: with dx = x0 & 7, output word j of a row
+ * (8 bytes) is bytes dx..7 of block (x0 >> 3) + j followed by bytes 0..dx-1 of the block after it,
+ * so a wave of 64 blocks yields 63 words and tiles step by 63 blocks: OW = ceil(w / 8) words per
+ * row, S = ceil(OW / 63) tiles per block row, CBH = (h + 14) / 8 block rows (the most any y0 & 7
+ * needs), CBH * S tiles per crop. A crop that needs fewer block rows -- ((y0 & 7) + h + 7) / 8 --
+ * skips the rest before loading anything for them. The launch is n_crops * G workgroups of 8
+ * waves, workgroup g serving crop g / G, G = clamp(ceil(R / n_crops), 1, ceil(CBH * S / 8)), R the
+ * workgroups of this kernel resident on the device at once. */
+int mh_decode_crops(const mh_frame *frame, const mh_crop *d_crops, uint32_t n_crops,
+                    uint32_t w, uint32_t h, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                    const int32_t *d_frame_status, int32_t *d_crop_status, uint8_t *d_out,
+                    size_t out_pitch, size_t out_crop_stride, void *stream);
+
+/* The launch shape mh_decode_crops would use on `stream`'s device (no launch): workgroups per
+ * crop (G above) and waves per workgroup. For tests and tools. */
+int mh_decode_crops_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, uint32_t h,
+                          void *stream, uint32_t *groups_per_crop, uint32_t *waves_per_group);
 
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a

@@ -17,6 +17,8 @@ of mdejong/MetalHuffman).
                                     origin (random crops, a viewer's missing tiles, a moving box), one launch
   * decoder.decode_windows_scaled   the same list at 1/2, 1/4 or 1/8 scale (a viewer's missing tiles at a pyramid
                                     level, a thumbnail sheet, multi-scale crops), one launch
+  * decoder.decode_crops            a list of crops of one size at PIXEL origins, each stored from byte 0 of its
+                                    own slot (a dense [n, h, w] batch of random crops), one launch
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync;

@@ -45,6 +45,7 @@ EXPORTS = (
     "mh_decode_region_scaled", "mh_decode_region_scaled_shape", "mh_box_reduce",
     "mh_decode_windows", "mh_decode_windows_shape",
     "mh_decode_windows_scaled", "mh_decode_windows_scaled_shape",
+    "mh_decode_crops", "mh_decode_crops_shape",
     "mh_encode_frames_shared_workspace_bytes", "mh_encode_frames_shared_device_async",
     "mh_frame_histogram", "mh_encode_frame_with_header",
 )
@@ -86,6 +87,11 @@ class mh_region(ctypes.Structure):
 
 class mh_window(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_uint32), ("bx0", ctypes.c_uint32), ("by0", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class mh_crop(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
 
 
@@ -171,6 +177,11 @@ def lib() -> ctypes.CDLL:
                                                ctypes.c_size_t, ctypes.c_size_t, _vp]
         L.mh_decode_windows_scaled_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
                                                      ctypes.c_uint32, ctypes.c_uint32, _vp, _u32p, _u32p]
+        L.mh_decode_crops.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_size_t,
+                                      ctypes.c_size_t, _vp]
+        L.mh_decode_crops_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint32, _vp, _u32p, _u32p]
         L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
                                     ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]

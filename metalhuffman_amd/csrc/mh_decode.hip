@@ -295,6 +295,7 @@ using Lut13Flat = StepCfg<kLutBits, true, false, true>;
 typedef unsigned int v2u32_t __attribute__((ext_vector_type(2)));
 struct StoreRows {
   static constexpr int kLog2 = 0;
+  static constexpr bool kCrop = false;
   template <int kAux>
   __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t, uint32_t o0, uint32_t o1, uint32_t off,
                                       uint32_t, uint32_t) {
@@ -314,6 +315,7 @@ struct StoreRows {
 template <int kLog2_>
 struct BoxRows {
   static constexpr int kLog2 = kLog2_;
+  static constexpr bool kCrop = false;
   static_assert(kLog2 >= 1 && kLog2 <= 3, "cells of 2, 4 or 8 pixels");
   static constexpr uint32_t kZeroSel = 0x0C0C0C0Cu;  // v_perm_b32: every byte the constant 0
   uint32_t ch;          // in-frame rows of the tile's block row, 1..8 (wave-uniform)
@@ -366,6 +368,46 @@ struct BoxRows {
     else
       __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, out, off, 0, kAux);
     a0 = a1 = 0u;
+  }
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t r, v2u32_t v, uint32_t off, uint32_t rbase,
+                                      uint32_t pitch) {
+    row<kAux>(out, r, v.x, v.y, off, rbase, pitch);
+  }
+};
+
+// CropRows (mh_decode_crops): the row moved onto the crop's own byte grid. With dx = x0 & 7, output
+// word j of a crop row is bytes dx..7 of block j followed by bytes 0..dx-1 of block j + 1: bytes
+// dx..dx+7 of the 16 bytes [o0, o1, n0, n1], (n0, n1) the row of the lane to the right. The three
+// source words are (A, B, C) = (o0, o1, n0) for dx < 4 and (o1, n0, n1) for dx >= 4, and the output
+// is alignbyte(B, A, dx & 3), alignbyte(C, B, dx & 3). The choice is a bit select by a per-lane mask
+// `lo` (all ones: dx < 4), not a compare: a compare's result is an SGPR pair, live through the whole
+// chain, which has none to spare (BoxRows above). With X = lo ? o0 : o1 and Y = lo ? o1 : o0 the
+// neighbour's X and Y are C and, for dx >= 4, B: two DPP moves (wave_shl:1, lane i reads lane
+// i + 1; lane 63 reads 0), three v_bfi_b32 and two v_alignbyte_b32 per row, no LDS traffic. Every
+// lane runs every row in lock step (decode_block, flat8_block), so the neighbour's row is complete
+// when it is read; lane 63 of a tile never stores (out_tile), nor does the last lane of
+// decode_halves' first pass. dy and h are not here at all: they are in the tile's descriptor and
+// the lane's first offset (out_tile). One aligned 8-byte store per row, as StoreRows.
+struct CropRows {
+  static constexpr int kLog2 = 0;
+  static constexpr bool kCrop = true;
+  uint32_t lo;  // per lane, wave-uniform in value: ~0 for dx < 4, else 0
+  uint32_t k;   // per lane: dx & 3
+  static __device__ __forceinline__ uint32_t right(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
+  }
+  static __device__ __forceinline__ uint32_t pick(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t, uint32_t o0, uint32_t o1, uint32_t off,
+                                      uint32_t, uint32_t) {
+    const uint32_t X = pick(lo, o0, o1), Y = pick(lo, o1, o0);
+    const uint32_t nX = right(X), nY = right(Y);
+    const uint32_t B = pick(lo, Y, nY);
+    v2u32_t v;
+    v.x = __builtin_amdgcn_alignbyte(B, X, k);
+    v.y = __builtin_amdgcn_alignbyte(nX, B, k);
+    __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)off, 0, kAux);
   }
   template <int kAux>
   __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t r, v2u32_t v, uint32_t off, uint32_t rbase,
@@ -664,12 +706,21 @@ __device__ __forceinline__ uint32_t frame_of(const DecodeArgs &a, uint32_t tile)
 //   descriptor, and whose raster slot is the window's index `slot`, not the frame: `f` addresses
 //   what is read (offsets, codes, block_init), raster_slot() what is written. Its report() writes
 //   the window's status word (slice_decode calls every map's; the others report nothing).
+// CropMap (mh_decode_crops): a WindowMap at a pixel origin. Block row r of the crop is frame block
+//   row by0 + r, by0 = y0 >> 3; a tile is a run of <= 64 blocks that yields <= 63 output words (word
+//   j needs blocks j and j + 1), so tiles step by 63 blocks: tile (r, s) starts at block bx0 + 63 s,
+//   bx0 = x0 >> 3, and holds min(64, NB - 63 s) live blocks, NB = ceil((dx + w) / 8) the blocks a row
+//   of the crop touches (`bw`; x0 + w <= W keeps them inside the grid). `rem` packs what the output
+//   addressing needs: dx | dy << 4 | OW << 8, OW = ceil(w / 8) <= 8192.
 struct FrameMap {
   static constexpr bool kRegion = false;
+  static constexpr bool kCrop = false;
   __device__ __forceinline__ void report(uint32_t, uint32_t) const {}
 };
 struct RegionMap {
   static constexpr bool kRegion = true;
+  static constexpr bool kCrop = false;
+  static constexpr uint32_t kStep = 64u;  // blocks from one tile of a row to the next
   uint32_t f, bx0, by0, bw, S;
   // BoxRows only: the frame's pixels from the region's origin on, (W - 8 bx0) | (H - 8 by0) << 16
   // (both <= 65535) -- one SGPR for a tile's edge facts, where W, H and the origin would be four
@@ -685,6 +736,14 @@ struct WindowMap : RegionMap {
   __device__ __forceinline__ void report(uint32_t frame_status, uint32_t slice) const {
     if (wstatus && slice == 0 && threadIdx.x == 0) wstatus[slot] = (int32_t)frame_status;
   }
+};
+
+struct CropMap : WindowMap {
+  static constexpr bool kCrop = true;
+  static constexpr uint32_t kStep = 63u;
+  __device__ __forceinline__ uint32_t dx() const { return rem & 7u; }
+  __device__ __forceinline__ uint32_t dy() const { return (rem >> 4) & 7u; }
+  __device__ __forceinline__ uint32_t ow() const { return rem >> 8; }
 };
 
 struct TileHdrBase {
@@ -703,6 +762,8 @@ struct TileHdrOf<RegionMap> : TileHdrBase {
 };
 template <>
 struct TileHdrOf<WindowMap> : TileHdrOf<RegionMap> {};
+template <>
+struct TileHdrOf<CropMap> : TileHdrOf<RegionMap> {};
 using TileHdr = TileHdrOf<FrameMap>;
 
 // tile -> (r, s). One segment per row skips the division (a uniform branch), as frame_of does
@@ -729,7 +790,7 @@ __device__ __forceinline__ void hdr_issue(const DecodeArgs &a, uint32_t tile, ui
   if constexpr (Map::kRegion) {
     region_rs(m, tile, h.r, h.s);
     f = m.f;
-    b = (live ? (m.by0 + h.r) * a.bw + m.bx0 + 64u * h.s : 0u) + lane;
+    b = (live ? (m.by0 + h.r) * a.bw + m.bx0 + Map::kStep * h.s : 0u) + lane;
   } else {
     f = live ? frame_of(a, tile) : 0u;
     b = (live ? (tile - f * a.tiles_per_frame) * 64u : 0u) + lane;
@@ -771,6 +832,8 @@ struct TileOf<RegionMap> : TileBase {
 };
 template <>
 struct TileOf<WindowMap> : TileOf<RegionMap> {};
+template <>
+struct TileOf<CropMap> : TileOf<RegionMap> {};
 using Tile = TileOf<FrameMap>;
 
 template <class Map = FrameMap>
@@ -782,8 +845,8 @@ __device__ __forceinline__ TileOf<Map> hdr_resolve(const DecodeArgs &a, const Ti
     t.f = m.raster_slot();
     t.r = h.r;
     t.s = h.s;
-    t.n = min(64u, m.bw - 64u * h.s);
-    t.b0 = (m.by0 + h.r) * a.bw + m.bx0 + 64u * h.s;
+    t.n = min(64u, m.bw - Map::kStep * h.s);
+    t.b0 = (m.by0 + h.r) * a.bw + m.bx0 + Map::kStep * h.s;
   } else {
     t.f = frame_of(a, h.tile);
     t.b0 = (h.tile - t.f * a.tiles_per_frame) * 64u;
@@ -848,9 +911,30 @@ struct OutTile {
   uint32_t row0;
 };
 template <class Map = FrameMap, int kLog2 = 0>
-__device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane) {
+__device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
+                                            const Map &m = Map()) {
   static_assert(Map::kRegion || kLog2 == 0, "only a region is decoded at a reduced scale");
-  if constexpr (Map::kRegion) {
+  if constexpr (Map::kCrop) {
+    // Block row r holds crop rows 8 r - dy .. 8 r - dy + 7. The descriptor is based at the first of
+    // them that exists (crop row 0 for r = 0) and limited by h * pitch (a.out_frame_bytes), so rows
+    // >= h are dropped. The dy rows above the crop lie BELOW the base: the lane's first offset is
+    // 8 (word) - dy * pitch in 32-bit arithmetic, so those rows' offsets are "negative", above every
+    // descriptor's range (dy * pitch <= 7 * 2^20), and are dropped too; row dy lands on offset
+    // 8 (word). The sum is formed in a register, never in the instruction's offset fields.
+    // A lane stores word 63 s + lane while that is below OW and lane < 63; every other lane (the
+    // 64th block, blocks past the crop, lanes without a block) takes the dead offset.
+    const uint32_t dy = m.dy(), words = min(63u, m.ow() - 63u * t.s);
+    const uint32_t top = t.r ? 8u * t.r - dy : 0u;
+    const uint64_t base = (uint64_t)top * a.out_pitch;
+    const uint64_t rem = a.out_frame_bytes > base ? a.out_frame_bytes - base : 0u;
+    OutTile o;
+    o.rsrc = uniform_rsrc(a.out + (uint64_t)t.f * a.out_frame_stride + base,
+                          (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
+    const uint32_t above = t.r ? 0u : dy * (uint32_t)a.out_pitch;
+    o.row0 = lane < words ? (63u * t.s + lane) * 8u - above : 0x80000000u;
+    asm volatile("" : "+v"(o.row0));
+    return o;
+  } else if constexpr (Map::kRegion) {
     // based at region row 8 r of the raster slot t.f (the frame; a window's index) and limited by
     // RH * pitch (a.out_frame_bytes): rows >= RH are dropped.
     // At scale 2^kLog2 a block row is c = 8 >> kLog2 output rows of c bytes per block, and the
@@ -882,7 +966,14 @@ __device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Ma
 // one block row, so this is wave-uniform) and the lane's column selectors.
 template <class Out, class Map>
 __device__ __forceinline__ Out rows_of(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane, const Map &m) {
-  if constexpr (Out::kLog2 == 0) {
+  if constexpr (Out::kCrop) {
+    static_assert(Map::kCrop, "a crop's output stage takes a crop's map");
+    Out o;
+    o.lo = m.dx() < 4u ? ~0u : 0u;
+    o.k = m.dx() & 3u;
+    asm volatile("" : "+v"(o.lo), "+v"(o.k));  // per-lane registers: the chain has no SGPR for either
+    return o;
+  } else if constexpr (Out::kLog2 == 0) {
     return Out();
   } else {
     static_assert(Map::kRegion, "only a region is decoded at a reduced scale");
@@ -951,6 +1042,10 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 // Oversize tile: stage + decode lanes [0,32) then [32,64), each from its own span.
+// A crop's output stage reads the lane to the right, so its first pass is lanes [0,33): lane 32
+// decodes there for lane 31's sake alone (its own stores go to the dead offset) and again, for its
+// own word, in the second pass, where lane 33 runs beside it. 33 blocks are at most 33 x 128 B
+// plus the span's slack of under 64 B, inside the 4352-byte window.
 template <bool kDelta, class Cfg, class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
                                               const uint8_t *lut, uint8_t *stage,
@@ -961,6 +1056,7 @@ __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<
 #pragma unroll 1
   for (uint32_t h = 0; h < 2; ++h) {
     const uint32_t first = h * 32u;
+    const uint32_t lanes = 32u + ((Out::kCrop && h == 0u) ? 1u : 0u);
     const uint32_t sb = __builtin_amdgcn_readlane(my_off, first);
     // end of the half: start bit of lane first+32 (or the tile's last block end)
     uint32_t nblk;  // blocks in this tile (may be < 64)
@@ -970,8 +1066,8 @@ __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<
       nblk = a.nb - t.b0;
     if (first >= nblk) break;
     uint32_t eb;
-    if (first + 32u < nblk) {
-      eb = __builtin_amdgcn_readlane(my_off, first + 32u);
+    if (first + lanes < nblk) {
+      eb = __builtin_amdgcn_readlane(my_off, first + lanes);
     } else {
       eb = t.span_end_bits;
     }
@@ -989,10 +1085,11 @@ __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<
       *reinterpret_cast<v4u32 *>(stage + (Cfg::kSwz ? swz_off(c * 16u) : c * 16u)) = v;
     }
     wave_sync();
-    if (lane >= first && lane < first + 32u) {
+    if (lane >= first && lane < first + lanes) {
       LdsWords src{stage};
-      decode_block<kDelta, Cfg>(src, lut, t.valid ? my_off - start * 8u : 0u, t.init, out, row0,
-                                (uint32_t)a.out_pitch, dead MH_ROWS_NONE, sink);  // (a lane decodes in one half only)
+      const uint32_t r0 = (Out::kCrop && h == 0u && lane == 32u) ? 0x80000000u : row0;
+      decode_block<kDelta, Cfg>(src, lut, t.valid ? my_off - start * 8u : 0u, t.init, out, r0,
+                                (uint32_t)a.out_pitch, dead MH_ROWS_NONE, sink);  // (a lane stores in one half only)
     }
     wave_sync();
   }
@@ -1061,7 +1158,7 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     wave_sync();  // this tile's staging writes -> reads
     {
       const bool dead = !cur.valid;
-      const OutTile ot = out_tile<Map, Out::kLog2>(a, cur, lane);
+      const OutTile ot = out_tile<Map, Out::kLog2>(a, cur, lane, m);
       LdsWords src{stage};
       // waves with more tiles left run first (the arbiter otherwise favours the oldest)
       set_prio(min((a.total_tiles - 1u - cur.tile) / gstride, 3u));
@@ -1088,7 +1185,7 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     TileHdrOf<Map> h;
     hdr_issue(a, t, lane, h, m);
     const TileOf<Map> tt = hdr_resolve(a, h, lane, m);
-    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane);
+    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane, m);
     decode_halves<kDelta, Cfg, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid, rows_of<Out>(a, tt, lane, m));
   }
 }
@@ -1126,10 +1223,10 @@ __device__ __forceinline__ void flat8_issue(const DecodeArgs &a, const TileBase 
 
 template <bool kDelta, class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ void flat8_block(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
-                                            const Flat8Codes &c, Out sink = Out()) {
+                                            const Flat8Codes &c, Out sink = Out(), const Map &m = Map()) {
   typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
   const uint32_t sb = (t.start + (t.p >> 3)) & 3u;
-  const OutTile ot = out_tile<Map, Out::kLog2>(a, t, lane);
+  const OutTile ot = out_tile<Map, Out::kLog2>(a, t, lane, m);
   const uint32_t rbase = (t.valid && !MH_DIAG_DROP_STORES) ? ot.row0 : 0x80000000u;
   const uint32_t pitch = (uint32_t)a.out_pitch;
   uint32_t s = t.init;  // running delta sum (byte 0)
@@ -1180,7 +1277,7 @@ __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, u
     const TileOf<Map> nxt = hdr_resolve(a, h, lane, m);
     flat8_issue(a, nxt, cn);
     hdr_issue(a, next_tile(a, nxt.tile, gstride), lane, h, m);
-    flat8_block<kDelta, Map>(a, cur, lane, cc, rows_of<Out>(a, cur, lane, m));
+    flat8_block<kDelta, Map>(a, cur, lane, cc, rows_of<Out>(a, cur, lane, m), m);
 #if MH_DIAG_STAMPS
     if (first_tile) MH_STAMP(4);  // the first tile's codes landed and its stores issued
     first_tile = false;
@@ -1196,7 +1293,7 @@ __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, u
     TileHdrOf<Map> hs;
     hdr_issue(a, t, lane, hs, m);
     const TileOf<Map> tt = hdr_resolve(a, hs, lane, m);
-    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane);
+    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane, m);
     decode_halves<kDelta, Batch8, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid,
                                        rows_of<Out>(a, tt, lane, m));
   }
@@ -1335,6 +1432,7 @@ struct HeaderScratch {
   int32_t base[16];
   uint8_t sorted[256];
 };
+static_assert(33 * 128 + 64 <= kStageBytes, "decode_halves' 33-lane pass fits the staging window");
 static_assert(sizeof(HeaderScratch) <= kStageBytes, "the builder's scratch fits one staging window");
 
 struct HeaderFacts {
@@ -1484,8 +1582,8 @@ __device__ __forceinline__ HeaderFacts header_build(uint32_t L, uint16_t *lut, H
   return hf;
 }
 
-// ---- one frame slice per workgroup (mh_decode_frames / _headers / _region* / _windows*) --------
-// The batch kernel's machinery with another decomposition, shared by six entries:
+// ---- one frame slice per workgroup (mh_decode_frames / _headers / _region* / _windows* / _crops) --
+// The batch kernel's machinery with another decomposition, shared by seven entries:
 // workgroup g serves ONE frame, f = g / G, as slice j = g % G of it, so it brings frame f's
 // table into LDS once and never crosses a frame. Wave w decodes the frame's tiles j*8 + w,
 // stepping by 8*G: the persistent loops run on a workgroup-local DecodeArgs whose total_tiles
@@ -1506,6 +1604,8 @@ __device__ __forceinline__ HeaderFacts header_build(uint32_t L, uint16_t *lut, H
 //   WindowMap: a RegionMap per workgroup (mh_decode_windows): frame and origin from the window's
 //              descriptor, the raster slot the window's index; behind the status load it writes the
 //              window's status word (the frame's), so a skipped frame's windows carry it.
+//   CropMap:   a WindowMap at a pixel origin (mh_decode_crops): tiles step by 63 blocks, and the
+//              output stage (CropRows) moves every row onto the crop's byte grid.
 // And where the 13-bit table comes from (a table source: `lut_of`, `issue`, `into_lds`):
 //   PreparedTable: frame f's prepared table at luts + f * stride (stride 0: one table for all
 //              frames), copied by four 16-byte loads per thread.
@@ -1624,7 +1724,7 @@ __device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_
     batch_loop<kDelta, Lut13, Map, Out>(a, lane, stage, lut, t0, gstride, hc, true MH_TS_ARG, m);
 }
 
-// The six kernels (ten with the scales, each in a raw and a delta instantiation: the rows of
+// The seven kernels (eleven with the scales, each in a raw and a delta instantiation: the rows of
 // kSliceTable): names, launch bounds and argument order are the ABI of the launchers, the ISA
 // guard and the diagnostic scripts; the leading 16 arguments are preloaded into SGPRs.
 template <bool kDelta>
@@ -1720,6 +1820,41 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
       aw, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
       PreparedTable{p_luts, p_lut_stride},
       WindowMap{{f, bx0, by0, p_rbw, p_segs, (a0.w - 8u * bx0) | ((a0.h - 8u * by0) << 16)}, p, p_wstatus});
+}
+
+// mh_decode_crops: workgroup g serves crop g / G, a w x h rectangle at a PIXEL origin read from the
+// crop's 16-byte descriptor, as the windows kernel reads a window's. The same verdict ahead of
+// everything: the origin is compared with the last one that fits, p_max_x0 = W - w and p_max_y0 =
+// H - h from the host, so no sum of descriptor values is formed. Behind it the crop's own geometry:
+// the blocks a row touches (NB), the block rows it touches -- (dy + h + 7) >> 3 of them, at most the
+// CBH the grid was sized for, so this workgroup's tiles end with its last needed block row and a
+// row the crop does not reach (which may lie outside the frame) is never addressed -- and the
+// packed (dx, dy, OW) of the output stage. a0.out_frame_bytes is h * pitch, every crop's row limit;
+// a0.out_frame_stride is the crop stride.
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_crops_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const mh_crop *p_crops, uint32_t p_nb, uint32_t p_tiles_per_crop, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0, uint32_t p_max_y0,
+    uint64_t p_lut_stride, int32_t *p_cstatus, const DecodeArgs a0) {
+  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
+  const v4u32 cd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_crops + p, 16u), 0, 0, 0);
+  const uint32_t f = __builtin_amdgcn_readfirstlane(cd.x), x0 = __builtin_amdgcn_readfirstlane(cd.y);
+  const uint32_t y0 = __builtin_amdgcn_readfirstlane(cd.z), reserved = __builtin_amdgcn_readfirstlane(cd.w);
+  if ((f >= p_nframes) | (x0 > p_max_x0) | (y0 > p_max_y0) | (reserved != 0u)) {  // workgroup-uniform
+    if (p_cstatus && slice == 0 && threadIdx.x == 0) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  (void)p_tiles_per_crop;  // the grid's worst case, CBH * S; this crop's own count follows
+  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
+  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
+  // as the scaled windows: the slot is folded into the raster's base, so `p` lives no longer than report()
+  DecodeArgs ac = a0;
+  ac.out = a0.out + (uint64_t)p * a0.out_frame_stride;
+  ac.out_frame_stride = 0;
+  slice_decode<kDelta, CropRows>(ac, p_offsets, p_frame_off, p_block_init, p_status, p_nb, rows * p_segs, p_groups, f,
+                                 slice, PreparedTable{p_luts, p_lut_stride},
+                                 CropMap{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, dx | (dy << 4) | (ow << 8)}, p, p_cstatus}});
 }
 
 template <bool kDelta>
@@ -2329,14 +2464,15 @@ __global__ void __launch_bounds__(64 * kLpWaves) mh_decode_lanepair_kernel(const
 constexpr int kMaxDevices = 64;
 // The kernels that decode one frame slice per workgroup (slice_decode): a SliceKernel is a row of
 // kSliceTable, its family's first row + log2_scale (the region and the windows kernels exist at
-// scale 2^0..2^3; scale 0 is the unscaled kernel).
+// scale 2^0..2^3; scale 0 is the unscaled kernel; the crops kernel at scale 0 only).
 constexpr int kSliceScales = 4;
 enum SliceKernel {
   kSliceFrames,
   kSliceHeaders,
   kSliceRegion,
   kSliceWindows = kSliceRegion + kSliceScales,
-  kSliceKernels = kSliceWindows + kSliceScales
+  kSliceCrops = kSliceWindows + kSliceScales,  // one scale only
+  kSliceKernels
 };
 #if !MH_LANE_PAIRS
 // One row per kernel, [kDelta]: the row device_info() queries the occupancy of is the row
@@ -2346,6 +2482,7 @@ using FramesFn = decltype(&mh_decode_multitable_kernel<false>);
 using HeadersFn = decltype(&mh_decode_headers_kernel<false>);
 using RegionFn = decltype(&mh_decode_region_kernel<false>);    // = mh_decode_region_scaled_kernel<_, 1..3>
 using WindowsFn = decltype(&mh_decode_windows_kernel<false>);  // = mh_decode_windows_scaled_kernel<_, 1..3>
+using CropsFn = decltype(&mh_decode_crops_kernel<false>);
 using AnyKernel = void (*)();
 struct SliceRow {
   AnyKernel fn[2];
@@ -2365,6 +2502,7 @@ const SliceRow kSliceTable[] = {
     slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 1>, mh_decode_windows_scaled_kernel<true, 1>),
     slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 2>, mh_decode_windows_scaled_kernel<true, 2>),
     slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 3>, mh_decode_windows_scaled_kernel<true, 3>),
+    slice_row<CropsFn>(mh_decode_crops_kernel<false>, mh_decode_crops_kernel<true>),
 };
 static_assert(sizeof(kSliceTable) / sizeof(kSliceTable[0]) == kSliceKernels, "one row per SliceKernel");
 #endif
@@ -2510,6 +2648,19 @@ bool region_extent(const mh_dims &d, const mh_region *rg, RegionExtent &e) {
   return true;
 }
 
+// A crop's: pixel size w x h (rg->bw x rg->bh, in PIXELS), OW = ceil(w / 8) output words per row, 63
+// of them per tile (word j needs blocks j and j + 1 of a wave's 64), S = ceil(OW / 63) tiles per
+// block row, and CBH = (h + 14) / 8 block rows, the most any y0 & 7 needs.
+// false: the size is empty or exceeds the frame.
+bool crop_extent(const mh_dims &d, const mh_region *rg, RegionExtent &e) {
+  if (!rg->bw || !rg->bh || rg->bw > d.width || rg->bh > d.height) return false;
+  e.pw = rg->bw;
+  e.ph = rg->bh;
+  e.segs = ((rg->bw + 7u) / 8u + 62u) / 63u;
+  e.tiles = ((rg->bh + 14u) / 8u) * e.segs;
+  return true;
+}
+
 // One decode call, as every entry point describes it to the helpers below: where its Huffman tables
 // come from (and so which table rules it checks), which part of the frames it decodes at which scale
 // and, once call_geometry() has passed, the rasters and tiles that makes.
@@ -2522,6 +2673,8 @@ struct DecodeCall {
                 // is one table for all frames
     kWindows,   // mh_decode_windows[_scaled]: kRegion with rg = {0, 0, bw, bh}, the windows' size, and
                 // n_windows rasters, described by the device array `windows`
+    kCrops,     // mh_decode_crops: kWindows with rg = {0, 0, w, h} in PIXELS, the crops' size, and the
+                // descriptors' origins in pixels (scale 0 only)
   } kind;
   const void *ptr = nullptr;
   uint64_t stride = 0;
@@ -2534,8 +2687,8 @@ struct DecodeCall {
   // number of rasters, which is the number of units the grid is cut into
   RegionExtent re = {};
   uint32_t n_units = 0;
-  bool windowed() const { return kind == kWindows; }
-  bool regional() const { return kind == kRegion || kind == kWindows; }
+  bool windowed() const { return kind == kWindows || kind == kCrops; }
+  bool regional() const { return kind == kRegion || windowed(); }
 };
 
 // The rules that the decode entries and the *_shape entries share, in their one order: flags, the
@@ -2552,6 +2705,7 @@ int call_geometry(const mh_frame *fr, DecodeCall &c) {
     c.re = {d.width, d.height, 0u, (d.block_width * d.block_height + 63) / 64};
     return MH_OK;
   }
+  if (c.kind == DecodeCall::kCrops) return crop_extent(d, c.rg, c.re) ? MH_OK : MH_ERR_DIMS;
   if (!region_extent(d, c.rg, c.re)) return MH_ERR_DIMS;
   if (c.windowed()) {
     c.re.pw = 8ull * c.rg->bw;
@@ -2891,6 +3045,31 @@ int mh_decode_windows_scaled_shape(const mh_frame *fr, uint32_t n_windows, uint3
 int mh_decode_windows_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh, void *stream,
                             uint32_t *groups_per_window, uint32_t *waves_per_group) {
   return mh_decode_windows_scaled_shape(fr, n_windows, bw, bh, 0, stream, groups_per_window, waves_per_group);
+}
+
+// A list of crops of one pixel size, each with its own frame and PIXEL origin: the windows kernel's
+// body with a crop's map and output stage (CropMap, CropRows). The checks are the windows', with
+// n_crops rasters of w x h: a pitch that is a multiple of 8 and >= w holds the round_up(w, 8) bytes
+// a row is written with.
+int mh_decode_crops(const mh_frame *fr, const mh_crop *d_crops, uint32_t n_crops, uint32_t w, uint32_t h,
+                    const uint16_t *d_luts, uint64_t lut_stride_bytes, const int32_t *d_frame_status,
+                    int32_t *d_crop_status, uint8_t *d_out, size_t out_pitch, size_t out_crop_stride, void *stream) {
+  if (d_crop_status && d_crop_status == d_frame_status) return MH_ERR_INVALID_ARG;
+  const mh_region size = {0u, 0u, w, h};
+  DecodeCall c{DecodeCall::kCrops, d_luts, lut_stride_bytes, &size, 0u, d_crops, n_crops};
+  SliceArgs p;
+  const int rc = slice_prologue(fr, d_out, out_pitch, out_crop_stride, c, p);
+  if (rc != MH_OK) return rc;
+  return launch_slices<CropsFn>(kSliceCrops, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts), d_frame_status,
+                                d_crops, c.re.segs, w, h, fr->n_frames, fr->dims.width - w, fr->dims.height - h,
+                                lut_stride_bytes, d_crop_status);
+}
+
+int mh_decode_crops_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h, void *stream,
+                          uint32_t *groups_per_crop, uint32_t *waves_per_group) {
+  const mh_region size = {0u, 0u, w, h};
+  return slice_shape_entry(kSliceCrops, fr, {DecodeCall::kCrops, nullptr, 0, &size, 0u, nullptr, n_crops}, stream,
+                           groups_per_crop, waves_per_group);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

@@ -716,6 +716,102 @@ def decode_windows_scaled(frames: DeviceFrames, tables, windows, size, log2_scal
                            extra_flags, skip_rejected)
 
 
+def _crop_size(frames: DeviceFrames, size) -> tuple:
+    w, h = (int(v) for v in size)
+    if w < 1 or h < 1 or w > frames.width or h > frames.height:
+        raise ValueError(f"a crop of {w}x{h} pixels does not fit the {frames.width}x{frames.height} frame")
+    return w, h
+
+
+def _host_crops(frames: DeviceFrames, crops, w: int, h: int):
+    """decode_crops' `crops` checked on the host, as _host_windows checks windows: a device tensor's
+    type and shape only -> None; a host sequence against the frames (ValueError) -> its int32 [n, 4]
+    descriptor array."""
+    if isinstance(crops, torch.Tensor) and crops.is_cuda:
+        dev = frames.codes.device
+        if (crops.device != dev or crops.dtype is not torch.int32 or crops.dim() != 2
+                or crops.shape[1] not in (3, 4) or crops.shape[0] < 1):
+            raise ValueError(f"a device crops tensor is int32 [n, 3] or [n, 4] on {dev}")
+        return None
+    c = np.asarray(crops.numpy() if isinstance(crops, torch.Tensor) else crops)
+    if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] < 1 or c.dtype.kind not in "iu":
+        raise ValueError("crops is a sequence of (frame, x0, y0) integers")
+    c = c.astype(np.int64)
+    bad = ((c < 0).any(axis=1) | (c[:, 0] >= frames.n_frames) | (c[:, 1] + w > frames.width)
+           | (c[:, 2] + h > frames.height))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"crop {i} = {tuple(int(v) for v in c[i])} of {w}x{h} pixels lies outside the "
+                         f"{frames.n_frames} frames of {frames.width}x{frames.height}")
+    full = np.zeros((c.shape[0], 4), np.int32)
+    full[:, :3] = c
+    return full
+
+
+def decode_crops_shape(frames: DeviceFrames, n_crops: int, size,
+                       stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
+    """(workgroups per crop, waves per workgroup) decode_crops would launch n_crops crops of
+    size = (w, h) pixels with (mh_decode_crops_shape)."""
+    w, h = _crop_size(frames, size)
+    if int(n_crops) < 1:
+        raise ValueError("no crops")
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    g, wv = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    N.check(N.lib().mh_decode_crops_shape(ctypes.byref(fr), int(n_crops), w, h, _raw_stream_ptr(stream, dev_index),
+                                          ctypes.byref(g), ctypes.byref(wv)), "mh_decode_crops_shape")
+    return int(g.value), int(wv.value)
+
+
+def decode_crops(frames: DeviceFrames, tables, crops, size, out: Optional[torch.Tensor] = None,
+                 status=None, stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                 skip_rejected: bool = True):
+    """Decode a list of crops of one size = (w, h) in PIXELS, crop p the pixels [x0, x0 + w) x
+    [y0, y0 + h) of frame `frame`, into out[n_crops, h, round_up(w, 8)] in one launch
+    (mh_decode_crops): every crop starts at byte 0 of its own slot, whatever its origin's offset in
+    the 8x8 block grid, so out[:, :, :w] is the batch -- dense when w is a multiple of 8. The decoder
+    shifts each row in registers as it stores it; no larger raster and no gather pass exist. A crop
+    lies wholly inside the frame (no clipping); crops may overlap, repeat and name frames in any order.
+    crops: an int32 tensor [n, 3] or [n, 4] of (frame, x0, y0[, 0]) on the frames' device -- used as it
+    is when [n, 4], contiguous and 16-byte aligned, never read on the host (no sync): the kernel
+    validates every crop and rejects, with status MH_ERR_DIMS and an untouched slot, one that names
+    no frame or leaves the frame -- or a host sequence / array of (frame, x0, y0), validated here
+    (ValueError) and uploaded.
+    out: a contiguous uint8 [n, h, round_up(w, 8)] tensor on the frames' device; None allocates a
+    ZERO-FILLED one (a rejected or skipped crop's slot is never written). Columns >= w of a written
+    row are unspecified.
+    status, tables, extra_flags, skip_rejected: decode_windows'."""
+    who = "decode_crops"
+    w, h = _crop_size(frames, size)
+    host = _host_crops(frames, crops, w, h)
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
+    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
+    dev = frames.codes.device
+    pitch = (w + 7) // 8 * 8
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        desc = _windows_tensor(frames, crops, host)  # (an upload or a padded copy belongs to `stream`)
+        n = int(desc.shape[0])
+        shape = (n, h, pitch)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.uint8, device=dev)
+        cstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
+    if (out.dtype is not torch.uint8 or tuple(out.shape) != shape or out.get_device() != dev_index
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on cuda:{dev_index}")
+    if cstatus is not None and (not isinstance(cstatus, torch.Tensor) or cstatus.dtype is not torch.int32
+                                or cstatus.numel() != n or cstatus.get_device() != dev_index
+                                or not cstatus.is_contiguous()):
+        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
+    rc = N.lib().mh_decode_crops(ctypes.byref(fr), desc.data_ptr(), n, w, h, luts.data_ptr(), stride,
+                                 fstatus.data_ptr() if fstatus is not None else None,
+                                 cstatus.data_ptr() if cstatus is not None else None, out.data_ptr(), pitch,
+                                 h * pitch, _raw_stream_ptr(stream, dev_index))
+    if rc:
+        N.check(rc, "mh_decode_crops")
+    return (out, cstatus) if status is True else out
+
+
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
                          extra_flags: int = 0) -> tuple:
     """(workgroups per frame, waves per workgroup) decode_headers would launch with
