@@ -7,8 +7,10 @@ there, always inside real allocations (no test declares a byte that is not alloc
 
 A. Block offsets high inside a frame (helpers.place_stream): `mid` straddles 2^31 inside tile 0,
    `top` puts the last block above 2^32 - 1024 (helpers.lead_top). 96x56 frames (84 blocks: tile 0
-   full, tile 1 partial) of every step flavour through every decode entry and mh_check, and one
-   8192x8192 frame under `top` through the pipelined loops.
+   full, tile 1 partial) of every step flavour through every decode entry and mh_check -- the
+   entries that decode a part of each frame included: a region, windows and crops that hold the
+   frame's last block, at full scale and reduced (SLICE_ROUTES) -- and one 8192x8192 frame under
+   `top` through the pipelined loops.
 B. Where frames lie and how big their slots are: a batch that starts at byte 4096, a batch beyond
    4 GiB, one frame declared with 0x20000000 / 0xFFFFFFE0 / 0xFFFFFFF0 bytes (0xFFFFFFF1 is
    refused), a batch whose slots exceed 4 GiB.
@@ -228,6 +230,81 @@ def _expect(out, wants, what):
 
 ROUTES3 = ("small", "inkernel", "frames", "headers", "check")
 ROUTES1 = ("frame", "inkernel", "frames", "headers", "check")
+# the entries that decode a part of each frame (slice_decode's region, windows and crop tiles); the
+# region, the first window and the first crop all hold the frame's last block, whose end bit wraps
+# under `top`
+SLICE_ROUTES = ("region", "region_scaled", "windows", "windows_scaled", "crops")
+SLICE_REGION = (1, 1, 11, 6)
+SLICE_WINDOWS = ((10, 3), ((2, 4), (0, 0)))
+SLICE_CROPS = ((83, 21), ((13, 35), (3, 2)))
+SLICE_K = {"region_scaled": 1, "windows_scaled": 2}
+
+
+def _slice_route(device, route, fr, canon, wants, what):
+    """One launch of a part-of-frame entry over `fr` into 0xA5-filled rasters, every pixel compared
+    with the slice of `wants` (box-reduced at a scale, zeros beyond the picture). The region routes
+    take one shared table and the rest a table per frame, so hdr_resolve sees both."""
+    import torch
+    from metalhuffman_amd import decoder as D
+    from scaled_helpers import box_reduce_np
+    n, k = fr.n_frames, SLICE_K.get(route, 0)
+    c = 8 >> k
+    assert SLICE_REGION[0] + SLICE_REGION[2] == W // 8 and SLICE_REGION[1] + SLICE_REGION[3] == H // 8
+    assert SLICE_WINDOWS[1][0][0] + 10 == W // 8 and SLICE_WINDOWS[1][0][1] + 3 == H // 8
+    assert SLICE_CROPS[1][0][0] + 83 == W and SLICE_CROPS[1][0][1] + 21 == H
+    if route in ("region", "region_scaled"):
+        tabs = D.DeviceTables.from_canonical_header(np.array(canon, np.uint8), device)   # (canon is read-only)
+        assert tabs.check_status() >= 0 and tabs.lut is not None
+        ts = None
+    else:
+        tabs = ts = D.DeviceTableSet.from_canonical_headers(np.stack([canon] * n), device)
+
+    def full(slots, rows, cols):
+        return torch.full((slots, rows, cols), 0xA5, dtype=torch.uint8, device=device)
+
+    if route in ("region", "region_scaled"):
+        bx0, by0, bw, bh = SLICE_REGION
+        rects = [(f, 8 * bx0, 8 * by0, 8 * bw, 8 * bh) for f in range(n)]
+        out = full(n, bh * c, bw * c)
+        if k:
+            assert D.decode_region_scaled(fr, tabs, D.Region(*SLICE_REGION), k, out=out) is out
+        else:
+            assert D.decode_region(fr, tabs, D.Region(*SLICE_REGION), out=out) is out
+    elif route in ("windows", "windows_scaled"):
+        (bw, bh), origins = SLICE_WINDOWS
+        wins = [(f, bx0, by0) for f in range(n) for bx0, by0 in origins]
+        rects = [(f, 8 * bx0, 8 * by0, 8 * bw, 8 * bh) for f, bx0, by0 in wins]
+        out = full(len(wins), bh * c, bw * c)
+        if k:
+            got, st = D.decode_windows_scaled(fr, tabs, wins, (bw, bh), k, out=out, status=True)
+        else:
+            got, st = D.decode_windows(fr, tabs, wins, (bw, bh), out=out, status=True)
+        assert got is out
+    elif route == "crops":
+        (w, h), origins = SLICE_CROPS
+        crops = [(f, x0, y0) for f in range(n) for x0, y0 in origins]
+        rects = [(f, x0, y0, w, h) for f, x0, y0 in crops]
+        out = full(len(crops), h, (w + 7) // 8 * 8)
+        got, st = D.decode_crops(fr, tabs, crops, (w, h), out=out, status=True)
+        assert got is out
+    else:
+        raise KeyError(route)
+    torch.cuda.synchronize(device)
+    if ts is not None:
+        assert not ts.status.any().item() and not st.any().item(), what
+    got = out.cpu().numpy()
+    for p, (f, x0, y0, w, h) in enumerate(rects):
+        want = np.ascontiguousarray(wants[f][y0: y0 + h, x0: x0 + w])
+        if k:
+            want = box_reduce_np(want, k)
+        sh, sw = want.shape
+        if not np.array_equal(got[p, :sh, :sw], want):
+            ys, xs = np.nonzero(got[p, :sh, :sw] != want)
+            raise AssertionError(f"{what}: raster {p} (frame {f}, {w} x {h} at ({x0}, {y0}), k {k}): {ys.size} wrong "
+                                 f"pixel(s), first at row {int(ys[0])}, column {int(xs[0])}: "
+                                 f"{int(got[p, ys[0], xs[0]]):#04x}, expected {int(want[ys[0], xs[0]]):#04x}")
+        if k:
+            assert not got[p, :sh, sw:].any(), f"{what}: raster {p}: columns beyond the picture are not 0"
 
 
 def _route(mh, oracle, device, cus, route, fr, canon, wants, what):
@@ -238,6 +315,8 @@ def _route(mh, oracle, device, cus, route, fr, canon, wants, what):
     n = fr.n_frames
     tiles = -(-NB // 64) * n
     what = f"{what}, {route}"
+    if route in SLICE_ROUTES:
+        return _slice_route(device, route, fr, canon, wants, what)
     out = torch.full((n, H, W), 0xA5, dtype=torch.uint8, device=device)
     if route in ("frame", "small", "large", "inkernel", "check"):
         t1, t2 = mh.Huffman.generateSplitLookupTables(canon)
@@ -277,12 +356,12 @@ def _route(mh, oracle, device, cus, route, fr, canon, wants, what):
 def test_one_placed_frame(mh, oracle, device, cus, bigbridge, case, placement):
     """One frame, its codes at the end of a buffer of 256 / 512 MiB: mh_decode with a prepared table
     (mh_decode_frame_kernel) and without (mh_decode_kernel, one frame), mh_decode_frames and
-    mh_decode_headers with n = 1, mh_check."""
+    mh_decode_headers with n = 1, mh_check, and the part-of-frame entries (SLICE_ROUTES)."""
     canon, frames, lead = _placed(mh, oracle, bigbridge, case, placement)
     _need(device, lead)
     fr = _pack(device, [(frames[1][0], lead)])
     assert fr.codes.numel() == lead + frames[1][0].codes.size and fr.frame_code_offsets is None
-    for route in ROUTES1:
+    for route in ROUTES1 + SLICE_ROUTES:
         _route(mh, oracle, device, cus, route, fr, canon, [frames[1][1]], f"{case[0]} {placement}")
     del fr
 
@@ -291,11 +370,11 @@ def test_one_placed_frame(mh, oracle, device, cus, bigbridge, case, placement):
 def test_three_frames_the_middle_one_placed(mh, oracle, device, cus, bigbridge, case, placement):
     """Three frames with an offset array, frame 1 the placed one, frames 0 and 2 ordinary:
     mh_decode_small_kernel, mh_decode_kernel with its own table, mh_decode_frames,
-    mh_decode_headers, mh_check."""
+    mh_decode_headers, mh_check, and the part-of-frame entries (SLICE_ROUTES)."""
     canon, frames, lead = _placed(mh, oracle, bigbridge, case, placement)
     _need(device, lead)
     fr = _pack(device, [(frames[0][0], 0), (frames[1][0], lead), (frames[2][0], 0)])
-    for route in ROUTES3:
+    for route in ROUTES3 + SLICE_ROUTES:
         _route(mh, oracle, device, cus, route, fr, canon, [f[1] for f in frames], f"{case[0]} {placement}")
     del fr
 
