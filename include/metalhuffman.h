@@ -536,7 +536,16 @@ size_t mh_encode_workspace_bytes(uint32_t width, uint32_t height);
  * MH_ENCODE_LIMIT_LENGTHS is set: then the tree workgroup limits the lengths) or
  * MH_ERR_CAPACITY (round_up(codes_len, 4) > codes_cap, or >= 2^32 code bits);
  * on an error no code bytes or offsets are written, *d_codes_len is 0 and the
- * header's content is unspecified.
+ * header's content is unspecified; d_block_init is then UNSPECIFIED too (the split
+ * writes it before the verdict exists: the tests see it written).
+ * What is written of d_codes: bytes [0, round_up(codes_len, 4)) and nothing behind
+ * them, whatever codes_cap -- the last code word is stored whole, so the up to three
+ * bytes [codes_len, round_up(codes_len, 4)) are written, as zero in every encoder
+ * here (tests/encode_helpers.py checks the bytes behind them, not their value).
+ * codes_cap counts as it stands: one that is no multiple of 4 and lies below
+ * round_up(codes_len, 4) is MH_ERR_CAPACITY even where codes_len itself would fit.
+ * d_gray needs no alignment (8-byte aligned frames of W % 8 == 0 take wider loads);
+ * d_canon_header and d_block_init none, d_block_offsets and d_status 4, d_codes_len 8.
  * d_workspace: 256-byte aligned, mh_encode_workspace_bytes(). The return value
  * covers only argument checks and launch errors. A frame encoded this way goes to
  * mh_build_tables_device (the header) and mh_decode without touching the host.
@@ -587,7 +596,14 @@ size_t mh_encode_frames_workspace_bytes(uint32_t width, uint32_t height, uint32_
  * mh_frame batch: for mh_decode_frames with one table per frame (mh_build_luts_device over
  * d_canon_headers; d_status goes in as d_frame_status), or for mh_decode when all frames
  * happen to share one canonical table (block shuffles of one image). A rejected frame writes
- * no codes or offsets and does not affect the others. d_workspace: 256-byte aligned,
+ * no codes or offsets and does not affect the others; its d_block_init slice is UNSPECIFIED
+ * (written by the split before the verdict exists). Of an accepted frame's slot the bytes
+ * [0, round_up(codes_len, 4)) are written ([codes_len, ..) as zero) and nothing behind them, so
+ * a slot of exactly round_up(codes_len, 4) rounded up to 16 bytes lies flush against the next.
+ * gray_frame_stride: any value >= W * H (padding between frames is never read), and any value
+ * at all for n_frames == 1; below W * H with n_frames > 1 -> MH_ERR_CAPACITY before any launch.
+ * d_gray and the stride need no alignment (frames that are all 8-byte aligned, with W % 8 == 0,
+ * take 8-byte loads, and 16-byte ones for an even width in blocks). d_workspace: 256-byte aligned,
  * mh_encode_frames_workspace_bytes(), any content (every part is written before it
  * is read within the call; MH_ENCODE_WORKSPACE_ZEROED is accepted and changes nothing).
  * Asynchronous on `stream`; the return value covers argument checks and launches. */
