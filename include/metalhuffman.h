@@ -690,7 +690,17 @@ typedef struct mh_stream mh_stream;
  * codes_capacity code bytes each, one HIP stream per slot (its copies, then its
  * decode), and one captured decode graph per slot. Slot i decodes into d_outputs[i] (caller
  * device buffers of round_up(W, 8) * H bytes, 8-byte aligned) or, when
- * d_outputs is NULL, into rasters the stream allocates. */
+ * d_outputs is NULL, into rasters the stream allocates.
+ * proto->flags: MH_FLAG_NO_DELTA only; any other bit -> MH_ERR_INVALID_ARG with the other
+ * argument checks, before any HIP call (mh_stream_create_headers and, through its members,
+ * mh_stream_group_create alike). MH_FLAG_ANY_ORDER in particular is refused: the stream itself
+ * queues the H2D copy that writes a slot's inputs ahead of the slot's decode, so that decode
+ * must keep its dispatch barrier.
+ * codes_capacity need not be a multiple of 16: a slot holds round_up(codes_capacity, 16) code
+ * bytes, and a submit is accepted up to that many (MH_CODES_PAD <= codes_bytes <=
+ * round_up(codes_capacity, 16)); a refused submit does not advance the slot rotation.
+ * Creation runs one warm-up decode per slot over zeroed slot buffers, so it does store into
+ * the rasters (d_outputs included), and only inside their round_up(W, 8) * H bytes. */
 int mh_stream_create(const mh_frame *proto, uint64_t codes_capacity, uint32_t n_slots,
                      uint8_t *const *d_outputs, mh_stream **out);
 /* Queue one frame: H2D copy of its host buffers (pinned memory for a DMA) into
@@ -719,8 +729,9 @@ int mh_stream_synchronize(mh_stream *s);
 int mh_stream_destroy(mh_stream *s);
 
 /* The stream in table-per-frame mode: every frame brings its own 256-byte canonical header
- * (what mh_encode_frame and the GPU encoders write per frame). proto: dims, flags and whether
- * frames carry init bytes, as mh_stream_create; its table fields are ignored and may be NULL.
+ * (what mh_encode_frame and the GPU encoders write per frame). proto: dims, flags
+ * (MH_FLAG_NO_DELTA only) and whether frames carry init bytes, and codes_capacity, as
+ * mh_stream_create; its table fields are ignored and may be NULL.
  * A slot is one allocation [status, 16 B][header, 256 B][block offsets, padded to 16 B][codes]
  * and its decode is one mh_decode_headers launch (n_frames = 1) that writes the header's
  * verdict into the slot's status word -- launched directly by default (it measured faster than

@@ -60,6 +60,9 @@ int mh_stream_create(const mh_frame *proto, uint64_t codes_capacity, uint32_t n_
   if (!proto || !out || !proto->d_table1 || !proto->d_table2 || n_slots < 1 || n_slots > 64 ||
       codes_capacity < MH_CODES_PAD)
     return MH_ERR_INVALID_ARG;
+  // MH_FLAG_NO_DELTA only: MH_FLAG_ANY_ORDER would launch a slot's decode without the barrier
+  // behind the slot's own H2D copy
+  if (proto->flags & ~MH_FLAG_NO_DELTA) return MH_ERR_INVALID_ARG;
   const mh_dims &d = proto->dims;
   if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
       d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)

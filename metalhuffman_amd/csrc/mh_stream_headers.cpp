@@ -41,6 +41,7 @@ extern "C" {
 int mh_stream_create_headers(const mh_frame *proto, uint64_t codes_capacity, uint32_t n_slots,
                              uint8_t *const *d_outputs, mh_stream **out) {
   if (!proto || !out || n_slots < 1 || n_slots > 64 || codes_capacity < MH_CODES_PAD) return MH_ERR_INVALID_ARG;
+  if (proto->flags & ~MH_FLAG_NO_DELTA) return MH_ERR_INVALID_ARG;  // as mh_stream_create
   const mh_dims &d = proto->dims;
   if (!d.width || !d.height || d.width > MH_MAX_DIM || d.height > MH_MAX_DIM ||
       d.block_width != (d.width + 7) / 8 || d.block_height != (d.height + 7) / 8)

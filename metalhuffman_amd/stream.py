@@ -136,12 +136,14 @@ class FrameStreamGroup:
     per member, each resident on that member's device (a device may repeat)."""
 
     def __init__(self, tables, width: int, height: int, codes_capacity: int, slots: int = 2,
-                 flags: int = 0):
+                 flags: int = 0, block_init: bool = False):
         self.width, self.height = width, height
         self.pitch = (width + 7) // 8 * 8
         n = len(tables)
         protos = (N.mh_frame * n)()
         devs = (ctypes.c_int * n)()
+        # frames carry per-block init bytes: only "non-NULL" is read from the prototype
+        self._init_dummy = (ctypes.c_uint8 * 8)() if block_init else None
         for i, t in enumerate(tables):
             p = protos[i]
             p.d_table1 = t.table1.data_ptr()
@@ -151,6 +153,7 @@ class FrameStreamGroup:
             p.dims = N.mh_dims(width, height, (width + 7) // 8, (height + 7) // 8)
             p.n_frames = 1
             p.flags = flags
+            p.d_block_init = ctypes.addressof(self._init_dummy) if block_init else None
             devs[i] = t.table1.device.index or 0
         self.devices = [int(d) for d in devs]
         self._tables = list(tables)
@@ -159,11 +162,14 @@ class FrameStreamGroup:
                                                ctypes.byref(self._h)), "mh_stream_group_create")
         self.size = int(N.lib().mh_stream_group_size(self._h))
 
-    def submit(self, codes: torch.Tensor, offsets: torch.Tensor) -> tuple[int, int]:
-        """Queue one frame from pinned host tensors -> (member, slot)."""
+    def submit(self, codes: torch.Tensor, offsets: torch.Tensor,
+               init: Optional[torch.Tensor] = None) -> tuple[int, int]:
+        """Queue one frame from pinned host tensors -> (member, slot). init: u8[NB], given iff the
+        group was created with block_init."""
         m, slot = ctypes.c_uint32(0), ctypes.c_uint32(0)
         N.check(N.lib().mh_stream_group_submit(self._h, codes.data_ptr(), codes.numel(), offsets.data_ptr(),
-                                               None, ctypes.byref(m), ctypes.byref(slot)),
+                                               init.data_ptr() if init is not None else None,
+                                               ctypes.byref(m), ctypes.byref(slot)),
                 "mh_stream_group_submit")
         return int(m.value), int(slot.value)
 

@@ -68,9 +68,14 @@ def test_stream_group_round_robin(mh, device, bigbridge, devices):
         g.wait(m, slot)
         assert g.slot_time_ms(m, slot) > 0
         assert torch.equal(g.output(m, slot)[:, :2048].cpu(), torch.from_numpy(imgs[k])), k
-    # back to back: the last frame of every member checked after a group sync
+    # back to back: the last frame of every (member, slot) checked after a group sync
     last = {}
     for k, (c, o) in enumerate(hosts):
-        last[g.submit(c, o)[0]] = (k, None)
+        m, slot = g.submit(c, o)
+        assert m == (len(hosts) + k) % len(devices)
+        last[m, slot] = k
     g.synchronize()
+    assert len(last) == 2 * len(devices)
+    for (m, slot), k in last.items():
+        assert torch.equal(g.output(m, slot)[:, :2048].cpu(), torch.from_numpy(imgs[k])), (m, slot, k)
     g.close()
