@@ -453,7 +453,8 @@ int mh_decode_windows_scaled_shape(const mh_frame *frame, uint32_t n_windows, ui
 /* the block grid: its caller decoded windows one block larger and viewed rectangle i at its own */
 /* (dx, dy) inside slot i, which is no array. Here the decoder moves every row onto the crop's   */
 /* byte grid in registers, at the moment it stores it; no intermediate raster exists.            */
-/* Not covered: crops at a reduced scale; crops of different sizes in one launch; flips; crops   */
+/* Not covered: crops at a reduced scale; crops of different sizes in one launch; flips of a byte */
+/* output (mh_decode_crops_norm below mirrors as it normalises); crops                            */
 /* for mh_decode_headers, the streams, the multi-GPU paths and mh_check; stores of exactly w     */
 /* bytes (a row is written in whole 8-byte words); a CPU twin.                                   */
 typedef struct {
@@ -503,6 +504,67 @@ int mh_decode_crops(const mh_frame *frame, const mh_crop *d_crops, uint32_t n_cr
  * crop (G above) and waves per workgroup. For tests and tools. */
 int mh_decode_crops_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, uint32_t h,
                           void *stream, uint32_t *groups_per_crop, uint32_t *waves_per_group);
+
+/* ---------------------------------------------------------------------- */
+/* Crops decoded straight into normalised binary16, bfloat16 or binary32 elements, optionally     */
+/* mirrored: what data loaders call crop-mirror-normalize, in the decode launch. The consumer of  */
+/* a batch of crops is a model, and no model eats bytes: after mh_decode_crops every caller       */
+/* converts, scales and shifts the batch, and flips some samples, each a pass over it. Here the   */
+/* decoder does all three on the row it holds in registers, and no byte batch ever exists.        */
+/* Not covered: mirrored crops whose width is no multiple of 8; vertical flips; a mirrored byte   */
+/* output; a scale or bias per crop or per frame; several channels; normalised output for the     */
+/* other entries; a general per-value output table; crops at a reduced scale.                     */
+#define MH_NORM_F16 0u  /* IEEE binary16 */
+#define MH_NORM_BF16 1u /* bfloat16      */
+#define MH_NORM_F32 2u
+#define MH_CROP_MIRROR 0x1u
+typedef struct {
+  uint32_t frame, x0, y0, flags; /* 16 bytes; pixels; flags: MH_CROP_MIRROR only */
+} mh_norm_crop;
+
+/* mh_decode_crops with elements of E = 2, 2 or 4 bytes (`format`) in the place of bytes. Crop p is
+ * the pixels [x0, x0 + w) x [y0, y0 + h) of its frame, wholly inside W x H; everything
+ * mh_decode_crops says about descriptors holds (a device array, never read on the host; crops may
+ * overlap and repeat).
+ * Output: crop p, row y starts at d_out + p * out_crop_stride + y * out_pitch (bytes), element X
+ * at + X * E. round_up(w, 8) elements of every row y < h are written: the first w are specified,
+ * the rest unspecified. Nothing else is touched, in that slot or outside it.
+ * Element (X, y): let v be the byte mh_decode_frames writes at (x0 + X, y0 + y) of that frame --
+ * with MH_CROP_MIRROR set, the byte at (x0 + w - 1 - X, y0 + y). The element is T[v] =
+ * cvt(fmaf((float)v, scale, bias)): one fused multiply-add in binary32 with a single rounding, then
+ * round-to-nearest-even to the format (the identity for MH_NORM_F32). Subnormals are kept, overflow
+ * gives +-inf, and finite scale and bias cannot produce a NaN. mh_norm_table below writes T on the
+ * host. Normalisation by a mean and a deviation is scale = 1 / (255 * std), bias = -mean / std.
+ * Device validation, by the crop's workgroups and before anything is addressed through the
+ * descriptor: frame >= n_frames, x0 > W - w, y0 > H - h (limits from the host, no sums of
+ * descriptor words), any bit of flags other than MH_CROP_MIRROR, or MH_CROP_MIRROR with w % 8 != 0
+ * (a mirrored row would carry its unspecified tail at its front) reject the crop: it loads nothing
+ * through its descriptor, writes no byte of the raster and gets MH_ERR_DIMS in d_crop_status[p].
+ * Status semantics and precedence, d_frame_status, the aliasing rule, tables, lut_stride_bytes ==
+ * 0, d_block_init and flags (MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER only): mh_decode_crops'.
+ * Checks: all before any HIP call, in mh_decode_crops' order and with its codes, except: format >
+ * 2 or a scale or bias that is not finite -> MH_ERR_INVALID_ARG, reported where a bad flag is;
+ * d_out, out_pitch and, for n_crops > 1, out_crop_stride are multiples of 16 (MH_ERR_ALIGN: a row
+ * is stored 16 bytes at a time); out_pitch >= round_up(w, 8) * E, the bytes a row is written with
+ * (for the 16-bit formats that is every multiple of 16 that is >= w * E), out_pitch <= 2^20 and,
+ * for n_crops > 1, out_crop_stride >= out_pitch * h (MH_ERR_CAPACITY).
+ * Tiles, CBH, S and the launch-shape rule are mh_decode_crops', with this kernel's occupancy. */
+int mh_decode_crops_norm(const mh_frame *frame, const mh_norm_crop *d_crops, uint32_t n_crops,
+                         uint32_t w, uint32_t h, uint32_t format, float scale, float bias,
+                         const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                         const int32_t *d_frame_status, int32_t *d_crop_status,
+                         void *d_out, size_t out_pitch, size_t out_crop_stride, void *stream);
+
+/* The launch shape mh_decode_crops_norm would use on `stream`'s device (no launch), as
+ * mh_decode_crops_shape; format > 2 -> MH_ERR_INVALID_ARG. */
+int mh_decode_crops_norm_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, uint32_t h,
+                               uint32_t format, void *stream,
+                               uint32_t *groups_per_crop, uint32_t *waves_per_group);
+
+/* Host: the 256 elements T[0..255] above, 512 or 1024 bytes -- the CPU twin of the kernel's
+ * conversion and the contract's reference. NULL table, format > 2 or a scale or bias that is not
+ * finite -> MH_ERR_INVALID_ARG; table_bytes below 256 * E -> MH_ERR_CAPACITY. */
+int mh_norm_table(uint32_t format, float scale, float bias, void *table, size_t table_bytes);
 
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a

@@ -19,6 +19,9 @@ of mdejong/MetalHuffman).
                                     level, a thumbnail sheet, multi-scale crops), one launch
   * decoder.decode_crops            a list of crops of one size at PIXEL origins, each stored from byte 0 of its
                                     own slot (a dense [n, h, w] batch of random crops), one launch
+  * decoder.decode_crops_normalized   the same crops straight into normalised float16 / bfloat16 / float32
+                                    elements, optionally mirrored (crop-mirror-normalize), one launch;
+                                    codec.norm_table is the CPU twin of the conversion
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync;
@@ -28,14 +31,15 @@ of mdejong/MetalHuffman).
   * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
 """
-from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS, MH_FLAG_NO_DELTA,
-                      MHError, lib)
+from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS,
+                      MH_FLAG_NO_DELTA, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
 from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, code_lengths_limited,
-                    decode_frame_cpu, encode_frame, frame_histogram, merge_blocks, shared_header, split_blocks)
+                    decode_frame_cpu, encode_frame, frame_histogram, merge_blocks, norm_table, shared_header, split_blocks)
 
 __all__ = [
     "EXPORTS", "LIB_PATH", "MH_CODES_PAD", "MH_FLAG_LANE_PAIRS", "MH_FLAG_NO_DELTA", "MHError", "lib", "BLOCK_DIM",
     "EncodedFrame", "Huffman", "block_grid", "decode_frame_cpu", "encode_frame", "merge_blocks", "split_blocks",
     "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
+    "norm_table", "MH_NORM_F16", "MH_NORM_BF16", "MH_NORM_F32", "MH_CROP_MIRROR",
 ]
 __version__ = "0.1.0"

@@ -17,6 +17,8 @@ MH_FLAG_LANE_PAIRS = 0x2  # lane-pair single-frame decode: diagnostic library on
 MH_FLAG_ANY_ORDER = 0x4  # the launch may overlap earlier work on the stream (caller guarantees independence)
 MH_ENCODE_WORKSPACE_ZEROED = 0x100  # the encoder workspace was zero-filled once (mh_encode_frame_device*)
 MH_ENCODE_LIMIT_LENGTHS = 0x200  # encoders only: a tree deeper than 16 gets package-merge lengths, not -3
+MH_NORM_F16, MH_NORM_BF16, MH_NORM_F32 = 0, 1, 2  # mh_decode_crops_norm's element formats
+MH_CROP_MIRROR = 0x1  # mh_norm_crop.flags: the crop's rows reversed along x
 MH_CODES_PAD = 4
 MH_TABLE2_MAX_ENTRIES = 257 * 256
 MH_MAX_DIM = 65535
@@ -46,6 +48,7 @@ EXPORTS = (
     "mh_decode_windows", "mh_decode_windows_shape",
     "mh_decode_windows_scaled", "mh_decode_windows_scaled_shape",
     "mh_decode_crops", "mh_decode_crops_shape",
+    "mh_decode_crops_norm", "mh_decode_crops_norm_shape", "mh_norm_table",
     "mh_encode_frames_shared_workspace_bytes", "mh_encode_frames_shared_device_async",
     "mh_frame_histogram", "mh_encode_frame_with_header",
 )
@@ -93,6 +96,11 @@ class mh_window(ctypes.Structure):
 class mh_crop(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+class mh_norm_crop(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
 
 
 _lib = None
@@ -182,6 +190,12 @@ def lib() -> ctypes.CDLL:
                                       ctypes.c_size_t, _vp]
         L.mh_decode_crops_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.c_uint32, _vp, _u32p, _u32p]
+        L.mh_decode_crops_norm.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_float, _vp,
+                                           ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
+        L.mh_decode_crops_norm_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.c_uint32, ctypes.c_uint32, _vp, _u32p, _u32p]
+        L.mh_norm_table.argtypes = [ctypes.c_uint32, ctypes.c_float, ctypes.c_float, _vp, ctypes.c_size_t]
         L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
                                     ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]

@@ -367,3 +367,42 @@ def box_reduce(img: np.ndarray, log2_scale: int) -> np.ndarray:
     out = np.empty(((h + s - 1) // s, (w + s - 1) // s), np.uint8)
     N.check(N.lib().mh_box_reduce(_p(img), w, h, w, k, _p(out), out.shape[1]), "mh_box_reduce")
     return out
+
+
+NORM_FORMATS = {"float16": N.MH_NORM_F16, "bfloat16": N.MH_NORM_BF16, "float32": N.MH_NORM_F32}
+
+
+def norm_format(dtype_or_format) -> int:
+    """MH_NORM_* of a format number, a numpy or torch dtype, or its name ("float16", "bfloat16",
+    "float32"); ValueError for anything else."""
+    if isinstance(dtype_or_format, (int, np.integer)) and not isinstance(dtype_or_format, bool):
+        if int(dtype_or_format) in NORM_FORMATS.values():
+            return int(dtype_or_format)
+        raise ValueError(f"format must be 0 (float16), 1 (bfloat16) or 2 (float32), not {dtype_or_format!r}")
+    name = str(dtype_or_format).rsplit(".", 1)[-1]  # "torch.bfloat16", "float16", dtype('float32')
+    if name not in NORM_FORMATS:
+        try:
+            name = np.dtype(dtype_or_format).name
+        except TypeError:
+            pass
+    if name not in NORM_FORMATS:
+        raise ValueError(f"no normalised output format for {dtype_or_format!r}: float16, bfloat16 or float32")
+    return NORM_FORMATS[name]
+
+
+def finite_f32(x: float) -> bool:
+    """x is finite once rounded to float32 (the midpoint above the largest float32 rounds to inf)."""
+    return x == x and abs(x) < 2.0 ** 128 - 2.0 ** 103
+
+
+def norm_table(dtype_or_format, scale: float, bias: float) -> np.ndarray:
+    """The 256 elements decode_crops_normalized can write, T[v] = cvt(fmaf(float32(v), scale, bias))
+    (mh_norm_table, the CPU twin of the kernel's conversion): float16 or float32 values, and for
+    bfloat16 the uint16 bit patterns. scale and bias are rounded to float32 first and must be finite."""
+    fmt = norm_format(dtype_or_format)
+    scale, bias = float(scale), float(bias)
+    if not (finite_f32(scale) and finite_f32(bias)):
+        raise ValueError(f"scale and bias must be finite in float32, not {scale!r}, {bias!r}")
+    out = np.empty(256, (np.float16, np.uint16, np.float32)[fmt])
+    N.check(N.lib().mh_norm_table(fmt, scale, bias, out.ctypes.data_as(ctypes.c_void_p), out.nbytes), "mh_norm_table")
+    return out

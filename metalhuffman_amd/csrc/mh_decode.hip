@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cmath>
 #include <mutex>
 
 #include "../../include/metalhuffman.h"
@@ -296,6 +297,7 @@ typedef unsigned int v2u32_t __attribute__((ext_vector_type(2)));
 struct StoreRows {
   static constexpr int kLog2 = 0;
   static constexpr bool kCrop = false;
+  static constexpr bool kNorm = false;
   template <int kAux>
   __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t, uint32_t o0, uint32_t o1, uint32_t off,
                                       uint32_t, uint32_t) {
@@ -316,6 +318,7 @@ template <int kLog2_>
 struct BoxRows {
   static constexpr int kLog2 = kLog2_;
   static constexpr bool kCrop = false;
+  static constexpr bool kNorm = false;
   static_assert(kLog2 >= 1 && kLog2 <= 3, "cells of 2, 4 or 8 pixels");
   static constexpr uint32_t kZeroSel = 0x0C0C0C0Cu;  // v_perm_b32: every byte the constant 0
   uint32_t ch;          // in-frame rows of the tile's block row, 1..8 (wave-uniform)
@@ -392,6 +395,7 @@ struct BoxRows {
 struct CropRows {
   static constexpr int kLog2 = 0;
   static constexpr bool kCrop = true;
+  static constexpr bool kNorm = false;
   uint32_t lo;  // per lane, wave-uniform in value: ~0 for dx < 4, else 0
   uint32_t k;   // per lane: dx & 3
   static __device__ __forceinline__ uint32_t right(uint32_t v) {
@@ -408,6 +412,97 @@ struct CropRows {
     v.x = __builtin_amdgcn_alignbyte(B, X, k);
     v.y = __builtin_amdgcn_alignbyte(nX, B, k);
     __builtin_amdgcn_raw_buffer_store_b64(v, out, (int)off, 0, kAux);
+  }
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t r, v2u32_t v, uint32_t off, uint32_t rbase,
+                                      uint32_t pitch) {
+    row<kAux>(out, r, v.x, v.y, off, rbase, pitch);
+  }
+};
+
+// NormRows<kFmt> (mh_decode_crops_norm): CropRows' crop-aligned row, optionally mirrored, converted
+// to the element T[v] = cvt(fmaf((float)v, scale, bias)) and stored 2 or 4 times as wide. The row's
+// two words pass two v_perm_b32 over (v.x, v.y) with a per-lane selector: the identity (0x03020100,
+// then 0x07060504) or the byte reversal (0x04050607, then 0x00010203) -- the second selector is the
+// first ^ 0x04040404 in both cases, so one register holds the choice and the chain sees no compare.
+// A mirrored word j lands at word OW - 1 - j of the row: that, and the element size, are in the
+// lane's first offset (out_tile), so `off` is already the row's byte offset in the wide raster.
+// scale, bias and the selector are per-lane VGPRs (the chain has no SGPR for them), and they are
+// a crop's, not a tile's: the kernel makes them once, ahead of the persistent loop (NormMap).
+// Conversion: v_cvt_f32_ubyte*, one fused multiply-add in binary32, then a plain C cast to the
+// format (round to nearest even, subnormals kept, overflow to inf). Converted and stored in halves
+// -- four elements at a time -- so no more than four floats are live. One unconditional b128 store
+// per row for the 16-bit formats, two for binary32.
+typedef unsigned int v4u32_t __attribute__((ext_vector_type(4)));
+template <uint32_t kFmt>
+struct NormRows : CropRows {
+  static_assert(kFmt <= MH_NORM_F32, "binary16, bfloat16 or binary32");
+  static constexpr bool kNorm = true;
+  static constexpr uint32_t kElem = kFmt == MH_NORM_F32 ? 4u : 2u;  // bytes per element
+  uint32_t sel;       // per lane: the first word's byte selector
+  float scale, bias;  // per lane
+  __device__ __forceinline__ float el(uint32_t w, int i) const {
+    return __builtin_fmaf((float)((w >> (8 * i)) & 0xFFu), scale, bias);
+  }
+  // two elements -> one word of the 16-bit format
+  static __device__ __forceinline__ uint32_t pack(float a, float b) {
+    if constexpr (kFmt == MH_NORM_F16) {
+      typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+      h2 h;
+      h.x = (_Float16)a;
+      h.y = (_Float16)b;
+      return __builtin_bit_cast(uint32_t, h);
+    } else {
+      typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+      b2 h;
+      h.x = (__bf16)a;
+      h.y = (__bf16)b;
+      return __builtin_bit_cast(uint32_t, h);
+    }
+  }
+  template <int kAux>
+  __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t, uint32_t o0, uint32_t o1, uint32_t off,
+                                      uint32_t, uint32_t) {
+    const uint32_t X = pick(lo, o0, o1), Y = pick(lo, o1, o0);
+    const uint32_t nX = right(X), nY = right(Y);
+    const uint32_t B = pick(lo, Y, nY);
+    const uint32_t c0 = __builtin_amdgcn_alignbyte(B, X, k), c1 = __builtin_amdgcn_alignbyte(nX, B, k);
+    // the second word's selector is the first's ^ 0x04040404, which is the first's with the two
+    // sources exchanged: no second selector register
+    const uint32_t w0 = __builtin_amdgcn_perm(c1, c0, sel);
+    uint32_t w1 = __builtin_amdgcn_perm(c0, c1, sel);
+    // converted where the row is stored, a word at a time (as BoxRows sums its rows where a store
+    // would have consumed them): left to the scheduler, the rows' floats stay live along the chain
+    v4u32_t v;
+    if constexpr (kFmt == MH_NORM_F32) {
+      // one v_fma_f32 per element, kept apart: packed (v_pk_fma_f32) they take scale and bias as
+      // aligned register PAIRS, two more VGPRs than the raw-pixel kernel has
+      asm volatile("" : "+v"(w1));
+      v.x = __builtin_bit_cast(uint32_t, el(w0, 0));
+      asm volatile("" : "+v"(v.x));
+      v.y = __builtin_bit_cast(uint32_t, el(w0, 1));
+      asm volatile("" : "+v"(v.y));
+      v.z = __builtin_bit_cast(uint32_t, el(w0, 2));
+      asm volatile("" : "+v"(v.z));
+      v.w = __builtin_bit_cast(uint32_t, el(w0, 3));
+      __builtin_amdgcn_raw_buffer_store_b128(v, out, (int)off, 0, kAux);
+      asm volatile("" : "+v"(w1));
+      v.x = __builtin_bit_cast(uint32_t, el(w1, 0));
+      asm volatile("" : "+v"(v.x));
+      v.y = __builtin_bit_cast(uint32_t, el(w1, 1));
+      asm volatile("" : "+v"(v.y));
+      v.z = __builtin_bit_cast(uint32_t, el(w1, 2));
+      asm volatile("" : "+v"(v.z));
+      v.w = __builtin_bit_cast(uint32_t, el(w1, 3));
+      __builtin_amdgcn_raw_buffer_store_b128(v, out, (int)(off + 16u), 0, kAux);
+    } else {
+      v.x = pack(el(w0, 0), el(w0, 1));
+      v.y = pack(el(w0, 2), el(w0, 3));
+      asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(w1));
+      v.z = pack(el(w1, 0), el(w1, 1));
+      v.w = pack(el(w1, 2), el(w1, 3));
+      __builtin_amdgcn_raw_buffer_store_b128(v, out, (int)off, 0, kAux);
+    }
   }
   template <int kAux>
   __device__ __forceinline__ void row(__amdgpu_buffer_rsrc_t out, uint32_t r, v2u32_t v, uint32_t off, uint32_t rbase,
@@ -746,6 +841,16 @@ struct CropMap : WindowMap {
   __device__ __forceinline__ uint32_t ow() const { return rem >> 8; }
 };
 
+// NormMap (mh_decode_crops_norm): a CropMap that also carries what the NormRows stage takes per
+//   tile: bit 3 of `rem` (free between dx and dy) is the crop's mirror flag; the stage's byte
+//   selector, scale and bias are per-lane VGPRs for the workgroup's whole life, so neither an SGPR
+//   nor a move per tile is spent on them.
+struct NormMap : CropMap {
+  uint32_t sel;
+  float scale, bias;
+  __device__ __forceinline__ uint32_t mirror() const { return (rem >> 3) & 1u; }
+};
+
 struct TileHdrBase {
   uint32_t tile;      // wave-uniform; >= total_tiles: no tile
   uint32_t off;       // this lane's block start bit
@@ -764,6 +869,8 @@ template <>
 struct TileHdrOf<WindowMap> : TileHdrOf<RegionMap> {};
 template <>
 struct TileHdrOf<CropMap> : TileHdrOf<RegionMap> {};
+template <>
+struct TileHdrOf<NormMap> : TileHdrOf<RegionMap> {};
 using TileHdr = TileHdrOf<FrameMap>;
 
 // tile -> (r, s). One segment per row skips the division (a uniform branch), as frame_of does
@@ -834,6 +941,8 @@ template <>
 struct TileOf<WindowMap> : TileOf<RegionMap> {};
 template <>
 struct TileOf<CropMap> : TileOf<RegionMap> {};
+template <>
+struct TileOf<NormMap> : TileOf<RegionMap> {};
 using Tile = TileOf<FrameMap>;
 
 template <class Map = FrameMap>
@@ -910,9 +1019,10 @@ struct OutTile {
   __amdgpu_buffer_rsrc_t rsrc;
   uint32_t row0;
 };
-template <class Map = FrameMap, int kLog2 = 0>
+template <class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Map> &t, uint32_t lane,
                                             const Map &m = Map()) {
+  constexpr int kLog2 = Out::kLog2;
   static_assert(Map::kRegion || kLog2 == 0, "only a region is decoded at a reduced scale");
   if constexpr (Map::kCrop) {
     // Block row r holds crop rows 8 r - dy .. 8 r - dy + 7. The descriptor is based at the first of
@@ -931,7 +1041,17 @@ __device__ __forceinline__ OutTile out_tile(const DecodeArgs &a, const TileOf<Ma
     o.rsrc = uniform_rsrc(a.out + (uint64_t)t.f * a.out_frame_stride + base,
                           (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
     const uint32_t above = t.r ? 0u : dy * (uint32_t)a.out_pitch;
-    o.row0 = lane < words ? (63u * t.s + lane) * 8u - above : 0x80000000u;
+    if constexpr (Out::kNorm) {
+      // a word is 8 elements of Out::kElem bytes, and a mirrored crop's word j is the row's word
+      // OW - 1 - j (w is a multiple of 8 then: the kernel's verdict). The second store of a binary32
+      // row lies 16 bytes on: (word + 1) * 32 <= pitch (the host's check), so a row above the crop
+      // stays "negative" and the dead offset stays out of range with it.
+      // (by arithmetic, ~j + OW = OW - 1 - j: a select's mask would be one more SGPR pair)
+      const uint32_t j = 63u * t.s + lane, mask = 0u - m.mirror(), word = (j ^ mask) + (mask & m.ow());
+      o.row0 = lane < words ? word * (8u * Out::kElem) - above : 0x80000000u;
+    } else {
+      o.row0 = lane < words ? (63u * t.s + lane) * 8u - above : 0x80000000u;
+    }
     asm volatile("" : "+v"(o.row0));
     return o;
   } else if constexpr (Map::kRegion) {
@@ -972,6 +1092,11 @@ __device__ __forceinline__ Out rows_of(const DecodeArgs &a, const TileOf<Map> &t
     o.lo = m.dx() < 4u ? ~0u : 0u;
     o.k = m.dx() & 3u;
     asm volatile("" : "+v"(o.lo), "+v"(o.k));  // per-lane registers: the chain has no SGPR for either
+    if constexpr (Out::kNorm) {
+      o.sel = m.sel;
+      o.scale = m.scale;
+      o.bias = m.bias;
+    }
     return o;
   } else if constexpr (Out::kLog2 == 0) {
     return Out();
@@ -1158,7 +1283,7 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     wave_sync();  // this tile's staging writes -> reads
     {
       const bool dead = !cur.valid;
-      const OutTile ot = out_tile<Map, Out::kLog2>(a, cur, lane, m);
+      const OutTile ot = out_tile<Map, Out>(a, cur, lane, m);
       LdsWords src{stage};
       // waves with more tiles left run first (the arbiter otherwise favours the oldest)
       set_prio(min((a.total_tiles - 1u - cur.tile) / gstride, 3u));
@@ -1185,7 +1310,7 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     TileHdrOf<Map> h;
     hdr_issue(a, t, lane, h, m);
     const TileOf<Map> tt = hdr_resolve(a, h, lane, m);
-    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane, m);
+    const OutTile ot = out_tile<Map, Out>(a, tt, lane, m);
     decode_halves<kDelta, Cfg, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid, rows_of<Out>(a, tt, lane, m));
   }
 }
@@ -1226,7 +1351,7 @@ __device__ __forceinline__ void flat8_block(const DecodeArgs &a, const TileOf<Ma
                                             const Flat8Codes &c, Out sink = Out(), const Map &m = Map()) {
   typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
   const uint32_t sb = (t.start + (t.p >> 3)) & 3u;
-  const OutTile ot = out_tile<Map, Out::kLog2>(a, t, lane, m);
+  const OutTile ot = out_tile<Map, Out>(a, t, lane, m);
   const uint32_t rbase = (t.valid && !MH_DIAG_DROP_STORES) ? ot.row0 : 0x80000000u;
   const uint32_t pitch = (uint32_t)a.out_pitch;
   uint32_t s = t.init;  // running delta sum (byte 0)
@@ -1293,7 +1418,7 @@ __device__ __forceinline__ void flat8_loop(const DecodeArgs &a, uint32_t lane, u
     TileHdrOf<Map> hs;
     hdr_issue(a, t, lane, hs, m);
     const TileOf<Map> tt = hdr_resolve(a, hs, lane, m);
-    const OutTile ot = out_tile<Map, Out::kLog2>(a, tt, lane, m);
+    const OutTile ot = out_tile<Map, Out>(a, tt, lane, m);
     decode_halves<kDelta, Batch8, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid,
                                        rows_of<Out>(a, tt, lane, m));
   }
@@ -1855,6 +1980,45 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   slice_decode<kDelta, CropRows>(ac, p_offsets, p_frame_off, p_block_init, p_status, p_nb, rows * p_segs, p_groups, f,
                                  slice, PreparedTable{p_luts, p_lut_stride},
                                  CropMap{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, dx | (dy << 4) | (ow << 8)}, p, p_cstatus}});
+}
+
+// mh_decode_crops_norm: the crops kernel's entry with one more verdict term -- a flag bit other than
+// MH_CROP_MIRROR, or MH_CROP_MIRROR on a width that is no multiple of 8 (p_odd_w = 1, from the host;
+// a mirrored row would carry its unspecified tail at its front) -- ahead of the same body with the
+// NormRows<kFmt> output stage. a0.out_pitch / out_frame_stride / out_frame_bytes are bytes of the
+// wide raster.
+template <bool kDelta, uint32_t kFmt>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_normcrops_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const mh_norm_crop *p_crops, uint32_t p_nb, uint32_t p_tiles_per_crop, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0, uint32_t p_max_y0,
+    uint64_t p_lut_stride, int32_t *p_cstatus, float p_scale, float p_bias, uint32_t p_odd_w, const DecodeArgs a0) {
+  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
+  const v4u32 cd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_crops + p, 16u), 0, 0, 0);
+  const uint32_t f = __builtin_amdgcn_readfirstlane(cd.x), x0 = __builtin_amdgcn_readfirstlane(cd.y);
+  const uint32_t y0 = __builtin_amdgcn_readfirstlane(cd.z), flags = __builtin_amdgcn_readfirstlane(cd.w);
+  if ((f >= p_nframes) | (x0 > p_max_x0) | (y0 > p_max_y0) | ((flags & ~MH_CROP_MIRROR) != 0u) |
+      ((flags & p_odd_w) != 0u)) {  // workgroup-uniform
+    if (p_cstatus && slice == 0 && threadIdx.x == 0) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  (void)p_tiles_per_crop;
+  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
+  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
+  DecodeArgs ac = a0;
+  ac.out = a0.out + (uint64_t)p * a0.out_frame_stride;
+  ac.out_frame_stride = 0;
+  uint32_t sel = flags ? 0x04050607u : 0x03020100u;
+  float scale = p_scale, bias = p_bias;
+  asm volatile("" : "+v"(sel), "+v"(scale), "+v"(bias));
+  // one opaque word: seen through, its parts stay live beside it and the raw-pixel body is an SGPR short
+  uint32_t rem = dx | (flags << 3) | (dy << 4) | (ow << 8);
+  asm volatile("" : "+s"(rem));
+  slice_decode<kDelta, NormRows<kFmt>>(
+      ac, p_offsets, p_frame_off, p_block_init, p_status, p_nb, rows * p_segs, p_groups, f, slice,
+      PreparedTable{p_luts, p_lut_stride},
+      NormMap{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, rem}, p, p_cstatus}},
+              sel, scale, bias});
 }
 
 template <bool kDelta>
@@ -2472,7 +2636,8 @@ enum SliceKernel {
   kSliceRegion,
   kSliceWindows = kSliceRegion + kSliceScales,
   kSliceCrops = kSliceWindows + kSliceScales,  // one scale only
-  kSliceKernels
+  kSliceNormCrops,                             // + the format (MH_NORM_*)
+  kSliceKernels = kSliceNormCrops + 3
 };
 #if !MH_LANE_PAIRS
 // One row per kernel, [kDelta]: the row device_info() queries the occupancy of is the row
@@ -2483,6 +2648,7 @@ using HeadersFn = decltype(&mh_decode_headers_kernel<false>);
 using RegionFn = decltype(&mh_decode_region_kernel<false>);    // = mh_decode_region_scaled_kernel<_, 1..3>
 using WindowsFn = decltype(&mh_decode_windows_kernel<false>);  // = mh_decode_windows_scaled_kernel<_, 1..3>
 using CropsFn = decltype(&mh_decode_crops_kernel<false>);
+using NormCropsFn = decltype(&mh_decode_normcrops_kernel<false, MH_NORM_F16>);
 using AnyKernel = void (*)();
 struct SliceRow {
   AnyKernel fn[2];
@@ -2503,6 +2669,10 @@ const SliceRow kSliceTable[] = {
     slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 2>, mh_decode_windows_scaled_kernel<true, 2>),
     slice_row<WindowsFn>(mh_decode_windows_scaled_kernel<false, 3>, mh_decode_windows_scaled_kernel<true, 3>),
     slice_row<CropsFn>(mh_decode_crops_kernel<false>, mh_decode_crops_kernel<true>),
+    slice_row<NormCropsFn>(mh_decode_normcrops_kernel<false, MH_NORM_F16>, mh_decode_normcrops_kernel<true, MH_NORM_F16>),
+    slice_row<NormCropsFn>(mh_decode_normcrops_kernel<false, MH_NORM_BF16>,
+                           mh_decode_normcrops_kernel<true, MH_NORM_BF16>),
+    slice_row<NormCropsFn>(mh_decode_normcrops_kernel<false, MH_NORM_F32>, mh_decode_normcrops_kernel<true, MH_NORM_F32>),
 };
 static_assert(sizeof(kSliceTable) / sizeof(kSliceTable[0]) == kSliceKernels, "one row per SliceKernel");
 #endif
@@ -2675,6 +2845,8 @@ struct DecodeCall {
                 // n_windows rasters, described by the device array `windows`
     kCrops,     // mh_decode_crops: kWindows with rg = {0, 0, w, h} in PIXELS, the crops' size, and the
                 // descriptors' origins in pixels (scale 0 only)
+    kNormCrops, // mh_decode_crops_norm: kCrops into rasters of `format`'s elements, 2 or 4 bytes each, under
+                // the map (scale, bias); rows are stored 16 bytes at a time
   } kind;
   const void *ptr = nullptr;
   uint64_t stride = 0;
@@ -2683,12 +2855,18 @@ struct DecodeCall {
   const void *windows = nullptr;
   uint32_t n_windows = 0;
   uint32_t allowed_flags = MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER;
+  uint32_t format = 0;  // kNormCrops: MH_NORM_*
+  float scale = 1.0f, bias = 0.0f;
   // call_geometry()'s results: one raster's pixel size and tiles (segs: a region's only), and the
   // number of rasters, which is the number of units the grid is cut into
   RegionExtent re = {};
   uint32_t n_units = 0;
-  bool windowed() const { return kind == kWindows || kind == kCrops; }
+  bool cropped() const { return kind == kCrops || kind == kNormCrops; }
+  bool windowed() const { return kind == kWindows || cropped(); }
   bool regional() const { return kind == kRegion || windowed(); }
+  // an element's bytes, and the row of its family in kSliceTable (the scale, or the format)
+  uint32_t elem() const { return kind != kNormCrops ? 1u : format == MH_NORM_F32 ? 4u : 2u; }
+  uint32_t table_row() const { return kind == kNormCrops ? format : log2_scale; }
 };
 
 // The rules that the decode entries and the *_shape entries share, in their one order: flags, the
@@ -2698,6 +2876,8 @@ struct DecodeCall {
 int call_geometry(const mh_frame *fr, DecodeCall &c) {
   if (fr->flags & ~c.allowed_flags) return MH_ERR_INVALID_ARG;
   if (c.log2_scale > 3u) return MH_ERR_INVALID_ARG;
+  if (c.kind == DecodeCall::kNormCrops && (c.format > MH_NORM_F32 || !std::isfinite(c.scale) || !std::isfinite(c.bias)))
+    return MH_ERR_INVALID_ARG;
   const mh_dims &d = fr->dims;
   if (!dims_ok(d)) return MH_ERR_DIMS;
   c.n_units = c.windowed() ? c.n_windows : fr->n_frames;
@@ -2705,7 +2885,7 @@ int call_geometry(const mh_frame *fr, DecodeCall &c) {
     c.re = {d.width, d.height, 0u, (d.block_width * d.block_height + 63) / 64};
     return MH_OK;
   }
-  if (c.kind == DecodeCall::kCrops) return crop_extent(d, c.rg, c.re) ? MH_OK : MH_ERR_DIMS;
+  if (c.cropped()) return crop_extent(d, c.rg, c.re) ? MH_OK : MH_ERR_DIMS;
   if (!region_extent(d, c.rg, c.re)) return MH_ERR_DIMS;
   if (c.windowed()) {
     c.re.pw = 8ull * c.rg->bw;
@@ -2739,7 +2919,11 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   const int rc = call_geometry(fr, c);
   if (rc != MH_OK) return rc;
   const uint32_t n_rasters = c.n_units;
-  const uint64_t am = (8u >> c.log2_scale) - 1u;  // the row store's width - 1
+  const bool norm = c.kind == DecodeCall::kNormCrops;
+  const uint64_t am = norm ? 15u : (8u >> c.log2_scale) - 1u;  // the row store's width - 1
+  // a row's bytes: normalised crops write round_up(w, 8) elements, which a pitch of w elements rounded
+  // up to 16 bytes does not hold at 4 bytes each, so the whole words are asked for
+  const uint64_t row_bytes = norm ? ((c.re.pw + 7u) & ~7ull) * c.elem() : c.re.pw;
   if (in_frame && (fr->table2_entries < 256 || (fr->table2_entries % 256) != 0 ||
                    fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
     return MH_ERR_TABLE;
@@ -2749,7 +2933,7 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (windowed && ((uintptr_t)c.windows & 15u)) return MH_ERR_ALIGN;
   if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)c.ptr & 15u) || (c.stride & 15u))))
     return MH_ERR_ALIGN;
-  if (out_pitch < c.re.pw || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * c.re.ph))
+  if (out_pitch < row_bytes || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * c.re.ph))
     return MH_ERR_CAPACITY;
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
@@ -2828,7 +3012,7 @@ int slice_prologue(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t 
 template <class Fn, class Table, class TableAux, class... Tail>
 int launch_slices(SliceKernel family, const DecodeCall &c, const SliceArgs &p, void *stream, Table table,
                   const int32_t *status, TableAux aux, Tail... tail) {
-  const SliceKernel k = (SliceKernel)(family + c.log2_scale);
+  const SliceKernel k = (SliceKernel)(family + c.table_row());
   const DecodeArgs &a = p.a;
   hipStream_t s = (hipStream_t)stream;
   uint32_t G = 0;
@@ -2853,7 +3037,7 @@ int slice_shape_entry(SliceKernel family, const mh_frame *fr, DecodeCall c, void
   int rc = call_geometry(fr, c);
   if (rc != MH_OK) return rc;
   if (c.regional() && !tiles_fit(c)) return MH_ERR_CAPACITY;
-  rc = slice_shape((SliceKernel)(family + c.log2_scale), c.n_units, c.re.tiles, !(fr->flags & MH_FLAG_NO_DELTA),
+  rc = slice_shape((SliceKernel)(family + c.table_row()), c.n_units, c.re.tiles, !(fr->flags & MH_FLAG_NO_DELTA),
                    (hipStream_t)stream, groups_per_unit);
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
@@ -3070,6 +3254,36 @@ int mh_decode_crops_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint
   const mh_region size = {0u, 0u, w, h};
   return slice_shape_entry(kSliceCrops, fr, {DecodeCall::kCrops, nullptr, 0, &size, 0u, nullptr, n_crops}, stream,
                            groups_per_crop, waves_per_group);
+}
+
+// The crops decoded straight into normalised elements: the crops kernel's entry and body with the
+// NormRows output stage, one row of kSliceTable per format. The checks are mh_decode_crops' through
+// the same helpers, with the format's element size in the raster rules and 16-byte row stores.
+int mh_decode_crops_norm(const mh_frame *fr, const mh_norm_crop *d_crops, uint32_t n_crops, uint32_t w, uint32_t h,
+                         uint32_t format, float scale, float bias, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                         const int32_t *d_frame_status, int32_t *d_crop_status, void *d_out, size_t out_pitch,
+                         size_t out_crop_stride, void *stream) {
+  if (d_crop_status && d_crop_status == d_frame_status) return MH_ERR_INVALID_ARG;
+  const mh_region size = {0u, 0u, w, h};
+  DecodeCall c{DecodeCall::kNormCrops, d_luts, lut_stride_bytes, &size, 0u, d_crops, n_crops};
+  c.format = format;
+  c.scale = scale;
+  c.bias = bias;
+  SliceArgs p;
+  const int rc = slice_prologue(fr, static_cast<uint8_t *>(d_out), out_pitch, out_crop_stride, c, p);
+  if (rc != MH_OK) return rc;
+  return launch_slices<NormCropsFn>(kSliceNormCrops, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
+                                    d_frame_status, d_crops, c.re.segs, w, h, fr->n_frames, fr->dims.width - w,
+                                    fr->dims.height - h, lut_stride_bytes, d_crop_status, scale, bias,
+                                    (w & 7u) ? 1u : 0u);
+}
+
+int mh_decode_crops_norm_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h, uint32_t format,
+                               void *stream, uint32_t *groups_per_crop, uint32_t *waves_per_group) {
+  const mh_region size = {0u, 0u, w, h};
+  DecodeCall c{DecodeCall::kNormCrops, nullptr, 0, &size, 0u, nullptr, n_crops};
+  c.format = format;
+  return slice_shape_entry(kSliceNormCrops, fr, c, stream, groups_per_crop, waves_per_group);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

@@ -13,6 +13,7 @@
 // No module statics (the reference keeps code tables in file statics,
 // HuffmanUtil.cpp:87-102): every entry point is reentrant.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -201,6 +202,31 @@ int encode_symbols(const uint8_t *sym, uint64_t n, uint64_t stride, uint8_t cano
 void fill_range(mh_lookup_symbol *tab, uint32_t first, uint32_t count, uint8_t sym, uint8_t len) {
   for (uint32_t i = 0; i < count; ++i) tab[first + i] = mh_lookup_symbol{sym, len};
 }
+
+// binary32 bits -> binary16 / bfloat16 bits, round to nearest even (mh_norm_table). The input is
+// finite or an infinity (a fused multiply-add of finite operands yields no NaN).
+uint16_t f32_to_f16(uint32_t x) {
+  const uint32_t sign = (x >> 16) & 0x8000u, mag = x & 0x7FFFFFFFu;
+  if (mag >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 rounds to inf
+  uint32_t q, rem, half;
+  if (mag < 0x38800000u) {  // below 2^-14: a subnormal, in units of 2^-24
+    const uint32_t e = mag >> 23, shift = 126u - e;
+    if (e == 0u || shift > 24u) return (uint16_t)sign;  // below 2^-25: zero
+    const uint32_t mant = (mag & 0x7FFFFFu) | 0x800000u;
+    q = mant >> shift;
+    rem = mant & ((1u << shift) - 1u);
+    half = 1u << (shift - 1u);
+  } else {
+    const uint32_t v = mag - 0x38000000u;  // exponent rebiased from 127 to 15
+    q = v >> 13;
+    rem = v & 0x1FFFu;
+    half = 0x1000u;
+  }
+  if (rem > half || (rem == half && (q & 1u))) ++q;  // a carry moves into the exponent, as it must
+  return (uint16_t)(sign | q);
+}
+
+uint16_t f32_to_bf16(uint32_t x) { return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1u)) >> 16); }
 
 }  // namespace
 
@@ -490,6 +516,23 @@ int mh_build_single_table(const uint8_t canon_header[256], mh_lookup_symbol tabl
   for (int s = 0; s < 256; ++s) {
     const int len = canon_header[s];
     if (len) fill_range(table, cc[s], 1u << (16 - len), (uint8_t)s, (uint8_t)len);
+  }
+  return MH_OK;
+}
+
+// The 256 elements mh_decode_crops_norm can write: one std::fmaf per byte value, then the narrowing
+// by integer arithmetic (round to nearest even, subnormals kept, overflow to inf).
+int mh_norm_table(uint32_t format, float scale, float bias, void *table, size_t table_bytes) {
+  if (!table || format > MH_NORM_F32 || !std::isfinite(scale) || !std::isfinite(bias)) return MH_ERR_INVALID_ARG;
+  if (table_bytes < 256u * (format == MH_NORM_F32 ? 4u : 2u)) return MH_ERR_CAPACITY;
+  for (uint32_t v = 0; v < 256u; ++v) {
+    const float f = std::fmaf((float)v, scale, bias);
+    uint32_t bits;
+    std::memcpy(&bits, &f, 4);
+    if (format == MH_NORM_F32)
+      static_cast<uint32_t *>(table)[v] = bits;
+    else
+      static_cast<uint16_t *>(table)[v] = format == MH_NORM_F16 ? f32_to_f16(bits) : f32_to_bf16(bits);
   }
   return MH_OK;
 }

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .codec import EncodedFrame, block_grid
+from .codec import EncodedFrame, block_grid, finite_f32
+from .codec import norm_format as _norm_format
 
 ALIGN = 16  # frame code starts inside a packed batch (16-byte buffer loads)
 
@@ -809,6 +810,108 @@ def decode_crops(frames: DeviceFrames, tables, crops, size, out: Optional[torch.
                                  h * pitch, _raw_stream_ptr(stream, dev_index))
     if rc:
         N.check(rc, "mh_decode_crops")
+    return (out, cstatus) if status is True else out
+
+
+_NORM_DTYPES = (torch.float16, torch.bfloat16, torch.float32)  # indexed by MH_NORM_*
+
+
+def _host_norm_crops(frames: DeviceFrames, crops, w: int, h: int):
+    """decode_crops_normalized's `crops` checked on the host: _host_crops' rules for (frame, x0, y0),
+    plus a fourth column of flags -- MH_CROP_MIRROR only, and only on a width that is a multiple of 8."""
+    if isinstance(crops, torch.Tensor) and crops.is_cuda:
+        return _host_crops(frames, crops, w, h)
+    c = np.asarray(crops.numpy() if isinstance(crops, torch.Tensor) else crops)
+    if c.ndim != 2 or c.shape[1] not in (3, 4) or c.shape[0] < 1 or c.dtype.kind not in "iu":
+        raise ValueError("crops is a sequence of (frame, x0, y0) or (frame, x0, y0, flags) integers")
+    full = _host_crops(frames, c[:, :3], w, h)
+    if c.shape[1] == 4:
+        flags = c[:, 3].astype(np.int64)
+        bad = (flags & ~N.MH_CROP_MIRROR) != 0
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"crop {i}: flags {int(flags[i]):#x} has bits other than MH_CROP_MIRROR")
+        if (w % 8) and flags.any():
+            i = int(np.flatnonzero(flags)[0])
+            raise ValueError(f"crop {i}: MH_CROP_MIRROR needs a width that is a multiple of 8, not {w}")
+        full[:, 3] = flags
+    return full
+
+
+def decode_crops_normalized_shape(frames: DeviceFrames, n_crops: int, size, dtype,
+                                  stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
+    """(workgroups per crop, waves per workgroup) decode_crops_normalized would launch n_crops crops
+    of size = (w, h) pixels with, for `dtype` (mh_decode_crops_norm_shape)."""
+    w, h = _crop_size(frames, size)
+    fmt = _norm_format(dtype)
+    if int(n_crops) < 1:
+        raise ValueError("no crops")
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    g, wv = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    N.check(N.lib().mh_decode_crops_norm_shape(ctypes.byref(fr), int(n_crops), w, h, fmt,
+                                               _raw_stream_ptr(stream, dev_index), ctypes.byref(g), ctypes.byref(wv)),
+            "mh_decode_crops_norm_shape")
+    return int(g.value), int(wv.value)
+
+
+def decode_crops_normalized(frames: DeviceFrames, tables, crops, size, dtype, scale: float = 1.0, bias: float = 0.0,
+                            out: Optional[torch.Tensor] = None, status=None,
+                            stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                            skip_rejected: bool = True):
+    """decode_crops straight into a model's input (mh_decode_crops_norm): crop p, the pixels [x0, x0 + w)
+    x [y0, y0 + h) of frame `frame`, becomes out[p, :, :w] of torch.float16, bfloat16 or float32
+    (`dtype`), every byte v as cvt(fma(float32(v), scale, bias)) -- one fused multiply-add in float32,
+    then round-to-nearest-even to dtype; codec.norm_table gives the 256 values. The conversion, the
+    affine map and the mirror are done on the row the decoder holds in registers: one launch, and no
+    uint8 batch exists. Normalising by a mean and a standard deviation of [0, 1] pixels is
+        scale = 1 / (255 * std), bias = -mean / std.
+    -> out[n, h, round_up(w, 8)]; columns >= w of a written row are unspecified.
+    crops: an int32 tensor [n, 4] of (frame, x0, y0, flags) on the frames' device -- used in place when
+    contiguous and 16-byte aligned, never read on the host (no sync): the kernel rejects, with status
+    MH_ERR_DIMS and an untouched slot, a crop that names no frame, leaves the frame, has a flag bit
+    other than MH_CROP_MIRROR, or is mirrored at a width that is no multiple of 8 ([n, 3] is padded
+    with flags 0) -- or a host sequence / array of (frame, x0, y0) or (frame, x0, y0, flags), validated
+    here by the same rules (ValueError) and uploaded. flags = MH_CROP_MIRROR reverses the crop's rows:
+    out[p, y, X] comes from pixel x0 + w - 1 - X.
+    scale, bias: finite in float32 (ValueError).
+    out: a contiguous [n, h, round_up(w, 8)] tensor of `dtype` on the frames' device; None allocates a
+    ZERO-FILLED one (a rejected or skipped crop's slot is never written).
+    status, tables, extra_flags, skip_rejected: decode_crops'."""
+    who = "decode_crops_normalized"
+    w, h = _crop_size(frames, size)
+    fmt = _norm_format(dtype)
+    tdtype, esize = _NORM_DTYPES[fmt], (2, 2, 4)[fmt]
+    scale, bias = float(scale), float(bias)
+    if not (finite_f32(scale) and finite_f32(bias)):
+        raise ValueError(f"scale and bias must be finite in float32, not {scale!r}, {bias!r}")
+    host = _host_norm_crops(frames, crops, w, h)
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
+    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
+    dev = frames.codes.device
+    cols = (w + 7) // 8 * 8
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        desc = _windows_tensor(frames, crops, host)  # (an upload or a padded copy belongs to `stream`)
+        n = int(desc.shape[0])
+        shape = (n, h, cols)
+        if out is None:
+            out = torch.zeros(shape, dtype=tdtype, device=dev)
+        cstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
+    if (out.dtype is not tdtype or tuple(out.shape) != shape or out.get_device() != dev_index
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {tdtype} {list(shape)} tensor on cuda:{dev_index}")
+    if cstatus is not None and (not isinstance(cstatus, torch.Tensor) or cstatus.dtype is not torch.int32
+                                or cstatus.numel() != n or cstatus.get_device() != dev_index
+                                or not cstatus.is_contiguous()):
+        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
+    pitch = cols * esize
+    rc = N.lib().mh_decode_crops_norm(ctypes.byref(fr), desc.data_ptr(), n, w, h, fmt, scale, bias, luts.data_ptr(),
+                                      stride, fstatus.data_ptr() if fstatus is not None else None,
+                                      cstatus.data_ptr() if cstatus is not None else None, out.data_ptr(), pitch,
+                                      h * pitch, _raw_stream_ptr(stream, dev_index))
+    if rc:
+        N.check(rc, "mh_decode_crops_norm")
     return (out, cstatus) if status is True else out
 
 
