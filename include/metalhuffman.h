@@ -512,8 +512,9 @@ int mh_decode_crops_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, u
 /* converts, scales and shifts the batch, and flips some samples, each a pass over it. Here the   */
 /* decoder does all three on the row it holds in registers, and no byte batch ever exists.        */
 /* Not covered: mirrored crops whose width is no multiple of 8; vertical flips; a mirrored byte   */
-/* output; a scale or bias per crop or per frame; several channels; normalised output for the     */
-/* other entries; a general per-value output table; crops at a reduced scale.                     */
+/* output; a scale or bias per crop (mh_decode_crops_norm_planes below takes one per plane of a   */
+/* C-plane image); normalised output for the other entries; a general per-value output table;     */
+/* crops at a reduced scale.                                                                      */
 #define MH_NORM_F16 0u  /* IEEE binary16 */
 #define MH_NORM_BF16 1u /* bfloat16      */
 #define MH_NORM_F32 2u
@@ -565,6 +566,74 @@ int mh_decode_crops_norm_shape(const mh_frame *frame, uint32_t n_crops, uint32_t
  * conversion and the contract's reference. NULL table, format > 2 or a scale or bias that is not
  * finite -> MH_ERR_INVALID_ARG; table_bytes below 256 * E -> MH_ERR_CAPACITY. */
 int mh_norm_table(uint32_t format, float scale, float bias, void *table, size_t table_bytes);
+
+/* ---------------------------------------------------------------------- */
+/* Crops of C-plane images decoded into normalised [n, C, h, w] tensors in one launch. A colour    */
+/* image is stored in this format as C grayscale planes, one frame each, and a model takes         */
+/* [n, C, h, w] with a mean and a deviation per channel. With mh_decode_crops_norm that is C       */
+/* launches, C descriptor arrays that must agree on the origin and the mirror flag, and C pairs;   */
+/* at a loader's batch sizes the launches, not the decode work, are the cost. Here a descriptor is */
+/* a SAMPLE: its C planes are the same crop of C frames, each under its own (scale, bias).         */
+/* Not covered: channels-last output; a pair per crop; vertical flips; crops at a reduced scale; a */
+/* byte output with planes (mh_decode_crops already gives planar bytes with C descriptors per      */
+/* sample).                                                                                        */
+#define MH_MAX_PLANES 4u
+
+/* mh_decode_crops_norm's contract, with these differences.
+ * Sample and planes: descriptor p is one sample. Its plane c (c < n_planes) is the crop [x0, x0 + w)
+ * x [y0, y0 + h) of frame `frame + c * plane_frame_stride`; all planes share the origin and the
+ * mirror flag. plane_frame_stride is 1 for images stored plane after plane and the number of
+ * images for plane-major storage; 0 is legal: one gray frame replicated into C differently
+ * normalised channels.
+ * Element (c, X, y) is T_c[v], v the byte mh_decode_frames writes at (x0 + X, y0 + y) of that
+ * plane's frame -- at (x0 + w - 1 - X, y0 + y) under MH_CROP_MIRROR -- and T_c =
+ * mh_norm_table(format, scale[c], bias[c]). scale and bias are HOST arrays of n_planes values each,
+ * read during the call and passed by value to the kernel.
+ * Output: plane c of sample p, row y starts at d_out + p * out_crop_stride + c * out_plane_stride +
+ * y * out_pitch. round_up(w, 8) elements of every row y < h are written, the first w specified, the
+ * rest unspecified; nothing else is touched, in or between planes and slots. A dense
+ * [n, C, h, round_up(w, 8)] tensor is out_plane_stride = h * out_pitch, out_crop_stride = C * h *
+ * out_pitch.
+ * Tables: plane c decodes with its own frame's prepared table, d_luts + (frame + c *
+ * plane_frame_stride) * lut_stride_bytes; a stride of 0 is one shared table.
+ * Device validation, by each of the sample's workgroups, from the descriptor alone and before
+ * anything is addressed through it: mh_decode_crops_norm's terms with `frame >= n_frames` replaced
+ * by `frame > n_frames - 1 - (n_planes - 1) * plane_frame_stride`. That limit comes from the host,
+ * so no sum of descriptor words is formed: frame = 0xFFFFFFFF is rejected. A rejected sample loads
+ * nothing through its descriptor, writes no byte of any plane and gets MH_ERR_DIMS in
+ * d_crop_status[p].
+ * Status: a sample is written whole or not at all. If d_frame_status is given and the word of any
+ * of the sample's C frames is non-zero, no byte of any of its planes is written and
+ * d_crop_status[p] is the first non-zero word in plane order; otherwise it is MH_OK. The word is
+ * written once, by one workgroup of the sample. d_crop_status must not alias d_frame_status.
+ * Checks: all before any HIP call, in mh_decode_crops_norm's order and with its codes, plus:
+ * n_planes == 0 or > MH_MAX_PLANES, NULL scale or bias, or any of the n_planes values not finite ->
+ * MH_ERR_INVALID_ARG, reported where a bad flag or format is (values at index >= n_planes are not
+ * read); (n_planes - 1) * plane_frame_stride >= n_frames -> MH_ERR_DIMS, right after the crop-size
+ * check; for n_planes > 1, out_plane_stride is a multiple of 16 (MH_ERR_ALIGN, with the other raster
+ * alignments) and >= out_pitch * h (MH_ERR_CAPACITY); for n_crops > 1, out_crop_stride >=
+ * (n_planes - 1) * out_plane_stride + out_pitch * h (MH_ERR_CAPACITY); n_crops * n_planes * CBH * S
+ * tiles or the grid above 2^31 - 1 -> MH_ERR_CAPACITY. With n_planes == 1, plane_frame_stride and
+ * out_plane_stride are ignored, and the call accepts and writes exactly what mh_decode_crops_norm
+ * does with scale[0], bias[0].
+ * One kernel launch of n_crops * n_planes * G workgroups of 8 waves: workgroup g serves unit g / G,
+ * which is sample unit / n_planes, plane unit % n_planes. G follows mh_decode_crops' rule with
+ * n_crops * n_planes units and this kernel's own occupancy. */
+int mh_decode_crops_norm_planes(const mh_frame *frame, const mh_norm_crop *d_crops, uint32_t n_crops,
+                                uint32_t w, uint32_t h, uint32_t format,
+                                uint32_t n_planes, uint32_t plane_frame_stride,
+                                const float *scale, const float *bias,
+                                const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                                const int32_t *d_frame_status, int32_t *d_crop_status,
+                                void *d_out, size_t out_pitch, size_t out_plane_stride,
+                                size_t out_crop_stride, void *stream);
+
+/* The launch shape mh_decode_crops_norm_planes would use on `stream`'s device (no launch):
+ * workgroups per (sample, plane) unit and waves per workgroup. format > 2, n_planes == 0 or
+ * n_planes > MH_MAX_PLANES -> MH_ERR_INVALID_ARG. */
+int mh_decode_crops_norm_planes_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, uint32_t h,
+                                      uint32_t format, uint32_t n_planes, void *stream,
+                                      uint32_t *groups_per_plane, uint32_t *waves_per_group);
 
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a

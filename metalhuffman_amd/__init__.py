@@ -22,6 +22,9 @@ of mdejong/MetalHuffman).
   * decoder.decode_crops_normalized   the same crops straight into normalised float16 / bfloat16 / float32
                                     elements, optionally mirrored (crop-mirror-normalize), one launch;
                                     codec.norm_table is the CPU twin of the conversion
+  * decoder.decode_crops_normalized_planes   crops of images stored as C planes (one frame each) straight into
+                                    a normalised [n, C, h, w] tensor, a (scale, bias) per plane, one launch;
+                                    codec.norm_coefficients makes the pairs from a mean and a deviation
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync;
@@ -32,14 +35,16 @@ of mdejong/MetalHuffman).
   * dist                            frame sharding, single-frame bands, table broadcast
 """
 from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS,
-                      MH_FLAG_NO_DELTA, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
+                      MH_FLAG_NO_DELTA, MH_MAX_PLANES, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
 from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, code_lengths_limited,
-                    decode_frame_cpu, encode_frame, frame_histogram, merge_blocks, norm_table, shared_header, split_blocks)
+                    decode_frame_cpu, encode_frame, frame_histogram, merge_blocks, norm_coefficients, norm_table, shared_header,
+                    split_blocks)
 
 __all__ = [
     "EXPORTS", "LIB_PATH", "MH_CODES_PAD", "MH_FLAG_LANE_PAIRS", "MH_FLAG_NO_DELTA", "MHError", "lib", "BLOCK_DIM",
     "EncodedFrame", "Huffman", "block_grid", "decode_frame_cpu", "encode_frame", "merge_blocks", "split_blocks",
     "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
     "norm_table", "MH_NORM_F16", "MH_NORM_BF16", "MH_NORM_F32", "MH_CROP_MIRROR",
+    "MH_MAX_PLANES", "norm_coefficients",
 ]
 __version__ = "0.1.0"

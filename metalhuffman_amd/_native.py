@@ -19,6 +19,7 @@ MH_ENCODE_WORKSPACE_ZEROED = 0x100  # the encoder workspace was zero-filled once
 MH_ENCODE_LIMIT_LENGTHS = 0x200  # encoders only: a tree deeper than 16 gets package-merge lengths, not -3
 MH_NORM_F16, MH_NORM_BF16, MH_NORM_F32 = 0, 1, 2  # mh_decode_crops_norm's element formats
 MH_CROP_MIRROR = 0x1  # mh_norm_crop.flags: the crop's rows reversed along x
+MH_MAX_PLANES = 4  # mh_decode_crops_norm_planes: the most planes of a sample
 MH_CODES_PAD = 4
 MH_TABLE2_MAX_ENTRIES = 257 * 256
 MH_MAX_DIM = 65535
@@ -49,6 +50,7 @@ EXPORTS = (
     "mh_decode_windows_scaled", "mh_decode_windows_scaled_shape",
     "mh_decode_crops", "mh_decode_crops_shape",
     "mh_decode_crops_norm", "mh_decode_crops_norm_shape", "mh_norm_table",
+    "mh_decode_crops_norm_planes", "mh_decode_crops_norm_planes_shape",
     "mh_encode_frames_shared_workspace_bytes", "mh_encode_frames_shared_device_async",
     "mh_frame_histogram", "mh_encode_frame_with_header",
 )
@@ -110,6 +112,7 @@ _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u16p = ctypes.POINTER(ctypes.c_uint16)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_f32p = ctypes.POINTER(ctypes.c_float)
 
 
 _diag_lp = None
@@ -196,6 +199,13 @@ def lib() -> ctypes.CDLL:
         L.mh_decode_crops_norm_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.c_uint32, ctypes.c_uint32, _vp, _u32p, _u32p]
         L.mh_norm_table.argtypes = [ctypes.c_uint32, ctypes.c_float, ctypes.c_float, _vp, ctypes.c_size_t]
+        L.mh_decode_crops_norm_planes.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                                  ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                  _f32p, _f32p, _vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_size_t,
+                                                  ctypes.c_size_t, ctypes.c_size_t, _vp]
+        L.mh_decode_crops_norm_planes_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
+                                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _u32p,
+                                                        _u32p]
         L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
                                     ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]

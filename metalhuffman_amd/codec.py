@@ -406,3 +406,22 @@ def norm_table(dtype_or_format, scale: float, bias: float) -> np.ndarray:
     out = np.empty(256, (np.float16, np.uint16, np.float32)[fmt])
     N.check(N.lib().mh_norm_table(fmt, scale, bias, out.ctypes.data_as(ctypes.c_void_p), out.nbytes), "mh_norm_table")
     return out
+
+
+def norm_coefficients(mean, std) -> tuple:
+    """(scale, bias) of decode_crops_normalized_planes for [0, 1] pixels normalised by a mean and a
+    standard deviation per channel: per channel the float32 values of 1 / (255 * std) and -mean / std,
+    computed in double and rounded once. mean and std are sequences of one length (or two numbers).
+    ValueError for a zero or non-finite std, a non-finite mean, or a result that is not finite in float32."""
+    m = np.atleast_1d(np.asarray(mean, np.float64))
+    s = np.atleast_1d(np.asarray(std, np.float64))
+    if m.ndim != 1 or m.shape != s.shape or m.size < 1:
+        raise ValueError("mean and std are sequences of one length, one value per channel")
+    if not np.isfinite(s).all() or (s == 0).any():
+        raise ValueError(f"std must be finite and not zero, not {s.tolist()!r}")
+    if not np.isfinite(m).all():
+        raise ValueError(f"mean must be finite, not {m.tolist()!r}")
+    scale, bias = (1.0 / (255.0 * s)).tolist(), (-m / s).tolist()
+    if not all(finite_f32(v) for v in scale + bias):
+        raise ValueError(f"scale and bias must be finite in float32, not {scale!r}, {bias!r}")
+    return [float(np.float32(v)) for v in scale], [float(np.float32(v)) for v in bias]

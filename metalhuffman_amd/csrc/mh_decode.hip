@@ -2021,6 +2021,87 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
               sel, scale, bias});
 }
 
+// mh_decode_crops_norm_planes: a descriptor is a SAMPLE of n_planes planes, plane c the same crop of
+// frame f + c * frame_stride under its own (scale[c], bias[c]), stored out_stride bytes behind plane
+// c - 1. Workgroup g serves unit g / G = (sample, plane). What a plane changes is workgroup-constant
+// and made here, once, ahead of slice_decode: the frame (and with it the table), the raster's base
+// and the stage's per-lane (scale, bias). The body, the maps and NormRows are the normalised crops'.
+// The verdict is that kernel's with the frame compared against p_max_frame = n_frames - 1 -
+// (n_planes - 1) * frame_stride from the host, so the sample's LAST plane names a frame and no sum
+// of descriptor words is formed ahead of it. A sample is written whole or not at all: every one of
+// its workgroups loads the status words of all its frames (workgroup-uniform, empty descriptors for
+// the planes past n_planes and without a status array), so all reach one decision, and the body gets
+// no status pointer. The sample's status word is written here, by plane 0's slice 0.
+struct PlaneArgs {
+  uint32_t n_planes, frame_stride;
+  uint64_t out_stride;
+  float scale[MH_MAX_PLANES], bias[MH_MAX_PLANES];
+};
+template <bool kDelta, uint32_t kFmt>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_planes_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const mh_norm_crop *p_crops, uint32_t p_nb, uint32_t p_tiles_per_crop, uint32_t p_groups,
+    uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_max_frame, uint32_t p_max_x0, uint32_t p_max_y0,
+    uint64_t p_lut_stride, int32_t *p_cstatus, uint32_t p_odd_w, const PlaneArgs pl, const DecodeArgs a0) {
+  const uint32_t unit = blockIdx.x / p_groups, slice = blockIdx.x - unit * p_groups;
+  uint32_t p = unit, c = 0u;
+  if (pl.n_planes != 1u) {  // uniform: one plane skips the division, as region_rs does for one segment
+    p = unit / pl.n_planes;
+    c = unit - p * pl.n_planes;
+  }
+  const v4u32 cd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_crops + p, 16u), 0, 0, 0);
+  const uint32_t f0 = __builtin_amdgcn_readfirstlane(cd.x), x0 = __builtin_amdgcn_readfirstlane(cd.y);
+  const uint32_t y0 = __builtin_amdgcn_readfirstlane(cd.z), flags = __builtin_amdgcn_readfirstlane(cd.w);
+  const bool writer = c == 0u && slice == 0u && threadIdx.x == 0u;
+  if ((f0 > p_max_frame) | (x0 > p_max_x0) | (y0 > p_max_y0) | ((flags & ~MH_CROP_MIRROR) != 0u) |
+      ((flags & p_odd_w) != 0u)) {  // workgroup-uniform
+    if (p_cstatus && writer) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  // f0 + (n_planes - 1) * frame_stride < n_frames from here on
+  uint32_t stv[MH_MAX_PLANES];
+#pragma unroll
+  for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) {
+    const bool on = p_status && i < pl.n_planes;
+    stv[i] = __builtin_amdgcn_raw_buffer_load_b32(
+        uniform_rsrc(on ? (const void *)(p_status + f0 + (uint64_t)i * pl.frame_stride) : (const void *)p_offsets,
+                     on ? 4u : 0u),
+        0, 0, 0);
+  }
+  uint32_t st = 0u;  // the first non-zero word in plane order
+#pragma unroll
+  for (int i = MH_MAX_PLANES - 1; i >= 0; --i) {
+    const uint32_t s = __builtin_amdgcn_readfirstlane(stv[i]);
+    st = s ? s : st;
+  }
+  if (p_cstatus && writer) p_cstatus[p] = (int32_t)st;
+  if (st != 0u) return;  // workgroup-uniform: a skipped sample, no plane of it is stored
+  (void)p_tiles_per_crop;
+  // The plane's frame and raster base, opaque from here on: seen through, the sums' terms stay live
+  // beside them through the body, and the raw 16-bit instantiations spilled three VGPRs.
+  uint32_t f = f0 + c * pl.frame_stride;
+  const uint64_t base = (uint64_t)a0.out + (uint64_t)p * a0.out_frame_stride + (uint64_t)c * pl.out_stride;
+  uint32_t base_lo = (uint32_t)base, base_hi = (uint32_t)(base >> 32);
+  asm volatile("" : "+s"(f), "+s"(base_lo), "+s"(base_hi));
+  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
+  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
+  DecodeArgs ac = a0;
+  ac.out = (uint8_t *)(((uint64_t)base_hi << 32) | base_lo);
+  ac.out_frame_stride = 0;
+  uint32_t sel = flags ? 0x04050607u : 0x03020100u;
+  float scale = c == 0u ? pl.scale[0] : c == 1u ? pl.scale[1] : c == 2u ? pl.scale[2] : pl.scale[3];
+  float bias = c == 0u ? pl.bias[0] : c == 1u ? pl.bias[1] : c == 2u ? pl.bias[2] : pl.bias[3];
+  asm volatile("" : "+v"(sel), "+v"(scale), "+v"(bias));
+  // one opaque word, as the normalised crops' entry
+  uint32_t rem = dx | (flags << 3) | (dy << 4) | (ow << 8);
+  asm volatile("" : "+s"(rem));
+  slice_decode<kDelta, NormRows<kFmt>>(
+      ac, p_offsets, p_frame_off, p_block_init, nullptr, p_nb, rows * p_segs, p_groups, f, slice,
+      PreparedTable{p_luts, p_lut_stride},
+      NormMap{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, rem}, 0u, nullptr}},
+              sel, scale, bias});
+}
+
 template <bool kDelta>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_headers_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_headers,
@@ -2637,7 +2718,8 @@ enum SliceKernel {
   kSliceWindows = kSliceRegion + kSliceScales,
   kSliceCrops = kSliceWindows + kSliceScales,  // one scale only
   kSliceNormCrops,                             // + the format (MH_NORM_*)
-  kSliceKernels = kSliceNormCrops + 3
+  kSlicePlanes = kSliceNormCrops + 3,          // + the format
+  kSliceKernels = kSlicePlanes + 3
 };
 #if !MH_LANE_PAIRS
 // One row per kernel, [kDelta]: the row device_info() queries the occupancy of is the row
@@ -2649,6 +2731,7 @@ using RegionFn = decltype(&mh_decode_region_kernel<false>);    // = mh_decode_re
 using WindowsFn = decltype(&mh_decode_windows_kernel<false>);  // = mh_decode_windows_scaled_kernel<_, 1..3>
 using CropsFn = decltype(&mh_decode_crops_kernel<false>);
 using NormCropsFn = decltype(&mh_decode_normcrops_kernel<false, MH_NORM_F16>);
+using PlanesFn = decltype(&mh_decode_planes_kernel<false, MH_NORM_F16>);
 using AnyKernel = void (*)();
 struct SliceRow {
   AnyKernel fn[2];
@@ -2673,6 +2756,9 @@ const SliceRow kSliceTable[] = {
     slice_row<NormCropsFn>(mh_decode_normcrops_kernel<false, MH_NORM_BF16>,
                            mh_decode_normcrops_kernel<true, MH_NORM_BF16>),
     slice_row<NormCropsFn>(mh_decode_normcrops_kernel<false, MH_NORM_F32>, mh_decode_normcrops_kernel<true, MH_NORM_F32>),
+    slice_row<PlanesFn>(mh_decode_planes_kernel<false, MH_NORM_F16>, mh_decode_planes_kernel<true, MH_NORM_F16>),
+    slice_row<PlanesFn>(mh_decode_planes_kernel<false, MH_NORM_BF16>, mh_decode_planes_kernel<true, MH_NORM_BF16>),
+    slice_row<PlanesFn>(mh_decode_planes_kernel<false, MH_NORM_F32>, mh_decode_planes_kernel<true, MH_NORM_F32>),
 };
 static_assert(sizeof(kSliceTable) / sizeof(kSliceTable[0]) == kSliceKernels, "one row per SliceKernel");
 #endif
@@ -2857,6 +2943,10 @@ struct DecodeCall {
   uint32_t allowed_flags = MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER;
   uint32_t format = 0;  // kNormCrops: MH_NORM_*
   float scale = 1.0f, bias = 0.0f;
+  // mh_decode_crops_norm_planes (kNormCrops): every descriptor is n_planes rasters, out_plane_stride
+  // bytes apart, the crops of frames plane_frame_stride apart; one plane is mh_decode_crops_norm
+  uint32_t n_planes = 1, plane_frame_stride = 0;
+  uint64_t out_plane_stride = 0;
   // call_geometry()'s results: one raster's pixel size and tiles (segs: a region's only), and the
   // number of rasters, which is the number of units the grid is cut into
   RegionExtent re = {};
@@ -2864,6 +2954,8 @@ struct DecodeCall {
   bool cropped() const { return kind == kCrops || kind == kNormCrops; }
   bool windowed() const { return kind == kWindows || cropped(); }
   bool regional() const { return kind == kRegion || windowed(); }
+  // the units the grid is cut into: a raster each (the tile cap bounds the product)
+  uint32_t units() const { return n_units * n_planes; }
   // an element's bytes, and the row of its family in kSliceTable (the scale, or the format)
   uint32_t elem() const { return kind != kNormCrops ? 1u : format == MH_NORM_F32 ? 4u : 2u; }
   uint32_t table_row() const { return kind == kNormCrops ? format : log2_scale; }
@@ -2885,7 +2977,11 @@ int call_geometry(const mh_frame *fr, DecodeCall &c) {
     c.re = {d.width, d.height, 0u, (d.block_width * d.block_height + 63) / 64};
     return MH_OK;
   }
-  if (c.cropped()) return crop_extent(d, c.rg, c.re) ? MH_OK : MH_ERR_DIMS;
+  if (c.cropped()) {
+    if (!crop_extent(d, c.rg, c.re)) return MH_ERR_DIMS;
+    // the last plane of a sample of frame 0 names a frame (64-bit: the product does not wrap)
+    return (uint64_t)(c.n_planes - 1u) * c.plane_frame_stride >= fr->n_frames ? MH_ERR_DIMS : MH_OK;
+  }
   if (!region_extent(d, c.rg, c.re)) return MH_ERR_DIMS;
   if (c.windowed()) {
     c.re.pw = 8ull * c.rg->bw;
@@ -2898,7 +2994,7 @@ int call_geometry(const mh_frame *fr, DecodeCall &c) {
 }
 
 // The tile cap: a launch addresses at most 2^31 - 1 tiles.
-bool tiles_fit(const DecodeCall &c) { return (uint64_t)c.re.tiles * c.n_units <= 0x7FFFFFFFull; }
+bool tiles_fit(const DecodeCall &c) { return (uint64_t)c.re.tiles * c.n_units * c.n_planes <= 0x7FFFFFFFull; }
 
 // The argument checks of the decode entry points, all before any HIP call. Every entry runs
 // the same rules in the same order; the frame's own table fields count only for kInFrame, and
@@ -2928,12 +3024,18 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
                    fr->table2_entries > MH_TABLE2_MAX_ENTRIES))
     return MH_ERR_TABLE;
   if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & am) || ((uintptr_t)d_out & am) ||
-      (n_rasters > 1 && (out_frame_stride & am)))
+      (n_rasters > 1 && (out_frame_stride & am)) || (c.n_planes > 1 && (c.out_plane_stride & am)))
     return MH_ERR_ALIGN;
   if (windowed && ((uintptr_t)c.windows & 15u)) return MH_ERR_ALIGN;
   if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)c.ptr & 15u) || (c.stride & 15u))))
     return MH_ERR_ALIGN;
   if (out_pitch < row_bytes || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * c.re.ph))
+    return MH_ERR_CAPACITY;
+  // planes: a plane holds its h rows, and a slot its planes -- (n_planes - 1) * out_plane_stride +
+  // out_pitch * h bytes, compared by division: the product may wrap
+  if (c.n_planes > 1 && (c.out_plane_stride < out_pitch * c.re.ph ||
+                         (n_rasters > 1 && (out_frame_stride - out_pitch * c.re.ph) / (c.n_planes - 1u) <
+                                               c.out_plane_stride)))
     return MH_ERR_CAPACITY;
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
@@ -2964,7 +3066,7 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
   a.nb = d.block_width * d.block_height;
   a.tiles_per_frame = c.re.tiles;
   if (!tiles_fit(c)) return MH_ERR_CAPACITY;
-  a.total_tiles = a.tiles_per_frame * c.n_units;
+  a.total_tiles = a.tiles_per_frame * c.units();
   return MH_OK;
 }
 
@@ -3016,9 +3118,9 @@ int launch_slices(SliceKernel family, const DecodeCall &c, const SliceArgs &p, v
   const DecodeArgs &a = p.a;
   hipStream_t s = (hipStream_t)stream;
   uint32_t G = 0;
-  const int rc = slice_shape(k, c.n_units, a.tiles_per_frame, p.delta, s, &G);
+  const int rc = slice_shape(k, c.units(), a.tiles_per_frame, p.delta, s, &G);
   if (rc != MH_OK) return rc;
-  const uint64_t grid = (uint64_t)G * c.n_units;
+  const uint64_t grid = (uint64_t)G * c.units();
   if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
   const Fn kernel = reinterpret_cast<Fn>(kSliceTable[k].fn[p.delta ? 1 : 0]);
   MH_LAUNCH(kernel, dim3((uint32_t)grid), dim3(kMaxWavesPerWG * 64), s, p.any_order, a.offsets, a.frame_off,
@@ -3037,7 +3139,7 @@ int slice_shape_entry(SliceKernel family, const mh_frame *fr, DecodeCall c, void
   int rc = call_geometry(fr, c);
   if (rc != MH_OK) return rc;
   if (c.regional() && !tiles_fit(c)) return MH_ERR_CAPACITY;
-  rc = slice_shape((SliceKernel)(family + c.table_row()), c.n_units, c.re.tiles, !(fr->flags & MH_FLAG_NO_DELTA),
+  rc = slice_shape((SliceKernel)(family + c.table_row()), c.units(), c.re.tiles, !(fr->flags & MH_FLAG_NO_DELTA),
                    (hipStream_t)stream, groups_per_unit);
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
@@ -3284,6 +3386,55 @@ int mh_decode_crops_norm_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w,
   DecodeCall c{DecodeCall::kNormCrops, nullptr, 0, &size, 0u, nullptr, n_crops};
   c.format = format;
   return slice_shape_entry(kSliceNormCrops, fr, c, stream, groups_per_crop, waves_per_group);
+}
+
+// Samples of n_planes planes into normalised [n, C, h, w] rasters: the normalised crops' checks with
+// the planes' rules beside them (DecodeCall::n_planes), n_crops * n_planes units in the shape rule and
+// the grid, and the planes kernel's rows of kSliceTable. The pairs are read here and travel by value.
+// A bad plane count or pair is reported ahead of the dims, as a bad format is; one plane is
+// mh_decode_crops_norm's call, the plane strides ignored.
+int mh_decode_crops_norm_planes(const mh_frame *fr, const mh_norm_crop *d_crops, uint32_t n_crops, uint32_t w,
+                                uint32_t h, uint32_t format, uint32_t n_planes, uint32_t plane_frame_stride,
+                                const float *scale, const float *bias, const uint16_t *d_luts,
+                                uint64_t lut_stride_bytes, const int32_t *d_frame_status, int32_t *d_crop_status,
+                                void *d_out, size_t out_pitch, size_t out_plane_stride, size_t out_crop_stride,
+                                void *stream) {
+  if (d_crop_status && d_crop_status == d_frame_status) return MH_ERR_INVALID_ARG;
+  if (n_planes == 0 || n_planes > MH_MAX_PLANES || !scale || !bias) return MH_ERR_INVALID_ARG;
+  PlaneArgs pl = {};
+  for (uint32_t i = 0; i < n_planes; ++i) {
+    if (!std::isfinite(scale[i]) || !std::isfinite(bias[i])) return MH_ERR_INVALID_ARG;
+    pl.scale[i] = scale[i];
+    pl.bias[i] = bias[i];
+  }
+  pl.n_planes = n_planes;
+  pl.frame_stride = n_planes > 1 ? plane_frame_stride : 0u;
+  pl.out_stride = n_planes > 1 ? out_plane_stride : 0u;
+  const mh_region size = {0u, 0u, w, h};
+  DecodeCall c{DecodeCall::kNormCrops, d_luts, lut_stride_bytes, &size, 0u, d_crops, n_crops};
+  c.format = format;
+  c.n_planes = n_planes;
+  c.plane_frame_stride = pl.frame_stride;
+  c.out_plane_stride = pl.out_stride;
+  SliceArgs p;
+  const int rc = slice_prologue(fr, static_cast<uint8_t *>(d_out), out_pitch, out_crop_stride, c, p);
+  if (rc != MH_OK) return rc;
+  // call_geometry: (n_planes - 1) * frame_stride < n_frames
+  const uint32_t max_frame = fr->n_frames - 1u - (n_planes - 1u) * pl.frame_stride;
+  return launch_slices<PlanesFn>(kSlicePlanes, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
+                                 d_frame_status, d_crops, c.re.segs, w, h, max_frame, fr->dims.width - w,
+                                 fr->dims.height - h, lut_stride_bytes, d_crop_status, (w & 7u) ? 1u : 0u, pl);
+}
+
+int mh_decode_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h, uint32_t format,
+                                      uint32_t n_planes, void *stream, uint32_t *groups_per_plane,
+                                      uint32_t *waves_per_group) {
+  if (n_planes == 0 || n_planes > MH_MAX_PLANES) return MH_ERR_INVALID_ARG;
+  const mh_region size = {0u, 0u, w, h};
+  DecodeCall c{DecodeCall::kNormCrops, nullptr, 0, &size, 0u, nullptr, n_crops};
+  c.format = format;
+  c.n_planes = n_planes;
+  return slice_shape_entry(kSlicePlanes, fr, c, stream, groups_per_plane, waves_per_group);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

@@ -915,6 +915,116 @@ def decode_crops_normalized(frames: DeviceFrames, tables, crops, size, dtype, sc
     return (out, cstatus) if status is True else out
 
 
+def _plane_coefficients(scale, bias):
+    """decode_crops_normalized_planes' (scale, bias): two sequences of one length C, 1..MH_MAX_PLANES,
+    every value finite in float32 -> (C, float[C] scale, float[C] bias) as ctypes arrays."""
+    try:
+        s, b = [float(v) for v in scale], [float(v) for v in bias]
+    except TypeError:
+        raise ValueError("scale and bias are sequences of one value per plane") from None
+    if len(s) != len(b) or not 1 <= len(s) <= N.MH_MAX_PLANES:
+        raise ValueError(f"scale and bias are sequences of one length, 1..{N.MH_MAX_PLANES} planes, "
+                         f"not {len(s)} and {len(b)}")
+    if not all(finite_f32(v) for v in s + b):
+        raise ValueError(f"scale and bias must be finite in float32, not {s!r}, {b!r}")
+    arr = ctypes.c_float * len(s)
+    return len(s), arr(*s), arr(*b)
+
+
+def _plane_stride(frames: DeviceFrames, n_planes: int, plane_stride) -> int:
+    ps = int(plane_stride)
+    if ps < 0 or ps > 0xFFFFFFFF or (n_planes - 1) * ps >= frames.n_frames:
+        raise ValueError(f"{n_planes} planes {ps} frames apart do not fit the {frames.n_frames} frames")
+    return ps
+
+
+def decode_crops_normalized_planes_shape(frames: DeviceFrames, n_crops: int, size, dtype, n_planes: int,
+                                         stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
+    """(workgroups per (sample, plane) unit, waves per workgroup) decode_crops_normalized_planes would
+    launch n_crops samples of n_planes planes of size = (w, h) pixels with, for `dtype`
+    (mh_decode_crops_norm_planes_shape)."""
+    w, h = _crop_size(frames, size)
+    fmt = _norm_format(dtype)
+    if int(n_crops) < 1:
+        raise ValueError("no crops")
+    if not 1 <= int(n_planes) <= N.MH_MAX_PLANES:
+        raise ValueError(f"1..{N.MH_MAX_PLANES} planes, not {n_planes}")
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    g, wv = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    N.check(N.lib().mh_decode_crops_norm_planes_shape(ctypes.byref(fr), int(n_crops), w, h, fmt, int(n_planes),
+                                                      _raw_stream_ptr(stream, dev_index), ctypes.byref(g),
+                                                      ctypes.byref(wv)),
+            "mh_decode_crops_norm_planes_shape")
+    return int(g.value), int(wv.value)
+
+
+def decode_crops_normalized_planes(frames: DeviceFrames, tables, crops, size, dtype, scale, bias,
+                                   plane_stride: int = 1, out: Optional[torch.Tensor] = None, status=None,
+                                   stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                                   skip_rejected: bool = True):
+    """decode_crops_normalized for images stored as C planes, one frame each, into a model's
+    [n, C, h, w] input in one launch (mh_decode_crops_norm_planes). A crop (frame, x0, y0[, flags]) is a
+    SAMPLE: its plane c is the crop at that origin, mirrored or not with the others, of frame
+    `frame + c * plane_stride`, every byte v as cvt(fma(float32(v), scale[c], bias[c])).
+    plane_stride is 1 for images stored plane after plane, the number of images for plane-major
+    storage, and 0 for one gray frame under C different maps.
+    -> out[n, C, h, round_up(w, 8)]; columns >= w of a written row are unspecified.
+    scale, bias: sequences of one length C, 1..MH_MAX_PLANES, each value finite in float32
+    (ValueError); codec.norm_coefficients makes them from a mean and a deviation per channel.
+    crops: decode_crops_normalized's -- a device int32 [n, 4] tensor is used in place and never read on
+    the host (the kernel rejects a sample, MH_ERR_DIMS and every plane untouched, whose last plane's
+    frame does not exist); a host list is validated here by the same rules, and also needs
+    frame + (C - 1) * plane_stride < n_frames (ValueError naming the crop).
+    A sample is written whole or not at all: with a DeviceTableSet and skip_rejected, a sample any of
+    whose C frames has a non-zero status word keeps every plane untouched, and its status is the
+    first such word in plane order.
+    out: a contiguous [n, C, h, round_up(w, 8)] tensor of `dtype` on the frames' device; None
+    allocates a ZERO-FILLED one.
+    status, tables, extra_flags, skip_rejected: decode_crops'."""
+    who = "decode_crops_normalized_planes"
+    w, h = _crop_size(frames, size)
+    fmt = _norm_format(dtype)
+    tdtype, esize = _NORM_DTYPES[fmt], (2, 2, 4)[fmt]
+    C, c_scale, c_bias = _plane_coefficients(scale, bias)
+    ps = _plane_stride(frames, C, plane_stride)
+    host = _host_norm_crops(frames, crops, w, h)
+    if host is not None:
+        bad = host[:, 0].astype(np.int64) + (C - 1) * ps >= frames.n_frames
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {C - 1} would be frame "
+                             f"{int(host[i, 0]) + (C - 1) * ps} of {frames.n_frames}")
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
+    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
+    dev = frames.codes.device
+    cols = (w + 7) // 8 * 8
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        desc = _windows_tensor(frames, crops, host)  # (an upload or a padded copy belongs to `stream`)
+        n = int(desc.shape[0])
+        shape = (n, C, h, cols)
+        if out is None:
+            out = torch.zeros(shape, dtype=tdtype, device=dev)
+        cstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
+    if (out.dtype is not tdtype or tuple(out.shape) != shape or out.get_device() != dev_index
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {tdtype} {list(shape)} tensor on cuda:{dev_index}")
+    if cstatus is not None and (not isinstance(cstatus, torch.Tensor) or cstatus.dtype is not torch.int32
+                                or cstatus.numel() != n or cstatus.get_device() != dev_index
+                                or not cstatus.is_contiguous()):
+        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
+    pitch = cols * esize
+    rc = N.lib().mh_decode_crops_norm_planes(ctypes.byref(fr), desc.data_ptr(), n, w, h, fmt, C, ps, c_scale, c_bias,
+                                             luts.data_ptr(), stride,
+                                             fstatus.data_ptr() if fstatus is not None else None,
+                                             cstatus.data_ptr() if cstatus is not None else None, out.data_ptr(),
+                                             pitch, h * pitch, C * h * pitch, _raw_stream_ptr(stream, dev_index))
+    if rc:
+        N.check(rc, "mh_decode_crops_norm_planes")
+    return (out, cstatus) if status is True else out
+
+
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
                          extra_flags: int = 0) -> tuple:
     """(workgroups per frame, waves per workgroup) decode_headers would launch with
