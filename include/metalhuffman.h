@@ -120,7 +120,32 @@ typedef struct {
  * 0xFFFFFF00 of a frame that large). Code bytes are addressed with 32 bits per frame: one
  * frame takes codes_bytes <= 0xFFFFFFF0 (more: MH_ERR_CAPACITY); a batch slot may be any
  * size and one over 0xFFFFFFF0 bytes is treated as 0xFFFFFFF0 bytes (bytes behind that read
- * as zero). frame_code_offsets themselves are 64-bit: a batch may lie beyond 4 GiB. */
+ * as zero). frame_code_offsets themselves are 64-bit: a batch may lie beyond 4 GiB.
+ *
+ * Defective streams: a defective frame harms only its own undecodable blocks. This holds for a
+ * launch whose tables or headers are valid (incomplete codes, with a Kraft sum below 1, included),
+ * in which every frame's block offsets are non-decreasing and at most 8 x the slot's bytes, and
+ * every declared byte is readable; the code bytes themselves may be anything.
+ * The reference walk of block b is 64 steps from offsets[b] over the slot's bytes -- a step looks
+ * up the 16-bit window at its bit position and advances by the entry's width -- where bytes at or
+ * past the slot's end read as zero and a zero-width lookup repeats `prev` and does not advance.
+ * Block b is SPECIFIED if its walk ends at or before offsets[b + 1]; the frame's last block, if it
+ * ends at or before 8 x the slot's bytes. A block whose code bits and offsets are intact is always
+ * specified. No margin applies: a tile's staged span runs to its last block's recorded end plus
+ * 24 bytes (16 at the slot's end, where zeros follow), and a specified walk's last window ends
+ * at most 16 bits past that end.
+ *   1. Every pixel of a specified block equals the reference walk's, through every decode entry
+ *      and at every scale (a scaled cell lies inside one block).
+ *   2. Pixels of unspecified blocks are unspecified, but written only where the entry's contract
+ *      lets that block write: write containment holds exactly as for valid streams.
+ *   3. No frame, window, crop or plane depends on any other frame's bytes, offsets or table. A
+ *      frame that mh_check reports 0, 0, 0, 0xFFFFFFFF decodes exactly, whatever its batch
+ *      neighbours hold.
+ *   4. mh_check's report is the reference walk's for every frame of ANY input: offsets that run
+ *      backwards or point past the slot and a truncated T2 included (see mh_check).
+ * The decoders do not walk as mh_check does: they stage a tile's code bytes once, so a block
+ * that walks past its recorded end reads whatever the staging window held. That is why such a
+ * block is unspecified, and all it costs. */
 typedef struct {
   const uint32_t *d_block_offsets;        /* slot [0], u32[n_frames * NB]      */
   const uint8_t *d_codes;                 /* slot [1], 16-byte aligned          */
@@ -155,13 +180,18 @@ typedef struct {
 int mh_decode(const mh_frame *frame, uint8_t *d_out, size_t out_pitch,
               size_t out_frame_stride, void *stream);
 
-/* Debug mode of the decode contract: walks every block of
- * `frame` exactly as mh_decode does and writes, per frame f, u32 d_report[4f..4f+3]:
+/* Debug mode of the decode contract: the reference walk of every block of
+ * `frame` (see mh_frame: 64 steps from the block's offset over the real bytes of the frame's slot,
+ * one thread per block, zero at or past the slot's end, whatever the offsets are -- NOT the
+ * decoders' staged walk, which agrees with it on specified blocks only). An escape at or past
+ * table2_entries counts in [1] and as a zero-width lookup in [0]. Writes, per frame f, all four
+ * words of u32 d_report[4f..4f+3], whatever they held, and nothing else:
  *   [0] zero-width lookups (windows no code matches -- the reference's {0,0}
  *       entry, HuffmanUtil.cpp:550-556, which repeats prev without advancing),
  *   [1] T1 escapes to a subtable at or past table2_entries (table index > k),
- *   [2] blocks whose 64 codes do not end at the next block's offset
- *       (a frame's last block is not checked),
+ *   [2] blocks whose 64 codes do not end at the next block's offset (a frame's last block,
+ *       whose end is not recorded: blocks whose codes run past the slot's end, bit 8 x the
+ *       slot's bytes -- so a frame that reports 0, 0, 0, 0xFFFFFFFF is specified in full),
  *   [3] the first such block (frame relative), or 0xFFFFFFFF.
  * Never writes the raster; valid reference streams report 0, 0, 0, 0xFFFFFFFF.
  * Asynchronous on `stream`. */

@@ -1,14 +1,16 @@
 // mh_check.hip -- the decode contract's optional debug mode (SURVEY.md 8(b),
-// "Errors"): walk every block exactly as the decoder does and report, per frame,
-// what the reference would silently accept:
+// "Errors"): the reference walk of every block (include/metalhuffman.h, mh_frame) -- 64 steps from
+// the block's offset over the slot's real bytes, zero at or past its end; the decoders' staged walk
+// agrees with it on specified blocks only -- reporting, per frame, what the reference would
+// silently accept:
 //   [0] zero-width lookups -- windows no code matches, the reference's {0, 0}
 //       entry (T2 dummy subtable, HuffmanUtil.cpp:550-556); the decoder emits
 //       `prev` again and does not advance (AAPLShaders.metal:258-262);
 //   [1] T1 escapes past table2_entries (a subtable index > k; the reference
 //       would read out of bounds, AAPLShaders.metal:159-170);
 //   [2] blocks whose 64 codes do not end at the next block's offset (the
-//       per-block offsets and the bitstream disagree; a frame's last block is
-//       not checked, its end is not recorded);
+//       per-block offsets and the bitstream disagree); a frame's last block, whose
+//       end is not recorded, counts when its codes run past the slot's end;
 //   [3] the first block (frame relative) with any of the above, or 0xFFFFFFFF.
 // It never writes the raster and is not on the decode path's clock: one thread
 // per block, tables read through the cache.
@@ -68,7 +70,8 @@ __global__ void __launch_bounds__(256) mh_check_kernel(const uint32_t *offsets, 
     zero_width += len == 0 ? 1u : 0u;
     pos += len;
   }
-  const uint32_t mismatch = (b + 1u < nb && pos != offsets[g + 1]) ? 1u : 0u;
+  // the last block's end is not recorded: it must lie inside the slot (fbytes < 2^61: no overflow)
+  const uint32_t mismatch = (b + 1u < nb ? pos != offsets[g + 1] : pos > 8u * fbytes) ? 1u : 0u;
   if (zero_width | bad_escape | mismatch) {
     uint32_t *r = report + 4u * f;
     if (zero_width) atomicAdd(&r[0], zero_width);

@@ -317,7 +317,9 @@ int orc_decode_frame_shader(const uint32_t *block_offsets, const uint8_t *codes,
  * per block, the same 64 steps as AAPLShaders.metal:241-268, counting
  * report[0] zero-width lookups ({0,0} entries, HuffmanUtil.cpp:550-556),
  * report[1] T1 escapes to a subtable at/after t2_entries (counted as zero width),
- * report[2] blocks (all but the last) whose codes end off the next block's offset,
+ * report[2] blocks whose codes end off the next block's offset -- the frame's last block: past the
+ *           slot's end, bit 8 * codes_bytes (its end is not recorded, but codes that run out of the
+ *           slot are not this frame's),
  * report[3] first offending block or 0xFFFFFFFF. Bytes past codes_bytes read 0. */
 void orc_check_frame(const uint32_t *block_offsets, const uint8_t *codes, uint64_t codes_bytes,
                      const orc_sym *t1, const orc_sym *t2, uint32_t t2_entries, uint32_t nb,
@@ -348,13 +350,46 @@ void orc_check_frame(const uint32_t *block_offsets, const uint8_t *codes, uint64
       if (e.bitWidth == 0) zw++;
       pos += e.bitWidth;
     }
-    const int mism = b + 1 < nb && pos != block_offsets[b + 1];
+    const int mism = b + 1 < nb ? pos != block_offsets[b + 1] : pos > 8 * codes_bytes;
     if (zw || esc || mism) {
       report[0] += zw;
       report[1] += esc;
       report[2] += (uint32_t)mism;
       if (b < report[3]) report[3] = b;
     }
+  }
+}
+
+/* The reference walk of every block, for the defect tests: orc_check_frame's 64 steps from
+ * block_offsets[b] over codes[0, codes_bytes) (bytes at or past codes_bytes read 0; a zero-width
+ * lookup, an escape at or past t2_entries included, does not advance), per block. end_bits[b] is
+ * the bit after the walk's last code, zero_width[b] its zero-width steps. Block b is "specified"
+ * (include/metalhuffman.h, mh_frame) when end_bits[b] <= block_offsets[b + 1], the frame's last
+ * block when end_bits[b] <= 8 * codes_bytes. */
+void orc_walk_frame(const uint32_t *block_offsets, const uint8_t *codes, uint64_t codes_bytes,
+                    const orc_sym *t1, const orc_sym *t2, uint32_t t2_entries, uint32_t nb,
+                    uint64_t *end_bits, uint32_t *zero_width) {
+  for (uint32_t b = 0; b < nb; b++) {
+    uint64_t pos = block_offsets[b];
+    uint32_t zw = 0;
+    for (int k = 0; k < 64; k++) {
+      const uint64_t i = pos >> 3;
+      const uint32_t m = (uint32_t)(pos & 7);
+      const uint32_t b0 = i < codes_bytes ? codes[i] : 0;
+      const uint32_t b1 = i + 1 < codes_bytes ? codes[i + 1] : 0;
+      const uint32_t b2 = i + 2 < codes_bytes ? codes[i + 2] : 0;
+      const uint32_t pat = ((((b0 << m) & 0xFF) << 8) | (b1 << m) | (b2 >> (8 - m))) & 0xFFFF;
+      orc_sym e = t1[pat >> 8];
+      if (e.bitWidth == 0) {
+        const uint32_t idx = (uint32_t)e.symbol * 256u + (pat & 0xFF);
+        if (idx < t2_entries) e = t2[idx];
+        else e.bitWidth = 0;
+      }
+      if (e.bitWidth == 0) zw++;
+      pos += e.bitWidth;
+    }
+    end_bits[b] = pos;
+    zero_width[b] = zw;
   }
 }
 

@@ -87,6 +87,14 @@ int orc_decode_frame_shader(const uint32_t *block_offsets, const uint8_t *codes,
                             uint32_t h, uint32_t bw, uint32_t bh,
                             const uint8_t *block_init, int delta, uint8_t *out);
 
+/* The reference walk per block (the defect tests): the 64 steps of AAPLShaders.metal:241-268 from
+ * block_offsets[b] over codes[0, codes_bytes), bytes at or past codes_bytes reading 0 and a
+ * zero-width lookup not advancing. end_bits[b]: the bit after the last code; zero_width[b]: the
+ * zero-width steps. */
+void orc_walk_frame(const uint32_t *block_offsets, const uint8_t *codes, uint64_t codes_bytes,
+                    const orc_sym *t1, const orc_sym *t2, uint32_t t2_entries, uint32_t nb,
+                    uint64_t *end_bits, uint32_t *zero_width);
+
 /* The whole producer pipeline of AAPLRenderer.m:374-688 for 8x8 blocks with
  * deltas on: split -> per-block delta -> encode -> offsets per block. codes
  * receives the encoder's bytes followed by 2 more zero bytes (the renderer's

@@ -73,6 +73,8 @@ def lib():
         L.orc_time_decode_pipeline.restype = ctypes.c_double
         L.orc_check_frame.argtypes = [_u32p, _u8p, ctypes.c_uint64, _u8p, _u8p, ctypes.c_uint32,
                                       ctypes.c_uint32, _u32p]
+        L.orc_walk_frame.argtypes = [_u32p, _u8p, ctypes.c_uint64, _u8p, _u8p, ctypes.c_uint32,
+                                     ctypes.c_uint32, _u64p, _u32p]
         _lib = L
     return _lib
 
@@ -196,6 +198,21 @@ def check_frame(offsets, codes, t1, t2) -> np.ndarray:
     lib().orc_check_frame(_p(offsets, _u32p), _p(codes), ctypes.c_uint64(codes.size), _p(t1), _p(t2),
                           ctypes.c_uint32(t2.size // 2), ctypes.c_uint32(offsets.size), _p(rep, _u32p))
     return rep
+
+
+def walk_frame(offsets, codes, t1, t2):
+    """The reference walk of every block of one frame over codes[0, codes.size) (see
+    orc_walk_frame) -> (end bit u64[nb], zero-width steps u32[nb])."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    t1 = np.ascontiguousarray(t1, dtype=np.uint8)
+    t2 = np.ascontiguousarray(t2, dtype=np.uint8)
+    ends = np.zeros(offsets.size, np.uint64)
+    zw = np.zeros(offsets.size, np.uint32)
+    lib().orc_walk_frame(_p(offsets, _u32p), _p(codes), ctypes.c_uint64(codes.size), _p(t1), _p(t2),
+                         ctypes.c_uint32(t2.size // 2), ctypes.c_uint32(offsets.size), _p(ends, _u64p),
+                         _p(zw, _u32p))
+    return ends, zw
 
 
 def encode_frame(img: np.ndarray):

@@ -233,7 +233,7 @@ def _launch(entry, up, tabs, what, k, d_out, pitch, stride, device):
     return status
 
 
-def run_contained(entry, device, geom, up, tabs, what=None, k=0):
+def run_contained(entry, device, geom, up, tabs, what=None, k=0, care=None):
     """One launch of any of the seven entries through the C ABI into rasters laid out inside
     helpers.containment_plan's pattern-filled buffer, then a check of EVERY byte of it: slot p may be
     written in its first rows_p rows x `cols` columns and nowhere else, holds its expected picture in
@@ -241,16 +241,41 @@ def run_contained(entry, device, geom, up, tabs, what=None, k=0):
     what: None (frames, headers), a block region (bx0, by0, bw, bh), ([(frame, bx0, by0)], (bw, bh))
     for windows or ([(frame, x0, y0)], (w, h)) for crops. geom: "tight", "loose"
     (scaled_helpers.scaled_geometry with c = 8 >> k) or (pitch, stride, lead, tail). Per-window and
-    per-crop status words must be 0, as must the headers' verdicts."""
+    per-crop status words must be 0, as must the headers' verdicts.
+    care: None, or one bool[H, W] per frame (uniform over every 8 x 8 block): a picture's pixels are
+    compared only where its frame's mask is True; the guard bytes are compared everywhere."""
     import torch
     c = 8 >> k
     cols, rows, pics = slots_of(entry, up, what, k)
     n = len(pics)
+    cares = None
+    if care is not None:
+        # a scaled cell lies inside one block, so the mask's cells reduce to 0 or 255 exactly
+        masks = dataclasses.replace(up, wants=[np.where(m, 255, 0).astype(np.uint8) for m in care])
+        cares = [m == 255 for m, _ in slots_of(entry, masks, what, k)[2]]
+        assert all(m.shape == pic.shape for m, (pic, _) in zip(cares, pics))
     if isinstance(geom, str):
         pitch, stride, lead = S.scaled_geometry(geom, cols, rows, c)
         tail = 8 * pitch + 4096
     else:
         pitch, stride, lead, tail = geom
+    if geom == "loose":
+        assert pitch % (2 * c) == c and stride % (2 * c) == c
+    rects = [(what[0][p], what[1]) if entry in ("windows", "windows_scaled", "crops") else what for p in range(n)]
+    run_slots(device, cols, rows, pics, (pitch, stride, lead, tail),
+              lambda d_out: _launch(entry, up, tabs, what, k, d_out, pitch, stride, device),
+              label=lambda p: f"{entry}, slot {p} = {rects[p]}, k {k}", cares=cares,
+              align=(256, 0) if geom == "tight" else (2 * c, c) if geom == "loose" else (16, 8))
+
+
+def run_slots(device, cols, rows, pics, geom, launch, label=lambda p: f"slot {p}", cares=None, align=None):
+    """run_contained's body for any launch: pics = [(picture u8[ph <= rows, pw <= cols], zeros beyond
+    it)] per slot, geom = (pitch, stride, lead, tail), launch(d_out) -> a status tensor (every word
+    must be 0) or None, cares = None or a bool mask per picture (compare only where True), align =
+    (modulus, remainder) d_out must have."""
+    import torch
+    pitch, stride, lead, tail = geom
+    n = len(pics)
     base = containment_plan(n, 1, rows, pitch, stride, lead, tail, written_cols=cols)
     may = np.zeros(base.size, bool)
     for p, (pic, _) in enumerate(pics):
@@ -262,31 +287,30 @@ def run_contained(entry, device, geom, up, tabs, what=None, k=0):
     plan = dataclasses.replace(base, W=0, may_write=may)
     buf = torch.from_numpy(base.pattern.copy()).to(device)
     d_out = buf.data_ptr() + plan.d_out
-    if geom == "tight":
-        assert d_out % 256 == 0
-    elif geom == "loose":
-        assert d_out % (2 * c) == c and pitch % (2 * c) == c and stride % (2 * c) == c
-    else:
-        assert d_out % 16 == 8
-    status = _launch(entry, up, tabs, what, k, d_out, pitch, stride, device)
+    if align is not None:
+        assert d_out % align[0] == align[1], (d_out, align)
+    status = launch(d_out)
     if status is not None:
         st = status.cpu().tolist()
         assert st == [0] * len(st), st
+    torch.cuda.synchronize(device)
     after = buf.cpu().numpy()
     del buf
     check_containment(after, plan, [np.empty((rows, 0), np.uint8)] * n)
     got = base.frame_view(after, cols)
     for p, (pic, zeros) in enumerate(pics):
         ph, pw = pic.shape
-        if not np.array_equal(got[p, :ph, :pw], pic):
-            ys, xs = np.nonzero(got[p, :ph, :pw] != pic)
+        wrong = got[p, :ph, :pw] != pic
+        if cares is not None:
+            wrong &= cares[p]
+        if wrong.any():
+            ys, xs = np.nonzero(wrong)
             y, x = int(ys[0]), int(xs[0])
-            rect = (what[0][p], what[1]) if entry in ("windows", "windows_scaled", "crops") else what
-            raise AssertionError(f"{entry}, slot {p} = {rect}, k {k}: {ys.size} wrong pixel(s) of {ph} x {pw}, first at "
+            raise AssertionError(f"{label(p)}: {ys.size} wrong pixel(s) of {ph} x {pw}, first at "
                                  f"row {y}, column {x}: {int(got[p, y, x]):#04x}, expected {int(pic[y, x]):#04x}; last at "
                                  f"row {int(ys[-1])}, column {int(xs[-1])}")
         if zeros:
-            assert (got[p, :ph, pw:] == 0).all(), f"{entry}, slot {p}, k {k}: written columns >= SW = {pw} are not 0"
+            assert (got[p, :ph, pw:] == 0).all(), f"{label(p)}: written columns >= SW = {pw} are not 0"
 
 
 # ---- the seeded sweep -------------------------------------------------------------------------------------

@@ -55,6 +55,18 @@ def test_oracle_zero_width(mh, oracle):
     assert rep[0] == 64 and rep[1] == 0 and rep[2] == 1 and rep[3] == 0
 
 
+def test_oracle_last_block_outside_the_slot(mh, oracle, bigbridge):
+    """A frame's last block has no recorded end; it counts in [2] when its codes run past the slot's
+    end (bytes from there on read zero), so a frame that reports clean is decodable in full."""
+    ef = _frame(mh, np.ascontiguousarray(bigbridge[:256, :256]))
+    t1, t2 = ef.tables()
+    last = ef.n_blocks - 1
+    cut = (int(ef.block_offsets[last]) + 7) // 8 + 1        # the slot ends one byte into the last block
+    assert cut < ef.payload_bytes
+    assert oracle.check_frame(ef.block_offsets, ef.codes[:cut], t1, t2).tolist() == [0, 0, 1, last]
+    assert oracle.check_frame(ef.block_offsets, ef.codes[: ef.payload_bytes], t1, t2).tolist() == CLEAN
+
+
 def test_oracle_escape_past_t2(mh, oracle, bigbridge):
     ef = _frame(mh, bigbridge)
     t1, t2 = ef.tables()

@@ -182,14 +182,29 @@ def test_tile_8192_roundtrip(mh, device, bigbridge):
     assert np.array_equal(out, img)
 
 
-def test_garbage_stream_no_fault(mh, device, bigbridge):
-    """Corrupt codes with valid tables/offsets: must complete without a fault."""
+def test_garbage_stream_no_fault(mh, oracle, device, bigbridge):
+    """Corrupt codes with valid tables/offsets: must complete without a fault, and every SPECIFIED block
+    -- one whose reference walk (64 steps from its offset over the slot, zero past its end) ends at or
+    before the next block's offset -- decodes as the oracle decodes it (include/metalhuffman.h,
+    mh_frame). The others may hold anything."""
     ef = mh.encode_frame(np.ascontiguousarray(bigbridge[:768, :1024]))
     bad = np.random.default_rng(5).integers(0, 256, size=ef.codes.size, dtype=np.uint8)
     bad[-4:] = 0
     ef.codes = bad
     out = _decode([ef], device)[0]
     assert out.shape == (768, 1024)
+    t1, t2 = ef.tables()
+    slot = np.zeros(-(-bad.size // 16) * 16, np.uint8)     # the packed frame's slot: zero-filled to 16 bytes
+    slot[: bad.size] = bad
+    ends, _ = oracle.walk_frame(ef.block_offsets, slot, t1, t2)
+    spec = ends <= np.append(ef.block_offsets[1:].astype(np.uint64), np.uint64(8 * slot.size))
+    print(f"garbage stream: {int(spec.sum())} of {spec.size} blocks are specified")
+    assert 100 <= int(spec.sum()) < spec.size
+    want = oracle.decode_frame_shader(ef.block_offsets, np.concatenate([slot, np.zeros(256, np.uint8)]), t1, t2,
+                                      1024, 768)
+    care = np.kron(spec.reshape(96, 128), np.ones((8, 8), bool)).astype(bool)
+    wrong = (out != want) & care
+    assert not wrong.any(), f"{int(wrong.sum())} wrong pixel(s) in specified blocks, first at {np.argwhere(wrong)[0]}"
 
 
 def test_raster_beyond_2_gib(mh, device):
