@@ -606,7 +606,7 @@ int mh_norm_table(uint32_t format, float scale, float bias, void *table, size_t 
 /* a SAMPLE: its C planes are the same crop of C frames, each under its own (scale, bias).         */
 /* Not covered: channels-last output; a pair per crop; vertical flips; crops at a reduced scale; a */
 /* byte output with planes (mh_decode_crops already gives planar bytes with C descriptors per      */
-/* sample).                                                                                        */
+/* sample). mh_encode_images_device_async produces such plane frames from interleaved pixels.      */
 #define MH_MAX_PLANES 4u
 
 /* mh_decode_crops_norm's contract, with these differences.
@@ -837,6 +837,97 @@ int mh_encode_frames_shared_device_async(
     uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
     int32_t *d_status,             /* optional, int32[n_frames] */
     int32_t *d_header_status,      /* optional, one int32: the header's verdict */
+    void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* Interleaved, pitched images encoded straight into C-plane frames: the producer of what     */
+/* mh_decode_crops_norm_planes consumes. Decoders, capture APIs and image tensors hand over    */
+/* [H, W, K] pixels, often with a row pitch above W * K or as a window of a larger picture;     */
+/* these entries read that layout in place -- no transposed copy, no second buffer -- and       */
+/* write one frame per taken plane, each byte for byte the host codec's for that plane.        */
+typedef struct {
+  uint64_t image_stride;   /* bytes from image i to image i + 1                       */
+  uint64_t row_pitch;      /* bytes from row y to row y + 1                           */
+  uint32_t pixel_stride;   /* bytes from pixel x to pixel x + 1 (3 = RGB, 4 = RGBA..) */
+  uint32_t first_channel;  /* plane c is byte first_channel + c of every pixel        */
+  uint32_t n_planes;       /* C, 1..MH_MAX_PLANES                                     */
+  uint32_t plane_major;    /* 0: frame = i*C + c   (plane_frame_stride 1 on decode)   */
+                           /* 1: frame = c*n + i   (plane_frame_stride n_images)      */
+} mh_image_layout;
+
+/* The kernels address one tile of 256 blocks through one 32-bit descriptor that starts at the
+ * tile's first pixel row. A tile lies in at most MH_IMAGE_TILE_ROWS(width) rows, so a layout
+ * is addressable when
+ *   (min(height, MH_IMAGE_TILE_ROWS(width)) - 1) * row_pitch + width * pixel_stride
+ *     <= MH_IMAGE_TILE_SPAN_MAX
+ * (16 rows for widths of 2,033 and more, 2,048 rows for widths up to 8). */
+#define MH_IMAGE_TILE_SPAN_MAX 0x7FFFFFF0ull
+#define MH_IMAGE_TILE_ROWS(width) (8u * (254u / (((width) + 7u) / 8u) + 2u))
+
+/* Device workspace of the two entries below: the frames entries' for n_images * n_planes
+ * frames (0 when that count is above 2^31 - 1). */
+size_t mh_encode_images_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_images, uint32_t n_planes);
+size_t mh_encode_images_shared_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_images,
+                                               uint32_t n_planes);
+
+/* mh_encode_frames_device_async reading n_images interleaved images of width x height pixels.
+ * Input: sample (i, c, x, y) -- image i, plane c < C = layout->n_planes -- is the byte at
+ * d_pixels + i * image_stride + y * row_pitch + x * pixel_stride + first_channel + c.
+ * Output: n_images * C frames of width x height, plane c of image i being frame i * C + c
+ * (plane_major 0) or c * n_images + i (plane_major 1). Every per-frame output -- header, code
+ * slot, d_codes_len, d_block_offsets, d_block_init, d_status, d_frame_code_offsets -- is indexed
+ * by that frame number and laid out as mh_encode_frames_device_async lays it out for n_frames =
+ * n_images * C, so the result is one mh_frame batch of n_images * C frames: for
+ * mh_build_luts_device, mh_decode_frames, the region / windows / crops entries, and
+ * mh_decode_crops_norm_planes with plane_frame_stride 1 (plane_major 0) or n_images (1).
+ * Exactness: for every accepted frame the header, the codes with their pad, d_codes_len, the
+ * block offsets and the init bytes are byte for byte mh_encode_frame's for the de-interleaved
+ * plane. With n_planes = 1, pixel_stride = 1, first_channel = 0 and row_pitch = width the call
+ * accepts and writes exactly what mh_encode_frames_device_async does with gray_frame_stride =
+ * image_stride.
+ * Reads: of image i only bytes in [i * image_stride, i * image_stride + (height - 1) * row_pitch
+ * + width * pixel_stride) are loaded: wide loads may touch row padding and unselected channels
+ * inside that span, nothing behind the last pixel of the last row and nothing between images.
+ * No output depends on a byte that is not a selected sample.
+ * Alignment: none is required of d_pixels or of any stride. With pixel_stride <= 4 and d_pixels,
+ * row_pitch (height > 1) and image_stride (n_images > 1) all multiples of 4, a block row's 8 *
+ * pixel_stride bytes are loaded as dwords and the plane's bytes picked in registers; every
+ * other layout takes one byte load per sample.
+ * Checks, all before any HIP call, in mh_encode_frames_device_async's order and with its codes
+ * (n_images where it has n_frames), plus: NULL layout, n_planes == 0 or > MH_MAX_PLANES, or
+ * plane_major > 1 -> MH_ERR_INVALID_ARG (with the NULL checks); pixel_stride == 0 or
+ * first_channel + n_planes > pixel_stride -> MH_ERR_DIMS (with the dims check); and, in the
+ * place of the gray_frame_stride check, MH_ERR_CAPACITY for height > 1 and row_pitch < width *
+ * pixel_stride, for n_images > 1 and image_stride below an image's span (above), and for a
+ * layout that is not addressable (MH_IMAGE_TILE_SPAN_MAX above; row_pitch is ignored for height
+ * == 1 and image_stride for n_images == 1). n_images * C counts as n_frames in every limit of
+ * the frames entry: above 2^31 - 1 frames or tiles -> MH_ERR_CAPACITY, and the workspace is
+ * mh_encode_images_workspace_bytes().
+ * flags, d_status and every other argument: mh_encode_frames_device_async's. A rejected plane
+ * frame disturbs neither its sibling planes nor the other images.
+ * Launches: three, as the frames entry; the split and the packer are its kernels with another
+ * pixel fetch. The planes of one tile are served by workgroups eight apart in the grid, so
+ * that the later ones find the source lines in the first one's L2. */
+int mh_encode_images_device_async(const uint8_t *d_pixels, const mh_image_layout *layout, uint32_t n_images,
+                                  uint32_t width, uint32_t height, uint32_t flags, uint8_t *d_canon_headers,
+                                  uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
+                                  uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
+                                  int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* mh_encode_frames_shared_device_async reading interleaved images: input, frame order, reads,
+ * alignment and the added checks are mh_encode_images_device_async's; modes, outputs, statuses
+ * and the remaining checks are mh_encode_frames_shared_device_async's with n_frames = n_images *
+ * C (built mode: n_images * C * NB * 64 < 2^32 symbols). For every accepted frame the codes,
+ * d_codes_len and the block offsets are byte for byte mh_encode_frame_with_header's for the
+ * de-interleaved plane and the one header; in built mode that header is mh_code_lengths (or
+ * the length-limited code) of the histogram summed over all n_images * C planes. */
+int mh_encode_images_shared_device_async(
+    const uint8_t *d_pixels, const mh_image_layout *layout, uint32_t n_images,
+    uint32_t width, uint32_t height, uint32_t flags,
+    const uint8_t *d_canon_in, uint8_t *d_canon_header,
+    uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
+    uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
+    int32_t *d_status, int32_t *d_header_status,
     void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------- */

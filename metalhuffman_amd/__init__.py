@@ -30,14 +30,17 @@ of mdejong/MetalHuffman).
                                     n tables -> decode on one stream, no host sync;
                                     encode_shared_async: the batch under ONE table (built from the summed
                                     histogram, or a supplied header) for decoder.decode;
-                                    codec.shared_header / encode_frame(header=) are the CPU twins
+                                    codec.shared_header / encode_frame(header=) are the CPU twins;
+                                    encode_images_async / encode_images_shared_async: interleaved, pitched
+                                    [n, H, W, K] pixels (any view with adjacent channels) straight into C-plane
+                                    frames, no transposed copy; codec.image_planes defines the planes
   * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
 """
 from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS,
                       MH_FLAG_NO_DELTA, MH_MAX_PLANES, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
 from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, code_lengths_limited,
-                    decode_frame_cpu, encode_frame, frame_histogram, merge_blocks, norm_coefficients, norm_table, shared_header,
+                    decode_frame_cpu, encode_frame, frame_histogram, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
                     split_blocks)
 
 __all__ = [
@@ -45,6 +48,6 @@ __all__ = [
     "EncodedFrame", "Huffman", "block_grid", "decode_frame_cpu", "encode_frame", "merge_blocks", "split_blocks",
     "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
     "norm_table", "MH_NORM_F16", "MH_NORM_BF16", "MH_NORM_F32", "MH_CROP_MIRROR",
-    "MH_MAX_PLANES", "norm_coefficients",
+    "MH_MAX_PLANES", "norm_coefficients", "image_planes",
 ]
 __version__ = "0.1.0"

@@ -53,6 +53,8 @@ EXPORTS = (
     "mh_decode_crops_norm_planes", "mh_decode_crops_norm_planes_shape",
     "mh_encode_frames_shared_workspace_bytes", "mh_encode_frames_shared_device_async",
     "mh_frame_histogram", "mh_encode_frame_with_header",
+    "mh_encode_images_workspace_bytes", "mh_encode_images_shared_workspace_bytes",
+    "mh_encode_images_device_async", "mh_encode_images_shared_device_async",
 )
 
 
@@ -103,6 +105,20 @@ class mh_crop(ctypes.Structure):
 class mh_norm_crop(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32)]
+
+
+class mh_image_layout(ctypes.Structure):
+    _fields_ = [("image_stride", ctypes.c_uint64), ("row_pitch", ctypes.c_uint64),
+                ("pixel_stride", ctypes.c_uint32), ("first_channel", ctypes.c_uint32),
+                ("n_planes", ctypes.c_uint32), ("plane_major", ctypes.c_uint32)]
+
+
+MH_IMAGE_TILE_SPAN_MAX = 0x7FFFFFF0  # mh_encode_images_*: the most bytes one tile's descriptor spans
+
+
+def image_tile_rows(width: int) -> int:
+    """MH_IMAGE_TILE_ROWS(width): the most pixel rows one tile of 256 blocks lies in."""
+    return 8 * (254 // ((width + 7) // 8) + 2)
 
 
 _lib = None
@@ -260,6 +276,13 @@ def lib() -> ctypes.CDLL:
                                                            ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
                                                            ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                            ctypes.c_size_t, _vp]
+        for name in ("mh_encode_images_workspace_bytes", "mh_encode_images_shared_workspace_bytes"):
+            getattr(L, name).argtypes = [ctypes.c_uint32] * 4
+            getattr(L, name).restype = ctypes.c_size_t
+        L.mh_encode_images_device_async.argtypes = (
+            [_vp, ctypes.POINTER(mh_image_layout)] + L.mh_encode_frames_device_async.argtypes[2:])
+        L.mh_encode_images_shared_device_async.argtypes = (
+            [_vp, ctypes.POINTER(mh_image_layout)] + L.mh_encode_frames_shared_device_async.argtypes[2:])
         L.mh_frame_histogram.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
                                          _u64p]
         L.mh_encode_frame_with_header.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p,

@@ -338,6 +338,26 @@ def encode_frame(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False
     return EncodedFrame(w, h, canon, codes[: ln.value].copy(), offs, init, flags)
 
 
+def image_planes(images, first_channel: int = 0, n_planes=None, plane_major: bool = False) -> np.ndarray:
+    """The plane frames of interleaved images, in the frame order of
+    BatchEncoder.encode_images_async (mh_encode_images_device_async): uint8 [n, H, W, K] (or one
+    [H, W, K] image) -> contiguous [n * C, H, W], plane c being byte first_channel + c of every
+    pixel and C = n_planes (default: every channel from first_channel on). Plane c of image i
+    is frame i * C + c, or c * n + i with plane_major. The definition the encoder's tests
+    compare against: its output is encode_frame of each of these frames."""
+    a = np.asarray(images)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4):
+        raise ValueError("expected uint8 images [n, H, W, K] or one image [H, W, K]")
+    if a.ndim == 3:
+        a = a[None]
+    n, h, w, k = a.shape
+    c = k - first_channel if n_planes is None else int(n_planes)
+    if first_channel < 0 or c < 1 or first_channel + c > k:
+        raise ValueError(f"planes {first_channel}..{first_channel + c - 1} of {k}-channel pixels")
+    planes = a[..., first_channel:first_channel + c].transpose((3, 0, 1, 2) if plane_major else (0, 3, 1, 2))
+    return np.ascontiguousarray(planes).reshape(n * c, h, w)
+
+
 def decode_frame_cpu(ef: EncodedFrame, threads: int = 1) -> np.ndarray:
     """CPU twin of the GPU decode for one frame (mh_decode_frame_cpu): the shader
     semantics per block, straight to the H x W raster, on `threads` host threads."""

@@ -18,7 +18,10 @@
 // Batches: mh_encode_frames_device_async (a tree per frame, three launches) and
 // mh_encode_frames_shared_device_async (ONE table for the batch, built from the summed
 // histogram -- five launches -- or supplied as 256 code lengths -- four; see "batched
-// frames under ONE table" below).
+// frames under ONE table" below). mh_encode_images_[shared_]device_async are those two
+// entries reading interleaved, pitched images: one frame per taken plane, the split and
+// the packer with another pixel fetch (see "interleaved, pitched images" below;
+// mh_encode_pack_wave.inc holds the packer's body for both).
 // mh_encode_frame_device_async never synchronises (header, code bytes and status are
 // written to device memory); mh_encode_frame_device runs it and synchronises once at
 // the end to return the header and the byte count on the host.
@@ -54,6 +57,9 @@ constexpr uint32_t kFusedMaxTiles = 512;  // frames up to this many tiles take t
 #endif
 #ifndef MH_DIAG_PACK_NO_OR  // diagnostic builds only: the batched packer without its LDS code-word
 #define MH_DIAG_PACK_NO_OR 0  // ORs (wrong output; the packer's time without them)
+#endif
+#ifndef MH_DIAG_IMG_PLAIN_MAP  // diagnostic builds only: image workgroup g = frame * units + unit, the
+#define MH_DIAG_IMG_PLAIN_MAP 0  // planes of a tile a whole frame apart (the A/B of img_unit's mapping)
 #endif
 #ifndef MH_CODE_STAMPS  // diagnostic builds only: s_memrealtime phase stamps of enc_code_kernel
 #define MH_CODE_STAMPS 0
@@ -396,6 +402,241 @@ __global__ void __launch_bounds__(256) enc_split_kernel(const uint8_t *gray, uin
   __builtin_amdgcn_s_waitcnt(0);
   MH_SPLIT_STAMP(4)
 #endif
+}
+
+// ---- interleaved, pitched images: mh_encode_images_[shared_]device_async ---------------
+// The batched path with another pixel fetch: sample (i, c, x, y) is the byte at
+// pixels + i * image_stride + y * pitch + x * ps + fc + c, and plane c of image i is frame
+// i * C + c (plane_major: c * n + i) of an n * C frame batch. Everything behind the fetch
+// -- row_symbols, histogram, trees, plan, packing -- is the planar path's.
+struct ImgSrc {
+  uint64_t image_stride;
+  uint32_t pitch;  // bytes from row to row (0 for a one-row image: never used)
+  uint32_t ps;     // bytes from pixel to pixel
+  uint32_t fc;     // byte of a pixel that is plane 0
+  uint32_t C;      // planes taken per image
+  uint32_t n;      // images
+  uint32_t plane_major;
+};
+// Fetch modes (template kPs): 1-4 = that pixel stride with a 4-byte aligned base, pitch and
+// image stride -- a block row's 8 * kPs bytes arrive as dwords and the plane's 8 bytes are
+// picked in registers (v_perm_b32); kBytePs = any stride and alignment, one byte load per
+// sample.
+constexpr uint32_t kBytePs = 0xFFu;
+// Largest extent of one tile's descriptor (enc_rsrc's clamp): the host refuses layouts
+// whose tile could reach past it (image_limits_ok).
+constexpr uint64_t kMaxTileSpan = 0x7FFFFFF0ull;
+
+// Workgroup g of a launch with `per` units (split: tiles; packer: workgroups) per frame ->
+// (frame f, unit t, image img, plane c). The C planes of a unit read the same source
+// lines, so within an image the units go in chunks of eight and a chunk's planes follow
+// each other: workgroups g and g + 8 are the same unit's planes c and c + 1, dispatched
+// moments apart and -- as observed on this part, for speed only -- to the same XCD, whose L2
+// then serves the second reader. A last chunk of m < 8 units puts
+// them m apart. All uniform.
+__device__ __forceinline__ void img_unit(const ImgSrc &im, uint32_t g, uint32_t per, uint32_t &f, uint32_t &t,
+                                         uint32_t &img, uint32_t &c) {
+  if (MH_DIAG_IMG_PLAIN_MAP) {
+    f = g / per;
+    t = g - f * per;
+    img = im.plane_major ? f % im.n : f / im.C;
+    c = im.plane_major ? f / im.n : f % im.C;
+    return;
+  }
+  const uint32_t per_img = per * im.C;
+  img = g / per_img;
+  const uint32_t idx = g - img * per_img, chunk = idx / (8u * im.C), base = chunk * 8u;
+  const uint32_t m = min(8u, per - base), j = idx - base * im.C;
+  c = j / m;
+  t = base + (j - c * m);
+  f = im.plane_major ? c * im.n + img : img * im.C + c;
+}
+
+// The 8 samples of byte `ch` of 8 pixels kPs bytes apart, from the 8 * kPs bytes at buffer
+// offset off (4-byte aligned; kOob or beyond: zeros) as dword loads, picked with
+// v_perm_b32 (selector bytes 0-3: the second operand's, 4-7: the first's, 0x0c: zero).
+template <uint32_t kPs>
+__device__ __forceinline__ uint64_t img_row_wide(__amdgpu_buffer_rsrc_t rg, uint32_t off, uint32_t ch) {
+  typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
+  typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
+  static_assert(kPs >= 1 && kPs <= 4, "dword modes");
+  if constexpr (kPs == 1) {
+    const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(rg, (int)off, 0, 0);
+    return ((uint64_t)v.y << 32) | v.x;
+  } else if constexpr (kPs == 2) {
+    const v4u32 a = __builtin_amdgcn_raw_buffer_load_b128(rg, (int)off, 0, 0);
+    const uint32_t sel = 0x06040200u + ch * 0x01010101u;  // bytes ch, ch + 2 of each dword
+    return ((uint64_t)__builtin_amdgcn_perm(a.w, a.z, sel) << 32) | __builtin_amdgcn_perm(a.y, a.x, sel);
+  } else {
+    // pairs of samples into the low halves, then two pairs into a dword
+    constexpr uint32_t kJoin = 0x05040100u;
+    const v4u32 a = __builtin_amdgcn_raw_buffer_load_b128(rg, (int)off, 0, 0);
+    const uint32_t c2 = ch * 0x0101u;
+    if constexpr (kPs == 3) {
+      // sample j is byte ch + 3 j of 24: j = 0, 1 lie in dwords 0-1, j = 2, 3 in 1-2,
+      // j = 4, 5 in 3-4, j = 6, 7 in 4-5 for every ch < 3
+      const v2u32 b = __builtin_amdgcn_raw_buffer_load_b64(rg, (int)(off + 16u), 0, 0);
+      const uint32_t s0 = 0x0c0c0300u + c2, s1 = 0x0c0c0502u + c2;
+      const uint32_t p0 = __builtin_amdgcn_perm(a.y, a.x, s0), p1 = __builtin_amdgcn_perm(a.z, a.y, s1);
+      const uint32_t p2 = __builtin_amdgcn_perm(b.x, a.w, s0), p3 = __builtin_amdgcn_perm(b.y, b.x, s1);
+      return ((uint64_t)__builtin_amdgcn_perm(p3, p2, kJoin) << 32) | __builtin_amdgcn_perm(p1, p0, kJoin);
+    } else {
+      const v4u32 b = __builtin_amdgcn_raw_buffer_load_b128(rg, (int)(off + 16u), 0, 0);
+      const uint32_t s = 0x0c0c0400u + c2;  // byte ch of two dwords
+      const uint32_t p0 = __builtin_amdgcn_perm(a.y, a.x, s), p1 = __builtin_amdgcn_perm(a.w, a.z, s);
+      const uint32_t p2 = __builtin_amdgcn_perm(b.y, b.x, s), p3 = __builtin_amdgcn_perm(b.w, b.z, s);
+      return ((uint64_t)__builtin_amdgcn_perm(p3, p2, kJoin) << 32) | __builtin_amdgcn_perm(p1, p0, kJoin);
+    }
+  }
+}
+
+// ... as byte loads: the first nv samples (the pixels inside the frame), zero behind them.
+__device__ __forceinline__ uint64_t img_row_bytes(__amdgpu_buffer_rsrc_t rg, uint32_t off, bool in, uint32_t nv,
+                                                  uint32_t ps, uint32_t ch) {
+  uint64_t q = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < 8; ++c)
+    q |= (uint64_t)__builtin_amdgcn_raw_buffer_load_b8(rg, (int)(in && c < nv ? off + c * ps + ch : kOob), 0, 0)
+         << (8 * c);
+  return q;
+}
+
+// A block row of plane byte ch: the pixels at buffer offset off (the row's first pixel), nv
+// (1..8) of them inside the frame, zero for a lane that is not `in`. span: the bytes of the
+// image behind the descriptor's base, the most a load may touch. Dword modes load the
+// whole 8 * kPs bytes -- row padding, unselected channels and, past the right edge, the
+// next row's pixels ride along and are masked off -- unless that would reach past the
+// image's last sample: such a lane (the end of the last rows; rare, so a branch) takes
+// byte loads instead.
+// img_row_dwords is the branch-free part (*fix: the lane must take the byte loads instead),
+// so that a caller with several rows in flight issues all their loads before any fix-up.
+template <uint32_t kPs>
+__device__ __forceinline__ uint64_t img_row_dwords(__amdgpu_buffer_rsrc_t rg, uint32_t off, bool in, uint32_t nv,
+                                                   uint32_t span, uint32_t ch, bool *fix) {
+  const bool wide = in && off + 8u * kPs <= span;
+  *fix = in && !wide;
+  const uint64_t q = img_row_wide<kPs>(rg, wide ? off : kOob, ch);
+  const uint32_t lo = nv >= 4u ? 0xFFFFFFFFu : (1u << (8u * nv)) - 1u;
+  const uint32_t hi = nv >= 8u ? 0xFFFFFFFFu : nv <= 4u ? 0u : (1u << (8u * nv - 32u)) - 1u;
+  return q & (((uint64_t)hi << 32) | lo);
+}
+template <uint32_t kPs>
+__device__ __forceinline__ uint64_t img_row(__amdgpu_buffer_rsrc_t rg, uint32_t off, bool in, uint32_t nv,
+                                            uint32_t span, uint32_t ps, uint32_t ch) {
+  if constexpr (kPs == kBytePs) {
+    return img_row_bytes(rg, off, in, nv, ps, ch);
+  } else {
+    bool fix;
+    uint64_t q = img_row_dwords<kPs>(rg, off, in, nv, span, ch, &fix);
+    if (fix) q = img_row_bytes(rg, off, true, nv, kPs, ch);
+    return q;
+  }
+}
+
+// tile_rows for an image plane: `image` is the image's first byte, the descriptor starts
+// at the tile's first row and ends with the image's last sample.
+template <uint32_t kPs, uint32_t N, uint32_t kTile>
+__device__ __forceinline__ void tile_rows_img(const uint8_t *image, uint32_t pitch, uint32_t ps_any, uint32_t ch,
+                                              uint32_t W, uint32_t H, uint32_t bw, uint64_t nb, uint32_t tb, uint32_t r,
+                                              uint64_t (&q)[N]) {
+  const uint32_t ps = kPs == kBytePs ? ps_any : kPs;
+  const uint32_t k = threadIdx.x >> 3, nb32 = (uint32_t)nb;
+  const uint32_t tby = tb / bw, tbx = tb - tby * bw;
+  const uint32_t y0 = tby * 8u, hrem = H - y0, p8 = 8u * pitch, xs = 8u * ps;  // tb < nb: y0 < H
+  const uint64_t span64 = (uint64_t)(hrem - 1u) * pitch + (uint64_t)W * ps;
+  const uint32_t span = (uint32_t)(span64 < kMaxTileSpan ? span64 : kMaxTileSpan);
+  const __amdgpu_buffer_rsrc_t rg = enc_rsrc(image + (uint64_t)y0 * pitch, span);
+  uint32_t rowoff = r * pitch;
+  asm volatile("" : "+v"(rowoff));
+  // group u's row: its buffer offset, whether it is inside the frame, its pixels inside
+  const auto place = [&](uint32_t u, uint32_t &off, bool &in, uint32_t &nv) {
+    uint32_t bx = tbx + k + 32u * u, dy = 0, doff = 0;
+    if (bw >= kTile) {
+      const bool wrap = bx >= bw;
+      bx = wrap ? bx - bw : bx;
+      dy = wrap ? 8u : 0u;
+      doff = wrap ? p8 : 0u;
+    } else {
+      const uint32_t d = bx / bw;
+      bx -= d * bw;
+      dy = d * 8u;
+      doff = dy * pitch;
+    }
+    in = tb + k + 32u * u < nb32 && dy + r < hrem;
+    off = doff + rowoff + bx * xs;
+    nv = min(8u, W - bx * 8u);
+  };
+  uint32_t fixes = 0;  // dword modes: the groups whose row this lane must fetch by bytes
+#pragma unroll
+  for (uint32_t u = 0; u < N; ++u) {
+    uint32_t off, nv;
+    bool in;
+    place(u, off, in, nv);
+    if constexpr (kPs == kBytePs) {
+      q[u] = img_row_bytes(rg, off, in, nv, ps, ch);
+    } else {
+      bool fix;
+      q[u] = img_row_dwords<kPs>(rg, off, in, nv, span, ch, &fix);
+      fixes |= (fix ? 1u : 0u) << u;
+    }
+  }
+  if (fixes) {  // the image's last rows only
+#pragma unroll
+    for (uint32_t u = 0; u < N; ++u)
+      if (fixes >> u & 1u) {
+        uint32_t off, nv;
+        bool in;
+        place(u, off, in, nv);
+        q[u] = img_row_bytes(rg, off, true, nv, ps, ch);
+      }
+  }
+}
+
+// The tiled split of the batched path (enc_split_kernel<.., true, kBatchTile>) over image
+// planes: workgroup g is tile t of plane c of image img (img_unit).
+template <uint32_t kPs>
+__global__ void __launch_bounds__(256) enc_split_img_kernel(const uint8_t *pixels, const ImgSrc im, uint32_t W,
+                                                            uint32_t H, uint32_t bw, uint64_t nb, uint32_t flags,
+                                                            uint8_t *block_init, uint16_t *tile_hist, uint32_t ncode,
+                                                            uint64_t *tile_tail) {
+  constexpr uint32_t kTile = kBatchTile, kGroups = kTile / 32;
+  uint32_t f, wg, img, c;
+  img_unit(im, blockIdx.x, ncode, f, wg, img, c);
+  pixels += img * im.image_stride;
+  if (block_init) block_init += (uint64_t)f * nb;
+  tile_hist += (uint64_t)f * ncode * 256;
+  tile_tail += (uint64_t)f * ncode * 8;
+  __shared__ __attribute__((aligned(16))) uint32_t h[256 * kHistCopies];
+  const uint32_t r = threadIdx.x & 7u;
+  const uint32_t copy = threadIdx.x % kHistCopies;
+  const bool delta = !(flags & MH_FLAG_NO_DELTA);
+  const __amdgpu_buffer_rsrc_t rinit = enc_rsrc(block_init, block_init ? nb : 0ull);
+  const uint32_t nb32 = (uint32_t)nb, tb = wg * kTile;
+  uint64_t q[kGroups];
+  tile_rows_img<kPs, kGroups, kTile>(pixels, im.pitch, im.ps, im.fc + c, W, H, bw, nb, tb, r, q);
+  {  // the histogram is cleared behind the loads
+    typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (uint32_t i = 0; i < kHistCopies / 4; ++i) reinterpret_cast<v4u32 *>(h)[threadIdx.x + 256u * i] = v4u32{0u, 0u, 0u, 0u};
+    lds_barrier();
+  }
+  uint64_t vlast = 0;
+#pragma unroll
+  for (uint32_t u = 0; u < kGroups; ++u) {
+    const uint32_t b = tb + 32u * u + (threadIdx.x >> 3);
+    uint32_t first;
+    const uint64_t v = row_symbols(q[u], r, delta, block_init != nullptr, &first);
+    if (block_init)  // kernel-uniform
+      __builtin_amdgcn_raw_buffer_store_b8((uint8_t)first, rinit, (int)(r == 0 && b < nb32 ? b : kOob), 0, 0);
+    if (b < nb32)
+      for (int j = 0; j < 8; ++j) atomicAdd(&h[((uint32_t)(v >> (8 * j)) & 0xFFu) * kHistCopies + copy], 1u);
+    vlast = v;
+  }
+  if (threadIdx.x >= 248u && tb + kTile - 1u < nb32) tile_tail[(uint64_t)wg * 8u + r] = vlast;
+  lds_barrier();
+  uint32_t cnt = 0;
+  for (uint32_t k = 0; k < kHistCopies; ++k) cnt += h[threadIdx.x * kHistCopies + ((k + threadIdx.x) % kHistCopies)];
+  tile_hist[(uint64_t)wg * 256 + threadIdx.x] = (uint16_t)cnt;  // <= kTile * 64
 }
 
 
@@ -1654,225 +1895,22 @@ __global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_kernel(
     const Pixels px, uint64_t gray_stride, uint64_t nb, uint32_t ncode, const uint32_t *table, const uint64_t *meta,
     const uint32_t *tile_off, uint32_t *offsets, uint8_t *codes, uint64_t codes_stride, uint32_t ncode_wg,
     const uint64_t *tile_tail) {
-  // ncode_wg: workgroups per frame (ncode rounded up to kPackWaves tiles): a workgroup's
-  // waves pack tiles of ONE frame and share its table, at a fixed LDS address (the
-  // gathers need no per-wave base: one VALU per symbol for the address)
-  __shared__ uint32_t tab[256];
-  __shared__ __attribute__((aligned(16))) uint32_t s_w[kPackWaves][kStepSlots];
-  // the wave index as a provably uniform value (readfirstlane): the tile, its offsets and
-  // the step cursor then live in SGPRs (SALU) instead of being carried per lane
-  const uint32_t lane = threadIdx.x & 63u, k = lane >> 3, r = lane & 7u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t f = blockIdx.x / ncode_wg, t = (blockIdx.x - f * ncode_wg) * kPackWaves + wave;
-  if (!(uint32_t)meta[(uint64_t)f * kMetaWords + 1]) return;  // rejected frame (workgroup-uniform): nothing written
-  {
-    // the frame's table as len << 16 | right-aligned code (the tree's words hold the
-    // code left-aligned in 16 bits): two symbols' codes combine in one v_lshl_or
-    const uint32_t e = table[(uint64_t)f * 256 + threadIdx.x];
-    const uint32_t L = e & 0x1Fu;
-    tab[threadIdx.x] = L ? (L << 16) | ((e >> 16) >> (16u - L)) : 0u;
-  }
-  lds_barrier();
-  if (t >= ncode) return;  // wave-uniform padding past the frame's last tile; no barrier follows
-  uint32_t *lw = s_w[wave];
-  const uint32_t E = tile_off[(uint64_t)f * (ncode + 1) + t];
-  const uint8_t *gray = px.gray + f * gray_stride;
-  const uint64_t b0 = (uint64_t)t * kBatchTile;
-  const uint32_t nsteps = (uint32_t)((min<uint64_t>(kBatchTile, nb - b0) + kStepBlocks - 1) / kStepBlocks);
-  const uint32_t by0 = (uint32_t)(b0 / px.bw), bx0 = (uint32_t)(b0 - (uint64_t)by0 * px.bw);
-  // one descriptor from the tile's first block row: 32-bit offsets for any frame
-  const uint32_t yb = by0 * 8u;
-  const __amdgpu_buffer_rsrc_t rg = enc_rsrc(gray + (uint64_t)yb * px.W, (uint64_t)(px.H - yb) * px.W);
-  // row r of block (bx + k, by) wrapped into the frame, zero when !live or past the frame
-  // (32-bit block indices, nb < 2^26; the step's row offset uniform, r * W per lane
-  // once, a wrapped block adds 8 W: no per-step v_mul_lo, which is quarter rate)
-  const uint32_t nb32 = (uint32_t)nb, w8 = 8u * px.W;
-  const auto load_row = [&](uint32_t sbx, uint32_t sby, uint32_t sb, uint32_t kk, uint32_t rr, uint32_t rrW,
-                            bool live) -> uint64_t {
-    uint32_t bx = sbx + kk, dy = 0, doff = 0;
-    if (px.bw >= kStepBlocks) {  // kk < kStepBlocks: one wrap at most
-      const bool wrap = bx >= px.bw;
-      bx = wrap ? bx - px.bw : bx;
-      dy = wrap ? 8u : 0u;
-      doff = wrap ? w8 : 0u;
-    } else {
-      const uint32_t d = bx / px.bw;
-      bx -= d * px.bw;
-      dy = d * 8u;
-      doff = dy * px.W;
-    }
-    const uint32_t ys = sby * 8u - yb;  // uniform: the step's first block row in the descriptor
-    const bool in = live && sb + kk < nb32 && ys + dy + rr < px.H - yb;
-    const uint32_t off = ys * px.W + doff + rrW + bx * 8u;
-    if constexpr (kVec) {
-      typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
-      const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(rg, (int)(in ? off : kOob), 0, 0);
-      return ((uint64_t)v.y << 32) | v.x;
-    } else {
-      uint64_t q = 0;
-#pragma unroll
-      for (uint32_t c = 0; c < 8; ++c)
-        q |= (uint64_t)__builtin_amdgcn_raw_buffer_load_b8(rg, (int)(in && bx * 8u + c < px.W ? off + c : kOob), 0, 0)
-             << (8 * c);
-      return q;
-    }
-  };
-  uint32_t first_unused;
-  // the tile's first word starts with the previous block's last E % 32 bits: lanes 0-7
-  // recompute that block's codes (the previous tile leaves the shared word to this one)
-  // from its symbols, which the split kept for this (tile_tail: one 64-B read)
-  uint32_t head = 0;
-  const uint32_t r0 = E & 31u;
-  if (r0) {  // wave-uniform; t > 0 here (tile 0 starts at bit 0)
-    const __amdgpu_buffer_rsrc_t rt = enc_rsrc(tile_tail + ((uint64_t)f * ncode + t - 1u) * 8u, 64u);
-    typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
-    const v2u32 tv = __builtin_amdgcn_raw_buffer_load_b64(rt, (int)(lane < 8 ? lane * 8u : kOob), 0, 0);
-    const uint64_t qp = ((uint64_t)tv.y << 32) | tv.x;
-    uint32_t lenp = 0;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t e = tab[(uint32_t)(qp >> (8 * j)) & 0xFFu];
-      const uint32_t len = e >> 16;
-      acc = (acc << len) | (e & 0xFFFFu);  // the lane's codes MSB-first, last 64 bits
-      lenp += len;
-    }
-    if (lane >= 8) lenp = 0;
-    // bits of lanes after this one in the block; the lane's last bit lands at word bit
-    // 32 - r0 + after (bits before the word fall off the top)
-    const uint32_t incp = wave_scan_dpp(lenp);
-    const uint32_t after = __builtin_amdgcn_readlane(incp, 7) - incp;
-    uint32_t h = lane < 8 && after < r0 ? (uint32_t)(acc << (32u - r0 + after)) : 0u;
-    for (uint32_t o = 1; o < 8; o <<= 1) h |= __shfl_xor(h, o);
-    head = __builtin_amdgcn_readfirstlane(h);
-  }
-  typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
-  v4u32 *lq = reinterpret_cast<v4u32 *>(lw);
-  // the step's words as quads: one 16-B LDS write / read and one 16-B store per lane
-  const auto clear_words = [&](uint32_t first) {
-    lq[lane] = v4u32{lane == 0 ? first : 0u, 0u, 0u, 0u};
-    lq[64 + lane] = v4u32{0u, 0u, 0u, 0u};
-    if (lane < kStepSlots / 4 - 128) lq[128 + lane] = v4u32{0u, 0u, 0u, 0u};
-  };
-  clear_words(bswap32(head));
-  const __amdgpu_buffer_rsrc_t rw = enc_rsrc(codes + f * codes_stride, codes_stride);
-  const __amdgpu_buffer_rsrc_t ro = enc_rsrc(offsets + (uint64_t)f * nb, nb * 4u);
-  uint32_t pos = E;
-  uint32_t sbx = bx0, sby = by0;
-  uint32_t sb = (uint32_t)b0;
-  uint32_t rW = r * px.W;
-  asm volatile("" : "+v"(rW));  // kept as is (else folded back into (ys + r) * W per step)
-  // row r of the pair (2 k, 2 k + 1) of the step starting at block (sbx, sby) = sb
-  const auto load_pair = [&](uint32_t bx_, uint32_t by_, uint32_t sb_, bool live, uint64_t &qa, uint64_t &qb) {
-    if constexpr (kPair) {
-      uint32_t bx = bx_ + 2u * k, doff = 0, dy = 0;
-      if (px.bw >= kStepBlocks) {
-        const bool wrap = bx >= px.bw;
-        bx = wrap ? bx - px.bw : bx;
-        dy = wrap ? 8u : 0u;
-        doff = wrap ? w8 : 0u;
-      } else {
-        const uint32_t d = bx / px.bw;
-        bx -= d * px.bw;
-        dy = d * 8u;
-        doff = dy * px.W;
-      }
-      const uint32_t ys = by_ * 8u - yb;
-      const bool in = live && sb_ + 2u * k < nb32 && ys + dy + r < px.H - yb;
-      // both blocks are inside the frame when the first is (an even width, an even first block)
-      const v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(rg, (int)(in ? ys * px.W + doff + rW + bx * 8u : kOob), 0, 0);
-      qa = ((uint64_t)v.y << 32) | v.x;
-      qb = ((uint64_t)v.w << 32) | v.z;
-    } else {
-      qa = load_row(bx_, by_, sb_, 2u * k, r, rW, live);
-      qb = load_row(bx_, by_, sb_, 2u * k + 1u, r, rW, live);
-    }
-  };
-  uint64_t qa, qb;
-  load_pair(sbx, sby, sb, true, qa, qb);
-  for (uint32_t s = 0; s < nsteps; ++s) {
-    // the next step's rows (a dead load past the tile's last step: fixed count)
-    uint32_t nbx = sbx + kStepBlocks, nby = sby;
-    while (nbx >= px.bw) {  // uniform; once per step at most when bw >= kStepBlocks
-      nbx -= px.bw;
-      ++nby;
-    }
-    uint64_t na, nbq;
-    load_pair(nbx, nby, sb + kStepBlocks, s + 1 < nsteps, na, nbq);
-    const uint32_t ba = sb + 2u * k;
-    const bool on_a = ba < nb32, on_b = ba + 1u < nb32;
-    // codes MSB-first: pairs of symbols in 32 bits (v_lshl_or), chunks of four in 64
-    uint64_t ch[4];
-    uint32_t cl[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const uint64_t v = row_symbols(h ? qb : qa, r, px.delta, px.init_byte, &first_unused);
-      uint32_t pc[4], pl[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t e0 = tab[(uint32_t)(v >> (16 * j)) & 0xFFu], e1 = tab[(uint32_t)(v >> (16 * j + 8)) & 0xFFu];
-        const uint32_t l1 = e1 >> 16;
-        pc[j] = ((e0 & 0xFFFFu) << l1) | (e1 & 0xFFFFu);
-        pl[j] = (e0 >> 16) + l1;
-      }
-      ch[2 * h] = ((uint64_t)pc[0] << pl[1]) | pc[1];
-      ch[2 * h + 1] = ((uint64_t)pc[2] << pl[3]) | pc[3];
-      cl[2 * h] = pl[0] + pl[1];
-      cl[2 * h + 1] = pl[2] + pl[3];
-    }
-    const uint32_t na_bits = on_a ? cl[0] + cl[1] : 0u, nb_bits = on_b ? cl[2] + cl[3] : 0u;
-    // bit order: block 2 k (rows 0-7), then block 2 k + 1: one scan of A | B << 16 (each
-    // half's sum over the wave <= 8,192), the pair's start and its A total by broadcast
-    const uint32_t x = na_bits | (nb_bits << 16);
-    const uint32_t S = wave_scan_dpp(x), ex = S - x;
-    const uint32_t g = __shfl(ex, lane & ~7u), ge = __shfl(S, lane | 7u);
-    const uint32_t Tw = __builtin_amdgcn_readlane(S, 63);
-    const uint32_t T = (Tw & 0xFFFFu) + (Tw >> 16);
-    const uint32_t start = (g & 0xFFFFu) + (g >> 16);             // the pair's first bit (step-relative)
-    const uint32_t atot = (ge & 0xFFFFu) - (g & 0xFFFFu);         // block 2 k's bits
-    const uint32_t pa = (g >> 16) + (ex & 0xFFFFu);                // this row of block 2 k
-    const uint32_t pb = (g & 0xFFFFu) + atot + (ex >> 16);         // this row of block 2 k + 1
-    // block offsets: lane r = 0 writes block 2 k's, lane r = 1 block 2 k + 1's
-    const bool wo = r == 0 ? on_a : r == 1 ? on_b : false;
-    __builtin_amdgcn_raw_buffer_store_b32(pos + start + (r == 1 ? atot : 0u), ro, (int)(wo ? (ba + r) * 4u : kOob), 0,
-                                          0);
-    const uint32_t rr = pos & 31u;
-    if (!MH_DIAG_PACK_NO_OR && on_a) {
-      or_bits(lw, rr + pa, ch[0], cl[0]);
-      or_bits(lw, rr + pa + cl[0], ch[1], cl[1]);
-    }
-    if (!MH_DIAG_PACK_NO_OR && on_b) {
-      or_bits(lw, rr + pb, ch[2], cl[2]);
-      or_bits(lw, rr + pb + cl[2], ch[3], cl[3]);
-    }
-    wave_sync();
-    // whole words out; the last partial word stays as the next step's first
-    const uint32_t nfull = (rr + T) >> 5, w0 = pos >> 5, nq4 = nfull >> 2;
-    const v4u32 q0 = lq[lane], q1 = lq[64 + lane];                    // words 4 lane .., 256 + 4 lane ..
-    const uint32_t tail = lw[min(4u * nq4 + lane, kStepSlots - 1u)];  // lanes < nfull % 4: the last words
-    const uint32_t carry = lw[nfull];
-    __builtin_amdgcn_raw_buffer_store_b128(q0, rw, (int)(lane < nq4 ? (w0 + 4u * lane) * 4u : kOob), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(q1, rw, (int)(64u + lane < nq4 ? (w0 + 256u + 4u * lane) * 4u : kOob), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(tail, rw, (int)(lane < (nfull & 3u) ? (w0 + 4u * nq4 + lane) * 4u : kOob), 0,
-                                          0);
-    wave_sync();
-    clear_words(carry);
-    wave_sync();
-    pos += T;
-    qa = na;
-    qb = nbq;
-    sbx = nbx;
-    sby = nby;
-    sb += kStepBlocks;
-  }
-  // the last tile writes its partial last word, then the zero pad up to the byte count
-  // rounded to words (the others leave that word to the next tile)
-  if (t + 1 == ncode) {
-    const uint32_t nw = (uint32_t)(((uint64_t)(pos + 7u) / 8u + MH_CODES_PAD + 3u) / 4u);
-    const uint32_t w = (pos >> 5) + lane;
-    const uint32_t val = lane == 0 ? lw[0] : 0u;
-    __builtin_amdgcn_raw_buffer_store_b32(val, rw, (int)(w < nw ? w * 4u : kOob), 0, 0);
-  }
+#define MH_PACK_IMAGES 0
+#include "mh_encode_pack_wave.inc"
+#undef MH_PACK_IMAGES
+}
+
+// ... over image planes: workgroup g packs kPackWaves tiles of plane c of image img
+// (img_unit: the planes of a unit eight workgroups apart).
+template <uint32_t kPs>
+__global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_img_kernel(
+    const Pixels px, const ImgSrc im, uint64_t nb, uint32_t ncode, const uint32_t *table, const uint64_t *meta,
+    const uint32_t *tile_off, uint32_t *offsets, uint8_t *codes, uint64_t codes_stride, uint32_t ncode_wg,
+    const uint64_t *tile_tail) {
+  [[maybe_unused]] constexpr bool kVec = false, kPair = false;  // the planar packer's load widths
+#define MH_PACK_IMAGES 1
+#include "mh_encode_pack_wave.inc"
+#undef MH_PACK_IMAGES
 }
 
 struct BatchWorkspace {  // per-frame slices, each part 256-B aligned; nothing needs zeroing
@@ -1915,6 +1953,112 @@ uint64_t carve_shared(uint8_t *base, uint64_t nb, uint32_t n, SharedWorkspace *w
   if (w) w->meta = reinterpret_cast<uint64_t *>(base + o);
   o += align256(kMetaWords * 8);
   return o;
+}
+
+// The pixels the batched entries read: n frames of planar gray, or (lay != null) the
+// planes of n interleaved images.
+struct Source {
+  const uint8_t *base;
+  uint64_t gray_stride;        // planar: bytes from frame to frame
+  const mh_image_layout *lay;  // images: the caller's layout (the entries' img argument says which)
+  uint32_t n;                  // frames or images
+};
+
+// The images entries' MH_ERR_CAPACITY rules for a layout whose fields passed the
+// MH_ERR_INVALID_ARG and MH_ERR_DIMS checks: rows and images do not overlap, and one
+// tile's descriptor -- from the tile's first row to the last row one of its blocks lies in,
+// at most MH_IMAGE_TILE_ROWS(width) rows -- spans at most kMaxTileSpan bytes, the kernels'
+// 32-bit offsets.
+bool image_layout_fits(const mh_image_layout &l, uint32_t n, uint32_t W, uint32_t H) {
+  const uint64_t row = (uint64_t)W * l.pixel_stride;  // < 2^48
+  if (row > kMaxTileSpan) return false;
+  if (H > 1 && (l.row_pitch < row || l.row_pitch > kMaxTileSpan)) return false;
+  const uint64_t pitch = H > 1 ? l.row_pitch : 0;
+  if (n > 1 && l.image_stride < (uint64_t)(H - 1) * pitch + row) return false;
+  const uint32_t bw = (W + 7) / 8;
+  const uint64_t rows = std::min<uint64_t>(H, 8ull * ((kBatchTile - 2) / bw + 2));
+  static_assert(MH_IMAGE_TILE_ROWS(8) == 8 * ((kBatchTile - 2) / 1 + 2) && MH_IMAGE_TILE_SPAN_MAX == kMaxTileSpan,
+                "the header states the kernels' limit");
+  return (rows - 1) * pitch + row <= kMaxTileSpan;
+}
+
+ImgSrc image_source(const mh_image_layout &l, uint32_t n, uint32_t H) {
+  return ImgSrc{l.image_stride, H > 1 ? (uint32_t)l.row_pitch : 0u, l.pixel_stride, l.first_channel, l.n_planes, n,
+                l.plane_major};
+}
+
+// Fetch mode of a layout: dword loads for pixel strides 1-4 when every row of every image
+// starts 4-byte aligned, else byte loads.
+uint32_t image_mode(const uint8_t *base, const ImgSrc &im, uint32_t H) {
+  const uint64_t a = (uint64_t)(uintptr_t)base | (im.n > 1 ? im.image_stride : 0) | (H > 1 ? im.pitch : 0u);
+  return im.ps <= 4 && !(a & 3u) ? im.ps : kBytePs;
+}
+
+#define MH_IMG_MODE(mode, KERNEL)                                                              \
+  ((mode) == 1 ? KERNEL<1> : (mode) == 2 ? KERNEL<2> : (mode) == 3 ? KERNEL<3> : (mode) == 4 ? KERNEL<4> \
+                                                                               : KERNEL<kBytePs>)
+
+// The split and the packer of the batched path for frames [0, n_frames) of a Source.
+void launch_split(hipStream_t s, const Source &src, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t flags,
+                  uint8_t *block_init, const BatchWorkspace &w) {
+  const uint32_t bw = (W + 7) / 8;
+  const uint64_t nb = (uint64_t)bw * ((H + 7) / 8), ncode = (nb + kBatchTile - 1) / kBatchTile;
+  const dim3 grid((uint32_t)(ncode * n_frames));
+  if (src.lay) {
+    const ImgSrc im = image_source(*src.lay, src.n, H);
+    hipLaunchKernelGGL(MH_IMG_MODE(image_mode(src.base, im, H), enc_split_img_kernel), grid, dim3(256), 0, s, src.base, im,
+                       W, H, bw, nb, flags, block_init, w.tile_hist, (uint32_t)ncode, w.tile_tail);
+    return;
+  }
+  const bool vec = W % 8 == 0 && ((uintptr_t)src.base & 7u) == 0 && (src.gray_stride & 7u) == 0;
+  // one workgroup per tile (a persistent split with the next tile's rows in flight
+  // measured slower: profiles/r04_v4_encoder_batch_ab.txt)
+  hipLaunchKernelGGL((vec ? enc_split_kernel<true, true, kBatchTile> : enc_split_kernel<false, true, kBatchTile>), grid,
+                     dim3(256), 0, s, src.base, W, H, bw, nb, flags, nullptr, block_init, nullptr, w.tile_hist, nullptr,
+                     (uint32_t)ncode, src.gray_stride, w.tile_tail);
+}
+
+void launch_pack(hipStream_t s, const Source &src, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t flags,
+                 bool init_byte, const BatchWorkspace &w, uint32_t *offsets, uint8_t *codes, uint64_t codes_stride) {
+  const uint32_t bw = (W + 7) / 8;
+  const uint64_t nb = (uint64_t)bw * ((H + 7) / 8), ncode = (nb + kBatchTile - 1) / kBatchTile;
+  const uint32_t ncode_wg = (uint32_t)((ncode + kPackWaves - 1) / kPackWaves);
+  const dim3 grid(ncode_wg * n_frames);
+  const bool vec = !src.lay && W % 8 == 0 && ((uintptr_t)src.base & 7u) == 0 && (src.gray_stride & 7u) == 0;
+  const Pixels px{src.base, W, H, bw, vec ? 1u : 0u, !(flags & MH_FLAG_NO_DELTA), init_byte};
+  if (src.lay) {
+    const ImgSrc im = image_source(*src.lay, src.n, H);
+    hipLaunchKernelGGL(MH_IMG_MODE(image_mode(src.base, im, H), enc_pack_wave_img_kernel), grid, dim3(kPackWaves * 64), 0,
+                       s, px, im, nb, (uint32_t)ncode, w.table, w.meta, w.tile_off, offsets, codes, codes_stride, ncode_wg,
+                       w.tile_tail);
+    return;
+  }
+  hipLaunchKernelGGL((!vec ? enc_pack_wave_kernel<false, false>
+                           : bw % 2 ? enc_pack_wave_kernel<true, false> : enc_pack_wave_kernel<true, true>),
+                     grid, dim3(kPackWaves * 64), 0, s, px, src.gray_stride, nb, (uint32_t)ncode, w.table, w.meta,
+                     w.tile_off, offsets, codes, codes_stride, ncode_wg, w.tile_tail);
+}
+
+// The argument checks both batched entries and their images twins share, in the
+// documented order; on MH_OK *n_frames is the batch's frame count (images: n * C).
+int check_batch_args(const Source &src, bool img, bool have_header_arg, const void *d_codes, const void *d_block_offsets,
+                     const void *d_workspace, uint32_t W, uint32_t H, uint32_t flags, uint64_t codes_frame_stride,
+                     uint32_t *n_frames) {
+  const mh_image_layout *l = src.lay;
+  if (!src.base || !have_header_arg || !d_codes || !d_block_offsets || !d_workspace || !src.n ||
+      (img && (!l || !l->n_planes || l->n_planes > MH_MAX_PLANES || l->plane_major > 1)))
+    return MH_ERR_INVALID_ARG;
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
+  if (!W || !H || W > MH_MAX_DIM || H > MH_MAX_DIM ||
+      (img && (!l->pixel_stride || (uint64_t)l->first_channel + l->n_planes > l->pixel_stride)))
+    return MH_ERR_DIMS;
+  if (((uintptr_t)d_codes & 15u) || (codes_frame_stride & 15u) || ((uintptr_t)d_workspace & 255u)) return MH_ERR_ALIGN;
+  if (img ? !image_layout_fits(*l, src.n, W, H) : src.gray_stride < (uint64_t)W * H && src.n > 1) return MH_ERR_CAPACITY;
+  const uint64_t nb = (uint64_t)((W + 7) / 8) * ((H + 7) / 8), ncode = (nb + kBatchTile - 1) / kBatchTile;
+  const uint64_t n = (uint64_t)src.n * (img ? l->n_planes : 1u);  // < 2^34
+  if (ncode * n > 0x7FFFFFFFull || n > 0x7FFFFFFFu) return MH_ERR_CAPACITY;
+  *n_frames = (uint32_t)n;
+  return MH_OK;
 }
 
 }  // namespace
@@ -2056,22 +2200,18 @@ size_t mh_encode_frames_workspace_bytes(uint32_t width, uint32_t height, uint32_
   return (size_t)carve_batch(nullptr, nb, n_frames, nullptr);
 }
 
-int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_stride, uint32_t n_frames,
-                                  uint32_t width, uint32_t height, uint32_t flags, uint8_t *d_canon_headers,
-                                  uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
-                                  uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
-                                  int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
-  if (!d_gray || !d_canon_headers || !d_codes || !d_block_offsets || !d_workspace || !n_frames)
-    return MH_ERR_INVALID_ARG;
-  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
-  if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
-  if (((uintptr_t)d_codes & 15u) || (codes_frame_stride & 15u) || ((uintptr_t)d_workspace & 255u))
-    return MH_ERR_ALIGN;
-  if (gray_frame_stride < (uint64_t)width * height && n_frames > 1) return MH_ERR_CAPACITY;
+// mh_encode_frames_device_async (img = false) and mh_encode_images_device_async
+static int encode_batch(const Source &src, bool img, uint32_t width, uint32_t height, uint32_t flags,
+                        uint8_t *d_canon_headers, uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
+                        uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
+                        int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
+  uint32_t n_frames = 0;
+  const int rc = check_batch_args(src, img, d_canon_headers != nullptr, d_codes, d_block_offsets, d_workspace, width,
+                                  height, flags, codes_frame_stride, &n_frames);
+  if (rc != MH_OK) return rc;
   const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
   const uint64_t nb = (uint64_t)bw * bh;
   const uint64_t ncode = (nb + kBatchTile - 1) / kBatchTile;
-  if (ncode * n_frames > 0x7FFFFFFFull || n_frames > 0x7FFFFFFFu) return MH_ERR_CAPACITY;
   if (workspace_bytes < mh_encode_frames_workspace_bytes(width, height, n_frames)) return MH_ERR_CAPACITY;
   BatchWorkspace w;
   carve_batch(static_cast<uint8_t *>(d_workspace), nb, n_frames, &w);
@@ -2080,42 +2220,41 @@ int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_str
   // counts by the split, the tables and tile offsets by the trees): nothing to clear
   const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;  // the tree kernels' own argument
   flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
-  const uint32_t vec = (width % 8 == 0 && ((uintptr_t)d_gray & 7u) == 0 && (gray_frame_stride & 7u) == 0) ? 1u : 0u;
-  const Pixels px0{d_gray, width, height, bw, vec, !(flags & MH_FLAG_NO_DELTA), d_block_init != nullptr};
-  // frames [f0, f0 + m): split, trees, packing on stream st
-  const auto sub_batch = [&](hipStream_t st, uint32_t f0, uint32_t m) {
-    const uint32_t nt = (uint32_t)(ncode * m);
-    const uint8_t *gray = d_gray + f0 * gray_frame_stride;
-    uint8_t *binit = d_block_init ? d_block_init + (uint64_t)f0 * nb : nullptr;
-    uint16_t *th = w.tile_hist + (uint64_t)f0 * ncode * 256;
-    uint32_t *table = w.table + (uint64_t)f0 * 256;
-    uint64_t *meta = w.meta + (uint64_t)f0 * kMetaWords;
-    uint32_t *to = w.tile_off + (uint64_t)f0 * (ncode + 1);
-    // one workgroup per tile (a persistent split with the next tile's rows in flight
-    // measured slower: profiles/r04_v4_encoder_batch_ab.txt)
-    uint64_t *tail = w.tile_tail + (uint64_t)f0 * ncode * 8;
-    hipLaunchKernelGGL((vec ? enc_split_kernel<true, true, kBatchTile> : enc_split_kernel<false, true, kBatchTile>), dim3(nt),
-                       dim3(256), 0, st,
-                       gray, width, height, bw, nb, flags, nullptr, binit, nullptr, th, nullptr, (uint32_t)ncode,
-                       gray_frame_stride, tail);
-    hipLaunchKernelGGL(enc_tree_batch_kernel, dim3(m), dim3(kTreeThreads), 0, st, nullptr,
-                       d_canon_headers + (uint64_t)f0 * 256, table, meta, d_codes_len ? d_codes_len + f0 : nullptr,
-                       codes_frame_stride, d_status ? d_status + f0 : nullptr, nb, th, (uint32_t)ncode, to,
-                       d_frame_code_offsets, f0, n_frames, limit);
-    Pixels px = px0;
-    px.gray = gray;
-    const uint32_t ncode_wg = (uint32_t)((ncode + kPackWaves - 1) / kPackWaves);
-    hipLaunchKernelGGL((!vec ? enc_pack_wave_kernel<false, false>
-                            : bw % 2 ? enc_pack_wave_kernel<true, false> : enc_pack_wave_kernel<true, true>),
-                       dim3(ncode_wg * m), dim3(kPackWaves * 64), 0, st, px, gray_frame_stride, nb, (uint32_t)ncode, table,
-                       meta, to, d_block_offsets + (uint64_t)f0 * nb, d_codes + f0 * codes_frame_stride,
-                       codes_frame_stride, ncode_wg, tail);
-  };
-  // One sub-batch: splitting the call into sub-batches alternated over a second stream
-  // (trees beside another sub-batch's split / packing) measured slower, and the packer's
-  // pixel re-reads did not drop (profiles/r04_v4_encoder_batch_ab.txt).
-  sub_batch(s, 0, n_frames);
+  // One batch, three launches: splitting the call into sub-batches alternated over a second
+  // stream (trees beside another sub-batch's split / packing) measured slower, and the
+  // packer's pixel re-reads did not drop (profiles/r04_v4_encoder_batch_ab.txt).
+  launch_split(s, src, n_frames, width, height, flags, d_block_init, w);
+  hipLaunchKernelGGL(enc_tree_batch_kernel, dim3(n_frames), dim3(kTreeThreads), 0, s, nullptr, d_canon_headers, w.table,
+                     w.meta, d_codes_len, codes_frame_stride, d_status, nb, w.tile_hist, (uint32_t)ncode, w.tile_off,
+                     d_frame_code_offsets, 0u, n_frames, limit);
+  launch_pack(s, src, n_frames, width, height, flags, d_block_init != nullptr, w, d_block_offsets, d_codes,
+              codes_frame_stride);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_stride, uint32_t n_frames,
+                                  uint32_t width, uint32_t height, uint32_t flags, uint8_t *d_canon_headers,
+                                  uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
+                                  uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
+                                  int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
+  return encode_batch(Source{d_gray, gray_frame_stride, nullptr, n_frames}, false, width, height, flags, d_canon_headers,
+                      d_codes, codes_frame_stride, d_codes_len, d_frame_code_offsets, d_block_offsets, d_block_init,
+                      d_status, d_workspace, workspace_bytes, stream);
+}
+
+size_t mh_encode_images_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_images, uint32_t n_planes) {
+  const uint64_t n = (uint64_t)n_images * n_planes;
+  return n > 0x7FFFFFFFull ? 0 : mh_encode_frames_workspace_bytes(width, height, (uint32_t)n);
+}
+
+int mh_encode_images_device_async(const uint8_t *d_pixels, const mh_image_layout *layout, uint32_t n_images,
+                                  uint32_t width, uint32_t height, uint32_t flags, uint8_t *d_canon_headers,
+                                  uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
+                                  uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
+                                  int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
+  return encode_batch(Source{d_pixels, 0, layout, n_images}, true, width, height, flags, d_canon_headers, d_codes,
+                      codes_frame_stride, d_codes_len, d_frame_code_offsets, d_block_offsets, d_block_init, d_status,
+                      d_workspace, workspace_bytes, stream);
 }
 
 size_t mh_encode_frames_shared_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_frames) {
@@ -2123,25 +2262,20 @@ size_t mh_encode_frames_shared_workspace_bytes(uint32_t width, uint32_t height, 
   return (size_t)carve_shared(nullptr, nb, n_frames, nullptr);
 }
 
-int mh_encode_frames_shared_device_async(const uint8_t *d_gray, uint64_t gray_frame_stride, uint32_t n_frames,
-                                         uint32_t width, uint32_t height, uint32_t flags,
-                                         const uint8_t *d_canon_in, uint8_t *d_canon_header, uint8_t *d_codes,
-                                         uint64_t codes_frame_stride, uint64_t *d_codes_len,
-                                         uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets,
-                                         uint8_t *d_block_init, int32_t *d_status, int32_t *d_header_status,
-                                         void *d_workspace, size_t workspace_bytes, void *stream) {
+// mh_encode_frames_shared_device_async (img = false) and mh_encode_images_shared_device_async
+static int encode_batch_shared(const Source &src, bool img, uint32_t width, uint32_t height, uint32_t flags,
+                               const uint8_t *d_canon_in, uint8_t *d_canon_header, uint8_t *d_codes,
+                               uint64_t codes_frame_stride, uint64_t *d_codes_len, uint64_t *d_frame_code_offsets,
+                               uint32_t *d_block_offsets, uint8_t *d_block_init, int32_t *d_status,
+                               int32_t *d_header_status, void *d_workspace, size_t workspace_bytes, void *stream) {
   // the checks of mh_encode_frames_device_async, in its order; every one before any HIP call
-  if (!d_gray || (!d_canon_in && !d_canon_header) || !d_codes || !d_block_offsets || !d_workspace || !n_frames)
-    return MH_ERR_INVALID_ARG;
-  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
-  if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
-  if (((uintptr_t)d_codes & 15u) || (codes_frame_stride & 15u) || ((uintptr_t)d_workspace & 255u))
-    return MH_ERR_ALIGN;
-  if (gray_frame_stride < (uint64_t)width * height && n_frames > 1) return MH_ERR_CAPACITY;
+  uint32_t n_frames = 0;
+  const int rc = check_batch_args(src, img, d_canon_in || d_canon_header, d_codes, d_block_offsets, d_workspace, width,
+                                  height, flags, codes_frame_stride, &n_frames);
+  if (rc != MH_OK) return rc;
   const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
   const uint64_t nb = (uint64_t)bw * bh;
   const uint64_t ncode = (nb + kBatchTile - 1) / kBatchTile;
-  if (ncode * n_frames > 0x7FFFFFFFull || n_frames > 0x7FFFFFFFu) return MH_ERR_CAPACITY;
   // built mode: the tree's node weights are u32 (tree_body), so the batch holds fewer than
   // 2^32 symbols (1,365 frames of 2048 x 1536); its bit total has no such limit
   const uint64_t nsym = (uint64_t)n_frames * nb * 64;  // < 2^31 x 2^26 x 2^6
@@ -2156,12 +2290,8 @@ int mh_encode_frames_shared_device_async(const uint8_t *d_gray, uint64_t gray_fr
     return MH_ERR_HIP;
   const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;
   flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
-  const uint32_t vec = (width % 8 == 0 && ((uintptr_t)d_gray & 7u) == 0 && (gray_frame_stride & 7u) == 0) ? 1u : 0u;
-  const Pixels px{d_gray, width, height, bw, vec, !(flags & MH_FLAG_NO_DELTA), d_block_init != nullptr};
   // the split and the packer: mh_encode_frames_device_async's launches
-  hipLaunchKernelGGL((vec ? enc_split_kernel<true, true, kBatchTile> : enc_split_kernel<false, true, kBatchTile>),
-                     dim3((uint32_t)(ncode * n_frames)), dim3(256), 0, s, d_gray, width, height, bw, nb, flags, nullptr,
-                     d_block_init, nullptr, w.b.tile_hist, nullptr, (uint32_t)ncode, gray_frame_stride, w.b.tile_tail);
+  launch_split(s, src, n_frames, width, height, flags, d_block_init, w.b);
   if (d_canon_in) {
     hipLaunchKernelGGL(enc_header_table_kernel, dim3(1), dim3(256), 0, s, d_canon_in, d_canon_header, w.table, w.meta);
   } else {
@@ -2174,13 +2304,40 @@ int mh_encode_frames_shared_device_async(const uint8_t *d_gray, uint64_t gray_fr
   hipLaunchKernelGGL(enc_plan_shared_kernel, dim3(n_frames), dim3(kTreeThreads), 0, s, w.table, w.meta, w.b.table,
                      w.b.meta, d_codes_len, codes_frame_stride, d_status, d_header_status, nb, w.b.tile_hist,
                      (uint32_t)ncode, w.b.tile_off, d_frame_code_offsets, n_frames);
-  const uint32_t ncode_wg = (uint32_t)((ncode + kPackWaves - 1) / kPackWaves);
-  hipLaunchKernelGGL((!vec ? enc_pack_wave_kernel<false, false>
-                           : bw % 2 ? enc_pack_wave_kernel<true, false> : enc_pack_wave_kernel<true, true>),
-                     dim3(ncode_wg * n_frames), dim3(kPackWaves * 64), 0, s, px, gray_frame_stride, nb, (uint32_t)ncode,
-                     w.b.table, w.b.meta, w.b.tile_off, d_block_offsets, d_codes, codes_frame_stride, ncode_wg,
-                     w.b.tile_tail);
+  launch_pack(s, src, n_frames, width, height, flags, d_block_init != nullptr, w.b, d_block_offsets, d_codes,
+              codes_frame_stride);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+int mh_encode_frames_shared_device_async(const uint8_t *d_gray, uint64_t gray_frame_stride, uint32_t n_frames,
+                                         uint32_t width, uint32_t height, uint32_t flags,
+                                         const uint8_t *d_canon_in, uint8_t *d_canon_header, uint8_t *d_codes,
+                                         uint64_t codes_frame_stride, uint64_t *d_codes_len,
+                                         uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets,
+                                         uint8_t *d_block_init, int32_t *d_status, int32_t *d_header_status,
+                                         void *d_workspace, size_t workspace_bytes, void *stream) {
+  return encode_batch_shared(Source{d_gray, gray_frame_stride, nullptr, n_frames}, false, width, height, flags, d_canon_in,
+                             d_canon_header, d_codes, codes_frame_stride, d_codes_len, d_frame_code_offsets,
+                             d_block_offsets, d_block_init, d_status, d_header_status, d_workspace, workspace_bytes,
+                             stream);
+}
+
+size_t mh_encode_images_shared_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_images, uint32_t n_planes) {
+  const uint64_t n = (uint64_t)n_images * n_planes;
+  return n > 0x7FFFFFFFull ? 0 : mh_encode_frames_shared_workspace_bytes(width, height, (uint32_t)n);
+}
+
+int mh_encode_images_shared_device_async(const uint8_t *d_pixels, const mh_image_layout *layout, uint32_t n_images,
+                                         uint32_t width, uint32_t height, uint32_t flags,
+                                         const uint8_t *d_canon_in, uint8_t *d_canon_header, uint8_t *d_codes,
+                                         uint64_t codes_frame_stride, uint64_t *d_codes_len,
+                                         uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets,
+                                         uint8_t *d_block_init, int32_t *d_status, int32_t *d_header_status,
+                                         void *d_workspace, size_t workspace_bytes, void *stream) {
+  return encode_batch_shared(Source{d_pixels, 0, layout, n_images}, true, width, height, flags, d_canon_in,
+                             d_canon_header, d_codes, codes_frame_stride, d_codes_len, d_frame_code_offsets,
+                             d_block_offsets, d_block_init, d_status, d_header_status, d_workspace, workspace_bytes,
+                             stream);
 }
 
 }  // extern "C"

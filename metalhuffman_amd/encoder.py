@@ -252,6 +252,102 @@ class BatchEncoder:
         return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status[:n], offs,
                                  init, flags, True, status[n:])
 
+    def _image_layout(self, images: torch.Tensor, plane_major: bool, first_channel: int, n_planes):
+        """The mh_image_layout of a uint8 [n, H, W, K] tensor with channel stride 1 and any other
+        strides (a window of a larger batch, RGB of RGBA, padded rows), and its image count."""
+        if images.dtype != torch.uint8 or images.dim() != 4:
+            raise ValueError("images must be a uint8 tensor [n, H, W, K]")
+        n, h, w, k = images.shape
+        c = k - first_channel if n_planes is None else int(n_planes)
+        if first_channel < 0 or c < 1 or first_channel + c > k:
+            raise ValueError(f"planes {first_channel}..{first_channel + c - 1} of {k}-channel pixels")
+        if (h, w) != (self.height, self.width) or n * c != self.n:
+            raise ValueError(f"images must be [n, {self.height}, {self.width}, K] with n * n_planes == {self.n}")
+        if k > 1 and images.stride(3) != 1:
+            raise ValueError("the channels of a pixel must be adjacent bytes (stride 1)")
+        if images.device != self.device:
+            raise ValueError("images must live on the encoder's device")
+        # a dimension of size 1 may carry any stride: the library ignores the image stride and the
+        # row pitch there, and a one-pixel row needs a pixel stride that holds its channels
+        ps = images.stride(2) if w > 1 else max(images.stride(2), k)
+        return N.mh_image_layout(images.stride(0), images.stride(1), ps, first_channel, c, 1 if plane_major else 0), n, c
+
+    def encode_images_async(self, images: torch.Tensor, plane_major: bool = False, first_channel: int = 0,
+                            n_planes=None, flags: int = 0, init_zero_delta: bool = False,
+                            stream: Optional[torch.cuda.Stream] = None,
+                            limit_lengths: bool = False) -> "AsyncEncodedBatch":
+        """encode_async reading interleaved pixels in place (mh_encode_images_device_async): `images`
+        is uint8 [n, H, W, K] with adjacent channels and ANY other strides -- imgs[:, y0:y1, x0:x1, :3]
+        of an RGBA batch goes in without a copy -- and the encoder was built for n_frames = n * C
+        frames, C = n_planes (default: the channels from first_channel on). Plane c of image i is
+        frame i * C + c, or c * n + i with plane_major; each is byte-identical to codec.encode_frame
+        of codec.image_planes(images, ...)[frame]. The batch carries n_planes and
+        plane_frame_stride for decoder.decode_crops_normalized_planes."""
+        lay, n_img, c = self._image_layout(images, plane_major, first_channel, n_planes)
+        n = self.n
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=self.device)
+            offs = torch.empty(n * self.nb, dtype=torch.int32, device=self.device)
+            init = torch.empty(n * self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
+            canon = torch.empty((n, 256), dtype=torch.uint8, device=self.device)
+            lens = torch.empty(n, dtype=torch.int64, device=self.device)
+            fco = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+        cbase = (codes.data_ptr() + 15) // 16 * 16
+        base = self.workspace.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        N.check(N.lib().mh_encode_images_device_async(
+            images.data_ptr(), ctypes.byref(lay), n_img, self.width, self.height,
+            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths), canon.data_ptr(), cbase, self.slot, lens.data_ptr(),
+            fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None, status.data_ptr(),
+            aligned, self.workspace.numel() - (aligned - base), _stream_ptr(stream, self.device)),
+            "mh_encode_images_device_async")
+        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
+        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status, offs,
+                                 init, flags, n_planes=c, plane_frame_stride=n_img if plane_major else 1)
+
+    def encode_images_shared_async(self, images: torch.Tensor, header=None, plane_major: bool = False,
+                                   first_channel: int = 0, n_planes=None, flags: int = 0,
+                                   init_zero_delta: bool = False, stream: Optional[torch.cuda.Stream] = None,
+                                   limit_lengths: bool = False) -> "AsyncEncodedBatch":
+        """encode_shared_async reading interleaved pixels in place
+        (mh_encode_images_shared_device_async): ONE table for all n * C plane frames, built from
+        their summed histogram (header=None: codec.shared_header of codec.image_planes(images, ...))
+        or supplied. `images`, the frame order and the batch's plane fields as in
+        encode_images_async; `header` and the result as in encode_shared_async."""
+        lay, n_img, c = self._image_layout(images, plane_major, first_channel, n_planes)
+        n = self.n
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=self.device)
+            offs = torch.empty(n * self.nb, dtype=torch.int32, device=self.device)
+            init = torch.empty(n * self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
+            canon = torch.empty(256, dtype=torch.uint8, device=self.device)
+            lens = torch.empty(n, dtype=torch.int64, device=self.device)
+            fco = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            status = torch.empty(n + 1, dtype=torch.int32, device=self.device)  # [n]: the header's verdict
+            canon_in = None
+            if header is not None:
+                if isinstance(header, torch.Tensor):
+                    canon_in = header.to(self.device, torch.uint8).contiguous()
+                else:
+                    canon_in = torch.from_numpy(np.ascontiguousarray(header, np.uint8)).to(self.device)
+                if canon_in.numel() != 256:
+                    raise ValueError("header must hold 256 code lengths")
+        cbase = (codes.data_ptr() + 15) // 16 * 16
+        base = self.workspace.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        N.check(N.lib().mh_encode_images_shared_device_async(
+            images.data_ptr(), ctypes.byref(lay), n_img, self.width, self.height,
+            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
+            canon_in.data_ptr() if canon_in is not None else None, canon.data_ptr(), cbase, self.slot,
+            lens.data_ptr(), fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None,
+            status.data_ptr(), status.data_ptr() + 4 * n, aligned, self.workspace.numel() - (aligned - base),
+            _stream_ptr(stream, self.device)), "mh_encode_images_shared_device_async")
+        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
+        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status[:n], offs,
+                                 init, flags, True, status[n:], n_planes=c,
+                                 plane_frame_stride=n_img if plane_major else 1)
+
 
 @dataclasses.dataclass
 class AsyncEncodedBatch:
@@ -275,6 +371,8 @@ class AsyncEncodedBatch:
     flags: int
     shared: bool = False              # encode_shared_async: ONE table; canon is then u8[256]
     header_status: Optional[torch.Tensor] = None  # shared: int32[1] on the device, the header's verdict
+    n_planes: int = 1            # encode_images_*: the planes taken per image (frames = images * n_planes)
+    plane_frame_stride: int = 1  # ... and the frames from a plane of an image to its next plane
 
     def frames(self, check: bool = True) -> DeviceFrames:
         """All slots as one DeviceFrames batch: for decoder.decode_frames with table_set()
