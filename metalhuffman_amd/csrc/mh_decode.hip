@@ -1885,10 +1885,17 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
                                                  (a0.w - 8u * p_rbx0) | ((a0.h - 8u * p_rby0) << 16)});
 }
 
+// A list entry's 16-byte descriptor, wave-uniform: the one dependent trip ahead of slice_decode's prologue.
+__device__ __forceinline__ v4u32 desc_load(const void *desc) {
+  v4u32 d = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(desc, 16u), 0, 0, 0);
+  d.x = __builtin_amdgcn_readfirstlane(d.x), d.y = __builtin_amdgcn_readfirstlane(d.y);
+  d.z = __builtin_amdgcn_readfirstlane(d.z), d.w = __builtin_amdgcn_readfirstlane(d.w);
+  return d;
+}
+
 // mh_decode_windows: workgroup g serves window g / G, whose frame and origin it reads from the
-// window's 16-byte descriptor -- one load per workgroup, the one dependent trip ahead of
-// slice_decode's prologue. The workgroup judges the descriptor by itself, before anything is
-// addressed through it: a window that names no frame, leaves the block grid or has a non-zero
+// window's 16-byte descriptor (desc_load, as the four list kernels below do). The workgroup judges
+// the descriptor by itself, before anything is addressed through it: a window that names no frame, leaves the block grid or has a non-zero
 // reserved word returns here, having loaded and stored nothing but its status word. The origin is
 // compared with the last one that fits, p_max_bx0 = block_width - bw and p_max_by0 = block_height -
 // bh from the host (which has checked bw <= block_width and bh <= block_height), so no sum of
@@ -1902,9 +1909,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbh, uint32_t p_nframes, uint32_t p_max_bx0, uint32_t p_max_by0,
     uint64_t p_lut_stride, int32_t *p_wstatus, const DecodeArgs a0) {
   const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 wd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_windows + p, 16u), 0, 0, 0);
-  const uint32_t f = __builtin_amdgcn_readfirstlane(wd.x), bx0 = __builtin_amdgcn_readfirstlane(wd.y);
-  const uint32_t by0 = __builtin_amdgcn_readfirstlane(wd.z), reserved = __builtin_amdgcn_readfirstlane(wd.w);
+  const v4u32 wd = desc_load(p_windows + p);
+  const uint32_t f = wd.x, bx0 = wd.y, by0 = wd.z, reserved = wd.w;
   if ((f >= p_nframes) | (bx0 > p_max_bx0) | (by0 > p_max_by0) | (reserved != 0u)) {  // workgroup-uniform
     if (p_wstatus && slice == 0 && threadIdx.x == 0) p_wstatus[p] = MH_ERR_DIMS;
     return;
@@ -1929,9 +1935,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbh, uint32_t p_nframes, uint32_t p_max_bx0, uint32_t p_max_by0,
     uint64_t p_lut_stride, int32_t *p_wstatus, const DecodeArgs a0) {
   const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 wd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_windows + p, 16u), 0, 0, 0);
-  const uint32_t f = __builtin_amdgcn_readfirstlane(wd.x), bx0 = __builtin_amdgcn_readfirstlane(wd.y);
-  const uint32_t by0 = __builtin_amdgcn_readfirstlane(wd.z), reserved = __builtin_amdgcn_readfirstlane(wd.w);
+  const v4u32 wd = desc_load(p_windows + p);
+  const uint32_t f = wd.x, bx0 = wd.y, by0 = wd.z, reserved = wd.w;
   if ((f >= p_nframes) | (bx0 > p_max_bx0) | (by0 > p_max_by0) | (reserved != 0u)) {  // workgroup-uniform
     if (p_wstatus && slice == 0 && threadIdx.x == 0) p_wstatus[p] = MH_ERR_DIMS;
     return;
@@ -1963,9 +1968,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0, uint32_t p_max_y0,
     uint64_t p_lut_stride, int32_t *p_cstatus, const DecodeArgs a0) {
   const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 cd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_crops + p, 16u), 0, 0, 0);
-  const uint32_t f = __builtin_amdgcn_readfirstlane(cd.x), x0 = __builtin_amdgcn_readfirstlane(cd.y);
-  const uint32_t y0 = __builtin_amdgcn_readfirstlane(cd.z), reserved = __builtin_amdgcn_readfirstlane(cd.w);
+  const v4u32 cd = desc_load(p_crops + p);
+  const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z, reserved = cd.w;
   if ((f >= p_nframes) | (x0 > p_max_x0) | (y0 > p_max_y0) | (reserved != 0u)) {  // workgroup-uniform
     if (p_cstatus && slice == 0 && threadIdx.x == 0) p_cstatus[p] = MH_ERR_DIMS;
     return;
@@ -1994,9 +1998,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0, uint32_t p_max_y0,
     uint64_t p_lut_stride, int32_t *p_cstatus, float p_scale, float p_bias, uint32_t p_odd_w, const DecodeArgs a0) {
   const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 cd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_crops + p, 16u), 0, 0, 0);
-  const uint32_t f = __builtin_amdgcn_readfirstlane(cd.x), x0 = __builtin_amdgcn_readfirstlane(cd.y);
-  const uint32_t y0 = __builtin_amdgcn_readfirstlane(cd.z), flags = __builtin_amdgcn_readfirstlane(cd.w);
+  const v4u32 cd = desc_load(p_crops + p);
+  const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z, flags = cd.w;
   if ((f >= p_nframes) | (x0 > p_max_x0) | (y0 > p_max_y0) | ((flags & ~MH_CROP_MIRROR) != 0u) |
       ((flags & p_odd_w) != 0u)) {  // workgroup-uniform
     if (p_cstatus && slice == 0 && threadIdx.x == 0) p_cstatus[p] = MH_ERR_DIMS;
@@ -2049,9 +2052,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     p = unit / pl.n_planes;
     c = unit - p * pl.n_planes;
   }
-  const v4u32 cd = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(p_crops + p, 16u), 0, 0, 0);
-  const uint32_t f0 = __builtin_amdgcn_readfirstlane(cd.x), x0 = __builtin_amdgcn_readfirstlane(cd.y);
-  const uint32_t y0 = __builtin_amdgcn_readfirstlane(cd.z), flags = __builtin_amdgcn_readfirstlane(cd.w);
+  const v4u32 cd = desc_load(p_crops + p);
+  const uint32_t f0 = cd.x, x0 = cd.y, y0 = cd.z, flags = cd.w;
   const bool writer = c == 0u && slice == 0u && threadIdx.x == 0u;
   if ((f0 > p_max_frame) | (x0 > p_max_x0) | (y0 > p_max_y0) | ((flags & ~MH_CROP_MIRROR) != 0u) |
       ((flags & p_odd_w) != 0u)) {  // workgroup-uniform
@@ -3128,6 +3130,36 @@ int launch_slices(SliceKernel family, const DecodeCall &c, const SliceArgs &p, v
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 
+// The DecodeCall of a list entry (windows, crops, normalised crops) or of its *_shape twin (no tables,
+// no descriptors). It owns the size c.rg points to: blocks for windows, pixels for crops.
+struct ListCall : DecodeCall {
+  mh_region size;
+  ListCall(Kind kind, uint32_t w, uint32_t h, uint32_t log2_scale, uint32_t n, const void *descriptors = nullptr,
+           const void *luts = nullptr, uint64_t stride = 0)
+      : DecodeCall{kind, luts, stride, &size, log2_scale, descriptors, n}, size{0u, 0u, w, h} {}
+  ListCall(const ListCall &) = delete;  // rg points into this object
+};
+
+// A list entry behind what it checks itself: the refusal of a status array that is the frame status it
+// reads (MH_ERR_INVALID_ARG, as every refusal ahead of the prologue), the prologue and the launch.
+// Behind the group count every list kernel takes the segments, the size, its verdict's frame limit
+// (n_frames less `frames_short`) and last origin that fits (blocks for windows, pixels for crops),
+// the table stride and its own status array, then `tail`.
+template <class Fn, class Desc, class... Tail>
+int decode_list(SliceKernel family, const mh_frame *fr, ListCall &c, const Desc *descriptors,
+                const int32_t *frame_status, int32_t *list_status, void *d_out, size_t out_pitch, size_t out_stride,
+                void *stream, uint32_t frames_short, Tail... tail) {
+  if (list_status && list_status == frame_status) return MH_ERR_INVALID_ARG;
+  SliceArgs p;
+  const int rc = slice_prologue(fr, static_cast<uint8_t *>(d_out), out_pitch, out_stride, c, p);
+  if (rc != MH_OK) return rc;
+  const mh_dims &d = fr->dims;
+  return launch_slices<Fn>(family, c, p, stream, static_cast<const uint8_t *>(c.ptr), frame_status, descriptors,
+                           c.re.segs, c.size.bw, c.size.bh, fr->n_frames - frames_short,
+                           (c.cropped() ? d.width : d.block_width) - c.size.bw,
+                           (c.cropped() ? d.height : d.block_height) - c.size.bh, c.stride, list_status, tail...);
+}
+
 // mh_decode_*_shape: slice_shape for a frame description, the units and the tiles counted by the
 // decode entries' own rules (call_geometry). The tile cap is reported for a region or windows only,
 // as it always was: the whole-frame entries leave it to the decode call.
@@ -3227,7 +3259,8 @@ int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_f
 
 #if !MH_LANE_PAIRS
 // The frame-slice entries. Each is its DecodeCall, the prologue and one launch of its row of
-// kSliceTable with its own trailing scalars; each *_shape twin is the same call without tables.
+// kSliceTable with its own trailing scalars (the list entries: a ListCall and decode_list); each
+// *_shape twin is the same call without tables.
 int mh_decode_frames(const mh_frame *fr, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                      const int32_t *d_frame_status, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                      void *stream) {
@@ -3300,16 +3333,9 @@ int mh_decode_windows_scaled(const mh_frame *fr, const mh_window *d_windows, uin
                              uint32_t bh, uint32_t log2_scale, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                              const int32_t *d_frame_status, int32_t *d_window_status, uint8_t *d_out,
                              size_t out_pitch, size_t out_window_stride, void *stream) {
-  if (d_window_status && d_window_status == d_frame_status) return MH_ERR_INVALID_ARG;
-  const mh_region size = {0u, 0u, bw, bh};
-  DecodeCall c{DecodeCall::kWindows, d_luts, lut_stride_bytes, &size, log2_scale, d_windows, n_windows};
-  SliceArgs p;
-  const int rc = slice_prologue(fr, d_out, out_pitch, out_window_stride, c, p);
-  if (rc != MH_OK) return rc;
-  return launch_slices<WindowsFn>(kSliceWindows, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
-                                  d_frame_status, d_windows, c.re.segs, bw, bh, fr->n_frames,
-                                  fr->dims.block_width - bw, fr->dims.block_height - bh, lut_stride_bytes,
-                                  d_window_status);
+  ListCall c(DecodeCall::kWindows, bw, bh, log2_scale, n_windows, d_windows, d_luts, lut_stride_bytes);
+  return decode_list<WindowsFn>(kSliceWindows, fr, c, d_windows, d_frame_status, d_window_status, d_out, out_pitch,
+                                out_window_stride, stream, 0u);
 }
 
 int mh_decode_windows(const mh_frame *fr, const mh_window *d_windows, uint32_t n_windows, uint32_t bw, uint32_t bh,
@@ -3323,9 +3349,8 @@ int mh_decode_windows(const mh_frame *fr, const mh_window *d_windows, uint32_t n
 int mh_decode_windows_scaled_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh,
                                    uint32_t log2_scale, void *stream, uint32_t *groups_per_window,
                                    uint32_t *waves_per_group) {
-  const mh_region size = {0u, 0u, bw, bh};
-  return slice_shape_entry(kSliceWindows, fr, {DecodeCall::kWindows, nullptr, 0, &size, log2_scale, nullptr, n_windows},
-                           stream, groups_per_window, waves_per_group);
+  return slice_shape_entry(kSliceWindows, fr, ListCall(DecodeCall::kWindows, bw, bh, log2_scale, n_windows), stream,
+                           groups_per_window, waves_per_group);
 }
 
 int mh_decode_windows_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw, uint32_t bh, void *stream,
@@ -3340,22 +3365,15 @@ int mh_decode_windows_shape(const mh_frame *fr, uint32_t n_windows, uint32_t bw,
 int mh_decode_crops(const mh_frame *fr, const mh_crop *d_crops, uint32_t n_crops, uint32_t w, uint32_t h,
                     const uint16_t *d_luts, uint64_t lut_stride_bytes, const int32_t *d_frame_status,
                     int32_t *d_crop_status, uint8_t *d_out, size_t out_pitch, size_t out_crop_stride, void *stream) {
-  if (d_crop_status && d_crop_status == d_frame_status) return MH_ERR_INVALID_ARG;
-  const mh_region size = {0u, 0u, w, h};
-  DecodeCall c{DecodeCall::kCrops, d_luts, lut_stride_bytes, &size, 0u, d_crops, n_crops};
-  SliceArgs p;
-  const int rc = slice_prologue(fr, d_out, out_pitch, out_crop_stride, c, p);
-  if (rc != MH_OK) return rc;
-  return launch_slices<CropsFn>(kSliceCrops, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts), d_frame_status,
-                                d_crops, c.re.segs, w, h, fr->n_frames, fr->dims.width - w, fr->dims.height - h,
-                                lut_stride_bytes, d_crop_status);
+  ListCall c(DecodeCall::kCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
+  return decode_list<CropsFn>(kSliceCrops, fr, c, d_crops, d_frame_status, d_crop_status, d_out, out_pitch,
+                              out_crop_stride, stream, 0u);
 }
 
 int mh_decode_crops_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h, void *stream,
                           uint32_t *groups_per_crop, uint32_t *waves_per_group) {
-  const mh_region size = {0u, 0u, w, h};
-  return slice_shape_entry(kSliceCrops, fr, {DecodeCall::kCrops, nullptr, 0, &size, 0u, nullptr, n_crops}, stream,
-                           groups_per_crop, waves_per_group);
+  return slice_shape_entry(kSliceCrops, fr, ListCall(DecodeCall::kCrops, w, h, 0u, n_crops), stream, groups_per_crop,
+                           waves_per_group);
 }
 
 // The crops decoded straight into normalised elements: the crops kernel's entry and body with the
@@ -3365,25 +3383,17 @@ int mh_decode_crops_norm(const mh_frame *fr, const mh_norm_crop *d_crops, uint32
                          uint32_t format, float scale, float bias, const uint16_t *d_luts, uint64_t lut_stride_bytes,
                          const int32_t *d_frame_status, int32_t *d_crop_status, void *d_out, size_t out_pitch,
                          size_t out_crop_stride, void *stream) {
-  if (d_crop_status && d_crop_status == d_frame_status) return MH_ERR_INVALID_ARG;
-  const mh_region size = {0u, 0u, w, h};
-  DecodeCall c{DecodeCall::kNormCrops, d_luts, lut_stride_bytes, &size, 0u, d_crops, n_crops};
+  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
   c.format = format;
   c.scale = scale;
   c.bias = bias;
-  SliceArgs p;
-  const int rc = slice_prologue(fr, static_cast<uint8_t *>(d_out), out_pitch, out_crop_stride, c, p);
-  if (rc != MH_OK) return rc;
-  return launch_slices<NormCropsFn>(kSliceNormCrops, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
-                                    d_frame_status, d_crops, c.re.segs, w, h, fr->n_frames, fr->dims.width - w,
-                                    fr->dims.height - h, lut_stride_bytes, d_crop_status, scale, bias,
-                                    (w & 7u) ? 1u : 0u);
+  return decode_list<NormCropsFn>(kSliceNormCrops, fr, c, d_crops, d_frame_status, d_crop_status, d_out, out_pitch,
+                                  out_crop_stride, stream, 0u, scale, bias, (w & 7u) ? 1u : 0u);
 }
 
 int mh_decode_crops_norm_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h, uint32_t format,
                                void *stream, uint32_t *groups_per_crop, uint32_t *waves_per_group) {
-  const mh_region size = {0u, 0u, w, h};
-  DecodeCall c{DecodeCall::kNormCrops, nullptr, 0, &size, 0u, nullptr, n_crops};
+  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops);
   c.format = format;
   return slice_shape_entry(kSliceNormCrops, fr, c, stream, groups_per_crop, waves_per_group);
 }
@@ -3399,7 +3409,6 @@ int mh_decode_crops_norm_planes(const mh_frame *fr, const mh_norm_crop *d_crops,
                                 uint64_t lut_stride_bytes, const int32_t *d_frame_status, int32_t *d_crop_status,
                                 void *d_out, size_t out_pitch, size_t out_plane_stride, size_t out_crop_stride,
                                 void *stream) {
-  if (d_crop_status && d_crop_status == d_frame_status) return MH_ERR_INVALID_ARG;
   if (n_planes == 0 || n_planes > MH_MAX_PLANES || !scale || !bias) return MH_ERR_INVALID_ARG;
   PlaneArgs pl = {};
   for (uint32_t i = 0; i < n_planes; ++i) {
@@ -3410,28 +3419,21 @@ int mh_decode_crops_norm_planes(const mh_frame *fr, const mh_norm_crop *d_crops,
   pl.n_planes = n_planes;
   pl.frame_stride = n_planes > 1 ? plane_frame_stride : 0u;
   pl.out_stride = n_planes > 1 ? out_plane_stride : 0u;
-  const mh_region size = {0u, 0u, w, h};
-  DecodeCall c{DecodeCall::kNormCrops, d_luts, lut_stride_bytes, &size, 0u, d_crops, n_crops};
+  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
   c.format = format;
   c.n_planes = n_planes;
   c.plane_frame_stride = pl.frame_stride;
   c.out_plane_stride = pl.out_stride;
-  SliceArgs p;
-  const int rc = slice_prologue(fr, static_cast<uint8_t *>(d_out), out_pitch, out_crop_stride, c, p);
-  if (rc != MH_OK) return rc;
-  // call_geometry: (n_planes - 1) * frame_stride < n_frames
-  const uint32_t max_frame = fr->n_frames - 1u - (n_planes - 1u) * pl.frame_stride;
-  return launch_slices<PlanesFn>(kSlicePlanes, c, p, stream, reinterpret_cast<const uint8_t *>(d_luts),
-                                 d_frame_status, d_crops, c.re.segs, w, h, max_frame, fr->dims.width - w,
-                                 fr->dims.height - h, lut_stride_bytes, d_crop_status, (w & 7u) ? 1u : 0u, pl);
+  // the kernel's p_max_frame = n_frames - 1 - (n_planes - 1) * frame_stride (call_geometry: it does not wrap)
+  return decode_list<PlanesFn>(kSlicePlanes, fr, c, d_crops, d_frame_status, d_crop_status, d_out, out_pitch,
+                               out_crop_stride, stream, 1u + (n_planes - 1u) * pl.frame_stride, (w & 7u) ? 1u : 0u, pl);
 }
 
 int mh_decode_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h, uint32_t format,
                                       uint32_t n_planes, void *stream, uint32_t *groups_per_plane,
                                       uint32_t *waves_per_group) {
   if (n_planes == 0 || n_planes > MH_MAX_PLANES) return MH_ERR_INVALID_ARG;
-  const mh_region size = {0u, 0u, w, h};
-  DecodeCall c{DecodeCall::kNormCrops, nullptr, 0, &size, 0u, nullptr, n_crops};
+  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops);
   c.format = format;
   c.n_planes = n_planes;
   return slice_shape_entry(kSlicePlanes, fr, c, stream, groups_per_plane, waves_per_group);

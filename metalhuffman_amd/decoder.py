@@ -259,6 +259,7 @@ def decode(frames: DeviceFrames, tables: DeviceTables, out: Optional[torch.Tenso
     fr, dev_index = _frame_entry(frames, tables, extra_flags)
     pitch = (frames.width + 7) // 8 * 8
     h = frames.height
+    # _out_raster and _raw_stream_ptr inlined on purpose: two calls show on the 5.3 us single-frame path
     if out is None:
         out = torch.empty((frames.n_frames, h, pitch), dtype=torch.uint8, device=frames.codes.device)
     else:
@@ -303,6 +304,15 @@ def _frames_entry(frames: DeviceFrames, extra_flags: int = 0):
     return _frame_entry(frames, None, extra_flags)
 
 
+def _slice_entry(who: str, frames: DeviceFrames, extra_flags: int):
+    """_frames_entry for the decode entries of the product library, none of which has the lane-pair
+    kernel: (mh_frame, device index), or ValueError naming `who` under MH_FLAG_LANE_PAIRS."""
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    if fr.flags & N.MH_FLAG_LANE_PAIRS:
+        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
+    return fr, dev_index
+
+
 def _out_raster(frames: DeviceFrames, out: Optional[torch.Tensor], h: int, pitch: int, dev_index: int,
                 stream: Optional[torch.cuda.Stream]) -> torch.Tensor:
     """decode()'s `out` contract for a raster of h rows: allocated (on `stream`) when None,
@@ -336,15 +346,28 @@ def _check_table_set(ts: DeviceTableSet, frames: DeviceFrames, dev_index: int) -
 
 
 def _slice_shape(entry: str, frames: DeviceFrames, stream: Optional[torch.cuda.Stream], extra_flags: int,
-                 region=None, windows=None, log2_scale=None) -> tuple:
-    """(workgroups per frame or window, waves per workgroup) from the C entry `entry`
+                 region=None, windows=None, log2_scale=None, crops=None) -> tuple:
+    """(workgroups per frame, window or crop, waves per workgroup) from the C entry `entry`
     (mh_decode_*_shape). Between the frame and the stream the entry takes `region`, or
-    windows = (n_windows, (bw, bh)), and then `log2_scale` -- each when given."""
+    windows = (n_windows, (bw, bh)) and then `log2_scale`, or crops = (n_crops, (w, h)[, dtype
+    [, n_planes]]), the pixel size followed by the format and the plane count -- each when given."""
     scale = () if log2_scale is None else (_log2_scale(log2_scale),)
-    size = () if windows is None else _window_size(frames, windows[1])
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
     what = ()
     if windows is not None:
+        size = _window_size(frames, windows[1])
+    elif crops is not None:
+        what = _crop_size(frames, crops[1])
+        if len(crops) > 2:
+            what += (_norm_format(crops[2]),)
+        if int(crops[0]) < 1:
+            raise ValueError("no crops")
+        if len(crops) > 3:
+            if not 1 <= int(crops[3]) <= N.MH_MAX_PLANES:
+                raise ValueError(f"1..{N.MH_MAX_PLANES} planes, not {crops[3]}")
+            what += (int(crops[3]),)
+        what = (int(crops[0]), *what)
+    fr, dev_index = _frame_entry(frames, None, extra_flags)
+    if windows is not None:  # (the windows' count is checked behind the frame entry, the crops' ahead of it)
         if int(windows[0]) < 1:
             raise ValueError("no windows")
         what = (int(windows[0]), *size)
@@ -380,9 +403,7 @@ def decode_frames(frames, table_set="cuda", out: Optional[torch.Tensor] = None,
         return _decode_frames_host(frames, table_set)
     if not isinstance(table_set, DeviceTableSet):
         raise TypeError("decode_frames(DeviceFrames, ...) takes a DeviceTableSet")
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_frames")
+    fr, dev_index = _slice_entry("decode_frames", frames, extra_flags)
     _check_table_set(table_set, frames, dev_index)
     pitch = (frames.width + 7) // 8 * 8
     h = frames.height
@@ -462,9 +483,7 @@ def _decode_region(who: str, k: Optional[int], frames: DeviceFrames, tables, reg
                    extra_flags: int, skip_rejected: bool) -> torch.Tensor:
     """decode_region (k None: the C entry takes no scale) and decode_region_scaled: the arguments
     checked, the default raster made, one launch."""
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
+    fr, dev_index = _slice_entry(who, frames, extra_flags)
     rg = _region_struct(frames, region)
     luts, stride, status = _region_tables(who, frames, tables, dev_index, skip_rejected)
     k0 = k or 0
@@ -583,29 +602,36 @@ def _window_size(frames: DeviceFrames, size) -> tuple:
     return bw, bh
 
 
-def _host_windows(frames: DeviceFrames, windows, bw: int, bh: int):
-    """decode_windows' `windows` checked on the host: a device tensor's type and shape only (it is
-    not read: no host sync, the kernel validates it) -> None; a host sequence against the frames
-    and the block grid (ValueError) -> its int32 [n, 4] descriptor array."""
-    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+def _host_list(frames: DeviceFrames, items, noun: str, origin: str, w: int, h: int, unit: str, limits: tuple,
+               of: str):
+    """A descriptor list checked on the host: a device tensor's type and shape only (it is not read: no
+    host sync, the kernel validates it) -> None; a host sequence of (frame, `origin`) -> its int32 [n, 4]
+    descriptor array, or ValueError when a `noun` of w x h `unit` names no frame or leaves `limits`."""
+    if isinstance(items, torch.Tensor) and items.is_cuda:
         dev = frames.codes.device
-        if (windows.device != dev or windows.dtype is not torch.int32 or windows.dim() != 2
-                or windows.shape[1] not in (3, 4) or windows.shape[0] < 1):
-            raise ValueError(f"a device windows tensor is int32 [n, 3] or [n, 4] on {dev}")
+        if (items.device != dev or items.dtype is not torch.int32 or items.dim() != 2
+                or items.shape[1] not in (3, 4) or items.shape[0] < 1):
+            raise ValueError(f"a device {noun}s tensor is int32 [n, 3] or [n, 4] on {dev}")
         return None
-    w = np.asarray(windows.numpy() if isinstance(windows, torch.Tensor) else windows)
-    if w.ndim != 2 or w.shape[1] != 3 or w.shape[0] < 1 or w.dtype.kind not in "iu":
-        raise ValueError("windows is a sequence of (frame, bx0, by0) integers")
-    w = w.astype(np.int64)
-    gw, gh = block_grid(frames.width, frames.height)
-    bad = ((w < 0).any(axis=1) | (w[:, 0] >= frames.n_frames) | (w[:, 1] + bw > gw) | (w[:, 2] + bh > gh))
+    a = np.asarray(items.numpy() if isinstance(items, torch.Tensor) else items)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1 or a.dtype.kind not in "iu":
+        raise ValueError(f"{noun}s is a sequence of (frame, {origin}) integers")
+    a = a.astype(np.int64)
+    lw, lh = limits
+    bad = ((a < 0).any(axis=1) | (a[:, 0] >= frames.n_frames) | (a[:, 1] + w > lw) | (a[:, 2] + h > lh))
     if bad.any():
         i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"window {i} = {tuple(int(v) for v in w[i])} of {bw}x{bh} blocks lies outside the "
-                         f"{frames.n_frames} frames of {gw}x{gh} blocks")
-    full = np.zeros((w.shape[0], 4), np.int32)
-    full[:, :3] = w
+        raise ValueError(f"{noun} {i} = {tuple(int(v) for v in a[i])} of {w}x{h} {unit} lies outside the "
+                         f"{frames.n_frames} frames of {lw}x{lh}{of}")
+    full = np.zeros((a.shape[0], 4), np.int32)
+    full[:, :3] = a
     return full
+
+
+def _host_windows(frames: DeviceFrames, windows, bw: int, bh: int):
+    """decode_windows' `windows` checked on the host (_host_list) against the frames and the block grid."""
+    return _host_list(frames, windows, "window", "bx0, by0", bw, bh, "blocks",
+                      block_grid(frames.width, frames.height), " blocks")
 
 
 def _windows_tensor(frames: DeviceFrames, windows, host) -> torch.Tensor:
@@ -628,42 +654,52 @@ def decode_windows_shape(frames: DeviceFrames, n_windows: int, size,
     return _slice_shape("mh_decode_windows_shape", frames, stream, extra_flags, windows=(n_windows, size))
 
 
+_NO_STREAM = contextlib.nullcontext()  # (reusable: one per call costs what two function calls do)
+
+
+def _decode_list(who: str, entry: str, frames: DeviceFrames, tables, items, host, mid: tuple, slot: tuple, dtype,
+                 strides: tuple, out, status, stream, extra_flags: int, skip_rejected: bool):
+    """What the window and crop entries share behind their own checks: the frame entry, the tables, the
+    descriptor array, the default ZERO-FILLED raster [n, *slot] of `dtype` and the status tensor (all made
+    under `stream`), `out` and `status` checked, and one launch of the C entry `entry`, which takes `mid`
+    between the descriptor count and the tables and, behind the rasters, their byte `strides` (row, [plane,]
+    slot). `host`: _host_list's result for `items`. Called once per batch: no loop, no list, no closure."""
+    fr, dev_index = _slice_entry(who, frames, extra_flags)
+    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
+    dev = frames.codes.device
+    with torch.cuda.stream(stream) if stream is not None else _NO_STREAM:
+        desc = _windows_tensor(frames, items, host)  # (an upload or a padded copy belongs to `stream`)
+        n = int(desc.shape[0])
+        shape = (n, *slot)
+        if out is None:
+            out = torch.zeros(shape, dtype=dtype, device=dev)
+        lstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
+    if (out.dtype is not dtype or out.shape != shape or out.get_device() != dev_index
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {'uint8' if dtype is torch.uint8 else dtype} {list(shape)} "
+                         f"tensor on cuda:{dev_index}")
+    if lstatus is not None and (not isinstance(lstatus, torch.Tensor) or lstatus.dtype is not torch.int32
+                                or lstatus.numel() != n or lstatus.get_device() != dev_index
+                                or not lstatus.is_contiguous()):
+        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
+    rc = getattr(N.lib(), entry)(ctypes.byref(fr), desc.data_ptr(), n, *mid, luts.data_ptr(), stride,
+                                 fstatus.data_ptr() if fstatus is not None else None,
+                                 lstatus.data_ptr() if lstatus is not None else None, out.data_ptr(), *strides,
+                                 _raw_stream_ptr(stream, dev_index))
+    if rc:
+        N.check(rc, entry)
+    return (out, lstatus) if status is True else out
+
+
 def _decode_windows(who: str, k: int, frames: DeviceFrames, tables, windows, size, out, status, stream,
                     extra_flags: int, skip_rejected: bool):
-    """decode_windows (k = 0) and decode_windows_scaled: the arguments checked, the descriptor array and
-    the default rasters made, one launch."""
+    """decode_windows (k = 0: the C entry takes no scale) and decode_windows_scaled."""
     bw, bh = _window_size(frames, size)
     c = 8 >> k
     host = _host_windows(frames, windows, bw, bh)
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
-    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
-    dev = frames.codes.device
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        wins = _windows_tensor(frames, windows, host)  # (an upload or a padded copy belongs to `stream`)
-        n = int(wins.shape[0])
-        shape = (n, c * bh, c * bw)
-        if out is None:
-            out = torch.zeros(shape, dtype=torch.uint8, device=dev)
-        wstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
-    if (out.dtype is not torch.uint8 or tuple(out.shape) != shape or out.get_device() != dev_index
-            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on cuda:{dev_index}")
-    if wstatus is not None and (not isinstance(wstatus, torch.Tensor) or wstatus.dtype is not torch.int32
-                                or wstatus.numel() != n or wstatus.get_device() != dev_index
-                                or not wstatus.is_contiguous()):
-        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
-    sp = _raw_stream_ptr(stream, dev_index)
-    tail = (luts.data_ptr(), stride, fstatus.data_ptr() if fstatus is not None else None,
-            wstatus.data_ptr() if wstatus is not None else None, out.data_ptr(), c * bw, c * bh * c * bw, sp)
-    if k:
-        rc = N.lib().mh_decode_windows_scaled(ctypes.byref(fr), wins.data_ptr(), n, bw, bh, k, *tail)
-    else:
-        rc = N.lib().mh_decode_windows(ctypes.byref(fr), wins.data_ptr(), n, bw, bh, *tail)
-    if rc:
-        N.check(rc, "mh_decode_windows_scaled" if k else "mh_decode_windows")
-    return (out, wstatus) if status is True else out
+    return _decode_list(who, "mh_decode_windows_scaled" if k else "mh_decode_windows", frames, tables, windows, host,
+                        (bw, bh, k) if k else (bw, bh), (c * bh, c * bw), torch.uint8, (c * bw, c * bh * c * bw),
+                        out, status, stream, extra_flags, skip_rejected)
 
 
 def decode_windows(frames: DeviceFrames, tables, windows, size, out: Optional[torch.Tensor] = None,
@@ -725,42 +761,15 @@ def _crop_size(frames: DeviceFrames, size) -> tuple:
 
 
 def _host_crops(frames: DeviceFrames, crops, w: int, h: int):
-    """decode_crops' `crops` checked on the host, as _host_windows checks windows: a device tensor's
-    type and shape only -> None; a host sequence against the frames (ValueError) -> its int32 [n, 4]
-    descriptor array."""
-    if isinstance(crops, torch.Tensor) and crops.is_cuda:
-        dev = frames.codes.device
-        if (crops.device != dev or crops.dtype is not torch.int32 or crops.dim() != 2
-                or crops.shape[1] not in (3, 4) or crops.shape[0] < 1):
-            raise ValueError(f"a device crops tensor is int32 [n, 3] or [n, 4] on {dev}")
-        return None
-    c = np.asarray(crops.numpy() if isinstance(crops, torch.Tensor) else crops)
-    if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] < 1 or c.dtype.kind not in "iu":
-        raise ValueError("crops is a sequence of (frame, x0, y0) integers")
-    c = c.astype(np.int64)
-    bad = ((c < 0).any(axis=1) | (c[:, 0] >= frames.n_frames) | (c[:, 1] + w > frames.width)
-           | (c[:, 2] + h > frames.height))
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"crop {i} = {tuple(int(v) for v in c[i])} of {w}x{h} pixels lies outside the "
-                         f"{frames.n_frames} frames of {frames.width}x{frames.height}")
-    full = np.zeros((c.shape[0], 4), np.int32)
-    full[:, :3] = c
-    return full
+    """decode_crops' `crops` checked on the host (_host_list) against the frames and their pixel size."""
+    return _host_list(frames, crops, "crop", "x0, y0", w, h, "pixels", (frames.width, frames.height), "")
 
 
 def decode_crops_shape(frames: DeviceFrames, n_crops: int, size,
                        stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
     """(workgroups per crop, waves per workgroup) decode_crops would launch n_crops crops of
     size = (w, h) pixels with (mh_decode_crops_shape)."""
-    w, h = _crop_size(frames, size)
-    if int(n_crops) < 1:
-        raise ValueError("no crops")
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    g, wv = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    N.check(N.lib().mh_decode_crops_shape(ctypes.byref(fr), int(n_crops), w, h, _raw_stream_ptr(stream, dev_index),
-                                          ctypes.byref(g), ctypes.byref(wv)), "mh_decode_crops_shape")
-    return int(g.value), int(wv.value)
+    return _slice_shape("mh_decode_crops_shape", frames, stream, extra_flags, crops=(n_crops, size))
 
 
 def decode_crops(frames: DeviceFrames, tables, crops, size, out: Optional[torch.Tensor] = None,
@@ -781,36 +790,11 @@ def decode_crops(frames: DeviceFrames, tables, crops, size, out: Optional[torch.
     ZERO-FILLED one (a rejected or skipped crop's slot is never written). Columns >= w of a written
     row are unspecified.
     status, tables, extra_flags, skip_rejected: decode_windows'."""
-    who = "decode_crops"
     w, h = _crop_size(frames, size)
     host = _host_crops(frames, crops, w, h)
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
-    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
-    dev = frames.codes.device
     pitch = (w + 7) // 8 * 8
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        desc = _windows_tensor(frames, crops, host)  # (an upload or a padded copy belongs to `stream`)
-        n = int(desc.shape[0])
-        shape = (n, h, pitch)
-        if out is None:
-            out = torch.zeros(shape, dtype=torch.uint8, device=dev)
-        cstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
-    if (out.dtype is not torch.uint8 or tuple(out.shape) != shape or out.get_device() != dev_index
-            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on cuda:{dev_index}")
-    if cstatus is not None and (not isinstance(cstatus, torch.Tensor) or cstatus.dtype is not torch.int32
-                                or cstatus.numel() != n or cstatus.get_device() != dev_index
-                                or not cstatus.is_contiguous()):
-        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
-    rc = N.lib().mh_decode_crops(ctypes.byref(fr), desc.data_ptr(), n, w, h, luts.data_ptr(), stride,
-                                 fstatus.data_ptr() if fstatus is not None else None,
-                                 cstatus.data_ptr() if cstatus is not None else None, out.data_ptr(), pitch,
-                                 h * pitch, _raw_stream_ptr(stream, dev_index))
-    if rc:
-        N.check(rc, "mh_decode_crops")
-    return (out, cstatus) if status is True else out
+    return _decode_list("decode_crops", "mh_decode_crops", frames, tables, crops, host, (w, h), (h, pitch),
+                        torch.uint8, (pitch, h * pitch), out, status, stream, extra_flags, skip_rejected)
 
 
 _NORM_DTYPES = (torch.float16, torch.bfloat16, torch.float32)  # indexed by MH_NORM_*
@@ -842,16 +826,7 @@ def decode_crops_normalized_shape(frames: DeviceFrames, n_crops: int, size, dtyp
                                   stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0) -> tuple:
     """(workgroups per crop, waves per workgroup) decode_crops_normalized would launch n_crops crops
     of size = (w, h) pixels with, for `dtype` (mh_decode_crops_norm_shape)."""
-    w, h = _crop_size(frames, size)
-    fmt = _norm_format(dtype)
-    if int(n_crops) < 1:
-        raise ValueError("no crops")
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    g, wv = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    N.check(N.lib().mh_decode_crops_norm_shape(ctypes.byref(fr), int(n_crops), w, h, fmt,
-                                               _raw_stream_ptr(stream, dev_index), ctypes.byref(g), ctypes.byref(wv)),
-            "mh_decode_crops_norm_shape")
-    return int(g.value), int(wv.value)
+    return _slice_shape("mh_decode_crops_norm_shape", frames, stream, extra_flags, crops=(n_crops, size, dtype))
 
 
 def decode_crops_normalized(frames: DeviceFrames, tables, crops, size, dtype, scale: float = 1.0, bias: float = 0.0,
@@ -877,42 +852,17 @@ def decode_crops_normalized(frames: DeviceFrames, tables, crops, size, dtype, sc
     out: a contiguous [n, h, round_up(w, 8)] tensor of `dtype` on the frames' device; None allocates a
     ZERO-FILLED one (a rejected or skipped crop's slot is never written).
     status, tables, extra_flags, skip_rejected: decode_crops'."""
-    who = "decode_crops_normalized"
     w, h = _crop_size(frames, size)
     fmt = _norm_format(dtype)
-    tdtype, esize = _NORM_DTYPES[fmt], (2, 2, 4)[fmt]
     scale, bias = float(scale), float(bias)
     if not (finite_f32(scale) and finite_f32(bias)):
         raise ValueError(f"scale and bias must be finite in float32, not {scale!r}, {bias!r}")
     host = _host_norm_crops(frames, crops, w, h)
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
-    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
-    dev = frames.codes.device
     cols = (w + 7) // 8 * 8
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        desc = _windows_tensor(frames, crops, host)  # (an upload or a padded copy belongs to `stream`)
-        n = int(desc.shape[0])
-        shape = (n, h, cols)
-        if out is None:
-            out = torch.zeros(shape, dtype=tdtype, device=dev)
-        cstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
-    if (out.dtype is not tdtype or tuple(out.shape) != shape or out.get_device() != dev_index
-            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous {tdtype} {list(shape)} tensor on cuda:{dev_index}")
-    if cstatus is not None and (not isinstance(cstatus, torch.Tensor) or cstatus.dtype is not torch.int32
-                                or cstatus.numel() != n or cstatus.get_device() != dev_index
-                                or not cstatus.is_contiguous()):
-        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
-    pitch = cols * esize
-    rc = N.lib().mh_decode_crops_norm(ctypes.byref(fr), desc.data_ptr(), n, w, h, fmt, scale, bias, luts.data_ptr(),
-                                      stride, fstatus.data_ptr() if fstatus is not None else None,
-                                      cstatus.data_ptr() if cstatus is not None else None, out.data_ptr(), pitch,
-                                      h * pitch, _raw_stream_ptr(stream, dev_index))
-    if rc:
-        N.check(rc, "mh_decode_crops_norm")
-    return (out, cstatus) if status is True else out
+    pitch = cols * (2, 2, 4)[fmt]
+    return _decode_list("decode_crops_normalized", "mh_decode_crops_norm", frames, tables, crops, host,
+                        (w, h, fmt, scale, bias), (h, cols), _NORM_DTYPES[fmt], (pitch, h * pitch), out, status,
+                        stream, extra_flags, skip_rejected)
 
 
 def _plane_coefficients(scale, bias):
@@ -943,19 +893,8 @@ def decode_crops_normalized_planes_shape(frames: DeviceFrames, n_crops: int, siz
     """(workgroups per (sample, plane) unit, waves per workgroup) decode_crops_normalized_planes would
     launch n_crops samples of n_planes planes of size = (w, h) pixels with, for `dtype`
     (mh_decode_crops_norm_planes_shape)."""
-    w, h = _crop_size(frames, size)
-    fmt = _norm_format(dtype)
-    if int(n_crops) < 1:
-        raise ValueError("no crops")
-    if not 1 <= int(n_planes) <= N.MH_MAX_PLANES:
-        raise ValueError(f"1..{N.MH_MAX_PLANES} planes, not {n_planes}")
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    g, wv = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    N.check(N.lib().mh_decode_crops_norm_planes_shape(ctypes.byref(fr), int(n_crops), w, h, fmt, int(n_planes),
-                                                      _raw_stream_ptr(stream, dev_index), ctypes.byref(g),
-                                                      ctypes.byref(wv)),
-            "mh_decode_crops_norm_planes_shape")
-    return int(g.value), int(wv.value)
+    return _slice_shape("mh_decode_crops_norm_planes_shape", frames, stream, extra_flags,
+                        crops=(n_crops, size, dtype, n_planes))
 
 
 def decode_crops_normalized_planes(frames: DeviceFrames, tables, crops, size, dtype, scale, bias,
@@ -981,10 +920,8 @@ def decode_crops_normalized_planes(frames: DeviceFrames, tables, crops, size, dt
     out: a contiguous [n, C, h, round_up(w, 8)] tensor of `dtype` on the frames' device; None
     allocates a ZERO-FILLED one.
     status, tables, extra_flags, skip_rejected: decode_crops'."""
-    who = "decode_crops_normalized_planes"
     w, h = _crop_size(frames, size)
     fmt = _norm_format(dtype)
-    tdtype, esize = _NORM_DTYPES[fmt], (2, 2, 4)[fmt]
     C, c_scale, c_bias = _plane_coefficients(scale, bias)
     ps = _plane_stride(frames, C, plane_stride)
     host = _host_norm_crops(frames, crops, w, h)
@@ -994,35 +931,11 @@ def decode_crops_normalized_planes(frames: DeviceFrames, tables, crops, size, dt
             i = int(np.flatnonzero(bad)[0])
             raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {C - 1} would be frame "
                              f"{int(host[i, 0]) + (C - 1) * ps} of {frames.n_frames}")
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError(f"MH_FLAG_LANE_PAIRS does not apply to {who}")
-    luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
-    dev = frames.codes.device
     cols = (w + 7) // 8 * 8
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        desc = _windows_tensor(frames, crops, host)  # (an upload or a padded copy belongs to `stream`)
-        n = int(desc.shape[0])
-        shape = (n, C, h, cols)
-        if out is None:
-            out = torch.zeros(shape, dtype=tdtype, device=dev)
-        cstatus = torch.empty(n, dtype=torch.int32, device=dev) if status is True else status
-    if (out.dtype is not tdtype or tuple(out.shape) != shape or out.get_device() != dev_index
-            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous {tdtype} {list(shape)} tensor on cuda:{dev_index}")
-    if cstatus is not None and (not isinstance(cstatus, torch.Tensor) or cstatus.dtype is not torch.int32
-                                or cstatus.numel() != n or cstatus.get_device() != dev_index
-                                or not cstatus.is_contiguous()):
-        raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
-    pitch = cols * esize
-    rc = N.lib().mh_decode_crops_norm_planes(ctypes.byref(fr), desc.data_ptr(), n, w, h, fmt, C, ps, c_scale, c_bias,
-                                             luts.data_ptr(), stride,
-                                             fstatus.data_ptr() if fstatus is not None else None,
-                                             cstatus.data_ptr() if cstatus is not None else None, out.data_ptr(),
-                                             pitch, h * pitch, C * h * pitch, _raw_stream_ptr(stream, dev_index))
-    if rc:
-        N.check(rc, "mh_decode_crops_norm_planes")
-    return (out, cstatus) if status is True else out
+    pitch = cols * (2, 2, 4)[fmt]
+    return _decode_list("decode_crops_normalized_planes", "mh_decode_crops_norm_planes", frames, tables, crops, host,
+                        (w, h, fmt, C, ps, c_scale, c_bias), (C, h, cols), _NORM_DTYPES[fmt],
+                        (pitch, h * pitch, C * h * pitch), out, status, stream, extra_flags, skip_rejected)
 
 
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
@@ -1041,9 +954,7 @@ def decode_headers(frames: DeviceFrames, canons, out: Optional[torch.Tensor] = N
     non-zero word skips the frame. header_status (optional int32[n] on the device, not the same
     tensor): receives each decoded frame's verdict, 0, -3 or -5; a rejected frame's raster is
     left untouched. Returns the device raster out[n, H, pitch] (decode()'s `out` contract)."""
-    fr, dev_index = _frame_entry(frames, None, extra_flags)
-    if fr.flags & N.MH_FLAG_LANE_PAIRS:
-        raise ValueError("MH_FLAG_LANE_PAIRS does not apply to decode_headers")
+    fr, dev_index = _slice_entry("decode_headers", frames, extra_flags)
     dev = frames.codes.device
     hdr = _header_tensor(canons, dev, convert=False)
     if (hdr.dtype is not torch.uint8 or hdr.dim() != 2 or tuple(hdr.shape) != (frames.n_frames, 256)
