@@ -52,6 +52,9 @@ extern "C" {
 #define MH_ERR_ALIGN (-6)         /* codes not 16-byte aligned / pitch % 8 != 0  */
 #define MH_ERR_HIP (-7)           /* HIP runtime error (launch / no device)      */
 #define MH_ERR_EMPTY (-8)         /* no symbols to encode                        */
+#define MH_ERR_STREAM (-9)        /* a frame's code bits and block offsets disagree: its
+                                     report is not 0, 0, 0, 0xFFFFFFFF (mh_check_frames /
+                                     mh_check_headers, in the per-frame verdict only)  */
 
 /* --- constants (Shared/AAPLShaderTypes.h:109-123) --------------------- */
 #define MH_BLOCK_DIM 8           /* HUFF_BLOCK_DIM                              */
@@ -232,8 +235,9 @@ int mh_build_tables_device(const uint8_t *d_canon_header, mh_lookup_symbol *d_ta
 /* -> mh_decode_frames are three asynchronous steps on one stream, no host     */
 /* synchronisation in between; mh_decode_headers is the same decode in one     */
 /* step, straight from the canonical headers, and mh_stream_create_headers     */
-/* streams such frames from host memory. Not covered: mh_check with per-frame  */
-/* tables, stream groups and the multi-GPU paths with per-frame tables, and an */
+/* streams such frames from host memory; mh_check_frames / mh_check_headers    */
+/* are mh_check for such a batch. Not covered: a truncated-T2 report with per- */
+/* frame tables, stream groups and the multi-GPU paths with per-frame tables, and an */
 /* in-kernel table build from T1/T2 for mh_decode_frames (it needs prepared    */
 /* tables). A batch of different frames that should decode under ONE table     */
 /* (mh_decode, the fastest route) is encoded by                                */
@@ -293,12 +297,58 @@ int mh_decode_headers(const mh_frame *frame, const uint8_t *d_canon_headers,
 int mh_decode_headers_shape(const mh_frame *frame, void *stream, uint32_t *groups_per_frame,
                             uint32_t *waves_per_group);
 
+/* mh_check for a batch whose frame f has its own prepared table, by mh_decode_region's table rule:
+ * d_luts + f * lut_stride_bytes, lut_stride_bytes == 0 one table for all frames, any other stride a
+ * multiple of 16 and >= mh_lut_bytes(). frame->d_table1 / d_table2 / table2_entries / d_lut are
+ * ignored. flags: MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER only; neither changes anything (the walk
+ * does not depend on the delta, and both launches keep the stream's order), they are accepted so
+ * that one mh_frame serves the check and the decode.
+ * d_report (required, u32[4 * n_frames], 4-byte aligned): all four words of every frame are
+ * written, whatever they held, and nothing else. For a walked frame they are exactly mh_check's
+ * words for that frame alone under its own whole tables -- the reference walk of mh_frame's
+ * comment, 64 steps from offsets[b] over the slot's real bytes, zero at or past the slot's end, a
+ * zero-width lookup not advancing, whatever the offsets are (backwards, equal, past the slot up
+ * to 0xFFFFFFFF); sums wrap mod 2^32. Word [1] is always 0: a prepared or header-built table has
+ * no truncated T2.
+ * d_verdict (optional, int32[n_frames], 4-byte aligned): MH_OK for a frame whose report is 0, 0,
+ * 0, 0xFFFFFFFF, MH_ERR_STREAM otherwise. It goes unchanged into d_frame_status of any decode
+ * entry on the same stream, no host synchronisation in between.
+ * d_frame_status (optional input): a frame whose word is non-zero is not walked; its report is
+ * the clean pattern and its verdict is that word, so one array carries the encoder's or the table
+ * build's rejections and the stream's into the decode. d_verdict must not alias d_frame_status
+ * (MH_ERR_INVALID_ARG: a frame's workgroups read the one while others write the other).
+ * All checks before any HIP call, in mh_decode_frames' order with its codes, without the raster
+ * rules: the aliasing pairs and NULL d_report -> MH_ERR_INVALID_ARG with the other NULL checks;
+ * a misaligned d_report or d_verdict -> MH_ERR_ALIGN with the other alignments. Two launches (a
+ * small one that writes the clean reports and the passed-through verdicts, then the walk: n_frames
+ * * G workgroups of 8 waves by mh_decode_frames' shape rule with the walk kernel's occupancy);
+ * asynchronous, no host synchronisation. */
+int mh_check_frames(const mh_frame *frame, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                    const int32_t *d_frame_status, uint32_t *d_report, int32_t *d_verdict, void *stream);
+
+/* mh_check_frames with the tables of mh_decode_headers: frame f's canonical header at
+ * d_canon_headers + 256 f, built in LDS. A rejected header is not walked: its report is the clean
+ * pattern and its verdict the header's code (MH_ERR_CODE_TOO_LONG / MH_ERR_TABLE).
+ * d_header_status (optional output) is written as mh_decode_headers writes it. d_verdict,
+ * d_frame_status and d_header_status are pairwise distinct (MH_ERR_INVALID_ARG). Checks in
+ * mh_decode_headers' order. */
+int mh_check_headers(const mh_frame *frame, const uint8_t *d_canon_headers, const int32_t *d_frame_status,
+                     int32_t *d_header_status, uint32_t *d_report, int32_t *d_verdict, void *stream);
+
+/* The launch shape of the walk of mh_check_frames / mh_check_headers on `stream`'s device (no
+ * launch): workgroups per frame and waves per workgroup. For tests and tools. */
+int mh_check_frames_shape(const mh_frame *frame, void *stream, uint32_t *groups_per_frame,
+                          uint32_t *waves_per_group);
+int mh_check_headers_shape(const mh_frame *frame, void *stream, uint32_t *groups_per_frame,
+                           uint32_t *waves_per_group);
+
 /* ---------------------------------------------------------------------- */
 /* A block-aligned region of every frame in one launch. Every block has its own bit offset,  */
 /* so the blocks [bx0, bx0 + bw) x [by0, by0 + bh) of the frame's 8x8 grid decode without the */
 /* rest of the frame and without a full-size raster: a window of a large scan, a pan of it,   */
 /* the same crop of every frame of a sequence. Not covered: regions for mh_decode_headers,    */
-/* the streams, the multi-GPU paths and mh_check; pixel-granular stores (a region is whole    */
+/* the streams and the multi-GPU paths; a check of a region alone (a frame's verdict from      */
+/* mh_check_frames covers every region of it); pixel-granular stores (a region is whole       */
 /* blocks; rectangles at pixel origins are mh_decode_crops below); a CPU twin; packing        */
 /* several rows of a region narrower than 64 blocks into one wave (lane utilisation is        */
 /* bw / (64 ceil(bw / 64))).                                                                  */
@@ -390,7 +440,7 @@ int mh_box_reduce(const uint8_t *raster, uint32_t width, uint32_t height, size_t
 /* jump, a tracked box that moves from frame to frame. mh_decode_region decodes the SAME        */
 /* rectangle of every frame; N rectangles took N launches of it. Windows at a reduced scale:  */
 /* mh_decode_windows_scaled below. Not covered: windows for mh_decode_headers, the streams, the */
-/* multi-GPU paths and mh_check;                                                                */
+/* multi-GPU paths; a check of a window list (mh_check_frames' verdict covers the whole frame); */
 /* windows of different sizes in one launch; packing several rows of a window narrower than 64  */
 /* blocks into one wave (lane utilisation is bw / (64 ceil(bw / 64)), as for a region);         */
 /* pixel-granular stores (windows are whole blocks; mh_decode_crops below takes pixel origins);  */
@@ -485,7 +535,8 @@ int mh_decode_windows_scaled_shape(const mh_frame *frame, uint32_t n_windows, ui
 /* byte grid in registers, at the moment it stores it; no intermediate raster exists.            */
 /* Not covered: crops at a reduced scale; crops of different sizes in one launch; flips of a byte */
 /* output (mh_decode_crops_norm below mirrors as it normalises); crops                            */
-/* for mh_decode_headers, the streams, the multi-GPU paths and mh_check; stores of exactly w     */
+/* for mh_decode_headers, the streams and the multi-GPU paths; a check of a crop list            */
+/* (mh_check_frames' verdict covers the whole frame); stores of exactly w                        */
 /* bytes (a row is written in whole 8-byte words); a CPU twin.                                   */
 typedef struct {
   uint32_t frame, x0, y0, reserved; /* 16 bytes; pixels; reserved must be 0 */
@@ -1123,6 +1174,13 @@ int mh_decode_frame_cpu(const uint32_t *block_offsets, const uint8_t *codes, uin
                         uint32_t table2_entries, const uint8_t *block_init, uint32_t width,
                         uint32_t height, uint32_t flags, uint8_t *out, size_t out_pitch,
                         uint32_t n_threads);
+
+/* The CPU twin of mh_check_headers for one frame: the reference walk of its n_blocks blocks
+ * under the table of canon_header, report[4] as mh_check_frames writes it. Returns the header's
+ * verdict (MH_OK, MH_ERR_CODE_TOO_LONG, MH_ERR_TABLE; a rejected header leaves the clean pattern)
+ * or MH_ERR_INVALID_ARG for a NULL pointer or n_blocks == 0. */
+int mh_check_frame_cpu(const uint32_t *block_offsets, uint32_t n_blocks, const uint8_t *codes,
+                       uint64_t codes_bytes, const uint8_t canon_header[256], uint32_t report[4]);
 
 /* The 8-byte container header HuffmanEncoder::encode emits ahead of the
  * canonical table (HuffmanEncoder.cpp:326-340: u32 LE 0xFFEEEEDD, u32 LE symbol

@@ -10,6 +10,8 @@ of mdejong/MetalHuffman).
   * decoder.DeviceTables            T1/T2 + prepared table (uploaded, or built on the device)
   * decoder.decode_frames / DeviceTableSet   a batch with a table per frame, one launch
   * decoder.decode_headers          the same batch straight from its canonical headers (table built in-kernel)
+  * decoder.check_frames / check_headers   mh_check for such a batch: a report and a verdict word per frame that
+                                    goes into the decode entries' frame_status; codec.check_frame is the CPU twin
   * decoder.decode_region / decode_rect   a block-aligned region (a pixel rectangle) of every frame, one launch
   * decoder.decode_region_scaled / decode_scaled   a region (the frame) at 1/2, 1/4 or 1/8 scale, one launch:
                                     box means taken in the decoder's registers; codec.box_reduce is the CPU twin
@@ -37,9 +39,10 @@ of mdejong/MetalHuffman).
   * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
 """
-from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE_LIMIT_LENGTHS, MH_FLAG_LANE_PAIRS,
+from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE_LIMIT_LENGTHS, MH_ERR_STREAM,
+                      MH_FLAG_LANE_PAIRS,
                       MH_FLAG_NO_DELTA, MH_MAX_PLANES, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
-from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, code_lengths_limited,
+from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, check_frame, code_lengths_limited,
                     decode_frame_cpu, encode_frame, frame_histogram, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
                     split_blocks)
 
@@ -48,6 +51,6 @@ __all__ = [
     "EncodedFrame", "Huffman", "block_grid", "decode_frame_cpu", "encode_frame", "merge_blocks", "split_blocks",
     "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
     "norm_table", "MH_NORM_F16", "MH_NORM_BF16", "MH_NORM_F32", "MH_CROP_MIRROR",
-    "MH_MAX_PLANES", "norm_coefficients", "image_planes",
+    "MH_MAX_PLANES", "norm_coefficients", "image_planes", "check_frame", "MH_ERR_STREAM",
 ]
 __version__ = "0.1.0"

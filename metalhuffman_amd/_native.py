@@ -12,6 +12,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MH_LIB") or os.path.join(_PKG, "libmetalhuffman_amd.so")
 
 MH_OK = 0
+MH_ERR_STREAM = -9  # a per-frame verdict of mh_check_frames / mh_check_headers: the report is not clean
 MH_FLAG_NO_DELTA = 0x1
 MH_FLAG_LANE_PAIRS = 0x2  # lane-pair single-frame decode: diagnostic library only (diag_lanepairs())
 MH_FLAG_ANY_ORDER = 0x4  # the launch may overlap earlier work on the stream (caller guarantees independence)
@@ -55,6 +56,8 @@ EXPORTS = (
     "mh_frame_histogram", "mh_encode_frame_with_header",
     "mh_encode_images_workspace_bytes", "mh_encode_images_shared_workspace_bytes",
     "mh_encode_images_device_async", "mh_encode_images_shared_device_async",
+    "mh_check_frames", "mh_check_frames_shape", "mh_check_headers", "mh_check_headers_shape",
+    "mh_check_frame_cpu",
 )
 
 
@@ -176,6 +179,11 @@ def lib() -> ctypes.CDLL:
                     "rebuild with `python -m metalhuffman_amd.build`")
         L.mh_decode.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
         L.mh_check.argtypes = [ctypes.POINTER(mh_frame), _vp, _vp]
+        L.mh_check_frames.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]
+        L.mh_check_headers.argtypes = [ctypes.POINTER(mh_frame), _vp, _vp, _vp, _vp, _vp, _vp]
+        L.mh_check_frames_shape.argtypes = [ctypes.POINTER(mh_frame), _vp, _u32p, _u32p]
+        L.mh_check_headers_shape.argtypes = [ctypes.POINTER(mh_frame), _vp, _u32p, _u32p]
+        L.mh_check_frame_cpu.argtypes = [_u32p, ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, _u32p]
         L.mh_lut_bytes.restype = ctypes.c_size_t
         L.mh_lut_bits.restype = ctypes.c_int
         L.mh_prepare_lut.argtypes = [_vp, _vp, ctypes.c_uint32, _vp, _vp]

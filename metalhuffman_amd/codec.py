@@ -372,6 +372,24 @@ def decode_frame_cpu(ef: EncodedFrame, threads: int = 1) -> np.ndarray:
     return out
 
 
+def check_frame(ef: EncodedFrame) -> tuple:
+    """CPU twin of decoder.check_headers for one frame (mh_check_frame_cpu): the reference walk of
+    every block under the table of ef.canon, over ef.codes as the frame's slot. Returns (status,
+    report): the header's verdict (0, -3 or -5) and the report u32[4] = (zero-width lookups, 0,
+    blocks whose codes miss the next block's offset, first offending block or 0xFFFFFFFF); a
+    rejected header leaves the clean report."""
+    offs = np.ascontiguousarray(ef.block_offsets, np.uint32)
+    codes = np.ascontiguousarray(ef.codes, np.uint8)
+    canon = np.ascontiguousarray(ef.canon, np.uint8)
+    if canon.size != 256:
+        raise ValueError("a canonical header is 256 code lengths")
+    report = np.zeros(4, np.uint32)
+    rc = N.lib().mh_check_frame_cpu(_p(offs, _u32p), offs.size, _p(codes), codes.size, _p(canon), _p(report, _u32p))
+    if rc not in (0, -3, -5):
+        N.check(rc, "mh_check_frame_cpu")
+    return int(rc), report
+
+
 def box_reduce(img: np.ndarray, log2_scale: int) -> np.ndarray:
     """The H x W image at scale s = 2^log2_scale (0..3) -> u8[ceil(H / s), ceil(W / s)]: every
     s x s cell's mean over its pixels inside the image, halves rounded up (mh_box_reduce, the CPU

@@ -358,6 +358,53 @@ int mh_decode_frame_cpu(const uint32_t *block_offsets, const uint8_t *codes, uin
   return MH_OK;
 }
 
+// The CPU twin of mh_check_headers for one frame: the header's verdict by the device builder's rule
+// (a length over 16, then a Kraft sum over 1; an incomplete code is valid), each 16-bit window's code
+// length from the canonical order -- the codes of length l fill [F, F + count[l] << (16 - l)) of the
+// window space in (length, symbol) order, windows no code reaches are width 0 -- and the reference
+// walk of every block: 64 steps from its offset, bytes at or past codes_bytes zero, a zero-width
+// lookup not advancing, 64-bit positions.
+int mh_check_frame_cpu(const uint32_t *block_offsets, uint32_t n_blocks, const uint8_t *codes,
+                       uint64_t codes_bytes, const uint8_t canon_header[256], uint32_t report[4]) {
+  if (!block_offsets || !n_blocks || !codes || !canon_header || !report) return MH_ERR_INVALID_ARG;
+  report[0] = report[1] = report[2] = 0u;
+  report[3] = 0xFFFFFFFFu;
+  uint64_t kraft = 0;
+  for (int s = 0; s < 256; ++s) {
+    if (canon_header[s] > 16) return MH_ERR_CODE_TOO_LONG;
+    if (canon_header[s]) kraft += 1ull << (16 - canon_header[s]);
+  }
+  if (kraft > 65536u) return MH_ERR_TABLE;
+  std::vector<uint8_t> width;
+  try {
+    width.assign(65536, 0);
+  } catch (...) {
+    return MH_ERR_CAPACITY;  // no exception crosses the C ABI
+  }
+  uint32_t first = 0;
+  for (uint32_t l = 1; l <= 16; ++l)
+    for (int s = 0; s < 256; ++s)
+      if (canon_header[s] == l) {
+        std::memset(width.data() + first, (int)l, 1u << (16 - l));
+        first += 1u << (16 - l);
+      }
+  for (uint32_t b = 0; b < n_blocks; ++b) {
+    uint64_t pos = block_offsets[b];
+    uint32_t zero = 0;
+    for (int k = 0; k < 64; ++k) {
+      const uint32_t len = width[window16(codes, codes_bytes, pos)];
+      zero += len == 0;
+      pos += len;
+    }
+    // the last block's end is not recorded: it must lie inside the slot
+    const bool bad = b + 1 < n_blocks ? pos != block_offsets[b + 1] : pos > 8 * codes_bytes;
+    report[0] += zero;
+    report[2] += bad;
+    if ((zero || bad) && report[3] == 0xFFFFFFFFu) report[3] = b;
+  }
+  return MH_OK;
+}
+
 // The CPU twin of mh_decode_region_scaled's output stage: every s x s cell's in-frame mean,
 // rounded by the function the kernels round an edge cell with (mh_box.hpp).
 int mh_box_reduce(const uint8_t *raster, uint32_t width, uint32_t height, size_t pitch, uint32_t log2_scale,

@@ -2132,6 +2132,231 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG) mh_header_luts_kernel(con
     reinterpret_cast<uint32_t *>(dst + kMaxLenOff)[tid] = tid == 0 ? hf.mx : tid == 1 ? hf.mn : tid == 2 ? hf.flat8 : 0u;
   if (status && tid == 0) status[hdr] = hf.status;
 }
+
+// ---- the reference walk, one frame slice per workgroup (mh_check_frames / mh_check_headers) ------
+// mh_check's report for a batch that brings a table per frame: the decomposition, the prologue and
+// the table sources of slice_decode (workgroup g = frame g / G, slice g % G; the frame's table in
+// LDS once), but every lane does the REFERENCE walk of its block (include/metalhuffman.h, mh_frame):
+// 64 steps from offsets[b] over the slot's real bytes, zero at or past the slot's end, whatever the
+// offsets are. Nothing is staged: a staged span is cut by the tile's recorded ends, which is what
+// makes the decoders differ from the reference on unspecified blocks.
+//
+// Code bits: the lane reads aligned dwords of its frame's slot through a descriptor that covers the
+// slot's whole dwords (a load is inside or outside as a whole); the slot's last 1..3 bytes come from
+// byte loads through a descriptor of the slot's exact size, once per wave, and stand in for the dword
+// they start (`tail`). kWalkGroup steps consume at most 16 * kWalkGroup bits, so the dwords a group
+// can touch are the kWalkWords from the one its first bit lies in: their addresses depend on the
+// group's start only, and all are issued before the first step. Inside the group they form a queue,
+// q[0] the dword of the cursor's bit `o` (0..31); a step crosses at most one dword boundary (a code
+// has at most 16 bits), where the queue moves up by one. Positions are 64 bits: an offset near 2^32
+// plus 1,024 bits does not fit 32.
+//
+// A wave keeps its lanes' zero-width count, mismatches and first offending block in registers over
+// all its tiles, reduces across lanes once, and lane 0 issues at most two atomic adds, one atomic min
+// and the verdict's store (word [1], the truncated-T2 count, stays 0: a prepared or header-built
+// table has no truncated T2). No workgroup waits for another.
+constexpr int kWalkGroup = 8;
+constexpr int kWalkWords = (31 + 16 * kWalkGroup + 31) / 32;  // 5
+static_assert(64 % kWalkGroup == 0, "a block's 64 steps in whole groups");
+
+struct WalkSlot {
+  __amdgpu_buffer_rsrc_t words;  // the slot's whole dwords
+  uint32_t tail_idx, tail;       // the dword the slot's last 1..3 bytes start, and those bytes (big-endian)
+  uint64_t bits;                 // 8 x the slot's bytes
+};
+
+__device__ __forceinline__ uint32_t walk_word(const WalkSlot &sl, uint32_t idx) {
+  return bswap32(__builtin_amdgcn_raw_buffer_load_b32(sl.words, (int)(idx * 4u), 0, 0));
+}
+
+// The step word of the 32 bits `w32` at the cursor: the 13-bit first level, the second level for an
+// entry in (0, kEscapeBelow). 0: no code matches, the zero-width step.
+__device__ __forceinline__ uint32_t walk_lookup(const uint16_t *lut, uint32_t w32) {
+  uint32_t e = lut[w32 >> (32 - kLutBits)];
+  if (e - 1u < kEscapeBelow - 1u)
+    e = lut[(uint32_t)kL1Entries + e * (1u << kL2Bits) + ((w32 >> 16) & ((1u << kL2Bits) - 1u))];
+  return e;
+}
+
+// The steps among the kWalkGroup from bit start + adv that advance, one at a time with two loads
+// each: the rare path of a group that ended stalled.
+__device__ __forceinline__ uint32_t walk_advancing(const WalkSlot &sl, const uint16_t *lut, uint32_t start,
+                                                   uint32_t adv) {
+  uint32_t n = 0;
+#pragma unroll 1
+  for (; n < (uint32_t)kWalkGroup; ++n) {
+    const uint64_t pos = (uint64_t)start + adv;
+    const uint32_t i = (uint32_t)(pos >> 5), o = (uint32_t)pos & 31u;
+    uint32_t q0 = walk_word(sl, i), q1 = walk_word(sl, i + 1u);
+    q0 = i == sl.tail_idx ? sl.tail : q0;
+    q1 = i + 1u == sl.tail_idx ? sl.tail : q1;
+    const uint32_t e = walk_lookup(lut, (uint32_t)(((((uint64_t)q0 << 32) | q1) << o) >> 32));
+    if (e == 0u) break;
+    adv += (0u - e) & 0xFFu;
+  }
+  return n;
+}
+
+// The end of the block that starts at bit `start` (64 steps), and its zero-width lookups. A
+// zero-width step does not advance, so the next step sees the same bits and is zero-width too: a
+// stall lasts to the block's end. Only a group whose last step is zero-width holds any, and it is
+// walked again, step by step, to find where they begin.
+__device__ __forceinline__ uint64_t walk_block(const WalkSlot &sl, const uint16_t *lut, uint32_t start, uint32_t &zero) {
+  uint32_t p = start;  // the cursor's low 32 bits; the walk adds at most 1,024 to the start
+#pragma unroll 1
+  for (int g = 0; g < 64 / kWalkGroup; ++g) {
+    const uint32_t p0 = p;
+    const uint32_t i0 = (uint32_t)(((uint64_t)start + (p - start)) >> 5);  // < 2^27 + 64: the byte offset fits 32 bits
+    uint32_t q[kWalkWords + 1];
+#pragma unroll
+    for (int j = 0; j < kWalkWords; ++j) q[j] = walk_word(sl, i0 + (uint32_t)j);
+    q[kWalkWords] = 0u;
+    if (sl.tail_idx - i0 < (uint32_t)kWalkWords) {  // the group reaches the slot's last, partial dword
+#pragma unroll
+      for (int j = 0; j < kWalkWords; ++j) q[j] = i0 + (uint32_t)j == sl.tail_idx ? sl.tail : q[j];
+    }
+    uint32_t o = p & 31u, e = 0u;
+#pragma unroll
+    for (int k = 0; k < kWalkGroup; ++k) {
+      e = walk_lookup(lut, (uint32_t)(((((uint64_t)q[0] << 32) | q[1]) << o) >> 32));  // 32 bits from the cursor
+      p += (0u - e) & 0xFFu;  // the step word's width; entry 0: the zero-width step
+      const uint32_t o2 = p & 31u;
+      const bool up = o2 < o;  // a step is at most 16 bits: the low five bits wrap at most once
+      o = o2;
+#pragma unroll
+      for (int j = 0; j < kWalkWords; ++j) q[j] = up ? q[j + 1] : q[j];
+    }
+    if (e == 0u) zero += (uint32_t)kWalkGroup - walk_advancing(sl, lut, start, p0 - start);
+  }
+  return (uint64_t)start + (p - start);
+}
+
+// The clean report and the passed-through status word of every frame, ahead of the walk.
+__global__ void __launch_bounds__(256) mh_walk_init_kernel(const int32_t *status, uint32_t *report, int32_t *verdict,
+                                                           uint32_t n_frames) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= 4ull * n_frames) return;
+  report[i] = (i & 3u) == 3u ? 0xFFFFFFFFu : 0u;
+  if (verdict && (i & 3u) == 0u) verdict[i >> 2] = status ? status[i >> 2] : MH_OK;
+}
+
+// HeaderTable whose rejection also reaches the check's verdict word (slice 0 writes both).
+struct WalkHeaderTable : HeaderTable {
+  int32_t *walk_verdict;
+  __device__ __forceinline__ bool into_lds(const Loads &ld, uint32_t f, uint32_t slice, TableFacts &tf) const {
+    const HeaderFacts hf = header_build(ld.L, s_lut, reinterpret_cast<HeaderScratch *>(s_stage), threadIdx.x, true);
+    if (slice == 0 && threadIdx.x == 0) {
+      if (verdict) verdict[f] = hf.status;
+      if (walk_verdict && hf.status != MH_OK) walk_verdict[f] = hf.status;
+    }
+    if (hf.status != MH_OK) return false;
+    lds_barrier();
+    tf = TableFacts{hf.mx, hf.mn, hf.flat8};
+    return true;
+  }
+};
+
+template <bool kBatch, class Src>
+__device__ __forceinline__ void slice_walk(const uint32_t *p_offsets, const uint64_t *p_frame_off,
+                                           const uint8_t *p_codes, uint64_t p_codes_bytes, const int32_t *p_status,
+                                           uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t G, uint32_t f,
+                                           uint32_t slice, const Src &src, uint32_t *p_report, int32_t *p_verdict) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  DecodeArgs a = {};
+  a.offsets = p_offsets;
+  a.frame_off = kBatch ? p_frame_off : nullptr;
+  a.lut = src.lut_of(f);
+  a.nb = p_nb;
+  a.tiles_per_frame = p_tiles_per_frame;
+  a.total_tiles = (f + 1u) * p_tiles_per_frame;  // this workgroup's tiles end with its frame
+  const uint32_t gstride = G * (uint32_t)kMaxWavesPerWG;
+  uint32_t tile = min(f * p_tiles_per_frame + slice * (uint32_t)kMaxWavesPerWG + wave, a.total_tiles);
+  // the prologue's loads, oldest first: the status word, the table, the first offsets
+  TileHdr hc;
+  const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
+      uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
+  typename Src::Loads ld;
+  src.issue(a, f, ld);
+  hdr_issue(a, tile, lane, hc);
+  if (__builtin_amdgcn_readfirstlane(stv) != 0u) return;  // workgroup-uniform: not walked, the init launch's words stand
+  TableFacts tf;
+  if (!src.into_lds(ld, f, slice, tf)) return;  // a rejected header: not walked either
+  if (tile >= a.total_tiles) return;            // no barrier below
+  // the frame's slot
+  uint64_t fbeg = 0, fbytes = p_codes_bytes;
+  if constexpr (kBatch) {
+    fbeg = ((uint64_t)__builtin_amdgcn_readlane(hc.fo_hi, 0) << 32) | __builtin_amdgcn_readlane(hc.fo_lo, 0);
+    fbytes = (((uint64_t)__builtin_amdgcn_readlane(hc.fo_hi, 1) << 32) | __builtin_amdgcn_readlane(hc.fo_lo, 1)) - fbeg;
+  }
+  // no walk reads at or past byte 2^29 + 160, so a larger slot's descriptor may end at 0xFFFFFFF0
+  const uint32_t fb32 = (uint32_t)(fbytes > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : fbytes);
+  WalkSlot sl;
+  sl.words = uniform_rsrc(p_codes + fbeg, fb32 & ~3u);
+  sl.tail_idx = fb32 >> 2;
+  sl.bits = fbytes * 8u;  // fbytes < 2^61
+  {
+    const __amdgpu_buffer_rsrc_t rb = uniform_rsrc(p_codes + fbeg, fb32);
+    uint32_t t = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; ++k)
+      t |= (__builtin_amdgcn_raw_buffer_load_b8(rb, (int)((fb32 & ~3u) + k), 0, 0) & 0xFFu) << (24u - 8u * k);
+    sl.tail = __builtin_amdgcn_readfirstlane(t);
+  }
+  uint32_t zero = 0, mism = 0, first = 0xFFFFFFFFu;
+  while (tile < a.total_tiles) {
+    const uint32_t b = (tile - f * p_tiles_per_frame) * 64u + lane;
+    const uint32_t off = hc.off, nxt = hc.nxt;
+    tile = __builtin_amdgcn_readfirstlane(min(tile + gstride, a.total_tiles));
+    hdr_issue(a, tile, lane, hc);  // the next tile's offsets, behind this tile's walk
+    if (b < p_nb) {                // lanes without a block contribute nothing
+      uint32_t z = 0;
+      // the flat 8-bit code has no table in LDS and needs none: every lookup is 8 bits wide
+      const uint64_t end = tf.flat8 ? (uint64_t)off + 512u
+                                    : walk_block(sl, reinterpret_cast<const uint16_t *>(s_lut), off, z);
+      // the last block's end is not recorded: it must lie inside the slot
+      const bool bad = b + 1u < p_nb ? end != (uint64_t)nxt : end > sl.bits;
+      zero += z;
+      mism += bad ? 1u : 0u;
+      if (z | (uint32_t)bad) first = min(first, b);
+    }
+  }
+#pragma unroll
+  for (uint32_t d = 32; d; d >>= 1) {
+    zero += (uint32_t)__shfl_xor(zero, d);
+    mism += (uint32_t)__shfl_xor(mism, d);
+    first = min(first, (uint32_t)__shfl_xor(first, d));
+  }
+  if (lane == 0 && first != 0xFFFFFFFFu) {
+    uint32_t *r = p_report + 4ull * f;
+    if (zero) atomicAdd(&r[0], zero);
+    if (mism) atomicAdd(&r[2], mism);
+    atomicMin(&r[3], first);
+    if (p_verdict) p_verdict[f] = MH_ERR_STREAM;
+  }
+}
+
+// The two walk kernels, each with (kBatch) and without a frame-offset array; the leading 16
+// arguments are preloaded into SGPRs, as the decode kernels'.
+template <bool kBatch>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG) mh_walk_frames_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_codes, const uint8_t *p_luts,
+    const int32_t *p_status, uint64_t p_lut_stride, uint64_t p_codes_bytes, uint32_t p_nb,
+    uint32_t p_tiles_per_frame, uint32_t p_groups, uint32_t *p_report, int32_t *p_verdict) {
+  const uint32_t f = blockIdx.x / p_groups, slice = blockIdx.x - f * p_groups;
+  slice_walk<kBatch>(p_offsets, p_frame_off, p_codes, p_codes_bytes, p_status, p_nb, p_tiles_per_frame, p_groups, f,
+                     slice, PreparedTable{p_luts, p_lut_stride}, p_report, p_verdict);
+}
+
+template <bool kBatch>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG) mh_walk_headers_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_codes, const uint8_t *p_headers,
+    const int32_t *p_status, int32_t *p_header_status, uint64_t p_codes_bytes, uint32_t p_nb,
+    uint32_t p_tiles_per_frame, uint32_t p_groups, uint32_t *p_report, int32_t *p_verdict) {
+  const uint32_t f = blockIdx.x / p_groups, slice = blockIdx.x - f * p_groups;
+  slice_walk<kBatch>(p_offsets, p_frame_off, p_codes, p_codes_bytes, p_status, p_nb, p_tiles_per_frame, p_groups, f,
+                     slice, WalkHeaderTable{{p_headers, p_header_status}, p_verdict}, p_report, p_verdict);
+}
 #endif  // !MH_LANE_PAIRS
 
 // ---- small launches (<= one wave per SIMD, e.g. one 2048x1536 frame) -------------
@@ -2769,6 +2994,7 @@ struct DeviceInfo {
   std::atomic<int> cus{0};  // nonzero once the entry is complete
   int occ[2][kMaxWavesPerWG + 1] = {};
   int occ_slice[kSliceKernels][2] = {};  // the frame-slice kernels at 8 waves (raw / delta)
+  int occ_walk[2][2] = {};               // the walk kernels at 8 waves: [frames / headers][kBatch]
 };
 DeviceInfo g_devinfo[kMaxDevices];
 
@@ -2815,6 +3041,10 @@ const DeviceInfo *device_info(hipStream_t s) {
   for (int k = 0; k < kSliceKernels; ++k)
     for (int delta = 0; delta < 2; ++delta)
       d.occ_slice[k][delta] = occupancy_of(kSliceTable[k].fn[delta], kMaxWavesPerWG);
+  d.occ_walk[0][0] = occupancy_of(mh_walk_frames_kernel<false>, kMaxWavesPerWG);
+  d.occ_walk[0][1] = occupancy_of(mh_walk_frames_kernel<true>, kMaxWavesPerWG);
+  d.occ_walk[1][0] = occupancy_of(mh_walk_headers_kernel<false>, kMaxWavesPerWG);
+  d.occ_walk[1][1] = occupancy_of(mh_walk_headers_kernel<true>, kMaxWavesPerWG);
 #endif
   if (swap) (void)hipSetDevice(cur);
   d.cus.store(prop.multiProcessorCount, std::memory_order_release);  // last: marks the entry complete
@@ -2949,6 +3179,11 @@ struct DecodeCall {
   // bytes apart, the crops of frames plane_frame_stride apart; one plane is mh_decode_crops_norm
   uint32_t n_planes = 1, plane_frame_stride = 0;
   uint64_t out_plane_stride = 0;
+  // mh_check_frames / mh_check_headers (kPrepared / kHeaders): no raster and none of its rules, one
+  // table for all frames at stride 0 as a region's, and `words`, the OR of the report's and the
+  // verdict's addresses, 4-byte aligned
+  bool walk = false;
+  uintptr_t words = 0;
   // call_geometry()'s results: one raster's pixel size and tiles (segs: a region's only), and the
   // number of rasters, which is the number of units the grid is cut into
   RegionExtent re = {};
@@ -3009,7 +3244,7 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
                       DecodeCall &c) {
   const bool in_frame = c.kind == DecodeCall::kInFrame, windowed = c.windowed(), regional = c.regional();
   const bool prepared = c.kind == DecodeCall::kPrepared || regional;
-  if (!fr || !d_out || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
+  if (!fr || (!c.walk && !d_out) || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
   if (regional && !c.rg) return MH_ERR_INVALID_ARG;
   if (windowed && (!c.windows || c.n_windows == 0)) return MH_ERR_INVALID_ARG;
   if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !c.ptr) return MH_ERR_INVALID_ARG;
@@ -3031,7 +3266,9 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (windowed && ((uintptr_t)c.windows & 15u)) return MH_ERR_ALIGN;
   if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)c.ptr & 15u) || (c.stride & 15u))))
     return MH_ERR_ALIGN;
-  if (out_pitch < row_bytes || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * c.re.ph))
+  if (c.words & 3u) return MH_ERR_ALIGN;
+  if (!c.walk &&
+      (out_pitch < row_bytes || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * c.re.ph)))
     return MH_ERR_CAPACITY;
   // planes: a plane holds its h rows, and a slot its planes -- (n_planes - 1) * out_plane_stride +
   // out_pitch * h bytes, compared by division: the product may wrap
@@ -3042,7 +3279,7 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
     return MH_ERR_CAPACITY;
-  if (prepared && c.stride < (uint64_t)kPreparedBytes && !(regional && c.stride == 0))
+  if (prepared && c.stride < (uint64_t)kPreparedBytes && !((regional || c.walk) && c.stride == 0))
     return MH_ERR_CAPACITY;  // mh_lut_bytes()
   return MH_OK;
 }
@@ -3078,15 +3315,27 @@ int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_
 // R = the workgroups resident on the device at once (CUs x the kernel's occupancy): about
 // one resident round when the frames are few, one workgroup per frame when they are many.
 // One rule for every row of kSliceTable, each with its own occupancy and (a region, windows) its own tiles.
+// (the walk kernels of mh_check_frames / mh_check_headers follow it with their own occupancy: walk_shape)
+uint32_t groups_for(const DeviceInfo *di, int occupancy, uint32_t n_frames, uint32_t tiles_per_frame) {
+  const uint64_t resident = (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)occupancy;
+  const uint64_t want = (resident + n_frames - 1) / n_frames;
+  const uint64_t most = (tiles_per_frame + (uint32_t)kMaxWavesPerWG - 1) / (uint32_t)kMaxWavesPerWG;
+  return (uint32_t)(want < 1 ? 1 : want > most ? most : want);
+}
+
 int slice_shape(SliceKernel k, uint32_t n_frames, uint32_t tiles_per_frame, bool delta, hipStream_t s,
                 uint32_t *groups) {
   const DeviceInfo *di = device_info(s);
   if (!di) return MH_ERR_HIP;
-  const uint64_t resident =
-      (uint64_t)di->cus.load(std::memory_order_relaxed) * (uint64_t)di->occ_slice[k][delta ? 1 : 0];
-  const uint64_t want = (resident + n_frames - 1) / n_frames;
-  const uint64_t most = (tiles_per_frame + (uint32_t)kMaxWavesPerWG - 1) / (uint32_t)kMaxWavesPerWG;
-  *groups = (uint32_t)(want < 1 ? 1 : want > most ? most : want);
+  *groups = groups_for(di, di->occ_slice[k][delta ? 1 : 0], n_frames, tiles_per_frame);
+  return MH_OK;
+}
+
+int walk_shape(bool headers, bool batch, uint32_t n_frames, uint32_t tiles_per_frame, hipStream_t s,
+               uint32_t *groups) {
+  const DeviceInfo *di = device_info(s);
+  if (!di) return MH_ERR_HIP;
+  *groups = groups_for(di, di->occ_walk[headers ? 1 : 0][batch ? 1 : 0], n_frames, tiles_per_frame);
   return MH_OK;
 }
 
@@ -3173,6 +3422,58 @@ int slice_shape_entry(SliceKernel family, const mh_frame *fr, DecodeCall c, void
   if (c.regional() && !tiles_fit(c)) return MH_ERR_CAPACITY;
   rc = slice_shape((SliceKernel)(family + c.table_row()), c.units(), c.re.tiles, !(fr->flags & MH_FLAG_NO_DELTA),
                    (hipStream_t)stream, groups_per_unit);
+  if (rc != MH_OK) return rc;
+  *waves_per_group = kMaxWavesPerWG;
+  return MH_OK;
+}
+
+// mh_check_frames / mh_check_headers behind what they check themselves (the three aliasing pairs and
+// the report, MH_ERR_INVALID_ARG as every refusal ahead of the shared checks): the decode entries'
+// checks without a raster, then two ordinary launches on the stream -- the init launch must have
+// finished before a walk's atomics, so MH_FLAG_ANY_ORDER is accepted and not applied.
+int check_walk(const mh_frame *fr, bool headers, const void *tables, uint64_t stride, const int32_t *frame_status,
+               int32_t *header_status, uint32_t *report, int32_t *verdict, void *stream) {
+  if (verdict && (verdict == frame_status || verdict == header_status)) return MH_ERR_INVALID_ARG;
+  if (header_status && header_status == frame_status) return MH_ERR_INVALID_ARG;
+  if (!report) return MH_ERR_INVALID_ARG;
+  DecodeCall c{headers ? DecodeCall::kHeaders : DecodeCall::kPrepared, tables, stride};
+  c.walk = true;
+  c.words = (uintptr_t)report | (uintptr_t)verdict;
+  int rc = check_decode_args(fr, nullptr, 0, 0, c);
+  if (rc != MH_OK) return rc;
+  if (!tiles_fit(c)) return MH_ERR_CAPACITY;
+  const uint32_t nb = fr->dims.block_width * fr->dims.block_height, n = fr->n_frames;
+  const bool batch = fr->d_frame_code_offsets != nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t G = 0;
+  rc = walk_shape(headers, batch, n, c.re.tiles, s, &G);
+  if (rc != MH_OK) return rc;
+  const uint64_t grid = (uint64_t)G * n;
+  if (grid > 0x7FFFFFFFull) return MH_ERR_CAPACITY;
+  hipLaunchKernelGGL(mh_walk_init_kernel, dim3((uint32_t)((4ull * n + 255u) / 256u)), dim3(256), 0, s, frame_status,
+                     report, verdict, n);
+  const dim3 g((uint32_t)grid), b(kMaxWavesPerWG * 64);
+  const uint8_t *t = static_cast<const uint8_t *>(tables);
+  if (headers) {
+    const auto k = batch ? mh_walk_headers_kernel<true> : mh_walk_headers_kernel<false>;
+    hipLaunchKernelGGL(k, g, b, 0, s, fr->d_block_offsets, fr->d_frame_code_offsets, fr->d_codes, t, frame_status,
+                       header_status, fr->codes_bytes, nb, c.re.tiles, G, report, verdict);
+  } else {
+    const auto k = batch ? mh_walk_frames_kernel<true> : mh_walk_frames_kernel<false>;
+    hipLaunchKernelGGL(k, g, b, 0, s, fr->d_block_offsets, fr->d_frame_code_offsets, fr->d_codes, t, frame_status,
+                       stride, fr->codes_bytes, nb, c.re.tiles, G, report, verdict);
+  }
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+int check_walk_shape(const mh_frame *fr, bool headers, void *stream, uint32_t *groups_per_frame,
+                     uint32_t *waves_per_group) {
+  if (!fr || !groups_per_frame || !waves_per_group || fr->n_frames == 0) return MH_ERR_INVALID_ARG;
+  DecodeCall c{headers ? DecodeCall::kHeaders : DecodeCall::kPrepared};
+  int rc = call_geometry(fr, c);
+  if (rc != MH_OK) return rc;
+  rc = walk_shape(headers, fr->d_frame_code_offsets != nullptr, fr->n_frames, c.re.tiles, (hipStream_t)stream,
+                  groups_per_frame);
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
   return MH_OK;
@@ -3437,6 +3738,26 @@ int mh_decode_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, uint
   c.format = format;
   c.n_planes = n_planes;
   return slice_shape_entry(kSlicePlanes, fr, c, stream, groups_per_plane, waves_per_group);
+}
+
+// mh_check's report, frame by frame under the frame's own table, and a verdict word per frame that
+// the entries above take as d_frame_status (slice_walk).
+int mh_check_frames(const mh_frame *fr, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                    const int32_t *d_frame_status, uint32_t *d_report, int32_t *d_verdict, void *stream) {
+  return check_walk(fr, false, d_luts, lut_stride_bytes, d_frame_status, nullptr, d_report, d_verdict, stream);
+}
+
+int mh_check_frames_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame, uint32_t *waves_per_group) {
+  return check_walk_shape(fr, false, stream, groups_per_frame, waves_per_group);
+}
+
+int mh_check_headers(const mh_frame *fr, const uint8_t *d_canon_headers, const int32_t *d_frame_status,
+                     int32_t *d_header_status, uint32_t *d_report, int32_t *d_verdict, void *stream) {
+  return check_walk(fr, true, d_canon_headers, 0, d_frame_status, d_header_status, d_report, d_verdict, stream);
+}
+
+int mh_check_headers_shape(const mh_frame *fr, void *stream, uint32_t *groups_per_frame, uint32_t *waves_per_group) {
+  return check_walk_shape(fr, true, stream, groups_per_frame, waves_per_group);
 }
 
 int mh_header_luts_device(const uint8_t *d_canon_headers, uint32_t n_headers, uint16_t *d_luts,

@@ -548,6 +548,7 @@ const char *mh_error_string(int status) {
     case MH_ERR_ALIGN: return "misaligned buffer or pitch";
     case MH_ERR_HIP: return "HIP runtime error";
     case MH_ERR_EMPTY: return "no symbols";
+    case MH_ERR_STREAM: return "code bits and block offsets disagree";
     default: return "unknown error";
   }
 }

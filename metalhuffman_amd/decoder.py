@@ -978,6 +978,65 @@ def decode_headers(frames: DeviceFrames, canons, out: Optional[torch.Tensor] = N
     return out
 
 
+def _status_arg(name: str, st: Optional[torch.Tensor], frames: DeviceFrames, dev_index: int) -> None:
+    if st is not None and (st.dtype is not torch.int32 or st.numel() != frames.n_frames
+                           or st.get_device() != dev_index or not st.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous int32 [{frames.n_frames}] tensor on cuda:{dev_index}")
+
+
+def _check_outputs(frames: DeviceFrames, stream: Optional[torch.cuda.Stream]) -> tuple:
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        rep = torch.empty((frames.n_frames, 4), dtype=torch.int32, device=frames.codes.device)
+        verdict = torch.empty(frames.n_frames, dtype=torch.int32, device=frames.codes.device)
+    return rep, verdict
+
+
+def check_frames(frames: DeviceFrames, tables, frame_status: Optional[torch.Tensor] = None,
+                 stream: Optional[torch.cuda.Stream] = None) -> tuple:
+    """check() for a batch with a table per frame (mh_check_frames): tables is a DeviceTableSet, or a
+    DeviceTables with its prepared table (one table for all frames). Returns (report, verdict) on the
+    device: the report as check() returns it, int64 [n, 4]; the verdict int32 [n], 0 for a frame whose
+    report is clean and MH_ERR_STREAM otherwise, which the decode entries take as frame_status as it
+    is, on the same stream without a sync. frame_status (int32 [n]; None: the table set's own status):
+    a frame whose word is non-zero is not walked, its report is clean and its verdict that word."""
+    fr, dev_index = _slice_entry("check_frames", frames, 0)
+    luts, stride, own = _region_tables("check_frames", frames, tables, dev_index, True)
+    status = own if frame_status is None else frame_status
+    _status_arg("frame_status", status, frames, dev_index)
+    rep, verdict = _check_outputs(frames, stream)
+    rc = N.lib().mh_check_frames(ctypes.byref(fr), luts.data_ptr(), stride,
+                                 status.data_ptr() if status is not None else None, rep.data_ptr(),
+                                 verdict.data_ptr(), _raw_stream_ptr(stream, dev_index))
+    if rc:
+        N.check(rc, "mh_check_frames")
+    return rep.to(torch.int64) & 0xFFFFFFFF, verdict
+
+
+def check_headers(frames: DeviceFrames, canons, frame_status: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None) -> tuple:
+    """check_frames straight from the canonical headers (mh_check_headers; canons as decode_headers
+    takes them). Returns (report, verdict, header_status): a rejected header is not walked, its
+    report is clean, and its verdict and header_status word are the header's code (-3 or -5)."""
+    fr, dev_index = _slice_entry("check_headers", frames, 0)
+    hdr = _header_tensor(canons, frames.codes.device, convert=False)
+    if (hdr.dtype is not torch.uint8 or hdr.dim() != 2 or tuple(hdr.shape) != (frames.n_frames, 256)
+            or hdr.get_device() != dev_index or not hdr.is_contiguous()):
+        raise ValueError(f"canons must be a contiguous uint8 [{frames.n_frames}, 256] tensor on cuda:{dev_index}")
+    _status_arg("frame_status", frame_status, frames, dev_index)
+    rep, verdict = _check_outputs(frames, stream)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        # a skipped frame's word is not written by the kernel: 0, as its header was not judged
+        header_status = torch.zeros(frames.n_frames, dtype=torch.int32, device=frames.codes.device)
+    rc = N.lib().mh_check_headers(ctypes.byref(fr), hdr.data_ptr(),
+                                  frame_status.data_ptr() if frame_status is not None else None,
+                                  header_status.data_ptr(), rep.data_ptr(), verdict.data_ptr(),
+                                  _raw_stream_ptr(stream, dev_index))
+    if rc:
+        N.check(rc, "mh_check_headers")
+    frames.__dict__["_hdr_keep"] = hdr  # read by the launch in flight
+    return rep.to(torch.int64) & 0xFFFFFFFF, verdict, header_status
+
+
 def _decode_frames_host(encoded: Sequence[EncodedFrame], device="cuda") -> np.ndarray:
     t1, t2 = encoded[0].tables()
     tabs = DeviceTables.upload(t1, t2, device)

@@ -440,6 +440,20 @@ class AsyncEncodedBatch:
         self.tables = self.table_set(stream)
         return decode_frames(self.frames(check=False), self.tables, out=out, stream=stream)
 
+    def check(self, stream: Optional[torch.cuda.Stream] = None) -> tuple:
+        """(report, verdict) of decoder.check_frames for the batch on `stream`, no host
+        synchronisation: under table_set() (kept in `self.checked_tables`), or a shared batch
+        under its one table with the encoder's status. A frame the encoder or the table build
+        rejected is not walked and keeps that word as its verdict; the verdict goes into the
+        decode entries' frame_status as it is."""
+        from .decoder import check_frames
+        frames = self.frames(check=False)
+        if self.shared:
+            self.checked_tables = self.tables(stream=stream)
+            return check_frames(frames, self.checked_tables, frame_status=self.status, stream=stream)
+        self.checked_tables = self.table_set(stream)
+        return check_frames(frames, self.checked_tables, stream=stream)
+
     def frame(self, f: int) -> DeviceEncodedFrame:
         """Frame f (synchronises; raises MHError on a rejected frame)."""
         st, n = int(self.status[f].item()), int(self.codes_len[f].item())
