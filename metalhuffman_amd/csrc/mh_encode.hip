@@ -20,8 +20,8 @@
 // histogram -- five launches -- or supplied as 256 code lengths -- four; see "batched
 // frames under ONE table" below). mh_encode_images_[shared_]device_async are those two
 // entries reading interleaved, pitched images: one frame per taken plane, the split and
-// the packer with another pixel fetch (see "interleaved, pitched images" below;
-// mh_encode_pack_wave.inc holds the packer's body for both).
+// the packer with another pixel fetch (see "interleaved, pitched images" below; both
+// kernels are templates over the source, PlanarSrc or ImagesSrc).
 // mh_encode_frame_device_async never synchronises (header, code bytes and status are
 // written to device memory); mh_encode_frame_device runs it and synchronises once at
 // the end to return the header and the byte count on the host.
@@ -240,170 +240,6 @@ __device__ __forceinline__ uint64_t group_row(const uint8_t *gray, uint32_t W, u
   }
 }
 
-// The tiled split's rows: lane k's blocks tb + k + 32 u (u < N) of the tile starting at
-// block tb, row r, from one descriptor at the tile's first block row. The tile's
-// coordinates are uniform (one scalar division); a lane's block wraps into the next
-// block row at most once when the frame is >= kCodeTile blocks wide.
-template <bool kVec, uint32_t N, uint32_t kTile>
-__device__ __forceinline__ void tile_rows(const uint8_t *gray, uint32_t W, uint32_t H, uint32_t bw, uint64_t nb,
-                                          uint32_t tb, uint32_t r, uint64_t (&q)[N]) {
-  // no 64-bit compares and no per-load v_mul_lo (quarter rate): 32-bit block indices
-  // (nb < 2^26), the row offset r * W once, a wrapped block adds 8 W
-  const uint32_t k = threadIdx.x >> 3, nb32 = (uint32_t)nb;
-  const uint32_t tby = tb / bw, tbx = tb - tby * bw;
-  const uint32_t y0 = tby * 8u, hrem = H - y0, w8 = 8u * W;
-  const __amdgpu_buffer_rsrc_t rg = enc_rsrc(gray + (uint64_t)y0 * W, (uint64_t)hrem * W);
-  uint32_t rowoff = r * W;
-  asm volatile("" : "+v"(rowoff));  // kept as is (else folded back into (dy + r) * W per load)
-#pragma unroll
-  for (uint32_t u = 0; u < N; ++u) {
-    uint32_t bx = tbx + k + 32u * u, dy = 0, doff = 0;
-    if (bw >= kTile) {
-      const bool wrap = bx >= bw;
-      bx = wrap ? bx - bw : bx;
-      dy = wrap ? 8u : 0u;
-      doff = wrap ? w8 : 0u;
-    } else {
-      const uint32_t d = bx / bw;
-      bx -= d * bw;
-      dy = d * 8u;
-      doff = dy * W;
-    }
-    const bool in = tb + k + 32u * u < nb32 && dy + r < hrem;
-    const uint32_t off = doff + rowoff + bx * 8u;
-    if constexpr (kVec) {
-      typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
-      const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(rg, (int)(in ? off : kOob), 0, 0);
-      q[u] = ((uint64_t)v.y << 32) | v.x;
-    } else {
-      uint64_t x = 0;
-#pragma unroll
-      for (uint32_t c = 0; c < 8; ++c)
-        x |= (uint64_t)__builtin_amdgcn_raw_buffer_load_b8(rg, (int)(in && bx * 8u + c < W ? off + c : kOob), 0, 0)
-             << (8 * c);
-      q[u] = x;
-    }
-  }
-}
-
-template <bool kVec, bool kTiled, uint32_t kTile = kCodeTile>
-__global__ void __launch_bounds__(256) enc_split_kernel(const uint8_t *gray, uint32_t W, uint32_t H,
-                                                        uint32_t bw, uint64_t nb, uint32_t flags,
-                                                        uint8_t *sym, uint8_t *block_init,
-                                                        uint64_t *hist, uint16_t *tile_hist, uint64_t *meta,
-                                                        uint32_t ncode, uint64_t gray_stride,
-                                                        uint64_t *tile_tail) {
-  constexpr bool tiled = kTiled;
-  uint32_t wg = blockIdx.x;  // tiled: this frame's tile
-  if (tiled) {
-    const uint32_t f = blockIdx.x / ncode;
-    wg = blockIdx.x - f * ncode;
-    gray += f * gray_stride;
-    if (block_init) block_init += (uint64_t)f * nb;
-    if (hist) hist += (uint64_t)f * kHistParts * 256;
-    tile_hist += (uint64_t)f * ncode * 256;
-    if (tile_tail) tile_tail += (uint64_t)f * ncode * 8;
-  }
-  if (tiled && meta && blockIdx.x == 0 && threadIdx.x == 0) {  // the code kernel runs after this one
-    meta[kFlag] = 0;
-    meta[kAbort] = 0;
-    meta[kGen] += 1;  // a new tag for the code table words (table_tag)
-  }
-  MH_SPLIT_STAMP(0)
-  __shared__ __attribute__((aligned(16))) uint32_t h[256 * kHistCopies];
-  // the histogram is cleared behind the first batch's loads (their HBM round trip
-  // covers it), before any atomic: 16-byte writes, consecutive per lane (no conflicts)
-  bool cleared = false;
-  const auto clear_hist = [&]() {
-    typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (uint32_t i = 0; i < kHistCopies / 4; ++i) reinterpret_cast<v4u32 *>(h)[threadIdx.x + 256u * i] = v4u32{0u, 0u, 0u, 0u};
-    lds_barrier();
-    cleared = true;
-  };
-  const uint32_t r = threadIdx.x & 7u;
-  const uint32_t copy = threadIdx.x % kHistCopies;
-  const bool delta = !(flags & MH_FLAG_NO_DELTA);
-  // block_init: buffer stores (lanes without a byte out of range)
-  const __amdgpu_buffer_rsrc_t rinit = enc_rsrc(block_init, block_init ? nb : 0ull);
-  // one group of 32 blocks: deltas, init bytes, symbols out (four-kernel path; the
-  // fused path's packer re-derives them from the pixels), histogram
-  // one group of 32 blocks (four-kernel path): deltas, init bytes, symbols out, histogram
-  auto process = [&](uint64_t g, uint64_t q) {
-    const uint64_t b = g * 32 + (threadIdx.x >> 3);
-    const bool on = b < nb;
-    uint32_t first;
-    const uint64_t v = row_symbols(q, r, delta, block_init != nullptr, &first);
-    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)first, rinit, (int)(r == 0 && on ? (uint32_t)b : kOob), 0, 0);
-    if (on) {
-      if (sym) reinterpret_cast<uint64_t *>(sym + b * 64)[r] = v;  // large frames: 64-bit offsets
-      for (int j = 0; j < 8; ++j) atomicAdd(&h[((uint32_t)(v >> (8 * j)) & 0xFFu) * kHistCopies + copy], 1u);
-    }
-  };
-  const uint64_t ngroups = (nb + 31) / 32;
-  constexpr uint32_t kGroups = kTile / 32;  // tiled: groups of 32 blocks per tile
-  if constexpr (kTiled) {
-    // One tile: its kGroups groups' rows loaded at once (8 bytes per lane in flight would
-    // leave the read latency-bound), then each group's deltas and histogram. The init
-    // bytes are stored only when the format has them (a uniform branch: no dead store per
-    // row), and the tile's last block's symbols (batched path, tile_tail) once at the end.
-    const uint32_t nb32 = (uint32_t)nb, tb = wg * kTile;
-    uint64_t q[kGroups];
-    tile_rows<kVec, kGroups, kTile>(gray, W, H, bw, nb, tb, r, q);
-    clear_hist();
-#if MH_CODE_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);
-    MH_SPLIT_STAMP(1)
-#endif
-    uint64_t vlast = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < kGroups; ++u) {
-      const uint32_t b = tb + 32u * u + (threadIdx.x >> 3);
-      uint32_t first;
-      const uint64_t v = row_symbols(q[u], r, delta, block_init != nullptr, &first);
-      if (block_init)  // kernel-uniform
-        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)first, rinit, (int)(r == 0 && b < nb32 ? b : kOob), 0, 0);
-      if (!MH_DIAG_SPLIT_NO_HIST && b < nb32)
-        for (int j = 0; j < 8; ++j) atomicAdd(&h[((uint32_t)(v >> (8 * j)) & 0xFFu) * kHistCopies + copy], 1u);
-      vlast = v;
-    }
-    // the tile's last block (lanes 248-255 of group kGroups - 1): its symbols for the next
-    // tile's packer, whose first code word starts with this block's last bits -- 64 B per
-    // tile instead of the packer re-reading the block's eight pixel rows (eight 128-B lines)
-    if (tile_tail && threadIdx.x >= 248u && tb + kTile - 1u < nb32) tile_tail[(uint64_t)wg * 8u + r] = vlast;
-  } else {
-    // grid-stride over groups, kSplitBatch groups' rows loaded before any is processed
-    // (32-bit group indices: a frame has < 2^26 blocks, < 2^21 groups)
-    const uint32_t ng32 = (uint32_t)ngroups, gdim = gridDim.x, gstride = kSplitBatch * gdim;
-    for (uint32_t g0 = blockIdx.x; g0 < ng32; g0 += gstride) {
-      uint64_t q[kSplitBatch];
-#pragma unroll
-      for (uint32_t u = 0; u < kSplitBatch; ++u) q[u] = group_row<kVec>(gray, W, H, bw, nb, g0 + u * gdim, r);
-      if (!cleared) clear_hist();  // workgroup-uniform
-#pragma unroll
-      for (uint32_t u = 0; u < kSplitBatch; ++u) {
-        const uint32_t g = g0 + u * gdim;
-        if (g < ng32) process(g, q[u]);
-      }
-    }
-  }
-  MH_SPLIT_STAMP(2)
-  if (!cleared) clear_hist();  // no group at all
-  lds_barrier();
-  uint32_t c = 0;
-  for (uint32_t k = 0; k < kHistCopies; ++k) c += h[threadIdx.x * kHistCopies + ((k + threadIdx.x) % kHistCopies)];
-  if (tiled) tile_hist[(uint64_t)wg * 256 + threadIdx.x] = (uint16_t)c;  // <= kTile * 64
-  MH_SPLIT_STAMP(3)
-  // kHistParts partial histograms (workgroups round-robin over them, as over the
-  // XCDs): one address per bin would serialise every workgroup's atomic on it
-  // (the batched path passes no hist: its tree kernel sums the tile counts itself)
-  if (c && hist) atomicAdd((unsigned long long *)&hist[(wg % kHistParts) * 256 + threadIdx.x], (unsigned long long)c);
-#if MH_CODE_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);
-  MH_SPLIT_STAMP(4)
-#endif
-}
-
 // ---- interleaved, pitched images: mh_encode_images_[shared_]device_async ---------------
 // The batched path with another pixel fetch: sample (i, c, x, y) is the byte at
 // pixels + i * image_stride + y * pitch + x * ps + fc + c, and plane c of image i is frame
@@ -533,110 +369,250 @@ __device__ __forceinline__ uint64_t img_row(__amdgpu_buffer_rsrc_t rg, uint32_t 
   }
 }
 
-// tile_rows for an image plane: `image` is the image's first byte, the descriptor starts
-// at the tile's first row and ends with the image's last sample.
-template <uint32_t kPs, uint32_t N, uint32_t kTile>
-__device__ __forceinline__ void tile_rows_img(const uint8_t *image, uint32_t pitch, uint32_t ps_any, uint32_t ch,
-                                              uint32_t W, uint32_t H, uint32_t bw, uint64_t nb, uint32_t tb, uint32_t r,
-                                              uint64_t (&q)[N]) {
-  const uint32_t ps = kPs == kBytePs ? ps_any : kPs;
+// What the batched kernels read, as a kernel argument: planar frames gray_stride bytes
+// apart, or the planes of interleaved images. The kernels are templates over it and keep
+// the source-specific parts under `if constexpr (Src::kImages)`; the planar instantiations
+// compile to what they were before the images existed.
+struct PlanarSrc {
+  static constexpr bool kImages = false;
+  uint64_t gray_stride;
+};
+struct ImagesSrc {
+  static constexpr bool kImages = true;
+  ImgSrc im;
+};
+
+// The tiled split's rows: lane k's blocks tb + k + 32 u (u < N) of the tile starting at
+// block tb, row r, from one descriptor at the tile's first block row. The tile's
+// coordinates are uniform (one scalar division); a lane's block wraps into the next
+// block row at most once when the frame is >= kCodeTile blocks wide.
+// Images: `gray` is the image's first byte, ch the plane's byte of a pixel, and the
+// descriptor ends with the image's last sample; kVec is false and kPs the fetch mode.
+template <bool kImages, uint32_t kPs, bool kVec, uint32_t N, uint32_t kTile>
+__device__ __forceinline__ void tile_rows(const uint8_t *gray, uint32_t rowb, uint32_t ps_any, uint32_t ch, uint32_t W,
+                                          uint32_t H, uint32_t bw, uint64_t nb, uint32_t tb, uint32_t r,
+                                          uint64_t (&q)[N]) {
+  // no 64-bit compares and no per-load v_mul_lo (quarter rate): 32-bit block indices
+  // (nb < 2^26), the row offset r * rowb once, a wrapped block adds 8 rows
+  const uint32_t ps = !kImages ? 1u : kPs == kBytePs ? ps_any : kPs;  // bytes from pixel to pixel
   const uint32_t k = threadIdx.x >> 3, nb32 = (uint32_t)nb;
   const uint32_t tby = tb / bw, tbx = tb - tby * bw;
-  const uint32_t y0 = tby * 8u, hrem = H - y0, p8 = 8u * pitch, xs = 8u * ps;  // tb < nb: y0 < H
-  const uint64_t span64 = (uint64_t)(hrem - 1u) * pitch + (uint64_t)W * ps;
-  const uint32_t span = (uint32_t)(span64 < kMaxTileSpan ? span64 : kMaxTileSpan);
-  const __amdgpu_buffer_rsrc_t rg = enc_rsrc(image + (uint64_t)y0 * pitch, span);
-  uint32_t rowoff = r * pitch;
-  asm volatile("" : "+v"(rowoff));
-  // group u's row: its buffer offset, whether it is inside the frame, its pixels inside
-  const auto place = [&](uint32_t u, uint32_t &off, bool &in, uint32_t &nv) {
-    uint32_t bx = tbx + k + 32u * u, dy = 0, doff = 0;
-    if (bw >= kTile) {
-      const bool wrap = bx >= bw;
-      bx = wrap ? bx - bw : bx;
-      dy = wrap ? 8u : 0u;
-      doff = wrap ? p8 : 0u;
-    } else {
-      const uint32_t d = bx / bw;
-      bx -= d * bw;
-      dy = d * 8u;
-      doff = dy * pitch;
-    }
-    in = tb + k + 32u * u < nb32 && dy + r < hrem;
-    off = doff + rowoff + bx * xs;
-    nv = min(8u, W - bx * 8u);
-  };
-  uint32_t fixes = 0;  // dword modes: the groups whose row this lane must fetch by bytes
-#pragma unroll
-  for (uint32_t u = 0; u < N; ++u) {
-    uint32_t off, nv;
-    bool in;
-    place(u, off, in, nv);
-    if constexpr (kPs == kBytePs) {
-      q[u] = img_row_bytes(rg, off, in, nv, ps, ch);
-    } else {
-      bool fix;
-      q[u] = img_row_dwords<kPs>(rg, off, in, nv, span, ch, &fix);
-      fixes |= (fix ? 1u : 0u) << u;
-    }
-  }
-  if (fixes) {  // the image's last rows only
-#pragma unroll
-    for (uint32_t u = 0; u < N; ++u)
-      if (fixes >> u & 1u) {
-        uint32_t off, nv;
-        bool in;
-        place(u, off, in, nv);
-        q[u] = img_row_bytes(rg, off, true, nv, ps, ch);
+  const uint32_t y0 = tby * 8u, hrem = H - y0, w8 = 8u * rowb;  // tb < nb: y0 < H
+  [[maybe_unused]] const uint32_t xs = 8u * ps;
+  // images: the bytes from the tile's first row to the image's last sample, the most a load may touch
+  [[maybe_unused]] const uint64_t span64 = (uint64_t)(hrem - 1u) * rowb + (uint64_t)W * ps;
+  [[maybe_unused]] const uint32_t span = (uint32_t)(span64 < kMaxTileSpan ? span64 : kMaxTileSpan);
+  const __amdgpu_buffer_rsrc_t rg = enc_rsrc(gray + (uint64_t)y0 * rowb, kImages ? (uint64_t)span : (uint64_t)hrem * W);
+  uint32_t rowoff = r * rowb;
+  asm volatile("" : "+v"(rowoff));  // kept as is (else folded back into (dy + r) * rowb per load)
+  if constexpr (kImages) {
+    // group u's row: its buffer offset, whether it is inside the frame, its pixels inside. (The
+    // planar loop below writes the same placement out: sharing this lambda with it, or
+    // handing bx out of it, changes the listings -- DESIGN.md section 4e.)
+    const auto place = [&](uint32_t u, uint32_t &off, bool &in, uint32_t &nv) {
+      uint32_t bx = tbx + k + 32u * u, dy = 0, doff = 0;
+      if (bw >= kTile) {
+        const bool wrap = bx >= bw;
+        bx = wrap ? bx - bw : bx;
+        dy = wrap ? 8u : 0u;
+        doff = wrap ? w8 : 0u;
+      } else {
+        const uint32_t d = bx / bw;
+        bx -= d * bw;
+        dy = d * 8u;
+        doff = dy * rowb;
       }
+      in = tb + k + 32u * u < nb32 && dy + r < hrem;
+      off = doff + rowoff + bx * xs;
+      nv = min(8u, W - bx * 8u);
+    };
+    uint32_t fixes = 0;  // dword modes: the groups whose row this lane must fetch by bytes
+#pragma unroll
+    for (uint32_t u = 0; u < N; ++u) {
+      uint32_t off, nv;
+      bool in;
+      place(u, off, in, nv);
+      if constexpr (kPs == kBytePs) {
+        q[u] = img_row_bytes(rg, off, in, nv, ps, ch);
+      } else {
+        bool fix;
+        q[u] = img_row_dwords<kPs>(rg, off, in, nv, span, ch, &fix);
+        fixes |= (fix ? 1u : 0u) << u;
+      }
+    }
+    // the fix-up pass, behind every group's loads: a lane whose dword load would reach past
+    // the image's last sample (the image's last rows only) fetches that row again by bytes
+    if (fixes) {
+#pragma unroll
+      for (uint32_t u = 0; u < N; ++u)
+        if (fixes >> u & 1u) {
+          uint32_t off, nv;
+          bool in;
+          place(u, off, in, nv);
+          q[u] = img_row_bytes(rg, off, true, nv, ps, ch);
+        }
+    }
+  } else {
+#pragma unroll
+    for (uint32_t u = 0; u < N; ++u) {
+      uint32_t bx = tbx + k + 32u * u, dy = 0, doff = 0;
+      if (bw >= kTile) {
+        const bool wrap = bx >= bw;
+        bx = wrap ? bx - bw : bx;
+        dy = wrap ? 8u : 0u;
+        doff = wrap ? w8 : 0u;
+      } else {
+        const uint32_t d = bx / bw;
+        bx -= d * bw;
+        dy = d * 8u;
+        doff = dy * W;
+      }
+      const bool in = tb + k + 32u * u < nb32 && dy + r < hrem;
+      const uint32_t off = doff + rowoff + bx * 8u;
+      if constexpr (kVec) {
+        typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
+        const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(rg, (int)(in ? off : kOob), 0, 0);
+        q[u] = ((uint64_t)v.y << 32) | v.x;
+      } else {
+        uint64_t x = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < 8; ++c)
+          x |= (uint64_t)__builtin_amdgcn_raw_buffer_load_b8(rg, (int)(in && bx * 8u + c < W ? off + c : kOob), 0, 0)
+               << (8 * c);
+        q[u] = x;
+      }
+    }
   }
 }
 
-// The tiled split of the batched path (enc_split_kernel<.., true, kBatchTile>) over image
-// planes: workgroup g is tile t of plane c of image img (img_unit).
-template <uint32_t kPs>
-__global__ void __launch_bounds__(256) enc_split_img_kernel(const uint8_t *pixels, const ImgSrc im, uint32_t W,
-                                                            uint32_t H, uint32_t bw, uint64_t nb, uint32_t flags,
-                                                            uint8_t *block_init, uint16_t *tile_hist, uint32_t ncode,
-                                                            uint64_t *tile_tail) {
-  constexpr uint32_t kTile = kBatchTile, kGroups = kTile / 32;
-  uint32_t f, wg, img, c;
-  img_unit(im, blockIdx.x, ncode, f, wg, img, c);
-  pixels += img * im.image_stride;
-  if (block_init) block_init += (uint64_t)f * nb;
-  tile_hist += (uint64_t)f * ncode * 256;
-  tile_tail += (uint64_t)f * ncode * 8;
+// Images (Src = ImagesSrc, tiled, kTile = kBatchTile, kPs the fetch mode, no sym, hist or
+// meta): workgroup g is tile t of plane c of image img (img_unit).
+template <typename Src, uint32_t kPs, bool kVec, bool kTiled, uint32_t kTile = kCodeTile>
+__global__ void __launch_bounds__(256) enc_split_kernel(const uint8_t *gray, uint32_t W, uint32_t H,
+                                                        uint32_t bw, uint64_t nb, uint32_t flags,
+                                                        uint8_t *sym, uint8_t *block_init,
+                                                        uint64_t *hist, uint16_t *tile_hist, uint64_t *meta,
+                                                        uint32_t ncode, const Src src,
+                                                        uint64_t *tile_tail) {
+  constexpr bool tiled = kTiled, kImages = Src::kImages;
+  static_assert(!kImages || (kTiled && !kVec), "image planes take the tiled split and their own fetch");
+  uint32_t wg = blockIdx.x;  // tiled: this frame's tile
+  [[maybe_unused]] uint32_t ch = 0;
+  if constexpr (kImages) {
+    uint32_t f, img, c;
+    img_unit(src.im, blockIdx.x, ncode, f, wg, img, c);
+    gray += img * src.im.image_stride;
+    ch = src.im.fc + c;
+    if (block_init) block_init += (uint64_t)f * nb;
+    tile_hist += (uint64_t)f * ncode * 256;
+    tile_tail += (uint64_t)f * ncode * 8;
+  } else if (tiled) {
+    const uint32_t f = blockIdx.x / ncode;
+    wg = blockIdx.x - f * ncode;
+    gray += f * src.gray_stride;
+    if (block_init) block_init += (uint64_t)f * nb;
+    if (hist) hist += (uint64_t)f * kHistParts * 256;
+    tile_hist += (uint64_t)f * ncode * 256;
+    if (tile_tail) tile_tail += (uint64_t)f * ncode * 8;
+  }
+  if (!kImages && tiled && meta && blockIdx.x == 0 && threadIdx.x == 0) {  // the code kernel runs after this one
+    meta[kFlag] = 0;
+    meta[kAbort] = 0;
+    meta[kGen] += 1;  // a new tag for the code table words (table_tag)
+  }
+  MH_SPLIT_STAMP(0)
   __shared__ __attribute__((aligned(16))) uint32_t h[256 * kHistCopies];
-  const uint32_t r = threadIdx.x & 7u;
-  const uint32_t copy = threadIdx.x % kHistCopies;
-  const bool delta = !(flags & MH_FLAG_NO_DELTA);
-  const __amdgpu_buffer_rsrc_t rinit = enc_rsrc(block_init, block_init ? nb : 0ull);
-  const uint32_t nb32 = (uint32_t)nb, tb = wg * kTile;
-  uint64_t q[kGroups];
-  tile_rows_img<kPs, kGroups, kTile>(pixels, im.pitch, im.ps, im.fc + c, W, H, bw, nb, tb, r, q);
-  {  // the histogram is cleared behind the loads
+  // the histogram is cleared behind the first batch's loads (their HBM round trip
+  // covers it), before any atomic: 16-byte writes, consecutive per lane (no conflicts)
+  bool cleared = false;
+  const auto clear_hist = [&]() {
     typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (uint32_t i = 0; i < kHistCopies / 4; ++i) reinterpret_cast<v4u32 *>(h)[threadIdx.x + 256u * i] = v4u32{0u, 0u, 0u, 0u};
     lds_barrier();
-  }
-  uint64_t vlast = 0;
-#pragma unroll
-  for (uint32_t u = 0; u < kGroups; ++u) {
-    const uint32_t b = tb + 32u * u + (threadIdx.x >> 3);
+    cleared = true;
+  };
+  const uint32_t r = threadIdx.x & 7u;
+  const uint32_t copy = threadIdx.x % kHistCopies;
+  const bool delta = !(flags & MH_FLAG_NO_DELTA);
+  // block_init: buffer stores (lanes without a byte out of range)
+  const __amdgpu_buffer_rsrc_t rinit = enc_rsrc(block_init, block_init ? nb : 0ull);
+  // one group of 32 blocks (four-kernel path; the fused path's packer re-derives the
+  // symbols from the pixels): deltas, init bytes, symbols out, histogram
+  auto process = [&](uint64_t g, uint64_t q) {
+    const uint64_t b = g * 32 + (threadIdx.x >> 3);
+    const bool on = b < nb;
     uint32_t first;
-    const uint64_t v = row_symbols(q[u], r, delta, block_init != nullptr, &first);
-    if (block_init)  // kernel-uniform
-      __builtin_amdgcn_raw_buffer_store_b8((uint8_t)first, rinit, (int)(r == 0 && b < nb32 ? b : kOob), 0, 0);
-    if (b < nb32)
+    const uint64_t v = row_symbols(q, r, delta, block_init != nullptr, &first);
+    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)first, rinit, (int)(r == 0 && on ? (uint32_t)b : kOob), 0, 0);
+    if (on) {
+      if (sym) reinterpret_cast<uint64_t *>(sym + b * 64)[r] = v;  // large frames: 64-bit offsets
       for (int j = 0; j < 8; ++j) atomicAdd(&h[((uint32_t)(v >> (8 * j)) & 0xFFu) * kHistCopies + copy], 1u);
-    vlast = v;
+    }
+  };
+  const uint64_t ngroups = (nb + 31) / 32;
+  constexpr uint32_t kGroups = kTile / 32;  // tiled: groups of 32 blocks per tile
+  if constexpr (kTiled) {
+    // One tile: its kGroups groups' rows loaded at once (8 bytes per lane in flight would
+    // leave the read latency-bound), then each group's deltas and histogram. The init
+    // bytes are stored only when the format has them (a uniform branch: no dead store per
+    // row), and the tile's last block's symbols (batched path, tile_tail) once at the end.
+    const uint32_t nb32 = (uint32_t)nb, tb = wg * kTile;
+    uint64_t q[kGroups];
+    if constexpr (kImages) tile_rows<true, kPs, false, kGroups, kTile>(gray, src.im.pitch, src.im.ps, ch, W, H, bw, nb, tb, r, q);
+    else tile_rows<false, 0, kVec, kGroups, kTile>(gray, W, 1u, 0u, W, H, bw, nb, tb, r, q);
+    clear_hist();
+#if MH_CODE_STAMPS
+    __builtin_amdgcn_s_waitcnt(0);
+    MH_SPLIT_STAMP(1)
+#endif
+    uint64_t vlast = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < kGroups; ++u) {
+      const uint32_t b = tb + 32u * u + (threadIdx.x >> 3);
+      uint32_t first;
+      const uint64_t v = row_symbols(q[u], r, delta, block_init != nullptr, &first);
+      if (block_init)  // kernel-uniform
+        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)first, rinit, (int)(r == 0 && b < nb32 ? b : kOob), 0, 0);
+      if (!MH_DIAG_SPLIT_NO_HIST && b < nb32)
+        for (int j = 0; j < 8; ++j) atomicAdd(&h[((uint32_t)(v >> (8 * j)) & 0xFFu) * kHistCopies + copy], 1u);
+      vlast = v;
+    }
+    // the tile's last block (lanes 248-255 of group kGroups - 1): its symbols for the next
+    // tile's packer, whose first code word starts with this block's last bits -- 64 B per
+    // tile instead of the packer re-reading the block's eight pixel rows (eight 128-B lines)
+    if ((kImages || tile_tail) && threadIdx.x >= 248u && tb + kTile - 1u < nb32) tile_tail[(uint64_t)wg * 8u + r] = vlast;
+  } else {
+    // grid-stride over groups, kSplitBatch groups' rows loaded before any is processed
+    // (32-bit group indices: a frame has < 2^26 blocks, < 2^21 groups)
+    const uint32_t ng32 = (uint32_t)ngroups, gdim = gridDim.x, gstride = kSplitBatch * gdim;
+    for (uint32_t g0 = blockIdx.x; g0 < ng32; g0 += gstride) {
+      uint64_t q[kSplitBatch];
+#pragma unroll
+      for (uint32_t u = 0; u < kSplitBatch; ++u) q[u] = group_row<kVec>(gray, W, H, bw, nb, g0 + u * gdim, r);
+      if (!cleared) clear_hist();  // workgroup-uniform
+#pragma unroll
+      for (uint32_t u = 0; u < kSplitBatch; ++u) {
+        const uint32_t g = g0 + u * gdim;
+        if (g < ng32) process(g, q[u]);
+      }
+    }
   }
-  if (threadIdx.x >= 248u && tb + kTile - 1u < nb32) tile_tail[(uint64_t)wg * 8u + r] = vlast;
+  MH_SPLIT_STAMP(2)
+  if (!cleared) clear_hist();  // no group at all
   lds_barrier();
-  uint32_t cnt = 0;
-  for (uint32_t k = 0; k < kHistCopies; ++k) cnt += h[threadIdx.x * kHistCopies + ((k + threadIdx.x) % kHistCopies)];
-  tile_hist[(uint64_t)wg * 256 + threadIdx.x] = (uint16_t)cnt;  // <= kTile * 64
+  uint32_t c = 0;
+  for (uint32_t k = 0; k < kHistCopies; ++k) c += h[threadIdx.x * kHistCopies + ((k + threadIdx.x) % kHistCopies)];
+  if (tiled) tile_hist[(uint64_t)wg * 256 + threadIdx.x] = (uint16_t)c;  // <= kTile * 64
+  MH_SPLIT_STAMP(3)
+  // kHistParts partial histograms (workgroups round-robin over them, as over the
+  // XCDs): one address per bin would serialise every workgroup's atomic on it
+  // (the batched path passes no hist: its tree kernel sums the tile counts itself)
+  if (!kImages && c && hist) atomicAdd((unsigned long long *)&hist[(wg % kHistParts) * 256 + threadIdx.x], (unsigned long long)c);
+#if MH_CODE_STAMPS
+  __builtin_amdgcn_s_waitcnt(0);
+  MH_SPLIT_STAMP(4)
+#endif
 }
 
 
@@ -1889,28 +1865,272 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 // kPair: 8-byte aligned rows and an even frame width in blocks (a pair never straddles
-// a block row): one 16-byte load per lane and step
-template <bool kVec, bool kPair>
+// a block row): one 16-byte load per lane and step.
+// Images (Src = ImagesSrc, kPs the fetch mode, kVec = kPair = false): workgroup g packs
+// kPackWaves tiles of plane c of image img (img_unit: the planes of a unit eight workgroups
+// apart); the workgroup mapping, the source pointer, the descriptor and load_row's fetch
+// (img_row<kPs>) differ, nothing behind the fetch does.
+template <typename Src, uint32_t kPs, bool kVec, bool kPair>
 __global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_kernel(
-    const Pixels px, uint64_t gray_stride, uint64_t nb, uint32_t ncode, const uint32_t *table, const uint64_t *meta,
+    const Pixels px, const Src src, uint64_t nb, uint32_t ncode, const uint32_t *table, const uint64_t *meta,
     const uint32_t *tile_off, uint32_t *offsets, uint8_t *codes, uint64_t codes_stride, uint32_t ncode_wg,
     const uint64_t *tile_tail) {
-#define MH_PACK_IMAGES 0
-#include "mh_encode_pack_wave.inc"
-#undef MH_PACK_IMAGES
+  constexpr bool kImages = Src::kImages;
+  static_assert(!kImages || (!kVec && !kPair), "image planes take their own fetch");
+  // ncode_wg: workgroups per frame (ncode rounded up to kPackWaves tiles): a workgroup's
+  // waves pack tiles of ONE frame and share its table, at a fixed LDS address (the
+  // gathers need no per-wave base: one VALU per symbol for the address)
+  __shared__ uint32_t tab[256];
+  __shared__ __attribute__((aligned(16))) uint32_t s_w[kPackWaves][kStepSlots];
+  // the wave index as a provably uniform value (readfirstlane): the tile, its offsets and
+  // the step cursor then live in SGPRs (SALU) instead of being carried per lane
+  const uint32_t lane = threadIdx.x & 63u, k = lane >> 3, r = lane & 7u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // frame f, its tile t; rowb: bytes from row to row; images: the plane's byte pch of a pixel,
+  // ps bytes from pixel to pixel
+  uint32_t f, t, rowb = px.W;
+  [[maybe_unused]] uint32_t img = 0, pch = 0, ps = 1;
+  if constexpr (kImages) {
+    uint32_t unit, plane;
+    img_unit(src.im, blockIdx.x, ncode_wg, f, unit, img, plane);
+    t = unit * kPackWaves + wave;
+    pch = src.im.fc + plane;
+    rowb = src.im.pitch;
+    ps = kPs == kBytePs ? src.im.ps : kPs;
+  } else {
+    f = blockIdx.x / ncode_wg;
+    t = (blockIdx.x - f * ncode_wg) * kPackWaves + wave;
+  }
+  if (!(uint32_t)meta[(uint64_t)f * kMetaWords + 1]) return;  // rejected frame (workgroup-uniform): nothing written
+  {
+    // the frame's table as len << 16 | right-aligned code (the tree's words hold the
+    // code left-aligned in 16 bits): two symbols' codes combine in one v_lshl_or
+    const uint32_t e = table[(uint64_t)f * 256 + threadIdx.x];
+    const uint32_t L = e & 0x1Fu;
+    tab[threadIdx.x] = L ? (L << 16) | ((e >> 16) >> (16u - L)) : 0u;
+  }
+  lds_barrier();
+  if (t >= ncode) return;  // wave-uniform padding past the frame's last tile; no barrier follows
+  uint32_t *lw = s_w[wave];
+  const uint32_t E = tile_off[(uint64_t)f * (ncode + 1) + t];
+  const uint8_t *gray = px.gray;  // the frame's, or the image's, first byte
+  if constexpr (kImages) gray += img * src.im.image_stride;
+  else gray += f * src.gray_stride;
+  const uint64_t b0 = (uint64_t)t * kBatchTile;
+  const uint32_t nsteps = (uint32_t)((min<uint64_t>(kBatchTile, nb - b0) + kStepBlocks - 1) / kStepBlocks);
+  const uint32_t by0 = (uint32_t)(b0 / px.bw), bx0 = (uint32_t)(b0 - (uint64_t)by0 * px.bw);
+  // one descriptor from the tile's first block row: 32-bit offsets for any frame
+  const uint32_t yb = by0 * 8u;
+  // ... images: up to the image's last sample (tile_rows)
+  [[maybe_unused]] const uint64_t span64 = (uint64_t)(px.H - yb - 1u) * rowb + (uint64_t)px.W * ps;
+  [[maybe_unused]] const uint32_t span = (uint32_t)(span64 < kMaxTileSpan ? span64 : kMaxTileSpan);
+  const __amdgpu_buffer_rsrc_t rg =
+      enc_rsrc(gray + (uint64_t)yb * rowb, kImages ? (uint64_t)span : (uint64_t)(px.H - yb) * px.W);
+  // row r of block (bx + k, by) wrapped into the frame, zero when !live or past the frame
+  // (32-bit block indices, nb < 2^26; the step's row offset uniform, r * W per lane
+  // once, a wrapped block adds 8 W: no per-step v_mul_lo, which is quarter rate)
+  const uint32_t nb32 = (uint32_t)nb, w8 = 8u * rowb;
+  const auto load_row = [&](uint32_t sbx, uint32_t sby, uint32_t sb, uint32_t kk, uint32_t rr, uint32_t rrW,
+                            bool live) -> uint64_t {
+    uint32_t bx = sbx + kk, dy = 0, doff = 0;
+    if (px.bw >= kStepBlocks) {  // kk < kStepBlocks: one wrap at most
+      const bool wrap = bx >= px.bw;
+      bx = wrap ? bx - px.bw : bx;
+      dy = wrap ? 8u : 0u;
+      doff = wrap ? w8 : 0u;
+    } else {
+      const uint32_t d = bx / px.bw;
+      bx -= d * px.bw;
+      dy = d * 8u;
+      doff = dy * rowb;
+    }
+    const uint32_t ys = sby * 8u - yb;  // uniform: the step's first block row in the descriptor
+    const bool in = live && sb + kk < nb32 && ys + dy + rr < px.H - yb;
+    if constexpr (kImages) {
+      return img_row<kPs>(rg, ys * rowb + doff + rrW + bx * (8u * ps), in, min(8u, px.W - bx * 8u), span, ps, pch);
+    } else {
+      const uint32_t off = ys * px.W + doff + rrW + bx * 8u;  // (px.W, not rowb: the byte-load packer's listing)
+      if constexpr (kVec) {
+        typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
+        const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(rg, (int)(in ? off : kOob), 0, 0);
+        return ((uint64_t)v.y << 32) | v.x;
+      } else {
+        uint64_t q = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < 8; ++c)
+          q |= (uint64_t)__builtin_amdgcn_raw_buffer_load_b8(rg, (int)(in && bx * 8u + c < px.W ? off + c : kOob), 0, 0)
+               << (8 * c);
+        return q;
+      }
+    }
+  };
+  uint32_t first_unused;
+  // the tile's first word starts with the previous block's last E % 32 bits: lanes 0-7
+  // recompute that block's codes (the previous tile leaves the shared word to this one)
+  // from its symbols, which the split kept for this (tile_tail: one 64-B read)
+  uint32_t head = 0;
+  const uint32_t r0 = E & 31u;
+  if (r0) {  // wave-uniform; t > 0 here (tile 0 starts at bit 0)
+    const __amdgpu_buffer_rsrc_t rt = enc_rsrc(tile_tail + ((uint64_t)f * ncode + t - 1u) * 8u, 64u);
+    typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
+    const v2u32 tv = __builtin_amdgcn_raw_buffer_load_b64(rt, (int)(lane < 8 ? lane * 8u : kOob), 0, 0);
+    const uint64_t qp = ((uint64_t)tv.y << 32) | tv.x;
+    uint32_t lenp = 0;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t e = tab[(uint32_t)(qp >> (8 * j)) & 0xFFu];
+      const uint32_t len = e >> 16;
+      acc = (acc << len) | (e & 0xFFFFu);  // the lane's codes MSB-first, last 64 bits
+      lenp += len;
+    }
+    if (lane >= 8) lenp = 0;
+    // bits of lanes after this one in the block; the lane's last bit lands at word bit
+    // 32 - r0 + after (bits before the word fall off the top)
+    const uint32_t incp = wave_scan_dpp(lenp);
+    const uint32_t after = __builtin_amdgcn_readlane(incp, 7) - incp;
+    uint32_t h = lane < 8 && after < r0 ? (uint32_t)(acc << (32u - r0 + after)) : 0u;
+    for (uint32_t o = 1; o < 8; o <<= 1) h |= __shfl_xor(h, o);
+    head = __builtin_amdgcn_readfirstlane(h);
+  }
+  typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
+  v4u32 *lq = reinterpret_cast<v4u32 *>(lw);
+  // the step's words as quads: one 16-B LDS write / read and one 16-B store per lane
+  const auto clear_words = [&](uint32_t first) {
+    lq[lane] = v4u32{lane == 0 ? first : 0u, 0u, 0u, 0u};
+    lq[64 + lane] = v4u32{0u, 0u, 0u, 0u};
+    if (lane < kStepSlots / 4 - 128) lq[128 + lane] = v4u32{0u, 0u, 0u, 0u};
+  };
+  clear_words(bswap32(head));
+  const __amdgpu_buffer_rsrc_t rw = enc_rsrc(codes + f * codes_stride, codes_stride);
+  const __amdgpu_buffer_rsrc_t ro = enc_rsrc(offsets + (uint64_t)f * nb, nb * 4u);
+  uint32_t pos = E;
+  uint32_t sbx = bx0, sby = by0;
+  uint32_t sb = (uint32_t)b0;
+  uint32_t rW = r * rowb;
+  asm volatile("" : "+v"(rW));  // kept as is (else folded back into (ys + r) * rowb per step)
+  // row r of the pair (2 k, 2 k + 1) of the step starting at block (sbx, sby) = sb
+  const auto load_pair = [&](uint32_t bx_, uint32_t by_, uint32_t sb_, bool live, uint64_t &qa, uint64_t &qb) {
+    if constexpr (kPair) {
+      uint32_t bx = bx_ + 2u * k, doff = 0, dy = 0;
+      if (px.bw >= kStepBlocks) {
+        const bool wrap = bx >= px.bw;
+        bx = wrap ? bx - px.bw : bx;
+        dy = wrap ? 8u : 0u;
+        doff = wrap ? w8 : 0u;
+      } else {
+        const uint32_t d = bx / px.bw;
+        bx -= d * px.bw;
+        dy = d * 8u;
+        doff = dy * rowb;
+      }
+      const uint32_t ys = by_ * 8u - yb;
+      const bool in = live && sb_ + 2u * k < nb32 && ys + dy + r < px.H - yb;
+      // both blocks are inside the frame when the first is (an even width, an even first block)
+      const v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(rg, (int)(in ? ys * rowb + doff + rW + bx * 8u : kOob), 0, 0);
+      qa = ((uint64_t)v.y << 32) | v.x;
+      qb = ((uint64_t)v.w << 32) | v.z;
+    } else {
+      qa = load_row(bx_, by_, sb_, 2u * k, r, rW, live);
+      qb = load_row(bx_, by_, sb_, 2u * k + 1u, r, rW, live);
+    }
+  };
+  uint64_t qa, qb;
+  load_pair(sbx, sby, sb, true, qa, qb);
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    // the next step's rows (a dead load past the tile's last step: fixed count)
+    uint32_t nbx = sbx + kStepBlocks, nby = sby;
+    while (nbx >= px.bw) {  // uniform; once per step at most when bw >= kStepBlocks
+      nbx -= px.bw;
+      ++nby;
+    }
+    uint64_t na, nbq;
+    load_pair(nbx, nby, sb + kStepBlocks, s + 1 < nsteps, na, nbq);
+    const uint32_t ba = sb + 2u * k;
+    const bool on_a = ba < nb32, on_b = ba + 1u < nb32;
+    // codes MSB-first: pairs of symbols in 32 bits (v_lshl_or), chunks of four in 64
+    uint64_t ch[4];
+    uint32_t cl[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const uint64_t v = row_symbols(h ? qb : qa, r, px.delta, px.init_byte, &first_unused);
+      uint32_t pc[4], pl[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t e0 = tab[(uint32_t)(v >> (16 * j)) & 0xFFu], e1 = tab[(uint32_t)(v >> (16 * j + 8)) & 0xFFu];
+        const uint32_t l1 = e1 >> 16;
+        pc[j] = ((e0 & 0xFFFFu) << l1) | (e1 & 0xFFFFu);
+        pl[j] = (e0 >> 16) + l1;
+      }
+      ch[2 * h] = ((uint64_t)pc[0] << pl[1]) | pc[1];
+      ch[2 * h + 1] = ((uint64_t)pc[2] << pl[3]) | pc[3];
+      cl[2 * h] = pl[0] + pl[1];
+      cl[2 * h + 1] = pl[2] + pl[3];
+    }
+    const uint32_t na_bits = on_a ? cl[0] + cl[1] : 0u, nb_bits = on_b ? cl[2] + cl[3] : 0u;
+    // bit order: block 2 k (rows 0-7), then block 2 k + 1: one scan of A | B << 16 (each
+    // half's sum over the wave <= 8,192), the pair's start and its A total by broadcast
+    const uint32_t x = na_bits | (nb_bits << 16);
+    const uint32_t S = wave_scan_dpp(x), ex = S - x;
+    const uint32_t g = __shfl(ex, lane & ~7u), ge = __shfl(S, lane | 7u);
+    const uint32_t Tw = __builtin_amdgcn_readlane(S, 63);
+    const uint32_t T = (Tw & 0xFFFFu) + (Tw >> 16);
+    const uint32_t start = (g & 0xFFFFu) + (g >> 16);             // the pair's first bit (step-relative)
+    const uint32_t atot = (ge & 0xFFFFu) - (g & 0xFFFFu);         // block 2 k's bits
+    const uint32_t pa = (g >> 16) + (ex & 0xFFFFu);                // this row of block 2 k
+    const uint32_t pb = (g & 0xFFFFu) + atot + (ex >> 16);         // this row of block 2 k + 1
+    // block offsets: lane r = 0 writes block 2 k's, lane r = 1 block 2 k + 1's
+    const bool wo = r == 0 ? on_a : r == 1 ? on_b : false;
+    __builtin_amdgcn_raw_buffer_store_b32(pos + start + (r == 1 ? atot : 0u), ro, (int)(wo ? (ba + r) * 4u : kOob), 0,
+                                          0);
+    const uint32_t rr = pos & 31u;
+    if (!MH_DIAG_PACK_NO_OR && on_a) {
+      or_bits(lw, rr + pa, ch[0], cl[0]);
+      or_bits(lw, rr + pa + cl[0], ch[1], cl[1]);
+    }
+    if (!MH_DIAG_PACK_NO_OR && on_b) {
+      or_bits(lw, rr + pb, ch[2], cl[2]);
+      or_bits(lw, rr + pb + cl[2], ch[3], cl[3]);
+    }
+    wave_sync();
+    // whole words out; the last partial word stays as the next step's first
+    const uint32_t nfull = (rr + T) >> 5, w0 = pos >> 5, nq4 = nfull >> 2;
+    const v4u32 q0 = lq[lane], q1 = lq[64 + lane];                    // words 4 lane .., 256 + 4 lane ..
+    const uint32_t tail = lw[min(4u * nq4 + lane, kStepSlots - 1u)];  // lanes < nfull % 4: the last words
+    const uint32_t carry = lw[nfull];
+    __builtin_amdgcn_raw_buffer_store_b128(q0, rw, (int)(lane < nq4 ? (w0 + 4u * lane) * 4u : kOob), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(q1, rw, (int)(64u + lane < nq4 ? (w0 + 256u + 4u * lane) * 4u : kOob), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(tail, rw, (int)(lane < (nfull & 3u) ? (w0 + 4u * nq4 + lane) * 4u : kOob), 0,
+                                          0);
+    wave_sync();
+    clear_words(carry);
+    wave_sync();
+    pos += T;
+    qa = na;
+    qb = nbq;
+    sbx = nbx;
+    sby = nby;
+    sb += kStepBlocks;
+  }
+  // the last tile writes its partial last word, then the zero pad up to the byte count
+  // rounded to words (the others leave that word to the next tile)
+  if (t + 1 == ncode) {
+    const uint32_t nw = (uint32_t)(((uint64_t)(pos + 7u) / 8u + MH_CODES_PAD + 3u) / 4u);
+    const uint32_t w = (pos >> 5) + lane;
+    const uint32_t val = lane == 0 ? lw[0] : 0u;
+    __builtin_amdgcn_raw_buffer_store_b32(val, rw, (int)(w < nw ? w * 4u : kOob), 0, 0);
+  }
 }
 
-// ... over image planes: workgroup g packs kPackWaves tiles of plane c of image img
-// (img_unit: the planes of a unit eight workgroups apart).
-template <uint32_t kPs>
-__global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_img_kernel(
-    const Pixels px, const ImgSrc im, uint64_t nb, uint32_t ncode, const uint32_t *table, const uint64_t *meta,
-    const uint32_t *tile_off, uint32_t *offsets, uint8_t *codes, uint64_t codes_stride, uint32_t ncode_wg,
-    const uint64_t *tile_tail) {
-  [[maybe_unused]] constexpr bool kVec = false, kPair = false;  // the planar packer's load widths
-#define MH_PACK_IMAGES 1
-#include "mh_encode_pack_wave.inc"
-#undef MH_PACK_IMAGES
+// A frame of the batched path in blocks: blocks a row, blocks, tiles of kBatchTile blocks.
+struct Geometry {
+  uint32_t bw;
+  uint64_t nb, ncode;
+};
+Geometry batch_geometry(uint32_t W, uint32_t H) {
+  const uint32_t bw = (W + 7) / 8;
+  const uint64_t nb = (uint64_t)bw * ((H + 7) / 8);
+  return Geometry{bw, nb, (nb + kBatchTile - 1) / kBatchTile};
 }
 
 struct BatchWorkspace {  // per-frame slices, each part 256-B aligned; nothing needs zeroing
@@ -1921,8 +2141,8 @@ struct BatchWorkspace {  // per-frame slices, each part 256-B aligned; nothing n
   uint64_t *tile_tail;  // n x ncode x 8: the symbols of each tile's last block (rows as u64)
 };
 
-uint64_t carve_batch(uint8_t *base, uint64_t nb, uint32_t n, BatchWorkspace *w) {
-  const uint64_t ncode = (nb + kBatchTile - 1) / kBatchTile;
+uint64_t carve_batch(uint8_t *base, const Geometry &g, uint32_t n, BatchWorkspace *w) {
+  const uint64_t ncode = g.ncode;
   uint64_t o = 0;
   if (w) w->table = reinterpret_cast<uint32_t *>(base + o);
   o += align256((uint64_t)n * 256 * 4);
@@ -1944,8 +2164,8 @@ struct SharedWorkspace {  // the batched path's parts, then the one table's
   uint64_t *meta;    // kMetaWords: [1] the header is usable, [kVerdict] its verdict
 };
 
-uint64_t carve_shared(uint8_t *base, uint64_t nb, uint32_t n, SharedWorkspace *w) {
-  uint64_t o = carve_batch(base, nb, n, w ? &w->b : nullptr);
+uint64_t carve_shared(uint8_t *base, const Geometry &g, uint32_t n, SharedWorkspace *w) {
+  uint64_t o = carve_batch(base, g, n, w ? &w->b : nullptr);
   if (w) w->hist = reinterpret_cast<uint64_t *>(base + o);
   o += align256(kHistParts * 256 * 8);
   if (w) w->table = reinterpret_cast<uint32_t *>(base + o);
@@ -1960,8 +2180,13 @@ uint64_t carve_shared(uint8_t *base, uint64_t nb, uint32_t n, SharedWorkspace *w
 struct Source {
   const uint8_t *base;
   uint64_t gray_stride;        // planar: bytes from frame to frame
-  const mh_image_layout *lay;  // images: the caller's layout (the entries' img argument says which)
+  const mh_image_layout *lay;  // images: the caller's layout
   uint32_t n;                  // frames or images
+  bool img;                    // an images entry's call (its lay may still be null: refused)
+  // how the kernels fetch, set once per call by check_batch_args when it accepts the call:
+  bool vec;       // planar: 8-byte aligned rows (W % 8 == 0, aligned base and frame stride)
+  ImgSrc im;      // images: the layout as the kernels take it
+  uint32_t mode;  // images: the fetch mode (MH_IMG_MODE)
 };
 
 // The images entries' MH_ERR_CAPACITY rules for a layout whose fields passed the
@@ -1982,82 +2207,101 @@ bool image_layout_fits(const mh_image_layout &l, uint32_t n, uint32_t W, uint32_
   return (rows - 1) * pitch + row <= kMaxTileSpan;
 }
 
-ImgSrc image_source(const mh_image_layout &l, uint32_t n, uint32_t H) {
-  return ImgSrc{l.image_stride, H > 1 ? (uint32_t)l.row_pitch : 0u, l.pixel_stride, l.first_channel, l.n_planes, n,
-                l.plane_major};
+// How the kernels fetch from a Source whose arguments passed the checks. Images: dword
+// loads for pixel strides 1-4 when every row of every image starts 4-byte aligned, else
+// byte loads.
+void resolve_fetch(Source &src, uint32_t W, uint32_t H) {
+  src.vec = !src.img && W % 8 == 0 && ((uintptr_t)src.base & 7u) == 0 && (src.gray_stride & 7u) == 0;
+  if (!src.img) return;
+  const mh_image_layout &l = *src.lay;
+  src.im = ImgSrc{l.image_stride, H > 1 ? (uint32_t)l.row_pitch : 0u, l.pixel_stride, l.first_channel, l.n_planes, src.n,
+                  l.plane_major};
+  const uint64_t a = (uint64_t)(uintptr_t)src.base | (src.n > 1 ? src.im.image_stride : 0) | (H > 1 ? src.im.pitch : 0u);
+  src.mode = src.im.ps <= 4 && !(a & 3u) ? src.im.ps : kBytePs;
 }
 
-// Fetch mode of a layout: dword loads for pixel strides 1-4 when every row of every image
-// starts 4-byte aligned, else byte loads.
-uint32_t image_mode(const uint8_t *base, const ImgSrc &im, uint32_t H) {
-  const uint64_t a = (uint64_t)(uintptr_t)base | (im.n > 1 ? im.image_stride : 0) | (H > 1 ? im.pitch : 0u);
-  return im.ps <= 4 && !(a & 3u) ? im.ps : kBytePs;
-}
-
-#define MH_IMG_MODE(mode, KERNEL)                                                              \
-  ((mode) == 1 ? KERNEL<1> : (mode) == 2 ? KERNEL<2> : (mode) == 3 ? KERNEL<3> : (mode) == 4 ? KERNEL<4> \
-                                                                               : KERNEL<kBytePs>)
+#define MH_IMG_MODE(mode, KERNEL, ...)                                                              \
+  ((mode) == 1   ? KERNEL<ImagesSrc, 1, __VA_ARGS__>                                                \
+   : (mode) == 2 ? KERNEL<ImagesSrc, 2, __VA_ARGS__>                                                \
+   : (mode) == 3 ? KERNEL<ImagesSrc, 3, __VA_ARGS__>                                                \
+   : (mode) == 4 ? KERNEL<ImagesSrc, 4, __VA_ARGS__>                                                \
+                 : KERNEL<ImagesSrc, kBytePs, __VA_ARGS__>)
 
 // The split and the packer of the batched path for frames [0, n_frames) of a Source.
-void launch_split(hipStream_t s, const Source &src, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t flags,
-                  uint8_t *block_init, const BatchWorkspace &w) {
-  const uint32_t bw = (W + 7) / 8;
-  const uint64_t nb = (uint64_t)bw * ((H + 7) / 8), ncode = (nb + kBatchTile - 1) / kBatchTile;
-  const dim3 grid((uint32_t)(ncode * n_frames));
-  if (src.lay) {
-    const ImgSrc im = image_source(*src.lay, src.n, H);
-    hipLaunchKernelGGL(MH_IMG_MODE(image_mode(src.base, im, H), enc_split_img_kernel), grid, dim3(256), 0, s, src.base, im,
-                       W, H, bw, nb, flags, block_init, w.tile_hist, (uint32_t)ncode, w.tile_tail);
+void launch_split(hipStream_t s, const Source &src, uint32_t n_frames, uint32_t W, uint32_t H, const Geometry &g,
+                  uint32_t flags, uint8_t *block_init, const BatchWorkspace &w) {
+  const dim3 grid((uint32_t)(g.ncode * n_frames));
+  if (src.img) {
+    hipLaunchKernelGGL(MH_IMG_MODE(src.mode, enc_split_kernel, false, true, kBatchTile), grid, dim3(256), 0, s, src.base, W,
+                       H, g.bw, g.nb, flags, nullptr, block_init, nullptr, w.tile_hist, nullptr, (uint32_t)g.ncode,
+                       ImagesSrc{src.im}, w.tile_tail);
     return;
   }
-  const bool vec = W % 8 == 0 && ((uintptr_t)src.base & 7u) == 0 && (src.gray_stride & 7u) == 0;
   // one workgroup per tile (a persistent split with the next tile's rows in flight
   // measured slower: profiles/r04_v4_encoder_batch_ab.txt)
-  hipLaunchKernelGGL((vec ? enc_split_kernel<true, true, kBatchTile> : enc_split_kernel<false, true, kBatchTile>), grid,
-                     dim3(256), 0, s, src.base, W, H, bw, nb, flags, nullptr, block_init, nullptr, w.tile_hist, nullptr,
-                     (uint32_t)ncode, src.gray_stride, w.tile_tail);
+  hipLaunchKernelGGL((src.vec ? enc_split_kernel<PlanarSrc, 0, true, true, kBatchTile>
+                              : enc_split_kernel<PlanarSrc, 0, false, true, kBatchTile>),
+                     grid, dim3(256), 0, s, src.base, W, H, g.bw, g.nb, flags, nullptr, block_init, nullptr, w.tile_hist,
+                     nullptr, (uint32_t)g.ncode, PlanarSrc{src.gray_stride}, w.tile_tail);
 }
 
-void launch_pack(hipStream_t s, const Source &src, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t flags,
-                 bool init_byte, const BatchWorkspace &w, uint32_t *offsets, uint8_t *codes, uint64_t codes_stride) {
-  const uint32_t bw = (W + 7) / 8;
-  const uint64_t nb = (uint64_t)bw * ((H + 7) / 8), ncode = (nb + kBatchTile - 1) / kBatchTile;
-  const uint32_t ncode_wg = (uint32_t)((ncode + kPackWaves - 1) / kPackWaves);
+void launch_pack(hipStream_t s, const Source &src, uint32_t n_frames, uint32_t W, uint32_t H, const Geometry &g,
+                 uint32_t flags, bool init_byte, const BatchWorkspace &w, uint32_t *offsets, uint8_t *codes,
+                 uint64_t codes_stride) {
+  const uint32_t ncode_wg = (uint32_t)((g.ncode + kPackWaves - 1) / kPackWaves);
   const dim3 grid(ncode_wg * n_frames);
-  const bool vec = !src.lay && W % 8 == 0 && ((uintptr_t)src.base & 7u) == 0 && (src.gray_stride & 7u) == 0;
-  const Pixels px{src.base, W, H, bw, vec ? 1u : 0u, !(flags & MH_FLAG_NO_DELTA), init_byte};
-  if (src.lay) {
-    const ImgSrc im = image_source(*src.lay, src.n, H);
-    hipLaunchKernelGGL(MH_IMG_MODE(image_mode(src.base, im, H), enc_pack_wave_img_kernel), grid, dim3(kPackWaves * 64), 0,
-                       s, px, im, nb, (uint32_t)ncode, w.table, w.meta, w.tile_off, offsets, codes, codes_stride, ncode_wg,
-                       w.tile_tail);
+  const Pixels px{src.base, W, H, g.bw, src.vec ? 1u : 0u, !(flags & MH_FLAG_NO_DELTA), init_byte};
+  if (src.img) {
+    hipLaunchKernelGGL(MH_IMG_MODE(src.mode, enc_pack_wave_kernel, false, false), grid, dim3(kPackWaves * 64), 0, s, px,
+                       ImagesSrc{src.im}, g.nb, (uint32_t)g.ncode, w.table, w.meta, w.tile_off, offsets, codes, codes_stride,
+                       ncode_wg, w.tile_tail);
     return;
   }
-  hipLaunchKernelGGL((!vec ? enc_pack_wave_kernel<false, false>
-                           : bw % 2 ? enc_pack_wave_kernel<true, false> : enc_pack_wave_kernel<true, true>),
-                     grid, dim3(kPackWaves * 64), 0, s, px, src.gray_stride, nb, (uint32_t)ncode, w.table, w.meta,
-                     w.tile_off, offsets, codes, codes_stride, ncode_wg, w.tile_tail);
+  hipLaunchKernelGGL((!src.vec    ? enc_pack_wave_kernel<PlanarSrc, 0, false, false>
+                      : g.bw % 2 ? enc_pack_wave_kernel<PlanarSrc, 0, true, false>
+                                 : enc_pack_wave_kernel<PlanarSrc, 0, true, true>),
+                     grid, dim3(kPackWaves * 64), 0, s, px, PlanarSrc{src.gray_stride}, g.nb, (uint32_t)g.ncode, w.table,
+                     w.meta, w.tile_off, offsets, codes, codes_stride, ncode_wg, w.tile_tail);
+}
+
+// The encoder entries' flags, taken apart: the frame format the kernels take
+// (MH_FLAG_NO_DELTA), whether the caller vouches for the workspace's zeroed state, and
+// the tree kernels' own `limit` argument. False for a flag no encoder entry knows.
+struct EncodeFlags {
+  uint32_t format;
+  bool zeroed;
+  uint32_t limit;
+};
+bool split_encode_flags(uint32_t flags, EncodeFlags *f) {
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return false;
+  *f = EncodeFlags{flags & MH_FLAG_NO_DELTA, (flags & MH_ENCODE_WORKSPACE_ZEROED) != 0,
+                   (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u};
+  return true;
 }
 
 // The argument checks both batched entries and their images twins share, in the
-// documented order; on MH_OK *n_frames is the batch's frame count (images: n * C).
-int check_batch_args(const Source &src, bool img, bool have_header_arg, const void *d_codes, const void *d_block_offsets,
+// documented order. On MH_OK the call's values are set, each computed here once: the
+// flags taken apart, the geometry, src's fetch fields and *n_frames, the batch's frame
+// count (images: n * C).
+int check_batch_args(Source &src, bool have_header_arg, const void *d_codes, const void *d_block_offsets,
                      const void *d_workspace, uint32_t W, uint32_t H, uint32_t flags, uint64_t codes_frame_stride,
-                     uint32_t *n_frames) {
+                     EncodeFlags *ef, Geometry *g, uint32_t *n_frames) {
   const mh_image_layout *l = src.lay;
+  const bool img = src.img;
   if (!src.base || !have_header_arg || !d_codes || !d_block_offsets || !d_workspace || !src.n ||
       (img && (!l || !l->n_planes || l->n_planes > MH_MAX_PLANES || l->plane_major > 1)))
     return MH_ERR_INVALID_ARG;
-  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
+  if (!split_encode_flags(flags, ef)) return MH_ERR_INVALID_ARG;
   if (!W || !H || W > MH_MAX_DIM || H > MH_MAX_DIM ||
       (img && (!l->pixel_stride || (uint64_t)l->first_channel + l->n_planes > l->pixel_stride)))
     return MH_ERR_DIMS;
   if (((uintptr_t)d_codes & 15u) || (codes_frame_stride & 15u) || ((uintptr_t)d_workspace & 255u)) return MH_ERR_ALIGN;
   if (img ? !image_layout_fits(*l, src.n, W, H) : src.gray_stride < (uint64_t)W * H && src.n > 1) return MH_ERR_CAPACITY;
-  const uint64_t nb = (uint64_t)((W + 7) / 8) * ((H + 7) / 8), ncode = (nb + kBatchTile - 1) / kBatchTile;
+  *g = batch_geometry(W, H);
   const uint64_t n = (uint64_t)src.n * (img ? l->n_planes : 1u);  // < 2^34
-  if (ncode * n > 0x7FFFFFFFull || n > 0x7FFFFFFFu) return MH_ERR_CAPACITY;
+  if (g->ncode * n > 0x7FFFFFFFull || n > 0x7FFFFFFFu) return MH_ERR_CAPACITY;
   *n_frames = (uint32_t)n;
+  resolve_fetch(src, W, H);
   return MH_OK;
 }
 
@@ -2116,7 +2360,8 @@ int mh_encode_frame_device_async(const uint8_t *d_gray, uint32_t width, uint32_t
                                  int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
   if (!d_gray || !d_canon_header || !d_codes || !d_block_offsets || !d_workspace)
     return MH_ERR_INVALID_ARG;
-  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
+  EncodeFlags ef;
+  if (!split_encode_flags(flags, &ef)) return MH_ERR_INVALID_ARG;
   if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
   if (((uintptr_t)d_codes & 3u) || ((uintptr_t)d_workspace & 255u)) return MH_ERR_ALIGN;
   const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
@@ -2139,16 +2384,16 @@ int mh_encode_frame_device_async(const uint8_t *d_gray, uint32_t width, uint32_t
   // previous call's table words -- even from a stale cache line -- nor a cleared one.
   // (zeroing meta[kGen] too gave every call the same tag.)
   const size_t state_bytes = align256(kHistParts * 256 * 8) + align256(256 * 4) + kGen * 8;
-  if (!(flags & MH_ENCODE_WORKSPACE_ZEROED) && hipMemsetAsync(w.hist, 0, state_bytes, s) != hipSuccess)
-    return MH_ERR_HIP;
-  const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;  // the tree kernels' own argument
-  flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
+  if (!ef.zeroed && hipMemsetAsync(w.hist, 0, state_bytes, s) != hipSuccess) return MH_ERR_HIP;
+  const uint32_t limit = ef.limit;
+  flags = ef.format;
   const uint32_t vec = (width % 8 == 0 && ((uintptr_t)d_gray & 7u) == 0) ? 1u : 0u;
   const int path = encode_kernels();
   if (ncode <= kFusedMaxTiles && path == 2) {
     // two launches: the tiled split, then tree + offsets + packing in one kernel
-    hipLaunchKernelGGL((vec ? enc_split_kernel<true, true> : enc_split_kernel<false, true>), dim3((uint32_t)ncode),
-                       dim3(256), 0, s, d_gray, width, height, bw, nb, flags, nullptr, d_block_init, w.hist, w.tile_hist, w.meta, (uint32_t)ncode, 0ull,
+    hipLaunchKernelGGL((vec ? enc_split_kernel<PlanarSrc, 0, true, true> : enc_split_kernel<PlanarSrc, 0, false, true>),
+                       dim3((uint32_t)ncode),
+                       dim3(256), 0, s, d_gray, width, height, bw, nb, flags, nullptr, d_block_init, w.hist, w.tile_hist, w.meta, (uint32_t)ncode, PlanarSrc{0},
                        nullptr);
     const Pixels px{d_gray, width, height, bw, vec, !(flags & MH_FLAG_NO_DELTA), d_block_init != nullptr};
     hipLaunchKernelGGL(enc_code_kernel, dim3((uint32_t)ncode + 1), dim3(kCodeThreads), 0, s, w.hist,
@@ -2157,8 +2402,9 @@ int mh_encode_frame_device_async(const uint8_t *d_gray, uint32_t width, uint32_t
     return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
   }
   const uint32_t gsplit = (uint32_t)std::min<uint64_t>((nb + 31) / 32, kSplitWgs);
-  hipLaunchKernelGGL((vec ? enc_split_kernel<true, false> : enc_split_kernel<false, false>), dim3(gsplit), dim3(256), 0,
-                     s, d_gray, width, height, bw, nb, flags, w.sym, d_block_init, w.hist, nullptr, w.meta, 0u, 0ull, nullptr);
+  hipLaunchKernelGGL((vec ? enc_split_kernel<PlanarSrc, 0, true, false> : enc_split_kernel<PlanarSrc, 0, false, false>),
+                     dim3(gsplit), dim3(256), 0,
+                     s, d_gray, width, height, bw, nb, flags, w.sym, d_block_init, w.hist, nullptr, w.meta, 0u, PlanarSrc{0}, nullptr);
   hipLaunchKernelGGL(enc_tree_kernel, dim3(1), dim3(kTreeThreads), 0, s, w.hist, d_canon_header, w.table, w.meta,
                      d_codes_len, codes_cap, d_status, nb * 64, limit);
   hipLaunchKernelGGL(enc_scan_kernel, dim3((uint32_t)ntiles), dim3(kScanTile), 0, s, w.sym, w.table, nb, w.blen,
@@ -2196,38 +2442,34 @@ int mh_encode_frame_device(const uint8_t *d_gray, uint32_t width, uint32_t heigh
 }
 
 size_t mh_encode_frames_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_frames) {
-  const uint64_t nb = (uint64_t)((width + 7) / 8) * ((height + 7) / 8);
-  return (size_t)carve_batch(nullptr, nb, n_frames, nullptr);
+  return (size_t)carve_batch(nullptr, batch_geometry(width, height), n_frames, nullptr);
 }
 
-// mh_encode_frames_device_async (img = false) and mh_encode_images_device_async
-static int encode_batch(const Source &src, bool img, uint32_t width, uint32_t height, uint32_t flags,
+// mh_encode_frames_device_async and mh_encode_images_device_async (src.img)
+static int encode_batch(Source src, uint32_t width, uint32_t height, uint32_t flags,
                         uint8_t *d_canon_headers, uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
                         uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
                         int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
   uint32_t n_frames = 0;
-  const int rc = check_batch_args(src, img, d_canon_headers != nullptr, d_codes, d_block_offsets, d_workspace, width,
-                                  height, flags, codes_frame_stride, &n_frames);
+  EncodeFlags ef;
+  Geometry g;
+  const int rc = check_batch_args(src, d_canon_headers != nullptr, d_codes, d_block_offsets, d_workspace, width, height,
+                                  flags, codes_frame_stride, &ef, &g, &n_frames);
   if (rc != MH_OK) return rc;
-  const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
-  const uint64_t nb = (uint64_t)bw * bh;
-  const uint64_t ncode = (nb + kBatchTile - 1) / kBatchTile;
-  if (workspace_bytes < mh_encode_frames_workspace_bytes(width, height, n_frames)) return MH_ERR_CAPACITY;
+  if (workspace_bytes < carve_batch(nullptr, g, n_frames, nullptr)) return MH_ERR_CAPACITY;
   BatchWorkspace w;
-  carve_batch(static_cast<uint8_t *>(d_workspace), nb, n_frames, &w);
+  carve_batch(static_cast<uint8_t *>(d_workspace), g, n_frames, &w);
   hipStream_t s = (hipStream_t)stream;
   // every part of the workspace is written before it is read within the call (the tile
   // counts by the split, the tables and tile offsets by the trees): nothing to clear
-  const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;  // the tree kernels' own argument
-  flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
   // One batch, three launches: splitting the call into sub-batches alternated over a second
   // stream (trees beside another sub-batch's split / packing) measured slower, and the
   // packer's pixel re-reads did not drop (profiles/r04_v4_encoder_batch_ab.txt).
-  launch_split(s, src, n_frames, width, height, flags, d_block_init, w);
+  launch_split(s, src, n_frames, width, height, g, ef.format, d_block_init, w);
   hipLaunchKernelGGL(enc_tree_batch_kernel, dim3(n_frames), dim3(kTreeThreads), 0, s, nullptr, d_canon_headers, w.table,
-                     w.meta, d_codes_len, codes_frame_stride, d_status, nb, w.tile_hist, (uint32_t)ncode, w.tile_off,
-                     d_frame_code_offsets, 0u, n_frames, limit);
-  launch_pack(s, src, n_frames, width, height, flags, d_block_init != nullptr, w, d_block_offsets, d_codes,
+                     w.meta, d_codes_len, codes_frame_stride, d_status, g.nb, w.tile_hist, (uint32_t)g.ncode, w.tile_off,
+                     d_frame_code_offsets, 0u, n_frames, ef.limit);
+  launch_pack(s, src, n_frames, width, height, g, ef.format, d_block_init != nullptr, w, d_block_offsets, d_codes,
               codes_frame_stride);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
@@ -2237,7 +2479,7 @@ int mh_encode_frames_device_async(const uint8_t *d_gray, uint64_t gray_frame_str
                                   uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
                                   uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
                                   int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
-  return encode_batch(Source{d_gray, gray_frame_stride, nullptr, n_frames}, false, width, height, flags, d_canon_headers,
+  return encode_batch(Source{d_gray, gray_frame_stride, nullptr, n_frames, false}, width, height, flags, d_canon_headers,
                       d_codes, codes_frame_stride, d_codes_len, d_frame_code_offsets, d_block_offsets, d_block_init,
                       d_status, d_workspace, workspace_bytes, stream);
 }
@@ -2252,59 +2494,53 @@ int mh_encode_images_device_async(const uint8_t *d_pixels, const mh_image_layout
                                   uint8_t *d_codes, uint64_t codes_frame_stride, uint64_t *d_codes_len,
                                   uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
                                   int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
-  return encode_batch(Source{d_pixels, 0, layout, n_images}, true, width, height, flags, d_canon_headers, d_codes,
+  return encode_batch(Source{d_pixels, 0, layout, n_images, true}, width, height, flags, d_canon_headers, d_codes,
                       codes_frame_stride, d_codes_len, d_frame_code_offsets, d_block_offsets, d_block_init, d_status,
                       d_workspace, workspace_bytes, stream);
 }
 
 size_t mh_encode_frames_shared_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_frames) {
-  const uint64_t nb = (uint64_t)((width + 7) / 8) * ((height + 7) / 8);
-  return (size_t)carve_shared(nullptr, nb, n_frames, nullptr);
+  return (size_t)carve_shared(nullptr, batch_geometry(width, height), n_frames, nullptr);
 }
 
-// mh_encode_frames_shared_device_async (img = false) and mh_encode_images_shared_device_async
-static int encode_batch_shared(const Source &src, bool img, uint32_t width, uint32_t height, uint32_t flags,
+// mh_encode_frames_shared_device_async and mh_encode_images_shared_device_async (src.img)
+static int encode_batch_shared(Source src, uint32_t width, uint32_t height, uint32_t flags,
                                const uint8_t *d_canon_in, uint8_t *d_canon_header, uint8_t *d_codes,
                                uint64_t codes_frame_stride, uint64_t *d_codes_len, uint64_t *d_frame_code_offsets,
                                uint32_t *d_block_offsets, uint8_t *d_block_init, int32_t *d_status,
                                int32_t *d_header_status, void *d_workspace, size_t workspace_bytes, void *stream) {
   // the checks of mh_encode_frames_device_async, in its order; every one before any HIP call
   uint32_t n_frames = 0;
-  const int rc = check_batch_args(src, img, d_canon_in || d_canon_header, d_codes, d_block_offsets, d_workspace, width,
-                                  height, flags, codes_frame_stride, &n_frames);
+  EncodeFlags ef;
+  Geometry g;
+  const int rc = check_batch_args(src, d_canon_in || d_canon_header, d_codes, d_block_offsets, d_workspace, width, height,
+                                  flags, codes_frame_stride, &ef, &g, &n_frames);
   if (rc != MH_OK) return rc;
-  const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
-  const uint64_t nb = (uint64_t)bw * bh;
-  const uint64_t ncode = (nb + kBatchTile - 1) / kBatchTile;
   // built mode: the tree's node weights are u32 (tree_body), so the batch holds fewer than
   // 2^32 symbols (1,365 frames of 2048 x 1536); its bit total has no such limit
-  const uint64_t nsym = (uint64_t)n_frames * nb * 64;  // < 2^31 x 2^26 x 2^6
+  const uint64_t nsym = (uint64_t)n_frames * g.nb * 64;  // < 2^31 x 2^26 x 2^6
   if (!d_canon_in && nsym >= (1ull << 32)) return MH_ERR_CAPACITY;
-  if (workspace_bytes < mh_encode_frames_shared_workspace_bytes(width, height, n_frames)) return MH_ERR_CAPACITY;
+  if (workspace_bytes < carve_shared(nullptr, g, n_frames, nullptr)) return MH_ERR_CAPACITY;
   SharedWorkspace w;
-  carve_shared(static_cast<uint8_t *>(d_workspace), nb, n_frames, &w);
+  carve_shared(static_cast<uint8_t *>(d_workspace), g, n_frames, &w);
   hipStream_t s = (hipStream_t)stream;
   // only the partial histograms carry state from call to call (the tree leaves them zeroed)
-  if (!d_canon_in && !(flags & MH_ENCODE_WORKSPACE_ZEROED) &&
-      hipMemsetAsync(w.hist, 0, kHistParts * 256 * 8, s) != hipSuccess)
-    return MH_ERR_HIP;
-  const uint32_t limit = (flags & MH_ENCODE_LIMIT_LENGTHS) ? 1u : 0u;
-  flags &= ~(MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS);
+  if (!d_canon_in && !ef.zeroed && hipMemsetAsync(w.hist, 0, kHistParts * 256 * 8, s) != hipSuccess) return MH_ERR_HIP;
   // the split and the packer: mh_encode_frames_device_async's launches
-  launch_split(s, src, n_frames, width, height, flags, d_block_init, w.b);
+  launch_split(s, src, n_frames, width, height, g, ef.format, d_block_init, w.b);
   if (d_canon_in) {
     hipLaunchKernelGGL(enc_header_table_kernel, dim3(1), dim3(256), 0, s, d_canon_in, d_canon_header, w.table, w.meta);
   } else {
-    const uint32_t nchunk = (uint32_t)((ncode + kReduceTiles - 1) / kReduceTiles);
-    hipLaunchKernelGGL(enc_hist_reduce_kernel, dim3(nchunk * n_frames), dim3(256), 0, s, w.b.tile_hist, (uint32_t)ncode,
+    const uint32_t nchunk = (uint32_t)((g.ncode + kReduceTiles - 1) / kReduceTiles);
+    hipLaunchKernelGGL(enc_hist_reduce_kernel, dim3(nchunk * n_frames), dim3(256), 0, s, w.b.tile_hist, (uint32_t)g.ncode,
                        nchunk, w.hist);
     hipLaunchKernelGGL(enc_tree_shared_kernel, dim3(1), dim3(kTreeThreads), 0, s, w.hist, d_canon_header, w.table,
-                       w.meta, nsym, limit);
+                       w.meta, nsym, ef.limit);
   }
   hipLaunchKernelGGL(enc_plan_shared_kernel, dim3(n_frames), dim3(kTreeThreads), 0, s, w.table, w.meta, w.b.table,
-                     w.b.meta, d_codes_len, codes_frame_stride, d_status, d_header_status, nb, w.b.tile_hist,
-                     (uint32_t)ncode, w.b.tile_off, d_frame_code_offsets, n_frames);
-  launch_pack(s, src, n_frames, width, height, flags, d_block_init != nullptr, w.b, d_block_offsets, d_codes,
+                     w.b.meta, d_codes_len, codes_frame_stride, d_status, d_header_status, g.nb, w.b.tile_hist,
+                     (uint32_t)g.ncode, w.b.tile_off, d_frame_code_offsets, n_frames);
+  launch_pack(s, src, n_frames, width, height, g, ef.format, d_block_init != nullptr, w.b, d_block_offsets, d_codes,
               codes_frame_stride);
   return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
@@ -2316,7 +2552,7 @@ int mh_encode_frames_shared_device_async(const uint8_t *d_gray, uint64_t gray_fr
                                          uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets,
                                          uint8_t *d_block_init, int32_t *d_status, int32_t *d_header_status,
                                          void *d_workspace, size_t workspace_bytes, void *stream) {
-  return encode_batch_shared(Source{d_gray, gray_frame_stride, nullptr, n_frames}, false, width, height, flags, d_canon_in,
+  return encode_batch_shared(Source{d_gray, gray_frame_stride, nullptr, n_frames, false}, width, height, flags, d_canon_in,
                              d_canon_header, d_codes, codes_frame_stride, d_codes_len, d_frame_code_offsets,
                              d_block_offsets, d_block_init, d_status, d_header_status, d_workspace, workspace_bytes,
                              stream);
@@ -2334,7 +2570,7 @@ int mh_encode_images_shared_device_async(const uint8_t *d_pixels, const mh_image
                                          uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets,
                                          uint8_t *d_block_init, int32_t *d_status, int32_t *d_header_status,
                                          void *d_workspace, size_t workspace_bytes, void *stream) {
-  return encode_batch_shared(Source{d_pixels, 0, layout, n_images}, true, width, height, flags, d_canon_in,
+  return encode_batch_shared(Source{d_pixels, 0, layout, n_images, true}, width, height, flags, d_canon_in,
                              d_canon_header, d_codes, codes_frame_stride, d_codes_len, d_frame_code_offsets,
                              d_block_offsets, d_block_init, d_status, d_header_status, d_workspace, workspace_bytes,
                              stream);

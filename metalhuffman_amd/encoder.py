@@ -18,7 +18,7 @@ import torch
 
 from . import _native as N
 from .codec import block_grid
-from .decoder import DeviceFrames, _dev, _stream_ptr
+from .decoder import DeviceFrames, _dev, _header_tensor, _stream_ptr
 
 
 def _limit(limit_lengths: bool) -> int:
@@ -45,6 +45,13 @@ class DeviceEncodedFrame:
                             self.block_init, self.flags, self.payload_bytes)
 
 
+def _workspace_ptr(workspace: torch.Tensor) -> tuple:
+    """(the workspace's first 256-byte aligned address, the bytes from there to its end)."""
+    base = workspace.data_ptr()
+    aligned = (base + 255) // 256 * 256
+    return aligned, workspace.numel() - (aligned - base)
+
+
 class Encoder:
     """Reusable device workspace + output buffers for frames of one size. Calls on
     one stream queue up behind each other; frames in flight on several streams need
@@ -61,26 +68,27 @@ class Encoder:
         self.workspace = torch.zeros(ws + 256, dtype=torch.uint8, device=self.device)
         self.cap = (self.nb * 64 * 2 + N.MH_CODES_PAD + 3) // 4 * 4 + 16
 
+    def _check_gray(self, gray: torch.Tensor) -> None:
+        if gray.dtype != torch.uint8 or gray.shape != (self.height, self.width) or not gray.is_contiguous():
+            raise ValueError(f"gray must be contiguous uint8 [{self.height}, {self.width}]")
+
     def encode(self, gray: torch.Tensor, flags: int = 0, init_zero_delta: bool = False,
                stream: Optional[torch.cuda.Stream] = None, limit_lengths: bool = False) -> DeviceEncodedFrame:
         """limit_lengths (here and in encode_async): a tree deeper than 16 gets the
         length-limited code on the device (MH_ENCODE_LIMIT_LENGTHS) instead of status -3.
         The keyword goes to the encoder only, never into the frame's `flags`."""
-        if gray.dtype != torch.uint8 or gray.shape != (self.height, self.width) or not gray.is_contiguous():
-            raise ValueError(f"gray must be contiguous uint8 [{self.height}, {self.width}]")
+        self._check_gray(gray)
         gray = gray.to(self.device)
         codes = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
         offs = torch.empty(self.nb, dtype=torch.int32, device=self.device)
         init = torch.empty(self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
         canon = np.zeros(256, np.uint8)
         n = ctypes.c_uint64(0)
-        base = self.workspace.data_ptr()
-        aligned = (base + 255) // 256 * 256
         N.check(N.lib().mh_encode_frame_device(
             gray.data_ptr(), self.width, self.height, flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
             canon.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), codes.data_ptr(), self.cap,
             ctypes.byref(n), offs.data_ptr(), init.data_ptr() if init is not None else None,
-            aligned, self.workspace.numel() - (aligned - base), _stream_ptr(stream, self.device)),
+            *_workspace_ptr(self.workspace), _stream_ptr(stream, self.device)),
             "mh_encode_frame_device")
         return DeviceEncodedFrame(self.width, self.height, canon, codes[: n.value], offs, init, flags)
 
@@ -91,8 +99,7 @@ class Encoder:
         at once. `gray` must be ready on that stream (make it wait on the stream
         that produced the frame). `codes` may be a reused u8 buffer of at least the
         encoder's capacity (the default allocates one)."""
-        if gray.dtype != torch.uint8 or gray.shape != (self.height, self.width) or not gray.is_contiguous():
-            raise ValueError(f"gray must be contiguous uint8 [{self.height}, {self.width}]")
+        self._check_gray(gray)
         if gray.device != self.device:
             raise ValueError("gray must live on the encoder's device")
         # outputs belong to the stream the kernels run on (the caching allocator must
@@ -106,13 +113,11 @@ class Encoder:
             meta = torch.empty(2, dtype=torch.int64, device=self.device)   # [codes_len, status]
         if codes.dtype != torch.uint8 or codes.device != self.device or codes.numel() < 4:
             raise ValueError("codes must be a uint8 buffer on the encoder's device")
-        base = self.workspace.data_ptr()
-        aligned = (base + 255) // 256 * 256
         N.check(N.lib().mh_encode_frame_device_async(
             gray.data_ptr(), self.width, self.height, flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
             canon.data_ptr(), codes.data_ptr(),
             codes.numel(), meta.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None,
-            meta.data_ptr() + 8, aligned, self.workspace.numel() - (aligned - base),
+            meta.data_ptr() + 8, *_workspace_ptr(self.workspace),
             _stream_ptr(stream, self.device)), "mh_encode_frame_device_async")
         return AsyncEncodedFrame(self.width, self.height, canon, codes, meta[0:1],
                                  meta[1:2].view(torch.int32)[0:1], offs, init, flags)
@@ -172,37 +177,55 @@ class BatchEncoder:
         self.workspace = torch.zeros(ws + 256, dtype=torch.uint8, device=self.device)
         self.slot = (self.nb * 64 * 2 + N.MH_CODES_PAD + 15) // 16 * 16 + 16
 
-    def encode_async(self, grays: torch.Tensor, flags: int = 0, init_zero_delta: bool = False,
-                     stream: Optional[torch.cuda.Stream] = None, limit_lengths: bool = False) -> "AsyncEncodedBatch":
-        """grays: contiguous uint8 [n, H, W] on the encoder's device, ready on `stream`.
-        limit_lengths: frames whose tree is deeper than 16 get the length-limited code
-        (MH_ENCODE_LIMIT_LENGTHS) instead of status -3; the batch's `flags` do not carry it."""
+    def _encode_batch(self, entry: str, source: tuple, *, shared: bool, header, flags: int, init_zero_delta: bool,
+                      stream: Optional[torch.cuda.Stream], limit_lengths: bool,
+                      plane_fields: tuple = (1, 1)) -> "AsyncEncodedBatch":
+        """The four methods' body: the outputs (allocated on the stream the kernels run on), the
+        call of library entry `entry`, whose first arguments are `source`, and the batch.
+        shared: one table (`header`: None to build it, else 256 code lengths, a device tensor or
+        a host array); plane_fields: the batch's (n_planes, plane_frame_stride)."""
+        n, dev = self.n, self.device
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=dev)
+            offs = torch.empty(n * self.nb, dtype=torch.int32, device=dev)
+            init = torch.empty(n * self.nb, dtype=torch.uint8, device=dev) if init_zero_delta else None
+            canon = torch.empty(256 if shared else (n, 256), dtype=torch.uint8, device=dev)
+            lens = torch.empty(n, dtype=torch.int64, device=dev)
+            fco = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            status = torch.empty(n + 1 if shared else n, dtype=torch.int32, device=dev)  # shared, [n]: the header's verdict
+            canon_in = _header_tensor(header, dev) if header is not None else None
+            if canon_in is not None and canon_in.numel() != 256:
+                raise ValueError("header must hold 256 code lengths")
+        cbase = (codes.data_ptr() + 15) // 16 * 16
+        tables = (canon_in.data_ptr() if canon_in is not None else None, canon.data_ptr()) if shared else (canon.data_ptr(),)
+        verdicts = (status.data_ptr(), status.data_ptr() + 4 * n) if shared else (status.data_ptr(),)
+        N.check(getattr(N.lib(), entry)(
+            *source, self.width, self.height, flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths), *tables,
+            cbase, self.slot, lens.data_ptr(), fco.data_ptr(), offs.data_ptr(),
+            init.data_ptr() if init is not None else None, *verdicts, *_workspace_ptr(self.workspace),
+            _stream_ptr(stream, dev)), entry)
+        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
+        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status[:n], offs, init,
+                                 flags, shared=shared, header_status=status[n:] if shared else None,
+                                 n_planes=plane_fields[0], plane_frame_stride=plane_fields[1])
+
+    def _check_grays(self, grays: torch.Tensor) -> tuple:
+        """The frames methods' input check -> the entries' first arguments."""
         if (grays.dtype != torch.uint8 or tuple(grays.shape) != (self.n, self.height, self.width)
                 or not grays.is_contiguous()):
             raise ValueError(f"grays must be contiguous uint8 [{self.n}, {self.height}, {self.width}]")
         if grays.device != self.device:
             raise ValueError("grays must live on the encoder's device")
-        n = self.n
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=self.device)
-            offs = torch.empty(n * self.nb, dtype=torch.int32, device=self.device)
-            init = torch.empty(n * self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
-            canon = torch.empty((n, 256), dtype=torch.uint8, device=self.device)
-            lens = torch.empty(n, dtype=torch.int64, device=self.device)
-            fco = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            status = torch.empty(n, dtype=torch.int32, device=self.device)
-        cbase = (codes.data_ptr() + 15) // 16 * 16
-        base = self.workspace.data_ptr()
-        aligned = (base + 255) // 256 * 256
-        N.check(N.lib().mh_encode_frames_device_async(
-            grays.data_ptr(), self.height * self.width, n, self.width, self.height,
-            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths), canon.data_ptr(), cbase, self.slot, lens.data_ptr(),
-            fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None, status.data_ptr(),
-            aligned, self.workspace.numel() - (aligned - base), _stream_ptr(stream, self.device)),
-            "mh_encode_frames_device_async")
-        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
-        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status, offs,
-                                 init, flags)
+        return grays.data_ptr(), self.height * self.width, self.n
+
+    def encode_async(self, grays: torch.Tensor, flags: int = 0, init_zero_delta: bool = False,
+                     stream: Optional[torch.cuda.Stream] = None, limit_lengths: bool = False) -> "AsyncEncodedBatch":
+        """grays: contiguous uint8 [n, H, W] on the encoder's device, ready on `stream`.
+        limit_lengths: frames whose tree is deeper than 16 get the length-limited code
+        (MH_ENCODE_LIMIT_LENGTHS) instead of status -3; the batch's `flags` do not carry it."""
+        return self._encode_batch("mh_encode_frames_device_async", self._check_grays(grays), shared=False, header=None,
+                                  flags=flags, init_zero_delta=init_zero_delta, stream=stream,
+                                  limit_lengths=limit_lengths)
 
     def encode_shared_async(self, grays: torch.Tensor, header=None, flags: int = 0, init_zero_delta: bool = False,
                             stream: Optional[torch.cuda.Stream] = None,
@@ -216,45 +239,15 @@ class BatchEncoder:
         is marked `shared`: `canon` is the one header (u8[256] on the device),
         `header_status` its verdict (int32[1] on the device), `status` the per-frame words
         (-5 for a frame that holds a symbol the header has no code for)."""
-        if (grays.dtype != torch.uint8 or tuple(grays.shape) != (self.n, self.height, self.width)
-                or not grays.is_contiguous()):
-            raise ValueError(f"grays must be contiguous uint8 [{self.n}, {self.height}, {self.width}]")
-        if grays.device != self.device:
-            raise ValueError("grays must live on the encoder's device")
-        n = self.n
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=self.device)
-            offs = torch.empty(n * self.nb, dtype=torch.int32, device=self.device)
-            init = torch.empty(n * self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
-            canon = torch.empty(256, dtype=torch.uint8, device=self.device)
-            lens = torch.empty(n, dtype=torch.int64, device=self.device)
-            fco = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            status = torch.empty(n + 1, dtype=torch.int32, device=self.device)  # [n]: the header's verdict
-            canon_in = None
-            if header is not None:
-                if isinstance(header, torch.Tensor):
-                    canon_in = header.to(self.device, torch.uint8).contiguous()
-                else:
-                    canon_in = torch.from_numpy(np.ascontiguousarray(header, np.uint8)).to(self.device)
-                if canon_in.numel() != 256:
-                    raise ValueError("header must hold 256 code lengths")
-        cbase = (codes.data_ptr() + 15) // 16 * 16
-        base = self.workspace.data_ptr()
-        aligned = (base + 255) // 256 * 256
-        N.check(N.lib().mh_encode_frames_shared_device_async(
-            grays.data_ptr(), self.height * self.width, n, self.width, self.height,
-            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
-            canon_in.data_ptr() if canon_in is not None else None, canon.data_ptr(), cbase, self.slot,
-            lens.data_ptr(), fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None,
-            status.data_ptr(), status.data_ptr() + 4 * n, aligned, self.workspace.numel() - (aligned - base),
-            _stream_ptr(stream, self.device)), "mh_encode_frames_shared_device_async")
-        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
-        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status[:n], offs,
-                                 init, flags, True, status[n:])
+        return self._encode_batch("mh_encode_frames_shared_device_async", self._check_grays(grays), shared=True,
+                                  header=header, flags=flags, init_zero_delta=init_zero_delta, stream=stream,
+                                  limit_lengths=limit_lengths)
 
     def _image_layout(self, images: torch.Tensor, plane_major: bool, first_channel: int, n_planes):
-        """The mh_image_layout of a uint8 [n, H, W, K] tensor with channel stride 1 and any other
-        strides (a window of a larger batch, RGB of RGBA, padded rows), and its image count."""
+        """The images methods' input check -> the entries' first arguments -- the address, the
+        mh_image_layout of a uint8 [n, H, W, K] tensor with channel stride 1 and any other strides (a
+        window of a larger batch, RGB of RGBA, padded rows) and the image count -- and the batch's
+        (n_planes, plane_frame_stride)."""
         if images.dtype != torch.uint8 or images.dim() != 4:
             raise ValueError("images must be a uint8 tensor [n, H, W, K]")
         n, h, w, k = images.shape
@@ -270,7 +263,8 @@ class BatchEncoder:
         # a dimension of size 1 may carry any stride: the library ignores the image stride and the
         # row pitch there, and a one-pixel row needs a pixel stride that holds its channels
         ps = images.stride(2) if w > 1 else max(images.stride(2), k)
-        return N.mh_image_layout(images.stride(0), images.stride(1), ps, first_channel, c, 1 if plane_major else 0), n, c
+        lay = N.mh_image_layout(images.stride(0), images.stride(1), ps, first_channel, c, 1 if plane_major else 0)
+        return (images.data_ptr(), ctypes.byref(lay), n), (c, n if plane_major else 1)
 
     def encode_images_async(self, images: torch.Tensor, plane_major: bool = False, first_channel: int = 0,
                             n_planes=None, flags: int = 0, init_zero_delta: bool = False,
@@ -283,28 +277,10 @@ class BatchEncoder:
         frame i * C + c, or c * n + i with plane_major; each is byte-identical to codec.encode_frame
         of codec.image_planes(images, ...)[frame]. The batch carries n_planes and
         plane_frame_stride for decoder.decode_crops_normalized_planes."""
-        lay, n_img, c = self._image_layout(images, plane_major, first_channel, n_planes)
-        n = self.n
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=self.device)
-            offs = torch.empty(n * self.nb, dtype=torch.int32, device=self.device)
-            init = torch.empty(n * self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
-            canon = torch.empty((n, 256), dtype=torch.uint8, device=self.device)
-            lens = torch.empty(n, dtype=torch.int64, device=self.device)
-            fco = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            status = torch.empty(n, dtype=torch.int32, device=self.device)
-        cbase = (codes.data_ptr() + 15) // 16 * 16
-        base = self.workspace.data_ptr()
-        aligned = (base + 255) // 256 * 256
-        N.check(N.lib().mh_encode_images_device_async(
-            images.data_ptr(), ctypes.byref(lay), n_img, self.width, self.height,
-            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths), canon.data_ptr(), cbase, self.slot, lens.data_ptr(),
-            fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None, status.data_ptr(),
-            aligned, self.workspace.numel() - (aligned - base), _stream_ptr(stream, self.device)),
-            "mh_encode_images_device_async")
-        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
-        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status, offs,
-                                 init, flags, n_planes=c, plane_frame_stride=n_img if plane_major else 1)
+        source, plane_fields = self._image_layout(images, plane_major, first_channel, n_planes)
+        return self._encode_batch("mh_encode_images_device_async", source, shared=False, header=None, flags=flags,
+                                  init_zero_delta=init_zero_delta, stream=stream, limit_lengths=limit_lengths,
+                                  plane_fields=plane_fields)
 
     def encode_images_shared_async(self, images: torch.Tensor, header=None, plane_major: bool = False,
                                    first_channel: int = 0, n_planes=None, flags: int = 0,
@@ -315,38 +291,10 @@ class BatchEncoder:
         their summed histogram (header=None: codec.shared_header of codec.image_planes(images, ...))
         or supplied. `images`, the frame order and the batch's plane fields as in
         encode_images_async; `header` and the result as in encode_shared_async."""
-        lay, n_img, c = self._image_layout(images, plane_major, first_channel, n_planes)
-        n = self.n
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            codes = torch.empty(n * self.slot + 16, dtype=torch.uint8, device=self.device)
-            offs = torch.empty(n * self.nb, dtype=torch.int32, device=self.device)
-            init = torch.empty(n * self.nb, dtype=torch.uint8, device=self.device) if init_zero_delta else None
-            canon = torch.empty(256, dtype=torch.uint8, device=self.device)
-            lens = torch.empty(n, dtype=torch.int64, device=self.device)
-            fco = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            status = torch.empty(n + 1, dtype=torch.int32, device=self.device)  # [n]: the header's verdict
-            canon_in = None
-            if header is not None:
-                if isinstance(header, torch.Tensor):
-                    canon_in = header.to(self.device, torch.uint8).contiguous()
-                else:
-                    canon_in = torch.from_numpy(np.ascontiguousarray(header, np.uint8)).to(self.device)
-                if canon_in.numel() != 256:
-                    raise ValueError("header must hold 256 code lengths")
-        cbase = (codes.data_ptr() + 15) // 16 * 16
-        base = self.workspace.data_ptr()
-        aligned = (base + 255) // 256 * 256
-        N.check(N.lib().mh_encode_images_shared_device_async(
-            images.data_ptr(), ctypes.byref(lay), n_img, self.width, self.height,
-            flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths),
-            canon_in.data_ptr() if canon_in is not None else None, canon.data_ptr(), cbase, self.slot,
-            lens.data_ptr(), fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None,
-            status.data_ptr(), status.data_ptr() + 4 * n, aligned, self.workspace.numel() - (aligned - base),
-            _stream_ptr(stream, self.device)), "mh_encode_images_shared_device_async")
-        view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + n * self.slot]
-        return AsyncEncodedBatch(self.width, self.height, n, self.slot, canon, view, lens, fco, status[:n], offs,
-                                 init, flags, True, status[n:], n_planes=c,
-                                 plane_frame_stride=n_img if plane_major else 1)
+        source, plane_fields = self._image_layout(images, plane_major, first_channel, n_planes)
+        return self._encode_batch("mh_encode_images_shared_device_async", source, shared=True, header=header,
+                                  flags=flags, init_zero_delta=init_zero_delta, stream=stream,
+                                  limit_lengths=limit_lengths, plane_fields=plane_fields)
 
 
 @dataclasses.dataclass

@@ -93,12 +93,20 @@ def listings(lib_path: str) -> dict:
     return listings_of(disasm(lib_path))
 
 
-def compare(old_lib: str, new_lib: str) -> tuple:
-    """(symbols only in old, symbols only in new, symbols in both whose listings differ, symbols equal)."""
-    old, new = listings(old_lib), listings(new_lib)
+def compare_listings(old: dict, new: dict, renames=None) -> tuple:
+    """compare() of two listings_of results. renames {old symbol: new symbol}: kernels whose symbol
+    changed (other template parameters) are compared under, and reported by, their new symbol."""
+    renames = renames or {}
+    old = {renames.get(k, k): v for k, v in old.items()}
     both = sorted(old.keys() & new.keys())
     return (sorted(old.keys() - new.keys()), sorted(new.keys() - old.keys()),
             [k for k in both if old[k] != new[k]], [k for k in both if old[k] == new[k]])
+
+
+def compare(old_lib: str, new_lib: str, renames=None) -> tuple:
+    """(symbols only in old, symbols only in new, symbols in both whose listings differ, symbols equal);
+    renames as for compare_listings."""
+    return compare_listings(listings(old_lib), listings(new_lib), renames)
 
 
 def _metadata(lib_path: str, fields) -> dict:

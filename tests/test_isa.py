@@ -71,6 +71,19 @@ def test_listings_keep_register_numbers():
     assert a["k_one"] != b["k_one"] and a["k_two"] == b["k_two"]
 
 
+def test_compare_pairs_renamed_symbols():
+    """A rename map pairs a kernel whose symbol changed with its successor: an equal listing is equal
+    under the new name, a changed one differs under it, and an unmapped old symbol stays unpaired."""
+    from metalhuffman_amd.isa_guard import compare_listings, listings_of
+    old = listings_of(_listing(0x1900))
+    new = {"k_one_v2": list(old["k_one"]), "k_two": list(old["k_two"])}
+    assert compare_listings(old, new) == (["k_one"], ["k_one_v2"], [], ["k_two"])
+    assert compare_listings(old, new, {"k_one": "k_one_v2"}) == ([], [], [], ["k_one_v2", "k_two"])
+    new["k_one_v2"][2] = "v_add_u32_e32 v3, v1, v2"
+    assert compare_listings(old, new, {"k_one": "k_one_v2"}) == ([], [], ["k_one_v2"], ["k_two"])
+    assert compare_listings(old, new, {"k_two": "k_one_v2"}) == (["k_one"], ["k_two"], ["k_one_v2"], [])
+
+
 def _disasm(lib_path):
     return _tools().disasm(lib_path)
 
