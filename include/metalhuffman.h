@@ -716,6 +716,97 @@ int mh_decode_crops_norm_planes_shape(const mh_frame *frame, uint32_t n_crops, u
                                       uint32_t format, uint32_t n_planes, void *stream,
                                       uint32_t *groups_per_plane, uint32_t *waves_per_group);
 
+/* ---------------------------------------------------------------------- */
+/* Crops from a SET of frames of different sizes in one launch. An mh_frame is a batch of frames   */
+/* of one size, and no image dataset is one size: a caller with K sizes kept K batches, sorted     */
+/* every sampled batch by size and made K launches into scattered slots of one tensor -- K times   */
+/* the cost of a whole batch, since at a loader's batch sizes the launch is the cost. A frame set  */
+/* is n frames, each with its own width, height and table; the two entries below decode crops of   */
+/* any mix of them in one launch, through the bodies of mh_decode_crops and                        */
+/* mh_decode_crops_norm_planes.                                                                    */
+/* Not covered: a set for the frame, region, window and scaled entries; mh_check_frames over a set */
+/* (a caller checks per size group and scatters the verdicts into one d_frame_status); sets in the */
+/* streams and the multi-GPU paths; a set encoder.                                                 */
+typedef struct {
+  uint32_t first_block;   /* index of the frame's block 0 in d_block_offsets / d_block_init */
+  uint32_t width, height; /* pixels, 1..65535 */
+  uint32_t reserved;      /* must be 0 */
+} mh_frame_geom;          /* 16 bytes */
+
+/* A set is an mh_frame read under these rules. n_frames frames; frame f is W_f x H_f =
+ * d_geoms[f].width x .height pixels and NB_f = ceil(W_f / 8) * ceil(H_f / 8) blocks.
+ * d_block_offsets and d_block_init (optional) hold total_blocks entries, frame f's at
+ * [first_block_f, first_block_f + NB_f); frames may lie in any order and may share entries.
+ * d_frame_code_offsets, d_codes and codes_bytes are as for every batch: frame f's codes are its own
+ * 16-byte aligned slot, and its block offsets are bits from that slot's start.
+ * dims.width and dims.height carry the LARGEST width and height in the set (1..65535);
+ * dims.block_width and dims.block_height are ignored. Table fields and flags are as for
+ * mh_decode_crops: the in-frame tables are ignored, MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER only.
+ * d_geoms is a DEVICE array of n_frames records, 16-byte aligned, never read on the host. The
+ * records are the packer's, not a sampler's; the device checks them all the same, so that a stale
+ * or corrupt record cannot move a read outside d_block_offsets or a store outside the crop's slot.
+ *
+ * mh_decode_set_crops is mh_decode_crops' contract over a set: descriptors (mh_crop), the output
+ * layout, what is written and what is unspecified, d_crop_status' semantics and precedence, the
+ * aliasing rule, tables addressed by the crop's frame number (d_luts + frame * lut_stride_bytes, 0
+ * for one shared table), d_frame_status indexed by the frame number, and the tiles (CBH, S, G) are
+ * all that entry's, with W_f x H_f in the place of W x H.
+ * Device validation, by each of the crop's workgroups, in this order, each step passing before
+ * anything is addressed through what it validates:
+ *  1. the descriptor's own words: frame >= n_frames or reserved != 0 reject the crop;
+ *  2. only then d_geoms[frame] is loaded: reserved != 0, width or height 0 or above 65535,
+ *     NB > total_blocks or first_block > total_blocks - NB (formed in that order: nothing wraps)
+ *     reject it;
+ *  3. w > W_f or h > H_f reject it; only then x0 > W_f - w or y0 > H_f - h do.
+ * A rejected crop gets MH_ERR_DIMS in d_crop_status[p], loads nothing further and writes no byte of
+ * the raster; the others are decoded.
+ * Checks: all before any HIP call, in mh_decode_crops' order and with its codes, except that w > W
+ * and h > H are taken against dims, the set's maxima (a crop larger than its own frame is rejected
+ * on the device), plus, reported where a NULL d_crops / its alignment is: NULL d_geoms or
+ * total_blocks == 0 -> MH_ERR_INVALID_ARG; d_geoms not 16-byte aligned -> MH_ERR_ALIGN.
+ * One kernel launch, asynchronous on `stream`: every workgroup makes one more dependent 16-byte
+ * load than mh_decode_crops' (the geometry record, behind the descriptor). */
+int mh_decode_set_crops(const mh_frame *frame, const mh_frame_geom *d_geoms, uint32_t total_blocks,
+                        const mh_crop *d_crops, uint32_t n_crops, uint32_t w, uint32_t h,
+                        const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                        const int32_t *d_frame_status, int32_t *d_crop_status, uint8_t *d_out,
+                        size_t out_pitch, size_t out_crop_stride, void *stream);
+
+/* The launch shape mh_decode_set_crops would use on `stream`'s device (no launch), as
+ * mh_decode_crops_shape with dims the set's maxima: G depends on the crop size and the device only. */
+int mh_decode_set_crops_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, uint32_t h,
+                              void *stream, uint32_t *groups_per_crop, uint32_t *waves_per_group);
+
+/* mh_decode_crops_norm_planes' contract over a set (above): its argument list with d_geoms and
+ * total_blocks behind `frame`, descriptors of type mh_norm_crop, and with n_planes == 1 the plain
+ * normalised crops (mh_decode_crops_norm with scale[0], bias[0]) over a set.
+ * Device validation, by each of the sample's workgroups, in this order:
+ *  1. the descriptor's words: frame > n_frames - 1 - (n_planes - 1) * plane_frame_stride (from the
+ *     host) or a flag bit other than MH_CROP_MIRROR reject the sample;
+ *  2. only then the geometry records of ALL the sample's n_planes frames are loaded, each is
+ *     judged as in mh_decode_set_crops' step 2, and every plane's (width, height) must equal
+ *     plane 0's: a sample is written whole or not at all, so each of its workgroups reaches the
+ *     same verdict from the same records;
+ *  3. w > W_f or h > H_f; then x0 > W_f - w, y0 > H_f - h, or MH_CROP_MIRROR with w % 8 != 0.
+ * A rejected sample gets MH_ERR_DIMS in d_crop_status[p] and no byte of any of its planes is
+ * written. Status words, precedence and everything else: mh_decode_crops_norm_planes'.
+ * Checks: that entry's, with the differences and additions listed for mh_decode_set_crops. */
+int mh_decode_set_crops_norm_planes(const mh_frame *frame, const mh_frame_geom *d_geoms,
+                                    uint32_t total_blocks, const mh_norm_crop *d_crops, uint32_t n_crops,
+                                    uint32_t w, uint32_t h, uint32_t format,
+                                    uint32_t n_planes, uint32_t plane_frame_stride,
+                                    const float *scale, const float *bias,
+                                    const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                                    const int32_t *d_frame_status, int32_t *d_crop_status,
+                                    void *d_out, size_t out_pitch, size_t out_plane_stride,
+                                    size_t out_crop_stride, void *stream);
+
+/* The launch shape mh_decode_set_crops_norm_planes would use (no launch), as
+ * mh_decode_crops_norm_planes_shape with dims the set's maxima. */
+int mh_decode_set_crops_norm_planes_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, uint32_t h,
+                                          uint32_t format, uint32_t n_planes, void *stream,
+                                          uint32_t *groups_per_plane, uint32_t *waves_per_group);
+
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a
  * prepared table) and the 16-byte lengths word at their prepared-table offsets in

@@ -27,6 +27,10 @@ of mdejong/MetalHuffman).
   * decoder.decode_crops_normalized_planes   crops of images stored as C planes (one frame each) straight into
                                     a normalised [n, C, h, w] tensor, a (scale, bias) per plane, one launch;
                                     codec.norm_coefficients makes the pairs from a mean and a deviation
+  * decoder.DeviceFrameSet / decode_set_crops / decode_set_crops_normalized_planes   the crop entries over a
+                                    frame SET -- frames of different sizes, a geometry record each -- so a
+                                    sampled batch over images of many sizes is one launch, not one per size;
+                                    codec.frame_set_layout is the host packer
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync;
@@ -42,8 +46,8 @@ of mdejong/MetalHuffman).
 from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE_LIMIT_LENGTHS, MH_ERR_STREAM,
                       MH_FLAG_LANE_PAIRS,
                       MH_FLAG_NO_DELTA, MH_MAX_PLANES, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
-from .codec import (BLOCK_DIM, EncodedFrame, Huffman, block_grid, box_reduce, check_frame, code_lengths_limited,
-                    decode_frame_cpu, encode_frame, frame_histogram, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
+from .codec import (BLOCK_DIM, EncodedFrame, FrameSetLayout, Huffman, block_grid, box_reduce, check_frame, code_lengths_limited,
+                    decode_frame_cpu, encode_frame, frame_histogram, frame_set_layout, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
                     split_blocks)
 
 __all__ = [
@@ -52,5 +56,6 @@ __all__ = [
     "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
     "norm_table", "MH_NORM_F16", "MH_NORM_BF16", "MH_NORM_F32", "MH_CROP_MIRROR",
     "MH_MAX_PLANES", "norm_coefficients", "image_planes", "check_frame", "MH_ERR_STREAM",
+    "FrameSetLayout", "frame_set_layout",
 ]
 __version__ = "0.1.0"

@@ -52,6 +52,8 @@ EXPORTS = (
     "mh_decode_crops", "mh_decode_crops_shape",
     "mh_decode_crops_norm", "mh_decode_crops_norm_shape", "mh_norm_table",
     "mh_decode_crops_norm_planes", "mh_decode_crops_norm_planes_shape",
+    "mh_decode_set_crops", "mh_decode_set_crops_shape",
+    "mh_decode_set_crops_norm_planes", "mh_decode_set_crops_norm_planes_shape",
     "mh_encode_frames_shared_workspace_bytes", "mh_encode_frames_shared_device_async",
     "mh_frame_histogram", "mh_encode_frame_with_header",
     "mh_encode_images_workspace_bytes", "mh_encode_images_shared_workspace_bytes",
@@ -108,6 +110,11 @@ class mh_crop(ctypes.Structure):
 class mh_norm_crop(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32)]
+
+
+class mh_frame_geom(ctypes.Structure):
+    _fields_ = [("first_block", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 class mh_image_layout(ctypes.Structure):
@@ -230,6 +237,13 @@ def lib() -> ctypes.CDLL:
         L.mh_decode_crops_norm_planes_shape.argtypes = [ctypes.POINTER(mh_frame), ctypes.c_uint32, ctypes.c_uint32,
                                                         ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _u32p,
                                                         _u32p]
+        # the set entries: their parents' lists with (d_geoms, total_blocks) behind the frame; the
+        # *_shape twins are the parents'
+        for name in ("mh_decode_crops", "mh_decode_crops_norm_planes"):
+            args = getattr(L, name).argtypes
+            set_name = name.replace("mh_decode_", "mh_decode_set_")
+            getattr(L, set_name).argtypes = [args[0], _vp, ctypes.c_uint32] + list(args[1:])
+            getattr(L, set_name + "_shape").argtypes = getattr(L, name + "_shape").argtypes
         L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
                                     ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]

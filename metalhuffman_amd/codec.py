@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -101,6 +101,60 @@ class EncodedFrame:
         init = None if self.block_init is None else self.block_init[b0:b1].copy()
         height = min(self.height, 8 * by1) - 8 * by0
         return EncodedFrame(self.width, height, self.canon, codes, band_offs, init, self.flags)
+
+
+class FrameSetLayout(NamedTuple):
+    """frame_set_layout's result: the host arrays of a frame set (include/metalhuffman.h,
+    mh_frame_geom). Frame f's block offsets (and block_init) are [first, first + NB_f) of the
+    concatenated arrays, first = geoms[f, 0]; its codes are codes[code_offsets[f]: code_offsets[f + 1]],
+    a 16-byte aligned slot that holds the frame's own bytes and then zeros."""
+    block_offsets: np.ndarray         # u32[total_blocks]
+    codes: np.ndarray                 # u8[code_offsets[n]]
+    code_offsets: np.ndarray          # int64[n + 1], multiples of 16
+    geoms: np.ndarray                 # u32[n, 4] = (first_block, width, height, 0)
+    total_blocks: int
+    block_init: Optional[np.ndarray]  # u8[total_blocks] or None
+    width: int                        # the largest width ...
+    height: int                       # ... and the largest height in the set
+    flags: int
+
+
+FRAME_SET_ALIGN = 16  # a frame's code slot starts on a 16-byte boundary, as in a packed batch
+
+
+def frame_set_layout(frames) -> FrameSetLayout:
+    """The packed host layout of a frame SET: a sequence of EncodedFrame of any sizes, each with its
+    own table, for decoder.DeviceFrameSet and the mh_decode_set_* entries. ValueError: no frames,
+    frames of mixed flags, or block_init present on some frames only."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("no frames")
+    if any(f.flags != frames[0].flags for f in frames):
+        raise ValueError("a frame set holds frames of one format (flags)")
+    with_init = [f.block_init is not None for f in frames]
+    if any(with_init) and not all(with_init):
+        raise ValueError("block_init is present on all frames of a set or on none")
+    n = len(frames)
+    geoms = np.zeros((n, 4), np.uint32)
+    starts = np.zeros(n + 1, np.int64)
+    first = 0
+    for i, f in enumerate(frames):
+        if not (1 <= f.width <= N.MH_MAX_DIM and 1 <= f.height <= N.MH_MAX_DIM):
+            raise ValueError(f"frame {i}: {f.width}x{f.height} is outside 1..{N.MH_MAX_DIM}")
+        if f.block_offsets.size != f.n_blocks:
+            raise ValueError(f"frame {i}: {f.block_offsets.size} block offsets for {f.n_blocks} blocks")
+        geoms[i] = (first, f.width, f.height, 0)
+        first += f.n_blocks
+        starts[i + 1] = starts[i] + -(-f.codes.size // FRAME_SET_ALIGN) * FRAME_SET_ALIGN
+    if first > 0xFFFFFFFF:
+        raise ValueError(f"{first} blocks do not fit the set's 32-bit block index")
+    codes = np.zeros(int(starts[-1]), np.uint8)
+    for f, s in zip(frames, starts):
+        codes[s: s + f.codes.size] = f.codes
+    offs = np.concatenate([np.asarray(f.block_offsets, np.uint32) for f in frames])
+    init = np.concatenate([np.asarray(f.block_init, np.uint8) for f in frames]) if with_init[0] else None
+    return FrameSetLayout(offs, codes, starts, geoms, first, init, max(f.width for f in frames),
+                          max(f.height for f in frames), frames[0].flags)
 
 
 class Huffman:

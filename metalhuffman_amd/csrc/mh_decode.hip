@@ -810,11 +810,13 @@ __device__ __forceinline__ uint32_t frame_of(const DecodeArgs &a, uint32_t tile)
 struct FrameMap {
   static constexpr bool kRegion = false;
   static constexpr bool kCrop = false;
+  static constexpr bool kOwnBase = false;
   __device__ __forceinline__ void report(uint32_t, uint32_t) const {}
 };
 struct RegionMap {
   static constexpr bool kRegion = true;
   static constexpr bool kCrop = false;
+  static constexpr bool kOwnBase = false;  // a.offsets / a.block_init are the batch's: frame f's entries at + f * a.nb
   static constexpr uint32_t kStep = 64u;  // blocks from one tile of a row to the next
   uint32_t f, bx0, by0, bw, S;
   // BoxRows only: the frame's pixels from the region's origin on, (W - 8 bx0) | (H - 8 by0) << 16
@@ -851,6 +853,18 @@ struct NormMap : CropMap {
   __device__ __forceinline__ uint32_t mirror() const { return (rem >> 3) & 1u; }
 };
 
+// SetCropMap / SetNormMap (mh_decode_set_crops, mh_decode_set_crops_norm_planes): the crop maps over
+//   a frame SET, whose frames differ in size. The entry has read the frame's geometry record and
+//   put the frame's own block grid into the workgroup's DecodeArgs: a.bw and a.nb are this frame's,
+//   and a.offsets / a.block_init are already based at the frame's first block (kOwnBase), so the
+//   header loads add no f * a.nb. `f` still addresses the codes, the table and the status word.
+struct SetCropMap : CropMap {
+  static constexpr bool kOwnBase = true;
+};
+struct SetNormMap : NormMap {
+  static constexpr bool kOwnBase = true;
+};
+
 struct TileHdrBase {
   uint32_t tile;      // wave-uniform; >= total_tiles: no tile
   uint32_t off;       // this lane's block start bit
@@ -871,6 +885,10 @@ template <>
 struct TileHdrOf<CropMap> : TileHdrOf<RegionMap> {};
 template <>
 struct TileHdrOf<NormMap> : TileHdrOf<RegionMap> {};
+template <>
+struct TileHdrOf<SetCropMap> : TileHdrOf<RegionMap> {};
+template <>
+struct TileHdrOf<SetNormMap> : TileHdrOf<RegionMap> {};
 using TileHdr = TileHdrOf<FrameMap>;
 
 // tile -> (r, s). One segment per row skips the division (a uniform branch), as frame_of does
@@ -903,7 +921,11 @@ __device__ __forceinline__ void hdr_issue(const DecodeArgs &a, uint32_t tile, ui
     b = (live ? (tile - f * a.tiles_per_frame) * 64u : 0u) + lane;
   }
   h.tile = tile;
-  const __amdgpu_buffer_rsrc_t ro = uniform_rsrc(a.offsets + (uint64_t)f * a.nb, live ? a.nb * 4u : 0u);
+  // the frame's first block in offsets / block_init: f * a.nb in a batch of one size; a set's entry
+  // has based both arrays at it (kOwnBase)
+  uint64_t fb = 0;
+  if constexpr (!Map::kOwnBase) fb = (uint64_t)f * a.nb;
+  const __amdgpu_buffer_rsrc_t ro = uniform_rsrc(a.offsets + fb, live ? a.nb * 4u : 0u);
   h.off = __builtin_amdgcn_raw_buffer_load_b32(ro, (int)(b * 4u), 0, 0);
   h.nxt = __builtin_amdgcn_raw_buffer_load_b32(ro, (int)(b * 4u + 4u), 0, 0);
   typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
@@ -914,7 +936,7 @@ __device__ __forceinline__ void hdr_issue(const DecodeArgs &a, uint32_t tile, ui
   h.fo_lo = v.x;
   h.fo_hi = v.y;
   const __amdgpu_buffer_rsrc_t ri = uniform_rsrc(
-      a.block_init ? (const void *)(a.block_init + (uint64_t)f * a.nb) : (const void *)a.offsets,
+      a.block_init ? (const void *)(a.block_init + fb) : (const void *)a.offsets,
       (live && a.block_init) ? a.nb : 0u);
   h.init = __builtin_amdgcn_raw_buffer_load_b8(ri, (int)b, 0, 0);
 }
@@ -943,6 +965,10 @@ template <>
 struct TileOf<CropMap> : TileOf<RegionMap> {};
 template <>
 struct TileOf<NormMap> : TileOf<RegionMap> {};
+template <>
+struct TileOf<SetCropMap> : TileOf<RegionMap> {};
+template <>
+struct TileOf<SetNormMap> : TileOf<RegionMap> {};
 using Tile = TileOf<FrameMap>;
 
 template <class Map = FrameMap>
@@ -2104,6 +2130,180 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
               sel, scale, bias});
 }
 
+// The crop entries over a frame SET (mh_decode_set_crops, mh_decode_set_crops_norm_planes): frames of
+// different sizes, frame f's geometry in the 16-byte record p_geoms[f]. The entry is its parent's with
+// a second dependent trip: desc_load and the verdict on the descriptor's own words; only then the
+// record (geom_load, wave-uniform as desc_load) and the verdict on it; then the crop against the
+// frame's own W_f x H_f, the limits formed from the accepted record (w <= W_f before W_f - w, so
+// nothing wraps). Behind the verdicts the workgroup's DecodeArgs get the frame's own grid: bw, nb and
+// the two arrays based at the frame's first block (first_block <= total_blocks - nb has passed, so
+// the sums stay inside the arrays; the maps' kOwnBase makes hdr_issue add nothing to them). The
+// offsets descriptor stays limited to the frame's nb * 4 bytes, so a frame's last block takes the
+// min(fbits, off + 1024) end and never reads a neighbour's first offset. Codes, table and status
+// word stay indexed by the frame number. p_total_blocks arrives where the parents' p_nb does;
+// p_max_x0 / p_max_y0 (from the set's maxima) are not used.
+__device__ __forceinline__ v4u32 geom_load(const mh_frame_geom *geoms, uint32_t f, bool on = true) {
+  // off: a descriptor of zero records, whose load returns 0 without touching memory
+  v4u32 d = __builtin_amdgcn_raw_buffer_load_b128(
+      uniform_rsrc(on ? (const void *)(geoms + f) : (const void *)geoms, on ? 16u : 0u), 0, 0, 0);
+  d.x = __builtin_amdgcn_readfirstlane(d.x), d.y = __builtin_amdgcn_readfirstlane(d.y);
+  d.z = __builtin_amdgcn_readfirstlane(d.z), d.w = __builtin_amdgcn_readfirstlane(d.w);
+  return d;
+}
+// the record's own verdict (step 2): true = rejected
+__device__ __forceinline__ bool geom_bad(const v4u32 g, uint32_t total_blocks) {
+  const uint32_t W = g.y, H = g.z;
+  const uint32_t nb = ((W + 7u) >> 3) * ((H + 7u) >> 3);  // <= 2^26 for an accepted W, H
+  return (g.w != 0u) | (W - 1u > 65534u) | (H - 1u > 65534u) | (nb > total_blocks) | (g.x > total_blocks - nb);
+}
+// The frame's grid and bases, opaque from here on: seen through, the record's words stay live beside
+// them through the body, which has no SGPR to spare.
+struct SetFrame {
+  const uint32_t *offsets;
+  const uint8_t *block_init;
+  uint32_t bw, nb;
+};
+__device__ __forceinline__ SetFrame set_frame(const uint32_t *p_offsets, const uint8_t *p_block_init, uint32_t first,
+                                              uint32_t W, uint32_t H) {
+  uint32_t bw = (W + 7u) >> 3;
+  uint32_t nb = bw * ((H + 7u) >> 3);
+  const uint64_t o = (uint64_t)p_offsets + 4ull * first;
+  const uint64_t i = p_block_init ? (uint64_t)p_block_init + first : 0ull;
+  uint32_t o_lo = (uint32_t)o, o_hi = (uint32_t)(o >> 32), i_lo = (uint32_t)i, i_hi = (uint32_t)(i >> 32);
+  asm volatile("" : "+s"(bw), "+s"(nb), "+s"(o_lo), "+s"(o_hi), "+s"(i_lo), "+s"(i_hi));
+  return {(const uint32_t *)(((uint64_t)o_hi << 32) | o_lo), (const uint8_t *)(((uint64_t)i_hi << 32) | i_lo), bw, nb};
+}
+
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_setcrops_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const mh_crop *p_crops, uint32_t p_total_blocks, uint32_t p_tiles_per_crop,
+    uint32_t p_groups, uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0,
+    uint32_t p_max_y0, uint64_t p_lut_stride, int32_t *p_cstatus, const mh_frame_geom *p_geoms, const DecodeArgs a0) {
+  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
+  const v4u32 cd = desc_load(p_crops + p);
+  const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z, reserved = cd.w;
+  const bool writer = p_cstatus && slice == 0 && threadIdx.x == 0;
+  if ((f >= p_nframes) | (reserved != 0u)) {  // workgroup-uniform
+    if (writer) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  const v4u32 gd = geom_load(p_geoms, f);
+  if (geom_bad(gd, p_total_blocks)) {
+    if (writer) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  const uint32_t W = gd.y, H = gd.z;
+  if ((p_w > W) | (p_h > H) | (x0 > W - p_w) | (y0 > H - p_h)) {  // the sizes are judged first: a wrapped limit is never the verdict
+    if (writer) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  (void)p_tiles_per_crop;
+  (void)p_max_x0;
+  (void)p_max_y0;
+  const SetFrame sf = set_frame(p_offsets, p_block_init, gd.x, W, H);
+  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
+  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
+  DecodeArgs ac = a0;
+  ac.out = a0.out + (uint64_t)p * a0.out_frame_stride;
+  ac.out_frame_stride = 0;
+  ac.bw = sf.bw;
+  slice_decode<kDelta, CropRows>(
+      ac, sf.offsets, p_frame_off, sf.block_init, p_status, sf.nb, rows * p_segs, p_groups, f, slice,
+      PreparedTable{p_luts, p_lut_stride},
+      SetCropMap{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, dx | (dy << 4) | (ow << 8)}, p, p_cstatus}}});
+}
+
+// ... and the samples of planes over a set. Step 2 covers the sample: every workgroup loads the
+// records of all its n_planes frames (empty descriptors for the planes past n_planes, as the status
+// words), judges each and requires every plane's (width, height) to equal plane 0's, so all the
+// sample's workgroups reach one verdict. The status words depend on the descriptor alone and are
+// loaded in the same trip; they are read behind the geometry's verdict, which keeps its precedence.
+template <bool kDelta, uint32_t kFmt>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_setplanes_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const mh_norm_crop *p_crops, uint32_t p_total_blocks, uint32_t p_tiles_per_crop,
+    uint32_t p_groups, uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_max_frame, uint32_t p_max_x0,
+    uint32_t p_max_y0, uint64_t p_lut_stride, int32_t *p_cstatus, uint32_t p_odd_w, const PlaneArgs pl,
+    const mh_frame_geom *p_geoms, const DecodeArgs a0) {
+  const uint32_t unit = blockIdx.x / p_groups, slice = blockIdx.x - unit * p_groups;
+  uint32_t p = unit, c = 0u;
+  if (pl.n_planes != 1u) {
+    p = unit / pl.n_planes;
+    c = unit - p * pl.n_planes;
+  }
+  const v4u32 cd = desc_load(p_crops + p);
+  const uint32_t f0 = cd.x, x0 = cd.y, y0 = cd.z, flags = cd.w;
+  const bool writer = p_cstatus && c == 0u && slice == 0u && threadIdx.x == 0u;
+  if ((f0 > p_max_frame) | ((flags & ~MH_CROP_MIRROR) != 0u)) {  // workgroup-uniform
+    if (writer) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  // f0 + (n_planes - 1) * frame_stride < n_frames from here on
+  v4u32 gd[MH_MAX_PLANES];
+  uint32_t stv[MH_MAX_PLANES];
+#pragma unroll
+  for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) gd[i] = geom_load(p_geoms, f0 + i * pl.frame_stride, i < pl.n_planes);
+#pragma unroll
+  for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) {
+    const bool on = p_status && i < pl.n_planes;
+    stv[i] = __builtin_amdgcn_raw_buffer_load_b32(
+        uniform_rsrc(on ? (const void *)(p_status + f0 + (uint64_t)i * pl.frame_stride) : (const void *)p_offsets,
+                     on ? 4u : 0u),
+        0, 0, 0);
+  }
+  const uint32_t W = gd[0].y, H = gd[0].z;
+  bool bad = false;
+  uint32_t first = gd[0].x;  // this workgroup's plane's
+#pragma unroll
+  for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) {
+    const bool on = i < pl.n_planes;
+    bad |= on & (geom_bad(gd[i], p_total_blocks) | (gd[i].y != W) | (gd[i].z != H));
+    first = c == i ? gd[i].x : first;
+  }
+  if (bad) {
+    if (writer) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  if ((p_w > W) | (p_h > H) | (x0 > W - p_w) | (y0 > H - p_h) | ((flags & p_odd_w) != 0u)) {
+    if (writer) p_cstatus[p] = MH_ERR_DIMS;
+    return;
+  }
+  uint32_t st = 0u;  // the first non-zero word in plane order
+#pragma unroll
+  for (int i = MH_MAX_PLANES - 1; i >= 0; --i) {
+    const uint32_t s = __builtin_amdgcn_readfirstlane(stv[i]);
+    st = s ? s : st;
+  }
+  if (writer) p_cstatus[p] = (int32_t)st;
+  if (st != 0u) return;  // workgroup-uniform: a skipped sample, no plane of it is stored
+  (void)p_tiles_per_crop;
+  (void)p_max_x0;
+  (void)p_max_y0;
+  const SetFrame sf = set_frame(p_offsets, p_block_init, first, W, H);
+  // as the planes entry: the plane's frame and raster base, opaque
+  uint32_t f = f0 + c * pl.frame_stride;
+  const uint64_t base = (uint64_t)a0.out + (uint64_t)p * a0.out_frame_stride + (uint64_t)c * pl.out_stride;
+  uint32_t base_lo = (uint32_t)base, base_hi = (uint32_t)(base >> 32);
+  asm volatile("" : "+s"(f), "+s"(base_lo), "+s"(base_hi));
+  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
+  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
+  DecodeArgs ac = a0;
+  ac.out = (uint8_t *)(((uint64_t)base_hi << 32) | base_lo);
+  ac.out_frame_stride = 0;
+  ac.bw = sf.bw;
+  uint32_t sel = flags ? 0x04050607u : 0x03020100u;
+  float scale = c == 0u ? pl.scale[0] : c == 1u ? pl.scale[1] : c == 2u ? pl.scale[2] : pl.scale[3];
+  float bias = c == 0u ? pl.bias[0] : c == 1u ? pl.bias[1] : c == 2u ? pl.bias[2] : pl.bias[3];
+  asm volatile("" : "+v"(sel), "+v"(scale), "+v"(bias));
+  uint32_t rem = dx | (flags << 3) | (dy << 4) | (ow << 8);
+  asm volatile("" : "+s"(rem));
+  slice_decode<kDelta, NormRows<kFmt>>(
+      ac, sf.offsets, p_frame_off, sf.block_init, nullptr, sf.nb, rows * p_segs, p_groups, f, slice,
+      PreparedTable{p_luts, p_lut_stride},
+      SetNormMap{{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, rem}, 0u, nullptr}}, sel, scale, bias}});
+}
+
 template <bool kDelta>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_headers_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_headers,
@@ -2946,7 +3146,9 @@ enum SliceKernel {
   kSliceCrops = kSliceWindows + kSliceScales,  // one scale only
   kSliceNormCrops,                             // + the format (MH_NORM_*)
   kSlicePlanes = kSliceNormCrops + 3,          // + the format
-  kSliceKernels = kSlicePlanes + 3
+  kSliceSetCrops = kSlicePlanes + 3,           // the crops and the planes over a frame set
+  kSliceSetPlanes,                             // + the format
+  kSliceKernels = kSliceSetPlanes + 3
 };
 #if !MH_LANE_PAIRS
 // One row per kernel, [kDelta]: the row device_info() queries the occupancy of is the row
@@ -2959,6 +3161,8 @@ using WindowsFn = decltype(&mh_decode_windows_kernel<false>);  // = mh_decode_wi
 using CropsFn = decltype(&mh_decode_crops_kernel<false>);
 using NormCropsFn = decltype(&mh_decode_normcrops_kernel<false, MH_NORM_F16>);
 using PlanesFn = decltype(&mh_decode_planes_kernel<false, MH_NORM_F16>);
+using SetCropsFn = decltype(&mh_decode_setcrops_kernel<false>);
+using SetPlanesFn = decltype(&mh_decode_setplanes_kernel<false, MH_NORM_F16>);
 using AnyKernel = void (*)();
 struct SliceRow {
   AnyKernel fn[2];
@@ -2986,6 +3190,13 @@ const SliceRow kSliceTable[] = {
     slice_row<PlanesFn>(mh_decode_planes_kernel<false, MH_NORM_F16>, mh_decode_planes_kernel<true, MH_NORM_F16>),
     slice_row<PlanesFn>(mh_decode_planes_kernel<false, MH_NORM_BF16>, mh_decode_planes_kernel<true, MH_NORM_BF16>),
     slice_row<PlanesFn>(mh_decode_planes_kernel<false, MH_NORM_F32>, mh_decode_planes_kernel<true, MH_NORM_F32>),
+    slice_row<SetCropsFn>(mh_decode_setcrops_kernel<false>, mh_decode_setcrops_kernel<true>),
+    slice_row<SetPlanesFn>(mh_decode_setplanes_kernel<false, MH_NORM_F16>,
+                           mh_decode_setplanes_kernel<true, MH_NORM_F16>),
+    slice_row<SetPlanesFn>(mh_decode_setplanes_kernel<false, MH_NORM_BF16>,
+                           mh_decode_setplanes_kernel<true, MH_NORM_BF16>),
+    slice_row<SetPlanesFn>(mh_decode_setplanes_kernel<false, MH_NORM_F32>,
+                           mh_decode_setplanes_kernel<true, MH_NORM_F32>),
 };
 static_assert(sizeof(kSliceTable) / sizeof(kSliceTable[0]) == kSliceKernels, "one row per SliceKernel");
 #endif
@@ -3179,6 +3390,12 @@ struct DecodeCall {
   // bytes apart, the crops of frames plane_frame_stride apart; one plane is mh_decode_crops_norm
   uint32_t n_planes = 1, plane_frame_stride = 0;
   uint64_t out_plane_stride = 0;
+  // mh_decode_set_crops[_norm_planes] (kCrops / kNormCrops): the frames are a SET described by the
+  // device array `geoms` over `total_blocks` offsets; dims carry the set's maxima and their block
+  // counts are ignored (call_dims)
+  bool set = false;
+  const void *geoms = nullptr;
+  uint32_t total_blocks = 0;
   // mh_check_frames / mh_check_headers (kPrepared / kHeaders): no raster and none of its rules, one
   // table for all frames at stride 0 as a region's, and `words`, the OR of the report's and the
   // verdict's addresses, 4-byte aligned
@@ -3202,12 +3419,23 @@ struct DecodeCall {
 // scale (a scale above 3 is reported where a bad flag is), dims, the region. A region's pixel size
 // RW x RH -- for windows the full 8 bw x 8 bh: windows differ in RW / RH, and a size that is empty
 // or exceeds the grid is MH_ERR_DIMS -- becomes SW x SH = ceil(RW / s) x ceil(RH / s) at scale s.
+// The dims a call is judged and tiled by: the frame's, or for a set its maxima with the block counts
+// that go with them (a width past MH_MAX_DIM may wrap here: dims_ok refuses it by the width).
+mh_dims call_dims(const mh_frame *fr, const DecodeCall &c) {
+  mh_dims d = fr->dims;
+  if (c.set) {
+    d.block_width = (d.width + 7u) / 8u;
+    d.block_height = (d.height + 7u) / 8u;
+  }
+  return d;
+}
+
 int call_geometry(const mh_frame *fr, DecodeCall &c) {
   if (fr->flags & ~c.allowed_flags) return MH_ERR_INVALID_ARG;
   if (c.log2_scale > 3u) return MH_ERR_INVALID_ARG;
   if (c.kind == DecodeCall::kNormCrops && (c.format > MH_NORM_F32 || !std::isfinite(c.scale) || !std::isfinite(c.bias)))
     return MH_ERR_INVALID_ARG;
-  const mh_dims &d = fr->dims;
+  const mh_dims d = call_dims(fr, c);
   if (!dims_ok(d)) return MH_ERR_DIMS;
   c.n_units = c.windowed() ? c.n_windows : fr->n_frames;
   if (!c.regional()) {
@@ -3247,6 +3475,7 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (!fr || (!c.walk && !d_out) || !fr->d_block_offsets || !fr->d_codes) return MH_ERR_INVALID_ARG;
   if (regional && !c.rg) return MH_ERR_INVALID_ARG;
   if (windowed && (!c.windows || c.n_windows == 0)) return MH_ERR_INVALID_ARG;
+  if (c.set && (!c.geoms || c.total_blocks == 0)) return MH_ERR_INVALID_ARG;
   if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !c.ptr) return MH_ERR_INVALID_ARG;
   if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
   const int rc = call_geometry(fr, c);
@@ -3263,7 +3492,7 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (((uintptr_t)fr->d_codes & 15u) || (out_pitch & am) || ((uintptr_t)d_out & am) ||
       (n_rasters > 1 && (out_frame_stride & am)) || (c.n_planes > 1 && (c.out_plane_stride & am)))
     return MH_ERR_ALIGN;
-  if (windowed && ((uintptr_t)c.windows & 15u)) return MH_ERR_ALIGN;
+  if (windowed && (((uintptr_t)c.windows | (uintptr_t)c.geoms) & 15u)) return MH_ERR_ALIGN;
   if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)c.ptr & 15u) || (c.stride & 15u))))
     return MH_ERR_ALIGN;
   if (c.words & 3u) return MH_ERR_ALIGN;
@@ -3288,7 +3517,7 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
 // are c.n_units rasters. MH_ERR_CAPACITY past the tile cap.
 int fill_decode_args(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                      DecodeArgs &a, const DecodeCall &c) {
-  const mh_dims &d = fr->dims;
+  const mh_dims d = call_dims(fr, c);
   a.offsets = fr->d_block_offsets;
   a.codes = fr->d_codes;
   a.frame_off = fr->d_frame_code_offsets;
@@ -3386,6 +3615,13 @@ struct ListCall : DecodeCall {
   ListCall(Kind kind, uint32_t w, uint32_t h, uint32_t log2_scale, uint32_t n, const void *descriptors = nullptr,
            const void *luts = nullptr, uint64_t stride = 0)
       : DecodeCall{kind, luts, stride, &size, log2_scale, descriptors, n}, size{0u, 0u, w, h} {}
+  // ... over a frame set (the crop kinds): the *_shape twins pass no records
+  ListCall &over_set(const void *d_geoms = nullptr, uint32_t blocks = 0) {
+    set = true;
+    geoms = d_geoms;
+    total_blocks = blocks;
+    return *this;
+  }
   ListCall(const ListCall &) = delete;  // rg points into this object
 };
 
@@ -3402,7 +3638,10 @@ int decode_list(SliceKernel family, const mh_frame *fr, ListCall &c, const Desc 
   SliceArgs p;
   const int rc = slice_prologue(fr, static_cast<uint8_t *>(d_out), out_pitch, out_stride, c, p);
   if (rc != MH_OK) return rc;
-  const mh_dims &d = fr->dims;
+  const mh_dims d = call_dims(fr, c);
+  // a set: the kernels take total_blocks where the others take the frames' nb, and make each
+  // workgroup's nb and bw from its frame's geometry record
+  if (c.set) p.a.nb = c.total_blocks;
   return launch_slices<Fn>(family, c, p, stream, static_cast<const uint8_t *>(c.ptr), frame_status, descriptors,
                            c.re.segs, c.size.bw, c.size.bh, fr->n_frames - frames_short,
                            (c.cropped() ? d.width : d.block_width) - c.size.bw,
@@ -3477,6 +3716,23 @@ int check_walk_shape(const mh_frame *fr, bool headers, void *stream, uint32_t *g
   if (rc != MH_OK) return rc;
   *waves_per_group = kMaxWavesPerWG;
   return MH_OK;
+}
+
+// The planes entries' by-value arguments from the host arrays; false: a bad plane count or pair
+// (values at index >= n_planes are not read). One plane ignores the strides.
+bool plane_args(uint32_t n_planes, uint32_t plane_frame_stride, const float *scale, const float *bias,
+                size_t out_plane_stride, PlaneArgs &pl) {
+  if (n_planes == 0 || n_planes > MH_MAX_PLANES || !scale || !bias) return false;
+  pl = {};
+  for (uint32_t i = 0; i < n_planes; ++i) {
+    if (!std::isfinite(scale[i]) || !std::isfinite(bias[i])) return false;
+    pl.scale[i] = scale[i];
+    pl.bias[i] = bias[i];
+  }
+  pl.n_planes = n_planes;
+  pl.frame_stride = n_planes > 1 ? plane_frame_stride : 0u;
+  pl.out_stride = n_planes > 1 ? out_plane_stride : 0u;
+  return true;
 }
 #endif
 
@@ -3710,16 +3966,8 @@ int mh_decode_crops_norm_planes(const mh_frame *fr, const mh_norm_crop *d_crops,
                                 uint64_t lut_stride_bytes, const int32_t *d_frame_status, int32_t *d_crop_status,
                                 void *d_out, size_t out_pitch, size_t out_plane_stride, size_t out_crop_stride,
                                 void *stream) {
-  if (n_planes == 0 || n_planes > MH_MAX_PLANES || !scale || !bias) return MH_ERR_INVALID_ARG;
-  PlaneArgs pl = {};
-  for (uint32_t i = 0; i < n_planes; ++i) {
-    if (!std::isfinite(scale[i]) || !std::isfinite(bias[i])) return MH_ERR_INVALID_ARG;
-    pl.scale[i] = scale[i];
-    pl.bias[i] = bias[i];
-  }
-  pl.n_planes = n_planes;
-  pl.frame_stride = n_planes > 1 ? plane_frame_stride : 0u;
-  pl.out_stride = n_planes > 1 ? out_plane_stride : 0u;
+  PlaneArgs pl;
+  if (!plane_args(n_planes, plane_frame_stride, scale, bias, out_plane_stride, pl)) return MH_ERR_INVALID_ARG;
   ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
   c.format = format;
   c.n_planes = n_planes;
@@ -3738,6 +3986,56 @@ int mh_decode_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, uint
   c.format = format;
   c.n_planes = n_planes;
   return slice_shape_entry(kSlicePlanes, fr, c, stream, groups_per_plane, waves_per_group);
+}
+
+// The crop entries over a frame set: their parents' calls with ListCall::over_set, the set kernels'
+// rows and the geometry records as the kernels' last scalar. The prologue sizes the rasters and the
+// grid from dims, the set's maxima; every workgroup takes its frame's own grid from its record.
+int mh_decode_set_crops(const mh_frame *fr, const mh_frame_geom *d_geoms, uint32_t total_blocks,
+                        const mh_crop *d_crops, uint32_t n_crops, uint32_t w, uint32_t h, const uint16_t *d_luts,
+                        uint64_t lut_stride_bytes, const int32_t *d_frame_status, int32_t *d_crop_status,
+                        uint8_t *d_out, size_t out_pitch, size_t out_crop_stride, void *stream) {
+  ListCall c(DecodeCall::kCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
+  c.over_set(d_geoms, total_blocks);
+  return decode_list<SetCropsFn>(kSliceSetCrops, fr, c, d_crops, d_frame_status, d_crop_status, d_out, out_pitch,
+                                 out_crop_stride, stream, 0u, d_geoms);
+}
+
+int mh_decode_set_crops_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h, void *stream,
+                              uint32_t *groups_per_crop, uint32_t *waves_per_group) {
+  return slice_shape_entry(kSliceSetCrops, fr, ListCall(DecodeCall::kCrops, w, h, 0u, n_crops).over_set(), stream,
+                           groups_per_crop, waves_per_group);
+}
+
+int mh_decode_set_crops_norm_planes(const mh_frame *fr, const mh_frame_geom *d_geoms, uint32_t total_blocks,
+                                    const mh_norm_crop *d_crops, uint32_t n_crops, uint32_t w, uint32_t h,
+                                    uint32_t format, uint32_t n_planes, uint32_t plane_frame_stride,
+                                    const float *scale, const float *bias, const uint16_t *d_luts,
+                                    uint64_t lut_stride_bytes, const int32_t *d_frame_status,
+                                    int32_t *d_crop_status, void *d_out, size_t out_pitch, size_t out_plane_stride,
+                                    size_t out_crop_stride, void *stream) {
+  PlaneArgs pl;
+  if (!plane_args(n_planes, plane_frame_stride, scale, bias, out_plane_stride, pl)) return MH_ERR_INVALID_ARG;
+  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
+  c.over_set(d_geoms, total_blocks);
+  c.format = format;
+  c.n_planes = n_planes;
+  c.plane_frame_stride = pl.frame_stride;
+  c.out_plane_stride = pl.out_stride;
+  return decode_list<SetPlanesFn>(kSliceSetPlanes, fr, c, d_crops, d_frame_status, d_crop_status, d_out, out_pitch,
+                                  out_crop_stride, stream, 1u + (n_planes - 1u) * pl.frame_stride,
+                                  (w & 7u) ? 1u : 0u, pl, d_geoms);
+}
+
+int mh_decode_set_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, uint32_t w, uint32_t h,
+                                          uint32_t format, uint32_t n_planes, void *stream,
+                                          uint32_t *groups_per_plane, uint32_t *waves_per_group) {
+  if (n_planes == 0 || n_planes > MH_MAX_PLANES) return MH_ERR_INVALID_ARG;
+  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops);
+  c.over_set();
+  c.format = format;
+  c.n_planes = n_planes;
+  return slice_shape_entry(kSliceSetPlanes, fr, c, stream, groups_per_plane, waves_per_group);
 }
 
 // mh_check's report, frame by frame under the frame's own table, and a verdict word per frame that

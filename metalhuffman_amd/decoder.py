@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .codec import EncodedFrame, block_grid, finite_f32
+from .codec import EncodedFrame, block_grid, finite_f32, frame_set_layout
 from .codec import norm_format as _norm_format
 
 ALIGN = 16  # frame code starts inside a packed batch (16-byte buffer loads)
@@ -203,6 +203,62 @@ class DeviceFrames:
         return cls(w, h, len(frames), torch.from_numpy(offs.view(np.int32)).to(dev),
                    torch.from_numpy(packed).to(dev), fco, init, fl,
                    sum(f.payload_bytes for f in frames))
+
+
+@dataclasses.dataclass
+class DeviceFrameSet:
+    """n frames of DIFFERENT sizes packed for the set entries (decode_set_crops,
+    decode_set_crops_normalized_planes; include/metalhuffman.h, mh_frame_geom): one offsets array
+    over all the frames' blocks, one code slot and one geometry record (first block, width, height)
+    per frame. width and height are the LARGEST in the set -- what the C entries take as dims."""
+    width: int
+    height: int
+    n_frames: int
+    sizes: tuple                         # ((width, height), ...) per frame
+    total_blocks: int
+    block_offsets: torch.Tensor          # u32 as int32[total_blocks]
+    codes: torch.Tensor                  # u8[total]
+    frame_code_offsets: Optional[torch.Tensor]  # int64[n + 1] (None for one frame)
+    geoms: torch.Tensor                  # u32 as int32[n, 4]: mh_frame_geom records
+    block_init: Optional[torch.Tensor] = None   # u8[total_blocks]
+    flags: int = 0
+    code_bytes: int = 0                  # payload bytes (sum over frames, pad excluded)
+
+    @classmethod
+    def pack(cls, frames: Sequence[EncodedFrame], device="cuda") -> "DeviceFrameSet":
+        """Upload codec.frame_set_layout(frames): frames of any sizes and any headers (a table per
+        frame from a DeviceTableSet, or one DeviceTables when they share a header) of one format."""
+        dev = _dev(device)
+        lay = frame_set_layout(frames)
+        n = len(lay.geoms)
+        init = torch.from_numpy(lay.block_init).to(dev) if lay.block_init is not None else None
+        fco = torch.from_numpy(lay.code_offsets).to(dev) if n > 1 else None
+        return cls(lay.width, lay.height, n, tuple((int(g[1]), int(g[2])) for g in lay.geoms), lay.total_blocks,
+                   torch.from_numpy(lay.block_offsets.view(np.int32)).to(dev), torch.from_numpy(lay.codes).to(dev),
+                   fco, torch.from_numpy(lay.geoms.view(np.int32)).to(dev), init, lay.flags,
+                   sum(f.payload_bytes for f in frames))
+
+    def size_limits(self) -> tuple:
+        """(widths, heights) as int64 arrays, one entry per frame (the host check of a crop list)."""
+        lim = self.__dict__.get("_limits")
+        if lim is None:
+            a = np.asarray(self.sizes, np.int64).reshape(-1, 2)
+            lim = self.__dict__["_limits"] = (a[:, 0].copy(), a[:, 1].copy())
+        return lim
+
+    def frame_struct(self, extra_flags: int = 0) -> N.mh_frame:
+        """The mh_frame of the set: dims carry the largest width and height, the table fields are NULL
+        (the set entries take prepared tables). Cached as DeviceFrames' structs are; never modified."""
+        return _frame_entry(self, None, extra_flags)[0]
+
+    def _head(self, dev_index: int) -> tuple:
+        """(d_geoms, total_blocks) for the C entries, the records checked as `out` tensors are."""
+        g = self.geoms
+        if (g.dtype is not torch.int32 or g.shape != (self.n_frames, 4) or g.get_device() != dev_index
+                or not g.is_contiguous() or g.data_ptr() % 16):
+            raise ValueError(f"geoms must be a contiguous, 16-byte aligned int32 [{self.n_frames}, 4] tensor on "
+                             f"cuda:{dev_index}")
+        return g.data_ptr(), self.total_blocks
 
 
 def _frame_entry(frames: DeviceFrames, tables: Optional[DeviceTables], extra_flags: int = 0):
@@ -618,9 +674,14 @@ def _host_list(frames: DeviceFrames, items, noun: str, origin: str, w: int, h: i
         raise ValueError(f"{noun}s is a sequence of (frame, {origin}) integers")
     a = a.astype(np.int64)
     lw, lh = limits
+    if isinstance(lw, np.ndarray):  # a frame set: one size per frame, every item against its own frame's
+        f = np.clip(a[:, 0], 0, frames.n_frames - 1)
+        lw, lh = lw[f], lh[f]
     bad = ((a < 0).any(axis=1) | (a[:, 0] >= frames.n_frames) | (a[:, 1] + w > lw) | (a[:, 2] + h > lh))
     if bad.any():
         i = int(np.flatnonzero(bad)[0])
+        if isinstance(lw, np.ndarray):
+            lw, lh = int(lw[i]), int(lh[i])
         raise ValueError(f"{noun} {i} = {tuple(int(v) for v in a[i])} of {w}x{h} {unit} lies outside the "
                          f"{frames.n_frames} frames of {lw}x{lh}{of}")
     full = np.zeros((a.shape[0], 4), np.int32)
@@ -658,12 +719,13 @@ _NO_STREAM = contextlib.nullcontext()  # (reusable: one per call costs what two 
 
 
 def _decode_list(who: str, entry: str, frames: DeviceFrames, tables, items, host, mid: tuple, slot: tuple, dtype,
-                 strides: tuple, out, status, stream, extra_flags: int, skip_rejected: bool):
+                 strides: tuple, out, status, stream, extra_flags: int, skip_rejected: bool, head: tuple = ()):
     """What the window and crop entries share behind their own checks: the frame entry, the tables, the
     descriptor array, the default ZERO-FILLED raster [n, *slot] of `dtype` and the status tensor (all made
     under `stream`), `out` and `status` checked, and one launch of the C entry `entry`, which takes `mid`
     between the descriptor count and the tables and, behind the rasters, their byte `strides` (row, [plane,]
-    slot). `host`: _host_list's result for `items`. Called once per batch: no loop, no list, no closure."""
+    slot), and `head` (a frame set's geometry records and block count) right behind the frame.
+    `host`: _host_list's result for `items`. Called once per batch: no loop, no list, no closure."""
     fr, dev_index = _slice_entry(who, frames, extra_flags)
     luts, stride, fstatus = _region_tables(who, frames, tables, dev_index, skip_rejected)
     dev = frames.codes.device
@@ -682,7 +744,7 @@ def _decode_list(who: str, entry: str, frames: DeviceFrames, tables, items, host
                                 or lstatus.numel() != n or lstatus.get_device() != dev_index
                                 or not lstatus.is_contiguous()):
         raise ValueError(f"status must be True or a contiguous int32 [{n}] tensor on cuda:{dev_index}")
-    rc = getattr(N.lib(), entry)(ctypes.byref(fr), desc.data_ptr(), n, *mid, luts.data_ptr(), stride,
+    rc = getattr(N.lib(), entry)(ctypes.byref(fr), *head, desc.data_ptr(), n, *mid, luts.data_ptr(), stride,
                                  fstatus.data_ptr() if fstatus is not None else None,
                                  lstatus.data_ptr() if lstatus is not None else None, out.data_ptr(), *strides,
                                  _raw_stream_ptr(stream, dev_index))
@@ -761,8 +823,10 @@ def _crop_size(frames: DeviceFrames, size) -> tuple:
 
 
 def _host_crops(frames: DeviceFrames, crops, w: int, h: int):
-    """decode_crops' `crops` checked on the host (_host_list) against the frames and their pixel size."""
-    return _host_list(frames, crops, "crop", "x0, y0", w, h, "pixels", (frames.width, frames.height), "")
+    """decode_crops' `crops` checked on the host (_host_list) against the frames and their pixel size
+    (a frame set: every crop against its own frame's)."""
+    limits = frames.size_limits() if isinstance(frames, DeviceFrameSet) else (frames.width, frames.height)
+    return _host_list(frames, crops, "crop", "x0, y0", w, h, "pixels", limits, "")
 
 
 def decode_crops_shape(frames: DeviceFrames, n_crops: int, size,
@@ -936,6 +1000,96 @@ def decode_crops_normalized_planes(frames: DeviceFrames, tables, crops, size, dt
     return _decode_list("decode_crops_normalized_planes", "mh_decode_crops_norm_planes", frames, tables, crops, host,
                         (w, h, fmt, C, ps, c_scale, c_bias), (C, h, cols), _NORM_DTYPES[fmt],
                         (pitch, h * pitch, C * h * pitch), out, status, stream, extra_flags, skip_rejected)
+
+
+def _frame_set(who: str, fs) -> "DeviceFrameSet":
+    if not isinstance(fs, DeviceFrameSet):
+        raise TypeError(f"{who} takes a DeviceFrameSet")
+    return fs
+
+
+def decode_set_crops_shape(fs: DeviceFrameSet, n_crops: int, size, stream: Optional[torch.cuda.Stream] = None,
+                           extra_flags: int = 0) -> tuple:
+    """(workgroups per crop, waves per workgroup) decode_set_crops would launch n_crops crops of
+    size = (w, h) pixels with (mh_decode_set_crops_shape): the crop size and the device decide, not
+    the frames' sizes."""
+    return _slice_shape("mh_decode_set_crops_shape", _frame_set("decode_set_crops_shape", fs), stream, extra_flags,
+                        crops=(n_crops, size))
+
+
+def decode_set_crops(fs: DeviceFrameSet, tables, crops, size, out: Optional[torch.Tensor] = None,
+                     status=None, stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                     skip_rejected: bool = True):
+    """decode_crops over a frame SET (mh_decode_set_crops): crop p is the pixels [x0, x0 + w) x
+    [y0, y0 + h) of frame `frame`, whatever that frame's size, and crops of frames of any mix of sizes
+    are decoded into out[n_crops, h, round_up(w, 8)] in ONE launch -- no grouping of a sampled batch by
+    image size, no launch per size.
+    size: (w, h) in pixels, at most the set's largest width and height (ValueError). A crop that does
+    not fit its OWN frame is rejected per crop: on the device for a device tensor (status MH_ERR_DIMS,
+    the slot untouched), here (ValueError) for a host list.
+    tables: a DeviceTableSet with one table per frame of the set, or one DeviceTables for all.
+    crops, out, status, extra_flags, skip_rejected: decode_crops'."""
+    fs = _frame_set("decode_set_crops", fs)
+    w, h = _crop_size(fs, size)
+    host = _host_crops(fs, crops, w, h)
+    pitch = (w + 7) // 8 * 8
+    head = fs._head(fs.codes.get_device())
+    return _decode_list("decode_set_crops", "mh_decode_set_crops", fs, tables, crops, host, (w, h), (h, pitch),
+                        torch.uint8, (pitch, h * pitch), out, status, stream, extra_flags, skip_rejected, head)
+
+
+def decode_set_crops_normalized_planes_shape(fs: DeviceFrameSet, n_crops: int, size, dtype, n_planes: int,
+                                             stream: Optional[torch.cuda.Stream] = None,
+                                             extra_flags: int = 0) -> tuple:
+    """(workgroups per (sample, plane) unit, waves per workgroup) decode_set_crops_normalized_planes
+    would launch with (mh_decode_set_crops_norm_planes_shape)."""
+    return _slice_shape("mh_decode_set_crops_norm_planes_shape",
+                        _frame_set("decode_set_crops_normalized_planes_shape", fs), stream, extra_flags,
+                        crops=(n_crops, size, dtype, n_planes))
+
+
+def decode_set_crops_normalized_planes(fs: DeviceFrameSet, tables, crops, size, dtype, scale, bias,
+                                       n_planes: Optional[int] = None, plane_stride: int = 1,
+                                       out: Optional[torch.Tensor] = None, status=None,
+                                       stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0,
+                                       skip_rejected: bool = True):
+    """decode_crops_normalized_planes over a frame SET (mh_decode_set_crops_norm_planes): samples of
+    images of any mix of sizes, each stored as C planes of ONE size, into a normalised
+    out[n, C, h, round_up(w, 8)] in one launch. With one plane (scale and bias of length 1) it is
+    decode_crops_normalized over a set.
+    n_planes: None, or C = len(scale) said again (ValueError when they differ).
+    A sample whose C frames are not of one size, or that does not fit them, is rejected whole: on the
+    device for a device tensor (MH_ERR_DIMS, no plane written), here (ValueError) for a host list.
+    Everything else -- crops, flags, scale, bias, plane_stride, out, status, tables -- is
+    decode_crops_normalized_planes', with `tables` as in decode_set_crops."""
+    fs = _frame_set("decode_set_crops_normalized_planes", fs)
+    w, h = _crop_size(fs, size)
+    fmt = _norm_format(dtype)
+    C, c_scale, c_bias = _plane_coefficients(scale, bias)
+    if n_planes is not None and int(n_planes) != C:
+        raise ValueError(f"n_planes = {n_planes}, but scale and bias hold {C} values")
+    ps = _plane_stride(fs, C, plane_stride)
+    host = _host_norm_crops(fs, crops, w, h)
+    if host is not None:
+        f0 = host[:, 0].astype(np.int64)
+        bad = f0 + (C - 1) * ps >= fs.n_frames
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {C - 1} would be frame "
+                             f"{int(host[i, 0]) + (C - 1) * ps} of {fs.n_frames}")
+        lw, lh = fs.size_limits()
+        for c in range(1, C):
+            bad = (lw[f0 + c * ps] != lw[f0]) | (lh[f0 + c * ps] != lh[f0])
+            if bad.any():
+                i = int(np.flatnonzero(bad)[0])
+                raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {c} (frame "
+                                 f"{int(f0[i]) + c * ps}) is not of plane 0's size")
+    cols = (w + 7) // 8 * 8
+    pitch = cols * (2, 2, 4)[fmt]
+    head = fs._head(fs.codes.get_device())
+    return _decode_list("decode_set_crops_normalized_planes", "mh_decode_set_crops_norm_planes", fs, tables, crops,
+                        host, (w, h, fmt, C, ps, c_scale, c_bias), (C, h, cols), _NORM_DTYPES[fmt],
+                        (pitch, h * pitch, C * h * pitch), out, status, stream, extra_flags, skip_rejected, head)
 
 
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
