@@ -726,7 +726,8 @@ int mh_decode_crops_norm_planes_shape(const mh_frame *frame, uint32_t n_crops, u
 /* mh_decode_crops_norm_planes.                                                                    */
 /* Not covered: a set for the frame, region, window and scaled entries; mh_check_frames over a set */
 /* (a caller checks per size group and scatters the verdicts into one d_frame_status); sets in the */
-/* streams and the multi-GPU paths; a set encoder.                                                 */
+/* streams and the multi-GPU paths. (The set's device producer is mh_encode_set_device_async; what */
+/* it does not cover -- a shared table over a set, compaction of the code slots -- is listed there.)*/
 typedef struct {
   uint32_t first_block;   /* index of the frame's block 0 in d_block_offsets / d_block_init */
   uint32_t width, height; /* pixels, 1..65535 */
@@ -1071,6 +1072,130 @@ int mh_encode_images_shared_device_async(
     uint64_t *d_frame_code_offsets, uint32_t *d_block_offsets, uint8_t *d_block_init,
     int32_t *d_status, int32_t *d_header_status,
     void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* A SET of frames of different sizes encoded in one call: the producer of what the            */
+/* mh_decode_set_* entries consume. n frames, each with its own width, height, source address  */
+/* and Huffman table, go straight into the frame-set layout (mh_frame_geom above) in three      */
+/* launches whatever n and whatever the number of sizes; every accepted frame is byte for byte */
+/* mh_encode_frame's. A host planner (no HIP call) turns the n source records into a plan blob */
+/* in device format; the caller uploads it and hands it to the entry.                          */
+/* Not covered: a shared table over a set; mh_check_frames over a set; compaction of the code  */
+/* slots (frame f keeps its whole codes_cap slot).                                              */
+typedef struct {
+  uint64_t pixels;        /* absolute device address of sample (0, 0); frames may be separate
+                             allocations */
+  uint64_t row_pitch;     /* bytes from row y to row y + 1 (ignored for height == 1) */
+  uint32_t pixel_stride;  /* bytes from pixel x to pixel x + 1, 1..255 */
+  uint32_t width, height; /* pixels, 1..65535 */
+  uint32_t reserved;      /* must be 0 */
+  uint64_t codes_cap;     /* the frame's code slot in bytes: a multiple of 16, at least 16 */
+} mh_set_source;          /* 40 bytes */
+
+/* Sample (x, y) of frame f is the byte at pixels + y * row_pitch + x * pixel_stride, so plane c of
+ * an interleaved K-channel image is a frame with pixel_stride = K and pixels = image +
+ * first_channel + c. Reads: of frame f only bytes in [pixels, pixels + (height - 1) * row_pitch +
+ * width * pixel_stride), and no output depends on a byte that is not a sample (as for
+ * mh_encode_images_device_async). */
+
+/* The plan's record of frame f, as the kernels read it (device format; written by the planner). */
+typedef struct {
+  uint64_t pixels;
+  uint64_t slot_offset;   /* the frame's code slot: the prefix sum of codes_cap in frame order */
+  uint64_t codes_cap;
+  uint32_t row_pitch;     /* 0 for height == 1 */
+  uint32_t pixel_stride;
+  uint32_t width, height;
+  uint32_t block_width;   /* ceil(width / 8) */
+  uint32_t n_blocks;      /* NB_f */
+  uint32_t n_tiles;       /* ceil(NB_f / MH_SET_TILE_BLOCKS) */
+  uint32_t first_tile;    /* the prefix sum of n_tiles */
+  uint32_t first_block;   /* the prefix sum of NB: mh_frame_geom.first_block */
+  uint32_t reserved;
+} mh_set_frame;           /* 64 bytes */
+
+#define MH_SET_TILE_BLOCKS 256u /* blocks per split workgroup and per packer wave */
+#define MH_SET_PACK_TILES 4u    /* tiles of ONE frame per pack workgroup */
+#define MH_SET_FETCH_BYTES 0xFFu
+
+/* What the planner derives from the n records: the entry takes it back as it is. */
+typedef struct {
+  uint64_t codes_bytes;      /* the sum of codes_cap: the least d_codes may hold */
+  uint64_t workspace_bytes;  /* the least d_workspace may hold */
+  uint64_t plan_bytes;       /* mh_encode_set_plan_bytes() */
+  uint64_t geoms_offset;     /* d_plan + geoms_offset: n mh_frame_geom records, 16-byte aligned,
+                                the d_geoms of the mh_decode_set_* entries */
+  uint64_t split_map_offset; /* split_grid x (u32 frame, u32 tile) */
+  uint64_t pack_map_offset;  /* pack_grid x (u32 frame, u32 first tile of MH_SET_PACK_TILES) */
+  uint32_t n_frames;
+  uint32_t total_blocks;     /* sum of NB_f: entries of d_block_offsets / d_block_init */
+  uint32_t total_tiles;
+  uint32_t split_grid;       /* workgroups of the split (= total_tiles) ... */
+  uint32_t pack_grid;        /* ... and of the packer */
+  uint32_t max_width, max_height; /* the largest in the set: the dims of the set's mh_frame */
+  uint32_t fetch_mode;       /* 1..4: dword loads at that pixel stride; MH_SET_FETCH_BYTES */
+} mh_set_totals;             /* 80 bytes */
+
+/* Bytes of the plan blob for these records; 0 when mh_encode_set_plan would refuse them. The blob
+ * holds the n mh_set_frame records at offset 0, then the geometry records, the split map and the
+ * pack map at the offsets in mh_set_totals (each 16-byte aligned). */
+size_t mh_encode_set_plan_bytes(uint32_t n_frames, const mh_set_source *sources);
+
+/* Write the plan of n_frames records into h_plan (host memory, plan_bytes) and its totals. Pure
+ * host code: no HIP call, runs without a GPU. flags are the entry's (they are only validated).
+ * Geometry: first_block is the prefix sum of NB_f in frame order, exactly what a packer of the
+ * host-encoded frames produces. Fetch mode, one per call: dword loads when every record has the
+ * same pixel_stride <= 4, every row_pitch (for height > 1) is a multiple of 4 and every pixels is
+ * either a multiple of 4 or the address of a later byte of a pixel that starts on one (pixels % 4
+ * < pixel_stride: plane c of an aligned interleaved image); byte loads otherwise. In the dword
+ * mode the loads are whole aligned dwords from the one that holds sample (0, 0) on, so the up to 3
+ * bytes between that dword's start and `pixels` may be loaded too (never used); no load reaches
+ * past the frame's last sample.
+ * Checks, in this order, each over all records before the next:
+ *  1. NULL sources, h_plan or totals, n_frames == 0 -> MH_ERR_INVALID_ARG;
+ *  2. a reserved word != 0 or a flag other than MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED |
+ *     MH_ENCODE_LIMIT_LENGTHS -> MH_ERR_INVALID_ARG;
+ *  3. width or height 0 or above 65535, pixel_stride 0 or above 255 -> MH_ERR_DIMS;
+ *  4. codes_cap not a multiple of 16, or 0 -> MH_ERR_ALIGN;
+ *  5. MH_ERR_CAPACITY: height > 1 and row_pitch < width * pixel_stride; a record that is not
+ *     addressable (MH_IMAGE_TILE_SPAN_MAX above, for this record's width, height, row_pitch and
+ *     pixel_stride); total_blocks above 2^32 - 1; more than 2^31 - 1 tiles or frames; a sum of
+ *     codes_cap above 2^64 - 1; plan_bytes below mh_encode_set_plan_bytes(). */
+int mh_encode_set_plan(uint32_t n_frames, const mh_set_source *sources, uint32_t flags, void *h_plan,
+                       size_t plan_bytes, mh_set_totals *totals);
+
+/* Encode the set. d_plan: the uploaded blob (16-byte aligned); totals: the planner's, unchanged.
+ * Outputs, per frame f: d_canon_headers + 256 f; codes at d_codes + slot_offset_f, the slot's size
+ * codes_cap_f being the frame's capacity; d_codes_len[f] (optional); d_block_offsets and
+ * d_block_init (optional) at [first_block_f, first_block_f + NB_f) of total_blocks entries;
+ * d_status[f] (optional); d_frame_code_offsets (REQUIRED, n_frames + 1 u64, written by the device
+ * from the plan: slot_offset_f, then codes_bytes). With d_plan + geoms_offset they are one frame
+ * set: for mh_build_luts_device over d_canon_headers and the mh_decode_set_* entries, d_status
+ * going in as d_frame_status, without touching the host.
+ * flags, the status values, what is written of a slot ([0, round_up(codes_len, 4)) and nothing
+ * behind it) and what a rejected frame leaves behind (no code byte, no offset, d_codes_len 0, its
+ * d_block_init entries unspecified) are mh_encode_frames_device_async's, with codes_cap_f in the
+ * place of codes_frame_stride. A rejected frame disturbs no other frame, whatever their sizes.
+ * Checks, all before any HIP call, in that entry's order: NULL d_plan, totals, d_canon_headers,
+ * d_codes, d_frame_code_offsets, d_block_offsets or d_workspace, n_frames, total_tiles or
+ * total_blocks 0, an unknown flag or fetch mode -> MH_ERR_INVALID_ARG; max_width or max_height 0
+ * or above 65535 -> MH_ERR_DIMS; d_codes or d_plan not 16-byte, d_workspace not 256-byte aligned
+ * -> MH_ERR_ALIGN; codes_bytes below totals->codes_bytes, more than 2^31 - 1 frames or tiles, grids
+ * that do not match the tile count, workspace_bytes below totals->workspace_bytes ->
+ * MH_ERR_CAPACITY.
+ * The plan is trusted as a prepared table is: the kernels do not validate its records. Their
+ * stores of init bytes, block offsets and code words are bounded by the totals all the same (a
+ * frame's descriptors end at total_blocks and codes_bytes), so a stale plan cannot store outside
+ * the caller's arrays.
+ * Launches: three (split, one tree workgroup per frame, packer), the batched entries' kernels
+ * with one more source type: each split and pack workgroup loads its map entry and then its
+ * frame's record, both wave-uniform. d_workspace: 256-byte aligned, any content. Asynchronous on
+ * `stream`; d_plan must stay alive and unchanged until the launches have run. */
+int mh_encode_set_device_async(const void *d_plan, const mh_set_totals *totals, uint32_t flags,
+                               uint8_t *d_canon_headers, uint8_t *d_codes, uint64_t codes_bytes,
+                               uint64_t *d_codes_len, uint64_t *d_frame_code_offsets,
+                               uint32_t *d_block_offsets, uint8_t *d_block_init, int32_t *d_status,
+                               void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------- */
 /* Streaming from host memory (BASELINE config 5; the reference's per-frame  */

@@ -40,6 +40,10 @@ of mdejong/MetalHuffman).
                                     encode_images_async / encode_images_shared_async: interleaved, pitched
                                     [n, H, W, K] pixels (any view with adjacent channels) straight into C-plane
                                     frames, no transposed copy; codec.image_planes defines the planes
+  * encoder.encode_set_async / encode_image_set_async   frames (planes of images) of DIFFERENT sizes, a table
+                                    each, straight into the frame-set layout in three launches; AsyncEncodedSet
+                                    .frame_set() / .table_set() feed decode_set_crops* with no host sync;
+                                    codec.encode_set_plan is the host planner (no GPU needed)
   * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
 """
@@ -47,7 +51,7 @@ from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE
                       MH_FLAG_LANE_PAIRS,
                       MH_FLAG_NO_DELTA, MH_MAX_PLANES, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
 from .codec import (BLOCK_DIM, EncodedFrame, FrameSetLayout, Huffman, block_grid, box_reduce, check_frame, code_lengths_limited,
-                    decode_frame_cpu, encode_frame, frame_histogram, frame_set_layout, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
+                    decode_frame_cpu, encode_frame, encode_set_plan, frame_histogram, frame_set_layout, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
                     split_blocks)
 
 __all__ = [
@@ -56,6 +60,6 @@ __all__ = [
     "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
     "norm_table", "MH_NORM_F16", "MH_NORM_BF16", "MH_NORM_F32", "MH_CROP_MIRROR",
     "MH_MAX_PLANES", "norm_coefficients", "image_planes", "check_frame", "MH_ERR_STREAM",
-    "FrameSetLayout", "frame_set_layout",
+    "FrameSetLayout", "frame_set_layout", "encode_set_plan",
 ]
 __version__ = "0.1.0"

@@ -60,6 +60,7 @@ EXPORTS = (
     "mh_encode_images_device_async", "mh_encode_images_shared_device_async",
     "mh_check_frames", "mh_check_frames_shape", "mh_check_headers", "mh_check_headers_shape",
     "mh_check_frame_cpu",
+    "mh_encode_set_plan_bytes", "mh_encode_set_plan", "mh_encode_set_device_async",
 )
 
 
@@ -123,6 +124,34 @@ class mh_image_layout(ctypes.Structure):
                 ("n_planes", ctypes.c_uint32), ("plane_major", ctypes.c_uint32)]
 
 
+class mh_set_source(ctypes.Structure):
+    """One frame of mh_encode_set_plan: sample (x, y) is the byte at pixels + y * row_pitch + x * pixel_stride."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("row_pitch", ctypes.c_uint64), ("pixel_stride", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("codes_cap", ctypes.c_uint64)]
+
+
+class mh_set_frame(ctypes.Structure):
+    """The plan's record of one frame (device format)."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("slot_offset", ctypes.c_uint64), ("codes_cap", ctypes.c_uint64),
+                ("row_pitch", ctypes.c_uint32), ("pixel_stride", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("block_width", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32),
+                ("n_tiles", ctypes.c_uint32), ("first_tile", ctypes.c_uint32), ("first_block", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class mh_set_totals(ctypes.Structure):
+    _fields_ = [("codes_bytes", ctypes.c_uint64), ("workspace_bytes", ctypes.c_uint64),
+                ("plan_bytes", ctypes.c_uint64), ("geoms_offset", ctypes.c_uint64),
+                ("split_map_offset", ctypes.c_uint64), ("pack_map_offset", ctypes.c_uint64),
+                ("n_frames", ctypes.c_uint32), ("total_blocks", ctypes.c_uint32), ("total_tiles", ctypes.c_uint32),
+                ("split_grid", ctypes.c_uint32), ("pack_grid", ctypes.c_uint32), ("max_width", ctypes.c_uint32),
+                ("max_height", ctypes.c_uint32), ("fetch_mode", ctypes.c_uint32)]
+
+
+MH_SET_TILE_BLOCKS = 256  # blocks per tile of the set encoder's maps
+MH_SET_PACK_TILES = 4     # tiles of one frame per pack workgroup
+MH_SET_FETCH_BYTES = 0xFF  # mh_set_totals.fetch_mode: byte loads (1..4: dword loads at that pixel stride)
 MH_IMAGE_TILE_SPAN_MAX = 0x7FFFFFF0  # mh_encode_images_*: the most bytes one tile's descriptor spans
 
 
@@ -305,6 +334,12 @@ def lib() -> ctypes.CDLL:
             [_vp, ctypes.POINTER(mh_image_layout)] + L.mh_encode_frames_device_async.argtypes[2:])
         L.mh_encode_images_shared_device_async.argtypes = (
             [_vp, ctypes.POINTER(mh_image_layout)] + L.mh_encode_frames_shared_device_async.argtypes[2:])
+        L.mh_encode_set_plan_bytes.argtypes = [ctypes.c_uint32, ctypes.POINTER(mh_set_source)]
+        L.mh_encode_set_plan_bytes.restype = ctypes.c_size_t
+        L.mh_encode_set_plan.argtypes = [ctypes.c_uint32, ctypes.POINTER(mh_set_source), ctypes.c_uint32, _vp,
+                                         ctypes.c_size_t, ctypes.POINTER(mh_set_totals)]
+        L.mh_encode_set_device_async.argtypes = [_vp, ctypes.POINTER(mh_set_totals), ctypes.c_uint32, _vp, _vp,
+                                                 ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
         L.mh_frame_histogram.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
                                          _u64p]
         L.mh_encode_frame_with_header.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p,

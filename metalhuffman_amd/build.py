@@ -41,7 +41,8 @@ SOURCES = {
     "mh_cpu.o": ("mh_cpu.cpp", ["g++", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-c"]),
 }
 HEADERS = [os.path.join(ROOT, "include", "metalhuffman.h"), os.path.join(CSRC, "mh_lut.hpp"),
-           os.path.join(CSRC, "mh_stream_internal.hpp"), os.path.join(CSRC, "mh_box.hpp")]
+           os.path.join(CSRC, "mh_stream_internal.hpp"), os.path.join(CSRC, "mh_box.hpp"),
+           os.path.join(CSRC, "mh_set_plan.hpp")]
 LINK_FLAGS = [f"--offload-arch={ARCH}", "-shared", "-fPIC", "-pthread"]
 
 

@@ -157,6 +157,63 @@ def frame_set_layout(frames) -> FrameSetLayout:
                           max(f.height for f in frames), frames[0].flags)
 
 
+class SetPlan(NamedTuple):
+    """encode_set_plan's result: the plan blob (device format, u8) and its mh_set_totals, with the
+    blob's parts as numpy views."""
+    plan: np.ndarray
+    totals: "N.mh_set_totals"
+
+    @property
+    def records(self) -> np.ndarray:
+        """The n mh_set_frame records as a ctypes array over the blob."""
+        return (N.mh_set_frame * self.totals.n_frames).from_buffer(self.plan)
+
+    @property
+    def geoms(self) -> np.ndarray:
+        """u32[n, 4]: the mh_frame_geom records (first_block, width, height, 0)."""
+        t = self.totals
+        return self.plan[t.geoms_offset: t.geoms_offset + 16 * t.n_frames].view(np.uint32).reshape(-1, 4)
+
+    @property
+    def split_map(self) -> np.ndarray:
+        """u32[split_grid, 2]: (frame, tile) of every split workgroup."""
+        t = self.totals
+        return self.plan[t.split_map_offset: t.split_map_offset + 8 * t.split_grid].view(np.uint32).reshape(-1, 2)
+
+    @property
+    def pack_map(self) -> np.ndarray:
+        """u32[pack_grid, 2]: (frame, first tile) of every pack workgroup's MH_SET_PACK_TILES tiles."""
+        t = self.totals
+        return self.plan[t.pack_map_offset: t.pack_map_offset + 8 * t.pack_grid].view(np.uint32).reshape(-1, 2)
+
+
+def set_sources(sources):
+    """A ctypes array of mh_set_source from records or (pixels, row_pitch, pixel_stride, width, height,
+    codes_cap[, reserved]) tuples."""
+    sources = list(sources)
+    arr = (N.mh_set_source * max(len(sources), 1))()
+    for i, s in enumerate(sources):
+        if isinstance(s, N.mh_set_source):
+            arr[i] = s
+        else:
+            pixels, pitch, ps, w, h, cap = s[:6]
+            arr[i] = N.mh_set_source(pixels, pitch, ps, w, h, s[6] if len(s) > 6 else 0, cap)
+    return arr, len(sources)
+
+
+def encode_set_plan(sources, flags: int = 0) -> SetPlan:
+    """The host planner of the set encoder (mh_encode_set_plan; no GPU needed): from one source record
+    per frame -- (pixels, row_pitch, pixel_stride, width, height, codes_cap) -- the plan blob the device
+    reads and the set's totals. MHError carries the planner's code."""
+    arr, n = set_sources(sources)
+    L = N.lib()
+    size = int(L.mh_encode_set_plan_bytes(n, arr))
+    plan = np.zeros(max(size, 16), np.uint8)
+    totals = N.mh_set_totals()
+    N.check(L.mh_encode_set_plan(n, arr, flags, plan.ctypes.data, size, ctypes.byref(totals)), "mh_encode_set_plan")
+    return SetPlan(plan[:size], totals)
+
+
 class Huffman:
     """Stateless mirror of the reference's `Huffman` class (Shared/Huffman.h)."""
 

@@ -22,6 +22,9 @@
 // entries reading interleaved, pitched images: one frame per taken plane, the split and
 // the packer with another pixel fetch (see "interleaved, pitched images" below; both
 // kernels are templates over the source, PlanarSrc or ImagesSrc).
+// mh_encode_set_device_async is the per-frame-table entry over a SET of frames of different
+// sizes (SetSrc: each workgroup's frame and tile come from a host-made plan, mh_set_plan.hpp
+// and mh_host.cpp), straight into the frame-set layout the mh_decode_set_* entries read.
 // mh_encode_frame_device_async never synchronises (header, code bytes and status are
 // written to device memory); mh_encode_frame_device runs it and synchronises once at
 // the end to return the header and the byte count on the host.
@@ -34,6 +37,7 @@
 #include <cstring>
 
 #include "../../include/metalhuffman.h"
+#include "mh_set_plan.hpp"
 
 
 namespace {
@@ -374,13 +378,30 @@ __device__ __forceinline__ uint64_t img_row(__amdgpu_buffer_rsrc_t rg, uint32_t 
 // the source-specific parts under `if constexpr (Src::kImages)`; the planar instantiations
 // compile to what they were before the images existed.
 struct PlanarSrc {
-  static constexpr bool kImages = false;
+  static constexpr bool kImages = false, kSet = false;
   uint64_t gray_stride;
 };
 struct ImagesSrc {
-  static constexpr bool kImages = true;
+  static constexpr bool kImages = true, kSet = false;
   ImgSrc im;
 };
+// A frame SET (mh_encode_set_device_async): every frame has its own size, address, pitch and
+// pixel stride, in the plan's records. Workgroup g loads map[g] = (frame, tile) and then
+// recs[frame], both wave-uniform; from there on it is an images workgroup of one plane (the
+// plane's byte is part of the record's address). The per-tile workspace parts are indexed
+// through the record's first_tile, the caller's per-block arrays through first_block, and the
+// stores into the caller's arrays are bounded by the set's totals.
+struct SetSrc {
+  static constexpr bool kImages = true, kSet = true;
+  const mh_set_frame *recs;
+  const uint2 *map;       // this launch's: the split's tiles or the packer's units
+  uint64_t codes_bytes;   // the set's code bytes ...
+  uint32_t total_blocks;  // ... and blocks: where the descriptors of the caller's arrays end
+};
+// The entries of [first, first + n) that lie inside a set's `total`.
+__device__ __forceinline__ uint64_t set_clip(uint64_t first, uint64_t n, uint64_t total) {
+  return first >= total ? 0ull : min(n, total - first);
+}
 
 // The tiled split's rows: lane k's blocks tb + k + 32 u (u < N) of the tile starting at
 // block tb, row r, from one descriptor at the tile's first block row. The tile's
@@ -498,7 +519,27 @@ __global__ void __launch_bounds__(256) enc_split_kernel(const uint8_t *gray, uin
   static_assert(!kImages || (kTiled && !kVec), "image planes take the tiled split and their own fetch");
   uint32_t wg = blockIdx.x;  // tiled: this frame's tile
   [[maybe_unused]] uint32_t ch = 0;
-  if constexpr (kImages) {
+  [[maybe_unused]] uint32_t set_pitch = 0, set_ps = 1;
+  [[maybe_unused]] uint64_t set_init = 0;  // a set: the frame's init bytes inside the set's total
+  if constexpr (Src::kSet) {
+    const uint2 m = src.map[blockIdx.x];
+    const mh_set_frame &rc = src.recs[__builtin_amdgcn_readfirstlane(m.x)];
+    wg = __builtin_amdgcn_readfirstlane(m.y);
+    // dword modes: the loads start at the aligned dword that holds sample (0, 0), whose byte in it
+    // is the plane's (below the pixel stride: the planner's rule for the mode)
+    ch = kPs == kBytePs ? 0u : (uint32_t)rc.pixels & 3u;
+    gray = reinterpret_cast<const uint8_t *>(rc.pixels) - ch;
+    W = rc.width;
+    H = rc.height;
+    bw = rc.block_width;
+    nb = rc.n_blocks;
+    set_pitch = rc.row_pitch;
+    set_ps = rc.pixel_stride;
+    set_init = set_clip(rc.first_block, rc.n_blocks, src.total_blocks);
+    if (block_init) block_init += rc.first_block;
+    tile_hist += (uint64_t)rc.first_tile * 256;
+    tile_tail += (uint64_t)rc.first_tile * 8;
+  } else if constexpr (kImages) {
     uint32_t f, img, c;
     img_unit(src.im, blockIdx.x, ncode, f, wg, img, c);
     gray += img * src.im.image_stride;
@@ -536,7 +577,7 @@ __global__ void __launch_bounds__(256) enc_split_kernel(const uint8_t *gray, uin
   const uint32_t copy = threadIdx.x % kHistCopies;
   const bool delta = !(flags & MH_FLAG_NO_DELTA);
   // block_init: buffer stores (lanes without a byte out of range)
-  const __amdgpu_buffer_rsrc_t rinit = enc_rsrc(block_init, block_init ? nb : 0ull);
+  const __amdgpu_buffer_rsrc_t rinit = enc_rsrc(block_init, block_init ? (Src::kSet ? set_init : nb) : 0ull);
   // one group of 32 blocks (four-kernel path; the fused path's packer re-derives the
   // symbols from the pixels): deltas, init bytes, symbols out, histogram
   auto process = [&](uint64_t g, uint64_t q) {
@@ -559,7 +600,8 @@ __global__ void __launch_bounds__(256) enc_split_kernel(const uint8_t *gray, uin
     // row), and the tile's last block's symbols (batched path, tile_tail) once at the end.
     const uint32_t nb32 = (uint32_t)nb, tb = wg * kTile;
     uint64_t q[kGroups];
-    if constexpr (kImages) tile_rows<true, kPs, false, kGroups, kTile>(gray, src.im.pitch, src.im.ps, ch, W, H, bw, nb, tb, r, q);
+    if constexpr (Src::kSet) tile_rows<true, kPs, false, kGroups, kTile>(gray, set_pitch, set_ps, ch, W, H, bw, nb, tb, r, q);
+    else if constexpr (kImages) tile_rows<true, kPs, false, kGroups, kTile>(gray, src.im.pitch, src.im.ps, ch, W, H, bw, nb, tb, r, q);
     else tile_rows<false, 0, kVec, kGroups, kTile>(gray, W, 1u, 0u, W, H, bw, nb, tb, r, q);
     clear_hist();
 #if MH_CODE_STAMPS
@@ -1649,6 +1691,23 @@ __device__ __forceinline__ void frame_tile_offsets(const uint16_t *th, uint32_t 
   if (tid == 0) to[ncode] = carry;
 }
 
+// One frame's tree workgroup of the batched path: its symbol counts from its tile counts th, the
+// tree (tree_body), then its ncode + 1 tile bit offsets. The pointers are the frame's own.
+__device__ __forceinline__ void tree_batch_body(uint8_t *canon, uint32_t *table, uint64_t *meta, uint64_t *codes_len,
+                                                uint64_t codes_cap, int32_t *status, uint64_t nb, const uint16_t *th,
+                                                uint32_t ncode, uint32_t *tile_off, uint32_t limit) {
+  const uint32_t tid = threadIdx.x;
+  __shared__ uint32_t s_cnt[256];
+  frame_symbol_counts(th, ncode, s_cnt);
+  const uint32_t e = tree_body<false>(nullptr, canon, table, meta, codes_len, codes_cap, status, nb * 64, limit != 0u, s_cnt);
+  if (tid >= 256) return;  // tree_body leaves the 256 symbol threads (4 waves)
+  __shared__ uint32_t s_len[256];
+  s_len[tid] = e & 0x1Fu;
+  lds_barrier();
+  if (e & 0x80u) return;  // rejected frame (uniform): the pack kernel writes nothing
+  frame_tile_offsets(th, ncode, tile_off, s_len);
+}
+
 __global__ void __launch_bounds__(kTreeThreads) enc_tree_batch_kernel(
     uint64_t *hist, uint8_t *canon, uint32_t *table, uint64_t *meta, uint64_t *codes_len, uint64_t codes_cap,
     int32_t *status, uint64_t nb, const uint16_t *tile_hist, uint32_t ncode, uint32_t *tile_off,
@@ -1671,6 +1730,30 @@ __global__ void __launch_bounds__(kTreeThreads) enc_tree_batch_kernel(
   lds_barrier();
   if (e & 0x80u) return;  // rejected frame (uniform): the pack kernel writes nothing
   frame_tile_offsets(tile_hist + (uint64_t)f * ncode * 256, ncode, tile_off + (uint64_t)f * (ncode + 1), s_len);
+}
+
+// ... of a frame SET: frame f's block and tile counts, capacity and slot come from its record,
+// its tile counts and offsets lie behind the plan's first-tile prefix (offsets: ncode_f + 1 per
+// frame, so f entries further), and d_frame_code_offsets is the plan's slot offsets. The frame's
+// part is tree_batch_body, the batch kernel's lines above over the frame's own pointers
+// (enc_tree_batch_kernel itself keeps them written out: calling the shared body from it moved
+// two of its instructions, and the kernels that existed stay instruction for instruction what
+// they were -- profiles/encode_set_isa.txt).
+__global__ void __launch_bounds__(kTreeThreads) enc_tree_set_kernel(
+    const mh_set_frame *recs, uint64_t codes_bytes, uint32_t n_frames, uint8_t *canon, uint32_t *table, uint64_t *meta,
+    uint64_t *codes_len, int32_t *status, const uint16_t *tile_hist, uint32_t *tile_off, uint64_t *frame_off,
+    uint32_t limit) {
+  const uint32_t f = blockIdx.x;
+  const mh_set_frame &rc = recs[f];
+  const uint64_t slot = rc.slot_offset, cap = rc.codes_cap;
+  const uint32_t nb = rc.n_blocks, ncode = rc.n_tiles, tile0 = rc.first_tile;
+  if (threadIdx.x == 0) {
+    frame_off[f] = slot;
+    if (f + 1 == n_frames) frame_off[n_frames] = codes_bytes;
+  }
+  tree_batch_body(canon + (uint64_t)f * 256, table + (uint64_t)f * 256, meta + (uint64_t)f * kMetaWords,
+                  codes_len ? codes_len + f : nullptr, cap, status ? status + f : nullptr, nb,
+                  tile_hist + (uint64_t)tile0 * 256, ncode, tile_off + (uint64_t)tile0 + f, limit);
 }
 
 // ---- batched frames under ONE table: mh_encode_frames_shared_device_async ------------
@@ -1872,10 +1955,10 @@ __device__ __forceinline__ void wave_sync() {
 // (img_row<kPs>) differ, nothing behind the fetch does.
 template <typename Src, uint32_t kPs, bool kVec, bool kPair>
 __global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_kernel(
-    const Pixels px, const Src src, uint64_t nb, uint32_t ncode, const uint32_t *table, const uint64_t *meta,
+    Pixels px, const Src src, uint64_t nb, uint32_t ncode, const uint32_t *table, const uint64_t *meta,
     const uint32_t *tile_off, uint32_t *offsets, uint8_t *codes, uint64_t codes_stride, uint32_t ncode_wg,
     const uint64_t *tile_tail) {
-  constexpr bool kImages = Src::kImages;
+  constexpr bool kImages = Src::kImages, kSet = Src::kSet;
   static_assert(!kImages || (!kVec && !kPair), "image planes take their own fetch");
   // ncode_wg: workgroups per frame (ncode rounded up to kPackWaves tiles): a workgroup's
   // waves pack tiles of ONE frame and share its table, at a fixed LDS address (the
@@ -1890,7 +1973,32 @@ __global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_kernel(
   // ps bytes from pixel to pixel
   uint32_t f, t, rowb = px.W;
   [[maybe_unused]] uint32_t img = 0, pch = 0, ps = 1;
-  if constexpr (kImages) {
+  // a set: the frame's first tile and block in the per-tile and per-block arrays, its code slot,
+  // and how much of the slot and of its block entries lies inside the set's totals
+  [[maybe_unused]] uint32_t set_tile0 = 0, set_block0 = 0;
+  [[maybe_unused]] uint64_t set_slot = 0, set_slot_n = 0, set_blocks_n = 0;
+  if constexpr (kSet) {
+    // the unit's map entry, then the frame's record (wave-uniform loads); px, nb and ncode become
+    // the frame's own
+    const uint2 m = src.map[blockIdx.x];
+    f = __builtin_amdgcn_readfirstlane(m.x);
+    t = __builtin_amdgcn_readfirstlane(m.y) + wave;
+    const mh_set_frame &rc = src.recs[f];
+    pch = kPs == kBytePs ? 0u : (uint32_t)rc.pixels & 3u;  // dword modes: as in the split
+    px.gray = reinterpret_cast<const uint8_t *>(rc.pixels) - pch;
+    px.W = rc.width;
+    px.H = rc.height;
+    px.bw = rc.block_width;
+    nb = rc.n_blocks;
+    ncode = rc.n_tiles;
+    rowb = rc.row_pitch;
+    ps = kPs == kBytePs ? rc.pixel_stride : kPs;
+    set_tile0 = rc.first_tile;
+    set_block0 = rc.first_block;
+    set_slot = rc.slot_offset;
+    set_slot_n = set_clip(rc.slot_offset, rc.codes_cap, src.codes_bytes);
+    set_blocks_n = set_clip(rc.first_block, rc.n_blocks, src.total_blocks);
+  } else if constexpr (kImages) {
     uint32_t unit, plane;
     img_unit(src.im, blockIdx.x, ncode_wg, f, unit, img, plane);
     t = unit * kPackWaves + wave;
@@ -1912,9 +2020,10 @@ __global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_kernel(
   lds_barrier();
   if (t >= ncode) return;  // wave-uniform padding past the frame's last tile; no barrier follows
   uint32_t *lw = s_w[wave];
-  const uint32_t E = tile_off[(uint64_t)f * (ncode + 1) + t];
+  const uint32_t E = tile_off[kSet ? (uint64_t)set_tile0 + f + t : (uint64_t)f * (ncode + 1) + t];
   const uint8_t *gray = px.gray;  // the frame's, or the image's, first byte
-  if constexpr (kImages) gray += img * src.im.image_stride;
+  if constexpr (kSet) {}  // the record's address
+  else if constexpr (kImages) gray += img * src.im.image_stride;
   else gray += f * src.gray_stride;
   const uint64_t b0 = (uint64_t)t * kBatchTile;
   const uint32_t nsteps = (uint32_t)((min<uint64_t>(kBatchTile, nb - b0) + kStepBlocks - 1) / kStepBlocks);
@@ -1971,7 +2080,8 @@ __global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_kernel(
   uint32_t head = 0;
   const uint32_t r0 = E & 31u;
   if (r0) {  // wave-uniform; t > 0 here (tile 0 starts at bit 0)
-    const __amdgpu_buffer_rsrc_t rt = enc_rsrc(tile_tail + ((uint64_t)f * ncode + t - 1u) * 8u, 64u);
+    const __amdgpu_buffer_rsrc_t rt =
+        enc_rsrc(tile_tail + (kSet ? (uint64_t)set_tile0 + t - 1u : (uint64_t)f * ncode + t - 1u) * 8u, 64u);
     typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
     const v2u32 tv = __builtin_amdgcn_raw_buffer_load_b64(rt, (int)(lane < 8 ? lane * 8u : kOob), 0, 0);
     const uint64_t qp = ((uint64_t)tv.y << 32) | tv.x;
@@ -2002,8 +2112,9 @@ __global__ void __launch_bounds__(kPackWaves * 64) enc_pack_wave_kernel(
     if (lane < kStepSlots / 4 - 128) lq[128 + lane] = v4u32{0u, 0u, 0u, 0u};
   };
   clear_words(bswap32(head));
-  const __amdgpu_buffer_rsrc_t rw = enc_rsrc(codes + f * codes_stride, codes_stride);
-  const __amdgpu_buffer_rsrc_t ro = enc_rsrc(offsets + (uint64_t)f * nb, nb * 4u);
+  const __amdgpu_buffer_rsrc_t rw = enc_rsrc(codes + (kSet ? set_slot : f * codes_stride), kSet ? set_slot_n : codes_stride);
+  const __amdgpu_buffer_rsrc_t ro =
+      enc_rsrc(offsets + (kSet ? (uint64_t)set_block0 : (uint64_t)f * nb), (kSet ? set_blocks_n : nb) * 4u);
   uint32_t pos = E;
   uint32_t sbx = bx0, sby = by0;
   uint32_t sb = (uint32_t)b0;
@@ -2497,6 +2608,61 @@ int mh_encode_images_device_async(const uint8_t *d_pixels, const mh_image_layout
   return encode_batch(Source{d_pixels, 0, layout, n_images, true}, width, height, flags, d_canon_headers, d_codes,
                       codes_frame_stride, d_codes_len, d_frame_code_offsets, d_block_offsets, d_block_init, d_status,
                       d_workspace, workspace_bytes, stream);
+}
+
+// The batched path over a frame set: the three launches of encode_batch with the set's source
+// type, everything per-frame coming from the uploaded plan (mh_encode_set_plan, mh_host.cpp).
+#define MH_SET_MODE(mode, KERNEL, ...)                                                           \
+  ((mode) == 1   ? KERNEL<SetSrc, 1, __VA_ARGS__>                                                \
+   : (mode) == 2 ? KERNEL<SetSrc, 2, __VA_ARGS__>                                                \
+   : (mode) == 3 ? KERNEL<SetSrc, 3, __VA_ARGS__>                                                \
+   : (mode) == 4 ? KERNEL<SetSrc, 4, __VA_ARGS__>                                                \
+                 : KERNEL<SetSrc, kBytePs, __VA_ARGS__>)
+
+int mh_encode_set_device_async(const void *d_plan, const mh_set_totals *totals, uint32_t flags,
+                               uint8_t *d_canon_headers, uint8_t *d_codes, uint64_t codes_bytes,
+                               uint64_t *d_codes_len, uint64_t *d_frame_code_offsets,
+                               uint32_t *d_block_offsets, uint8_t *d_block_init, int32_t *d_status,
+                               void *d_workspace, size_t workspace_bytes, void *stream) {
+  static_assert(mh_set::kTileBlocks == kBatchTile && mh_set::kPackTiles == kPackWaves && mh_set::kMetaWords == kMetaWords &&
+                    mh_set::kByteMode == kBytePs && MH_SET_TILE_BLOCKS == kBatchTile && MH_SET_PACK_TILES == kPackWaves &&
+                    MH_SET_FETCH_BYTES == kBytePs && sizeof(mh_set_frame) == 64 && sizeof(mh_set_totals) == 80,
+                "the planner's constants and records are the kernels'");
+  // mh_encode_frames_device_async's checks in its order, every one before any HIP call
+  if (!d_plan || !totals || !d_canon_headers || !d_codes || !d_frame_code_offsets || !d_block_offsets || !d_workspace)
+    return MH_ERR_INVALID_ARG;
+  const mh_set_totals &t = *totals;
+  if (!t.n_frames || !t.total_tiles || !t.total_blocks) return MH_ERR_INVALID_ARG;
+  EncodeFlags ef;
+  if (!split_encode_flags(flags, &ef)) return MH_ERR_INVALID_ARG;
+  if (!((t.fetch_mode >= 1 && t.fetch_mode <= 4) || t.fetch_mode == kBytePs)) return MH_ERR_INVALID_ARG;
+  if (!t.max_width || !t.max_height || t.max_width > MH_MAX_DIM || t.max_height > MH_MAX_DIM) return MH_ERR_DIMS;
+  if (((uintptr_t)d_codes & 15u) || ((uintptr_t)d_plan & 15u) || ((uintptr_t)d_workspace & 255u)) return MH_ERR_ALIGN;
+  if (codes_bytes < t.codes_bytes) return MH_ERR_CAPACITY;
+  if (t.n_frames > 0x7FFFFFFFu || t.total_tiles > 0x7FFFFFFFu || t.split_grid != t.total_tiles || !t.pack_grid ||
+      t.pack_grid > t.total_tiles)
+    return MH_ERR_CAPACITY;
+  if (workspace_bytes < mh_set::carve(nullptr, t.n_frames, t.total_tiles, nullptr) || workspace_bytes < t.workspace_bytes)
+    return MH_ERR_CAPACITY;
+  mh_set::Workspace w;
+  mh_set::carve(static_cast<uint8_t *>(d_workspace), t.n_frames, t.total_tiles, &w);
+  hipStream_t s = (hipStream_t)stream;
+  const uint8_t *plan = static_cast<const uint8_t *>(d_plan);
+  const mh_set_frame *recs = reinterpret_cast<const mh_set_frame *>(plan);
+  const SetSrc split_src{recs, reinterpret_cast<const uint2 *>(plan + t.split_map_offset), t.codes_bytes, t.total_blocks};
+  const SetSrc pack_src{recs, reinterpret_cast<const uint2 *>(plan + t.pack_map_offset), t.codes_bytes, t.total_blocks};
+  // every part of the workspace is written before it is read within the call (encode_batch)
+  hipLaunchKernelGGL(MH_SET_MODE(t.fetch_mode, enc_split_kernel, false, true, kBatchTile), dim3(t.split_grid), dim3(256), 0,
+                     s, nullptr, 0u, 0u, 0u, 0ull, ef.format, nullptr, d_block_init, nullptr, w.tile_hist, nullptr, 0u,
+                     split_src, w.tile_tail);
+  hipLaunchKernelGGL(enc_tree_set_kernel, dim3(t.n_frames), dim3(kTreeThreads), 0, s, recs, t.codes_bytes, t.n_frames,
+                     d_canon_headers, w.table, w.meta, d_codes_len, d_status, w.tile_hist, w.tile_off,
+                     d_frame_code_offsets, ef.limit);
+  const Pixels px{nullptr, 0u, 0u, 0u, 0u, !(ef.format & MH_FLAG_NO_DELTA), d_block_init != nullptr};
+  hipLaunchKernelGGL(MH_SET_MODE(t.fetch_mode, enc_pack_wave_kernel, false, false), dim3(t.pack_grid), dim3(kPackWaves * 64),
+                     0, s, px, pack_src, 0ull, 0u, w.table, w.meta, w.tile_off, d_block_offsets, d_codes, 0ull, 0u,
+                     w.tile_tail);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
 }
 
 size_t mh_encode_frames_shared_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_frames) {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/metalhuffman.h"
+#include "mh_set_plan.hpp"
 
 namespace {
 
@@ -534,6 +535,126 @@ int mh_norm_table(uint32_t format, float scale, float bias, void *table, size_t 
     else
       static_cast<uint16_t *>(table)[v] = format == MH_NORM_F16 ? f32_to_f16(bits) : f32_to_bf16(bits);
   }
+  return MH_OK;
+}
+
+// ---- the set encoder's planner (mh_encode_set_device_async, mh_encode.hip) ------------------
+// Everything the set kernels read that does not depend on a pixel, computed once on the host:
+// per-frame records, the decoders' geometry records, and the two workgroup maps.
+
+// One record under the images entries' addressing rule for one image (image_layout_fits,
+// mh_encode.hip): a row and the row pitch fit a tile's 32-bit descriptor, and so does the span
+// from a tile's first row to the last row one of its blocks lies in.
+static bool set_source_fits(const mh_set_source &s) {
+  const uint64_t row = (uint64_t)s.width * s.pixel_stride;  // < 2^24
+  if (s.height > 1 && (s.row_pitch < row || s.row_pitch > MH_IMAGE_TILE_SPAN_MAX)) return false;
+  const uint64_t pitch = s.height > 1 ? s.row_pitch : 0;
+  const uint64_t rows = std::min<uint64_t>(s.height, MH_IMAGE_TILE_ROWS(s.width));
+  return (rows - 1) * pitch + row <= MH_IMAGE_TILE_SPAN_MAX;
+}
+
+// Checks 1-5 but the blob's size, and the totals.
+static int set_plan_scan(uint32_t n, const mh_set_source *src, uint32_t flags, mh_set_totals *t) {
+  if (!src || !t || !n) return MH_ERR_INVALID_ARG;
+  if (flags & ~(MH_FLAG_NO_DELTA | MH_ENCODE_WORKSPACE_ZEROED | MH_ENCODE_LIMIT_LENGTHS)) return MH_ERR_INVALID_ARG;
+  for (uint32_t f = 0; f < n; ++f)
+    if (src[f].reserved) return MH_ERR_INVALID_ARG;
+  for (uint32_t f = 0; f < n; ++f) {
+    const mh_set_source &s = src[f];
+    if (!s.width || !s.height || s.width > MH_MAX_DIM || s.height > MH_MAX_DIM || !s.pixel_stride ||
+        s.pixel_stride > 255u)
+      return MH_ERR_DIMS;
+  }
+  for (uint32_t f = 0; f < n; ++f)
+    if (!src[f].codes_cap || (src[f].codes_cap & 15u)) return MH_ERR_ALIGN;
+  uint64_t blocks = 0, tiles = 0, units = 0, codes = 0;
+  uint32_t wmax = 0, hmax = 0;
+  uint64_t align = 0;
+  bool one_stride = true, in_pixel = true;
+  for (uint32_t f = 0; f < n; ++f) {
+    const mh_set_source &s = src[f];
+    if (!set_source_fits(s)) return MH_ERR_CAPACITY;
+    const uint64_t nb = (uint64_t)((s.width + 7) / 8) * ((s.height + 7) / 8);  // < 2^26
+    const uint64_t nt = (nb + mh_set::kTileBlocks - 1) / mh_set::kTileBlocks;
+    blocks += nb;
+    tiles += nt;
+    units += (nt + mh_set::kPackTiles - 1) / mh_set::kPackTiles;
+    if (codes + s.codes_cap < codes) return MH_ERR_CAPACITY;
+    codes += s.codes_cap;
+    wmax = std::max(wmax, s.width);
+    hmax = std::max(hmax, s.height);
+    align |= s.height > 1 ? s.row_pitch : 0;
+    one_stride = one_stride && s.pixel_stride == src[0].pixel_stride;
+    in_pixel = in_pixel && (s.pixels & 3u) < s.pixel_stride;
+  }
+  if (blocks > 0xFFFFFFFFull || tiles > 0x7FFFFFFFull || n > 0x7FFFFFFFu) return MH_ERR_CAPACITY;
+  std::memset(t, 0, sizeof(*t));
+  t->codes_bytes = codes;
+  t->workspace_bytes = mh_set::carve(nullptr, n, tiles, nullptr);
+  t->geoms_offset = (uint64_t)n * sizeof(mh_set_frame);
+  t->split_map_offset = t->geoms_offset + (uint64_t)n * sizeof(mh_frame_geom);
+  t->pack_map_offset = t->split_map_offset + mh_set::align16(tiles * 8);
+  t->plan_bytes = t->pack_map_offset + mh_set::align16(units * 8);
+  t->n_frames = n;
+  t->total_blocks = (uint32_t)blocks;
+  t->total_tiles = (uint32_t)tiles;
+  t->split_grid = (uint32_t)tiles;
+  t->pack_grid = (uint32_t)units;
+  t->max_width = wmax;
+  t->max_height = hmax;
+  t->fetch_mode = one_stride && in_pixel && src[0].pixel_stride <= 4u && !(align & 3u) ? src[0].pixel_stride : mh_set::kByteMode;
+  return MH_OK;
+}
+
+size_t mh_encode_set_plan_bytes(uint32_t n_frames, const mh_set_source *sources) {
+  mh_set_totals t;
+  return set_plan_scan(n_frames, sources, 0, &t) == MH_OK ? (size_t)t.plan_bytes : 0;
+}
+
+int mh_encode_set_plan(uint32_t n_frames, const mh_set_source *sources, uint32_t flags, void *h_plan,
+                       size_t plan_bytes, mh_set_totals *totals) {
+  if (!h_plan) return MH_ERR_INVALID_ARG;
+  mh_set_totals t;
+  const int rc = set_plan_scan(n_frames, sources, flags, totals ? &t : nullptr);
+  if (rc != MH_OK) return rc;
+  if (plan_bytes < t.plan_bytes) return MH_ERR_CAPACITY;
+  uint8_t *p = static_cast<uint8_t *>(h_plan);
+  std::memset(p, 0, (size_t)t.plan_bytes);
+  // the blob may sit at any host address: every record goes in by memcpy
+  uint64_t slot = 0;
+  uint32_t first_tile = 0, first_block = 0, unit = 0;
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    const mh_set_source &s = sources[f];
+    mh_set_frame r;
+    std::memset(&r, 0, sizeof(r));
+    r.pixels = s.pixels;
+    r.slot_offset = slot;
+    r.codes_cap = s.codes_cap;
+    r.row_pitch = s.height > 1 ? (uint32_t)s.row_pitch : 0u;  // <= MH_IMAGE_TILE_SPAN_MAX
+    r.pixel_stride = s.pixel_stride;
+    r.width = s.width;
+    r.height = s.height;
+    r.block_width = (s.width + 7) / 8;
+    r.n_blocks = r.block_width * ((s.height + 7) / 8);
+    r.n_tiles = (r.n_blocks + mh_set::kTileBlocks - 1) / mh_set::kTileBlocks;
+    r.first_tile = first_tile;
+    r.first_block = first_block;
+    std::memcpy(p + (size_t)f * sizeof(r), &r, sizeof(r));
+    const mh_frame_geom g = {first_block, s.width, s.height, 0};
+    std::memcpy(p + t.geoms_offset + (size_t)f * sizeof(g), &g, sizeof(g));
+    for (uint32_t k = 0; k < r.n_tiles; ++k) {
+      const uint32_t e[2] = {f, k};
+      std::memcpy(p + t.split_map_offset + (size_t)(first_tile + k) * 8, e, 8);
+    }
+    for (uint32_t k = 0; k < r.n_tiles; k += mh_set::kPackTiles, ++unit) {
+      const uint32_t e[2] = {f, k};
+      std::memcpy(p + t.pack_map_offset + (size_t)unit * 8, e, 8);
+    }
+    slot += s.codes_cap;
+    first_tile += r.n_tiles;
+    first_block += r.n_blocks;
+  }
+  *totals = t;
   return MH_OK;
 }
 

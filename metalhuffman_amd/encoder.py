@@ -419,3 +419,158 @@ def encode_frame_device(gray: torch.Tensor, flags: int = 0, init_zero_delta: boo
     """One-shot GPU encode of a [H, W] uint8 device tensor."""
     h, w = gray.shape
     return Encoder(w, h, gray.device).encode(gray, flags, init_zero_delta, limit_lengths=limit_lengths)
+
+
+def default_slot_bytes(width: int, height: int) -> int:
+    """BatchEncoder's slot rule for one frame size: the worst case of 16 bits per symbol plus the
+    pad, rounded up to 16 bytes, and 16 more."""
+    bw, bh = block_grid(width, height)
+    return (bw * bh * 64 * 2 + N.MH_CODES_PAD + 15) // 16 * 16 + 16
+
+
+def _plane_source(i: int, p: torch.Tensor, dev: torch.device) -> tuple:
+    """(address, row pitch, pixel stride, width, height) of one 2-D uint8 device view."""
+    if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 or p.dim() != 2:
+        raise ValueError(f"plane {i}: a 2-D uint8 tensor is required")
+    if p.device != dev:
+        raise ValueError(f"plane {i}: all planes must live on one HIP device")
+    h, w = p.shape
+    if not (1 <= w <= N.MH_MAX_DIM and 1 <= h <= N.MH_MAX_DIM):
+        raise ValueError(f"plane {i}: {w}x{h} is outside 1..{N.MH_MAX_DIM}")
+    # a dimension of size 1 may carry any stride: it is never stepped over
+    pitch = p.stride(0) if h > 1 else 0
+    ps = p.stride(1) if w > 1 else 1
+    if (h > 1 and pitch < 1) or not 1 <= ps <= 255:
+        raise ValueError(f"plane {i}: strides {tuple(p.stride())} -- rows need a positive stride, pixels one of 1..255")
+    return p.data_ptr(), pitch, ps, w, h
+
+
+def encode_set_async(planes, flags: int = 0, init_zero_delta: bool = False,
+                     stream: Optional[torch.cuda.Stream] = None, limit_lengths: bool = False,
+                     slot_bytes=None, n_planes: int = 1) -> "AsyncEncodedSet":
+    """Encode frames of DIFFERENT sizes, each under its own table, straight into the frame-set layout
+    in three launches (mh_encode_set_device_async): `planes` is a sequence of 2-D uint8 device
+    tensors or views with positive strides (img[..., c] of an HWC image, a window of a larger
+    picture), ready on `stream`. Every accepted frame is byte-identical to codec.encode_frame of that
+    plane. slot_bytes: one value or one per frame, multiples of 16 (default: BatchEncoder's rule for
+    each frame's size). The plan is made on the host and uploaded; nothing waits for the device.
+    n_planes: recorded on the result for the planes decode entries (frames i * n_planes + c)."""
+    planes = list(planes)
+    if not planes:
+        raise ValueError("no planes")
+    dev = planes[0].device if isinstance(planes[0], torch.Tensor) else None
+    if dev is None or dev.type != "cuda":
+        raise ValueError("the planes must be tensors on a HIP device")
+    heads = [_plane_source(i, p, dev) for i, p in enumerate(planes)]
+    n = len(heads)
+    if slot_bytes is None:
+        caps = [default_slot_bytes(s[3], s[4]) for s in heads]
+    elif isinstance(slot_bytes, int):
+        caps = [slot_bytes] * n
+    else:
+        caps = [int(c) for c in slot_bytes]
+        if len(caps) != n:
+            raise ValueError(f"{len(caps)} slot sizes for {n} planes")
+    from .codec import encode_set_plan
+    full_flags = flags | N.MH_ENCODE_WORKSPACE_ZEROED | _limit(limit_lengths)
+    host = encode_set_plan([s + (c,) for s, c in zip(heads, caps)], full_flags)
+    t = host.totals
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        plan = torch.from_numpy(host.plan).to(dev)
+        codes = torch.empty(t.codes_bytes + 16, dtype=torch.uint8, device=dev)
+        offs = torch.empty(t.total_blocks, dtype=torch.int32, device=dev)
+        init = torch.empty(t.total_blocks, dtype=torch.uint8, device=dev) if init_zero_delta else None
+        canon = torch.empty((n, 256), dtype=torch.uint8, device=dev)
+        lens = torch.empty(n, dtype=torch.int64, device=dev)
+        fco = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        workspace = torch.empty(t.workspace_bytes + 256, dtype=torch.uint8, device=dev)
+    if plan.data_ptr() % 16:
+        raise RuntimeError("the uploaded plan is not 16-byte aligned")
+    cbase = (codes.data_ptr() + 15) // 16 * 16
+    N.check(N.lib().mh_encode_set_device_async(
+        plan.data_ptr(), ctypes.byref(t), full_flags, canon.data_ptr(), cbase, t.codes_bytes, lens.data_ptr(),
+        fco.data_ptr(), offs.data_ptr(), init.data_ptr() if init is not None else None, status.data_ptr(),
+        *_workspace_ptr(workspace), _stream_ptr(stream, dev)), "mh_encode_set_device_async")
+    view = codes[cbase - codes.data_ptr(): cbase - codes.data_ptr() + t.codes_bytes]
+    es = AsyncEncodedSet(tuple((s[3], s[4]) for s in heads), tuple(caps), plan, t, canon, view, lens, fco, status, offs,
+                         init, flags, n_planes, 1)
+    es._alive = (planes, workspace, codes)  # read and written by the launches in flight
+    return es
+
+
+def encode_image_set_async(images, n_planes=None, first_channel: int = 0, flags: int = 0,
+                           init_zero_delta: bool = False, stream: Optional[torch.cuda.Stream] = None,
+                           limit_lengths: bool = False, slot_bytes=None) -> "AsyncEncodedSet":
+    """encode_set_async over interleaved images of different sizes: `images` is a sequence of uint8
+    [H_i, W_i, K] device tensors (any strides encode_set_async takes), C = n_planes planes are taken
+    from first_channel on (default: all behind it), and frame i * C + c is plane c of image i
+    (plane_frame_stride 1), read in place."""
+    images = list(images)
+    if not images:
+        raise ValueError("no images")
+    k = None
+    for i, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3:
+            raise ValueError(f"image {i}: a uint8 tensor [H, W, K] is required")
+        if k is not None and im.shape[2] != k:
+            raise ValueError(f"image {i}: {im.shape[2]} channels, the others have {k}")
+        k = int(im.shape[2])
+    c = k - first_channel if n_planes is None else int(n_planes)
+    if first_channel < 0 or c < 1 or first_channel + c > k:
+        raise ValueError(f"planes {first_channel}..{first_channel + c - 1} of {k}-channel pixels")
+    planes = [im[:, :, first_channel + j] for im in images for j in range(c)]
+    if slot_bytes is not None and not isinstance(slot_bytes, int):
+        slot_bytes = [int(s) for s in slot_bytes for _ in range(c)] if len(slot_bytes) == len(images) else slot_bytes
+    return encode_set_async(planes, flags, init_zero_delta, stream, limit_lengths, slot_bytes, n_planes=c)
+
+
+@dataclasses.dataclass
+class AsyncEncodedSet:
+    """A set encode in flight: everything on the device, in the frame-set layout. No method here
+    synchronises; `status` (int32[n], 0 = accepted) goes in as frame_status of the set decode
+    entries, and table_set() already carries it."""
+    sizes: tuple                      # ((width, height), ...) per frame
+    slots: tuple                      # each frame's code slot in bytes
+    plan: torch.Tensor                # u8: the uploaded plan (records, geometry, maps)
+    totals: "N.mh_set_totals"
+    canon: torch.Tensor               # u8[n, 256]
+    codes: torch.Tensor               # u8[codes_bytes]
+    codes_len: torch.Tensor           # int64[n] (payload + MH_CODES_PAD; 0 on an error)
+    frame_code_offsets: torch.Tensor  # int64[n + 1]: the slots' offsets, written by the device
+    status: torch.Tensor              # int32[n]
+    block_offsets: torch.Tensor       # int32 view of u32[total_blocks]
+    block_init: Optional[torch.Tensor]
+    flags: int
+    n_planes: int = 1
+    plane_frame_stride: int = 1
+
+    @property
+    def n_frames(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def geoms(self) -> torch.Tensor:
+        """int32[n, 4]: the mh_frame_geom records, a view into the uploaded plan."""
+        o, n = int(self.totals.geoms_offset), self.n_frames
+        return self.plan[o: o + 16 * n].view(torch.int32).view(n, 4)
+
+    def frame_set(self):
+        """The outputs as a DeviceFrameSet for decode_set_crops and
+        decode_set_crops_normalized_planes; `code_bytes` is the slots' capacity (an upper bound of
+        the payload: the byte counts are on the device)."""
+        from .decoder import DeviceFrameSet
+        t = self.totals
+        return DeviceFrameSet(int(t.max_width), int(t.max_height), self.n_frames, self.sizes, int(t.total_blocks),
+                              self.block_offsets, self.codes, self.frame_code_offsets, self.geoms, self.block_init,
+                              self.flags, int(self.codes.numel()) - self.n_frames * N.MH_CODES_PAD)
+
+    def table_set(self, stream: Optional[torch.cuda.Stream] = None):
+        """One prepared table per frame from the device headers in one launch
+        (mh_build_luts_device); its status is the encoder's word where the encoder rejected the
+        frame, else the table build's -- combined on the device."""
+        from .decoder import DeviceTableSet
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ts = DeviceTableSet.from_canonical_headers(self.canon, self.canon.device, stream)
+            ts.status = torch.where(self.status != 0, self.status, ts.status)
+        return ts

@@ -74,8 +74,9 @@ def disasm(lib_path: str) -> str:
 
 def listings_of(disasm_text: str) -> dict:
     """kernel symbol -> its instructions as text lines, from llvm-objdump -d output: no addresses,
-    no raw encodings and no trailing comments (objdump prints all three behind `//`), so two builds
-    whose code moved but did not change compare equal."""
+    no raw encodings and no trailing comments (objdump prints all three behind `//`), and no `...`
+    (the zero padding up to the next function), so two builds whose code moved but did not change
+    compare equal."""
     out, cur = {}, None
     for line in disasm_text.splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
@@ -83,7 +84,7 @@ def listings_of(disasm_text: str) -> dict:
             cur = out.setdefault(m.group(1), [])
             continue
         ins = " ".join(line.split("//", 1)[0].split())
-        if cur is not None and ins and line[:1].isspace():
+        if cur is not None and ins and ins != "..." and line[:1].isspace():  # "...": zero padding behind a function
             cur.append(ins)
     return out
 
