@@ -185,6 +185,11 @@ def test_planner_checks_in_order(mh):
     # 40 pixels wide: a tile lies in 8 * (254 // 5 + 2) = 416 rows; 30 rows of pitch p span 29 p + 40
     assert _plan_rc(mh, bad(0, row_pitch=(SPAN_MAX - 40) // 29)) == 0
     assert _plan_rc(mh, bad(0, row_pitch=(SPAN_MAX - 40) // 29 + 1), plan_bytes=4096) == CAPACITY
+    # the 13 x 3 frame of test_gpu_encode_set_limits.py, in the middle: (3 - 1) p + 13 ps, in both modes
+    for ps in (1, 3):
+        top = (SPAN_MAX - 13 * ps) // 2
+        for p, want in ((top, 0), (top - top % 4, 0), (top + 1, CAPACITY)):
+            assert _plan_rc(mh, bad(1, width=13, height=3, pixel_stride=ps, row_pitch=p), plan_bytes=4096) == want, (ps, p)
     assert _plan_rc(mh, bad(0, codes_cap=2 ** 64 - 16), plan_bytes=4096) == CAPACITY   # the slot sum wraps
     size = int(mh.lib().mh_encode_set_plan_bytes(3, mh.codec.set_sources(good)[0]))
     assert size > 0 and _plan_rc(mh, good, plan_bytes=size - 1) == CAPACITY
