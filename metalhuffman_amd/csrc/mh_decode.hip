@@ -872,23 +872,16 @@ struct TileHdrBase {
   uint32_t fo_lo, fo_hi;  // lanes 0/1: frame_off[f], frame_off[f+1]
   uint32_t init;      // per-block initial prev (block_init) or 0
 };
-// ... and what a map adds to it (FrameMap: nothing)
-template <class Map>
+// ... and what a map adds to it (FrameMap: nothing; a region map of any kind: the same two words).
+// A partial specialisation on Map::kRegion, so a new map adds no line here. (The same choice as a
+// std::conditional_t alias is not the same code: it moved instructions in 12 kernels, the
+// single-frame kernel among them -- DESIGN.md section 3i.)
+template <class Map, bool = Map::kRegion>
 struct TileHdrOf : TileHdrBase {};
-template <>
-struct TileHdrOf<RegionMap> : TileHdrBase {
+template <class Map>
+struct TileHdrOf<Map, true> : TileHdrBase {
   uint32_t r, s;      // the tile's region row and segment (wave-uniform)
 };
-template <>
-struct TileHdrOf<WindowMap> : TileHdrOf<RegionMap> {};
-template <>
-struct TileHdrOf<CropMap> : TileHdrOf<RegionMap> {};
-template <>
-struct TileHdrOf<NormMap> : TileHdrOf<RegionMap> {};
-template <>
-struct TileHdrOf<SetCropMap> : TileHdrOf<RegionMap> {};
-template <>
-struct TileHdrOf<SetNormMap> : TileHdrOf<RegionMap> {};
 using TileHdr = TileHdrOf<FrameMap>;
 
 // tile -> (r, s). One segment per row skips the division (a uniform branch), as frame_of does
@@ -953,22 +946,12 @@ struct TileBase {
   uint32_t init;
   uint32_t span_end_bits;  // end bit of the tile's last block (frame relative)
 };
-template <class Map>
+template <class Map, bool = Map::kRegion>
 struct TileOf : TileBase {};
-template <>
-struct TileOf<RegionMap> : TileBase {
+template <class Map>
+struct TileOf<Map, true> : TileBase {
   uint32_t r, s, n;    // region row, segment, blocks in the run (1..64)
 };
-template <>
-struct TileOf<WindowMap> : TileOf<RegionMap> {};
-template <>
-struct TileOf<CropMap> : TileOf<RegionMap> {};
-template <>
-struct TileOf<NormMap> : TileOf<RegionMap> {};
-template <>
-struct TileOf<SetCropMap> : TileOf<RegionMap> {};
-template <>
-struct TileOf<SetNormMap> : TileOf<RegionMap> {};
 using Tile = TileOf<FrameMap>;
 
 template <class Map = FrameMap>
@@ -1898,6 +1881,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
                        PreparedTable{p_luts, p_lut_stride}, RegionMap{f, p_rbx0, p_rby0, p_rbw, p_segs});
 }
 
+// BoxRows' edge word (RegionMap::rem): the frame's pixels from an accepted origin on
+__device__ __forceinline__ uint32_t box_rem(uint32_t W, uint32_t H, uint32_t bx0, uint32_t by0) {
+  return (W - 8u * bx0) | ((H - 8u * by0) << 16);
+}
+
 // ... and the region at scale 2^kLog2 (kLog2 = 1..3): the region kernel with the BoxRows output stage
 template <bool kDelta, int kLog2>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_region_scaled_kernel(
@@ -1908,10 +1896,41 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   slice_decode<kDelta, BoxRows<kLog2>>(a0, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame,
                                        p_groups, f, slice, PreparedTable{p_luts, p_lut_stride},
                                        RegionMap{f, p_rbx0, p_rby0, p_rbw, p_segs,
-                                                 (a0.w - 8u * p_rbx0) | ((a0.h - 8u * p_rby0) << 16)});
+                                                 box_rem(a0.w, a0.h, p_rbx0, p_rby0)});
 }
 
-// A list entry's 16-byte descriptor, wave-uniform: the one dependent trip ahead of slice_decode's prologue.
+// ---- the list entries' steps (mh_decode_windows* / _crops* / _set_crops*) -------------------------
+// A list kernel is an entry in front of slice_decode: workgroup g serves unit g / G of the list, reads
+// the unit's 16-byte descriptor, judges it by itself before anything is addressed through it, and
+// makes the workgroup's own DecodeArgs and map. Each step is written once here; a kernel below is
+// the steps it takes, in its order, and a comment on what it adds ("The list
+// entries' steps"). The kernels sit at the SGPR ceiling, so a step that makes a value opaque says
+// what was lost without it, and the opaque statements keep their order within a kernel.
+
+// unit -> (list index, slice)
+struct ListUnit {
+  uint32_t p, slice;
+};
+__device__ __forceinline__ ListUnit list_unit(uint32_t groups) {
+  const uint32_t p = blockIdx.x / groups;
+  return {p, blockIdx.x - p * groups};
+}
+// ... and for samples of planes, unit = (sample, plane): (sample p, plane c, slice). One plane skips
+// the division (uniform), as region_rs does for one segment.
+struct PlaneUnit {
+  uint32_t p, c, slice;
+};
+__device__ __forceinline__ PlaneUnit plane_unit(uint32_t groups, uint32_t n_planes) {
+  const ListUnit u = list_unit(groups);
+  uint32_t p = u.p, c = 0u;
+  if (n_planes != 1u) {
+    p = u.p / n_planes;
+    c = u.p - p * n_planes;
+  }
+  return {p, c, u.slice};
+}
+
+// The unit's 16-byte descriptor, wave-uniform: the one dependent trip ahead of slice_decode's prologue.
 __device__ __forceinline__ v4u32 desc_load(const void *desc) {
   v4u32 d = __builtin_amdgcn_raw_buffer_load_b128(uniform_rsrc(desc, 16u), 0, 0, 0);
   d.x = __builtin_amdgcn_readfirstlane(d.x), d.y = __builtin_amdgcn_readfirstlane(d.y);
@@ -1919,229 +1938,262 @@ __device__ __forceinline__ v4u32 desc_load(const void *desc) {
   return d;
 }
 
-// mh_decode_windows: workgroup g serves window g / G, whose frame and origin it reads from the
-// window's 16-byte descriptor (desc_load, as the four list kernels below do). The workgroup judges
-// the descriptor by itself, before anything is addressed through it: a window that names no frame, leaves the block grid or has a non-zero
-// reserved word returns here, having loaded and stored nothing but its status word. The origin is
-// compared with the last one that fits, p_max_bx0 = block_width - bw and p_max_by0 = block_height -
-// bh from the host (which has checked bw <= block_width and bh <= block_height), so no sum of
-// descriptor values is formed and nothing wraps; the limits arrive with the other scalars, ahead
-// of the descriptor. a0.out_frame_stride is the window stride; the workgroup's own row limit
-// RH_p * pitch replaces a0.out_frame_bytes.
+// A rejected descriptor (workgroup-uniform): MH_ERR_DIMS into the unit's status word, which one thread
+// writes -- `writer`: slice 0's first, of plane 0 for a sample -- and the kernel returns having loaded
+// nothing through the descriptor and stored nothing else. (The kernel forms `writer`: formed in a
+// helper it becomes one vector compare, and the delta windows kernel's SGPR count moves.)
+__device__ __forceinline__ void list_reject(int32_t *status, uint32_t p, bool writer) {
+  if (status && writer) status[p] = MH_ERR_DIMS;
+}
+
+// The verdict on a descriptor's own words (frame | origin | flags), true = rejected. The origin is
+// compared with the last one that fits, max_x0 = W - w and max_y0 = H - h from the host (which has
+// checked w <= W and h <= H; blocks for windows, pixels for crops), so no sum of descriptor values
+// is formed and nothing wraps; the limits arrive with the other scalars, ahead of the descriptor.
+// `no_frame` is the entry's own frame rule. Word 3 may hold the bits `flag_bits` (none: a reserved
+// word, zero), and MH_CROP_MIRROR is refused on a width that is no multiple of 8 (odd_w = 1, from
+// the host: a mirrored row would carry its unspecified tail at its front).
+__device__ __forceinline__ bool mirror_bad(uint32_t flags, uint32_t odd_w) { return (flags & odd_w) != 0u; }
+__device__ __forceinline__ bool desc_bad(const v4u32 d, bool no_frame, uint32_t max_x0, uint32_t max_y0,
+                                         uint32_t flag_bits = 0u, uint32_t odd_w = 0u) {
+  return no_frame | (d.y > max_x0) | (d.z > max_y0) | ((d.w & ~flag_bits) != 0u) | mirror_bad(d.w, odd_w);
+}
+
+// The slot folded into the raster's base, the slot stride 0 from then on: raster_slot() * 0 is no
+// instruction, and the slot index lives no longer than report(). The scaled windows' body has no
+// SGPR to spare for it (raw pixels at 1/4 scale spilled with it), and neither have the crops'.
+__device__ __forceinline__ DecodeArgs slot_args(const DecodeArgs &a0, uint8_t *base) {
+  DecodeArgs a = a0;
+  a.out = base;
+  a.out_frame_stride = 0;
+  return a;
+}
+__device__ __forceinline__ DecodeArgs slot_args(const DecodeArgs &a0, uint32_t p) {
+  return slot_args(a0, a0.out + (uint64_t)p * a0.out_frame_stride);
+}
+
+// The rows of a window that lie inside the frame: its row limit, in place of a0.out_frame_bytes.
+__device__ __forceinline__ uint32_t window_rows(uint32_t H, uint32_t by0, uint32_t bh) {
+  return min(H, 8u * (by0 + bh)) - 8u * by0;
+}
+
+// A crop's own geometry, from an accepted origin: the block rows it touches -- (dy + h + 7) >> 3 of
+// them, at most the CBH the grid was sized for (p_tiles_per_crop, the grid's worst case, is not used),
+// so the workgroup's tiles end with its last needed block row and a row the crop does not reach
+// (which may lie outside the frame) is never addressed --, the blocks a row touches (NB), and the
+// packed dx | flags << 3 | dy << 4 | OW << 8 of the output stage (CropMap, NormMap).
+struct CropGeom {
+  uint32_t rows, nblk, rem;
+};
+__device__ __forceinline__ CropGeom crop_geom(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags = 0u) {
+  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
+  const uint32_t rows = (dy + h + 7u) >> 3, nblk = (dx + w + 7u) >> 3, ow = (w + 7u) >> 3;
+  return {rows, nblk, dx | (flags << 3) | (dy << 4) | (ow << 8)};
+}
+// ... under NormRows, `rem` one opaque word: seen through, its parts stay live beside it and the
+// raw-pixel body is an SGPR short
+__device__ __forceinline__ CropGeom norm_geom(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags) {
+  CropGeom g = crop_geom(x0, y0, w, h, flags);
+  asm volatile("" : "+s"(g.rem));
+  return g;
+}
+
+// NormRows' byte selector (mirrored or not), scale and bias: per-lane and opaque (NormMap)
+struct NormConsts {
+  uint32_t sel;
+  float scale, bias;
+};
+__device__ __forceinline__ NormConsts norm_consts(uint32_t flags, float scale, float bias) {
+  NormConsts n{flags ? 0x04050607u : 0x03020100u, scale, bias};
+  asm volatile("" : "+v"(n.sel), "+v"(n.scale), "+v"(n.bias));
+  return n;
+}
+
+// mh_decode_windows: window g / G's frame and block origin from its descriptor, the slot the
+// window's index (WindowMap reports the frame's status word into the window's). a0.out_frame_stride
+// is the window stride.
 template <bool kDelta>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_windows_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
     const int32_t *p_status, const mh_window *p_windows, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
     uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbh, uint32_t p_nframes, uint32_t p_max_bx0, uint32_t p_max_by0,
     uint64_t p_lut_stride, int32_t *p_wstatus, const DecodeArgs a0) {
-  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 wd = desc_load(p_windows + p);
-  const uint32_t f = wd.x, bx0 = wd.y, by0 = wd.z, reserved = wd.w;
-  if ((f >= p_nframes) | (bx0 > p_max_bx0) | (by0 > p_max_by0) | (reserved != 0u)) {  // workgroup-uniform
-    if (p_wstatus && slice == 0 && threadIdx.x == 0) p_wstatus[p] = MH_ERR_DIMS;
-    return;
-  }
+  const ListUnit u = list_unit(p_groups);
+  const v4u32 wd = desc_load(p_windows + u.p);
+  const uint32_t f = wd.x, bx0 = wd.y, by0 = wd.z;
+  if (desc_bad(wd, f >= p_nframes, p_max_bx0, p_max_by0)) 
+    return list_reject(p_wstatus, u.p, u.slice == 0 && threadIdx.x == 0);
   DecodeArgs aw = a0;
-  aw.out_frame_bytes = (uint64_t)(min(a0.h, 8u * (by0 + p_rbh)) - 8u * by0) * a0.out_pitch;
-  slice_decode<kDelta>(aw, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
-                       PreparedTable{p_luts, p_lut_stride},
-                       WindowMap{{f, bx0, by0, p_rbw, p_segs}, p, p_wstatus});
+  aw.out_frame_bytes = (uint64_t)window_rows(a0.h, by0, p_rbh) * a0.out_pitch;
+  slice_decode<kDelta>(aw, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f,
+                       u.slice, PreparedTable{p_luts, p_lut_stride},
+                       WindowMap{{f, bx0, by0, p_rbw, p_segs}, u.p, p_wstatus});
 }
 
-// ... and the windows at scale 2^kLog2 (kLog2 = 1..3): the same descriptor trip and the same verdict
-// ahead of the same body with the BoxRows output stage. The window's edge word `rem` and its row
-// limit SH_p * pitch are formed behind the verdict, from the accepted origin only. The scaled
-// body has no SGPR to spare for the slot index (raw pixels at 1/4 scale spilled with it), so the
-// slot is folded into the raster's base here and the window stride is 0 from then on:
-// raster_slot() * 0 is no instruction, and `p` lives no longer than report().
+// ... and the windows at scale 2^kLog2 (kLog2 = 1..3): the BoxRows output stage, so the window's edge
+// word and its row limit SH_p * pitch, formed behind the verdict from the accepted origin only, and
+// the slot folded into the base.
 template <bool kDelta, int kLog2>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_windows_scaled_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
     const int32_t *p_status, const mh_window *p_windows, uint32_t p_nb, uint32_t p_tiles_per_frame, uint32_t p_groups,
     uint32_t p_segs, uint32_t p_rbw, uint32_t p_rbh, uint32_t p_nframes, uint32_t p_max_bx0, uint32_t p_max_by0,
     uint64_t p_lut_stride, int32_t *p_wstatus, const DecodeArgs a0) {
-  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 wd = desc_load(p_windows + p);
-  const uint32_t f = wd.x, bx0 = wd.y, by0 = wd.z, reserved = wd.w;
-  if ((f >= p_nframes) | (bx0 > p_max_bx0) | (by0 > p_max_by0) | (reserved != 0u)) {  // workgroup-uniform
-    if (p_wstatus && slice == 0 && threadIdx.x == 0) p_wstatus[p] = MH_ERR_DIMS;
-    return;
-  }
+  const ListUnit u = list_unit(p_groups);
+  const v4u32 wd = desc_load(p_windows + u.p);
+  const uint32_t f = wd.x, bx0 = wd.y, by0 = wd.z;
+  if (desc_bad(wd, f >= p_nframes, p_max_bx0, p_max_by0)) 
+    return list_reject(p_wstatus, u.p, u.slice == 0 && threadIdx.x == 0);
   constexpr uint32_t s = 1u << kLog2;
-  DecodeArgs aw = a0;
-  aw.out = a0.out + (uint64_t)p * a0.out_frame_stride;
-  aw.out_frame_stride = 0;
-  aw.out_frame_bytes = (uint64_t)((min(a0.h, 8u * (by0 + p_rbh)) - 8u * by0 + s - 1u) >> kLog2) * a0.out_pitch;
+  DecodeArgs aw = slot_args(a0, u.p);
+  aw.out_frame_bytes = (uint64_t)((window_rows(a0.h, by0, p_rbh) + s - 1u) >> kLog2) * a0.out_pitch;
   slice_decode<kDelta, BoxRows<kLog2>>(
-      aw, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, slice,
+      aw, p_offsets, p_frame_off, p_block_init, p_status, p_nb, p_tiles_per_frame, p_groups, f, u.slice,
       PreparedTable{p_luts, p_lut_stride},
-      WindowMap{{f, bx0, by0, p_rbw, p_segs, (a0.w - 8u * bx0) | ((a0.h - 8u * by0) << 16)}, p, p_wstatus});
+      WindowMap{{f, bx0, by0, p_rbw, p_segs, box_rem(a0.w, a0.h, bx0, by0)}, u.p, p_wstatus});
 }
 
-// mh_decode_crops: workgroup g serves crop g / G, a w x h rectangle at a PIXEL origin read from the
-// crop's 16-byte descriptor, as the windows kernel reads a window's. The same verdict ahead of
-// everything: the origin is compared with the last one that fits, p_max_x0 = W - w and p_max_y0 =
-// H - h from the host, so no sum of descriptor values is formed. Behind it the crop's own geometry:
-// the blocks a row touches (NB), the block rows it touches -- (dy + h + 7) >> 3 of them, at most the
-// CBH the grid was sized for, so this workgroup's tiles end with its last needed block row and a
-// row the crop does not reach (which may lie outside the frame) is never addressed -- and the
-// packed (dx, dy, OW) of the output stage. a0.out_frame_bytes is h * pitch, every crop's row limit;
-// a0.out_frame_stride is the crop stride.
+// mh_decode_crops: crop g / G, a w x h rectangle at a PIXEL origin: the windows' verdict in pixels,
+// then the crop's own tiles and the CropRows output stage. a0.out_frame_bytes is h * pitch, every
+// crop's row limit; a0.out_frame_stride is the crop stride.
 template <bool kDelta>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_crops_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
     const int32_t *p_status, const mh_crop *p_crops, uint32_t p_nb, uint32_t p_tiles_per_crop, uint32_t p_groups,
     uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0, uint32_t p_max_y0,
     uint64_t p_lut_stride, int32_t *p_cstatus, const DecodeArgs a0) {
-  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 cd = desc_load(p_crops + p);
-  const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z, reserved = cd.w;
-  if ((f >= p_nframes) | (x0 > p_max_x0) | (y0 > p_max_y0) | (reserved != 0u)) {  // workgroup-uniform
-    if (p_cstatus && slice == 0 && threadIdx.x == 0) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
-  (void)p_tiles_per_crop;  // the grid's worst case, CBH * S; this crop's own count follows
-  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
-  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
-  // as the scaled windows: the slot is folded into the raster's base, so `p` lives no longer than report()
-  DecodeArgs ac = a0;
-  ac.out = a0.out + (uint64_t)p * a0.out_frame_stride;
-  ac.out_frame_stride = 0;
-  slice_decode<kDelta, CropRows>(ac, p_offsets, p_frame_off, p_block_init, p_status, p_nb, rows * p_segs, p_groups, f,
-                                 slice, PreparedTable{p_luts, p_lut_stride},
-                                 CropMap{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, dx | (dy << 4) | (ow << 8)}, p, p_cstatus}});
+  const ListUnit u = list_unit(p_groups);
+  const v4u32 cd = desc_load(p_crops + u.p);
+  const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z;
+  if (desc_bad(cd, f >= p_nframes, p_max_x0, p_max_y0))
+    return list_reject(p_cstatus, u.p, u.slice == 0 && threadIdx.x == 0);
+  const CropGeom g = crop_geom(x0, y0, p_w, p_h);
+  const DecodeArgs ac = slot_args(a0, u.p);
+  slice_decode<kDelta, CropRows>(ac, p_offsets, p_frame_off, p_block_init, p_status, p_nb, g.rows * p_segs, p_groups,
+                                 f, u.slice, PreparedTable{p_luts, p_lut_stride},
+                                 CropMap{{{f, x0 >> 3, y0 >> 3, g.nblk, p_segs, g.rem}, u.p, p_cstatus}});
 }
 
-// mh_decode_crops_norm: the crops kernel's entry with one more verdict term -- a flag bit other than
-// MH_CROP_MIRROR, or MH_CROP_MIRROR on a width that is no multiple of 8 (p_odd_w = 1, from the host;
-// a mirrored row would carry its unspecified tail at its front) -- ahead of the same body with the
-// NormRows<kFmt> output stage. a0.out_pitch / out_frame_stride / out_frame_bytes are bytes of the
-// wide raster.
+// mh_decode_crops_norm: the crops' entry with the flags word in the verdict and the NormRows<kFmt>
+// output stage. a0.out_pitch / out_frame_stride / out_frame_bytes are bytes of the wide raster.
 template <bool kDelta, uint32_t kFmt>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_normcrops_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
     const int32_t *p_status, const mh_norm_crop *p_crops, uint32_t p_nb, uint32_t p_tiles_per_crop, uint32_t p_groups,
     uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0, uint32_t p_max_y0,
     uint64_t p_lut_stride, int32_t *p_cstatus, float p_scale, float p_bias, uint32_t p_odd_w, const DecodeArgs a0) {
-  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 cd = desc_load(p_crops + p);
+  const ListUnit u = list_unit(p_groups);
+  const v4u32 cd = desc_load(p_crops + u.p);
   const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z, flags = cd.w;
-  if ((f >= p_nframes) | (x0 > p_max_x0) | (y0 > p_max_y0) | ((flags & ~MH_CROP_MIRROR) != 0u) |
-      ((flags & p_odd_w) != 0u)) {  // workgroup-uniform
-    if (p_cstatus && slice == 0 && threadIdx.x == 0) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
-  (void)p_tiles_per_crop;
-  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
-  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
-  DecodeArgs ac = a0;
-  ac.out = a0.out + (uint64_t)p * a0.out_frame_stride;
-  ac.out_frame_stride = 0;
-  uint32_t sel = flags ? 0x04050607u : 0x03020100u;
-  float scale = p_scale, bias = p_bias;
-  asm volatile("" : "+v"(sel), "+v"(scale), "+v"(bias));
-  // one opaque word: seen through, its parts stay live beside it and the raw-pixel body is an SGPR short
-  uint32_t rem = dx | (flags << 3) | (dy << 4) | (ow << 8);
-  asm volatile("" : "+s"(rem));
+  if (desc_bad(cd, f >= p_nframes, p_max_x0, p_max_y0, MH_CROP_MIRROR, p_odd_w))
+    return list_reject(p_cstatus, u.p, u.slice == 0 && threadIdx.x == 0);
+  const DecodeArgs ac = slot_args(a0, u.p);
+  const NormConsts nc = norm_consts(flags, p_scale, p_bias);
+  const CropGeom g = norm_geom(x0, y0, p_w, p_h, flags);
   slice_decode<kDelta, NormRows<kFmt>>(
-      ac, p_offsets, p_frame_off, p_block_init, p_status, p_nb, rows * p_segs, p_groups, f, slice,
+      ac, p_offsets, p_frame_off, p_block_init, p_status, p_nb, g.rows * p_segs, p_groups, f, u.slice,
       PreparedTable{p_luts, p_lut_stride},
-      NormMap{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, rem}, p, p_cstatus}},
-              sel, scale, bias});
+      NormMap{{{{f, x0 >> 3, y0 >> 3, g.nblk, p_segs, g.rem}, u.p, p_cstatus}}, nc.sel, nc.scale, nc.bias});
 }
 
 // mh_decode_crops_norm_planes: a descriptor is a SAMPLE of n_planes planes, plane c the same crop of
 // frame f + c * frame_stride under its own (scale[c], bias[c]), stored out_stride bytes behind plane
 // c - 1. Workgroup g serves unit g / G = (sample, plane). What a plane changes is workgroup-constant
-// and made here, once, ahead of slice_decode: the frame (and with it the table), the raster's base
-// and the stage's per-lane (scale, bias). The body, the maps and NormRows are the normalised crops'.
-// The verdict is that kernel's with the frame compared against p_max_frame = n_frames - 1 -
+// and made ahead of slice_decode: the frame (and with it the table), the raster's base and the
+// stage's per-lane (scale, bias). The body, the maps and NormRows are the normalised crops'. The
+// verdict is that kernel's with the frame compared against p_max_frame = n_frames - 1 -
 // (n_planes - 1) * frame_stride from the host, so the sample's LAST plane names a frame and no sum
-// of descriptor words is formed ahead of it. A sample is written whole or not at all: every one of
-// its workgroups loads the status words of all its frames (workgroup-uniform, empty descriptors for
-// the planes past n_planes and without a status array), so all reach one decision, and the body gets
-// no status pointer. The sample's status word is written here, by plane 0's slice 0.
+// of descriptor words is formed ahead of it.
 struct PlaneArgs {
   uint32_t n_planes, frame_stride;
   uint64_t out_stride;
   float scale[MH_MAX_PLANES], bias[MH_MAX_PLANES];
 };
+// ... plane c's NormRows constants (pl by value: its eight words are loaded, then selected)
+__device__ __forceinline__ NormConsts plane_consts(uint32_t flags, const PlaneArgs pl, uint32_t c) {
+  return norm_consts(flags, c == 0u ? pl.scale[0] : c == 1u ? pl.scale[1] : c == 2u ? pl.scale[2] : pl.scale[3],
+                     c == 0u ? pl.bias[0] : c == 1u ? pl.bias[1] : c == 2u ? pl.bias[2] : pl.bias[3]);
+}
+// A sample is written whole or not at all: every one of its workgroups loads the status words of all
+// its frames (workgroup-uniform, empty descriptors for the planes past n_planes and without a status
+// array; f0 + (n_planes - 1) * frame_stride < n_frames has passed), so all reach one decision -- the
+// first non-zero word in plane order -- and the body gets no status pointer. plane_verdict writes
+// the sample's status word, by plane 0's slice 0.
+struct PlaneStatus {
+  uint32_t w[MH_MAX_PLANES];
+};
+__device__ __forceinline__ PlaneStatus plane_status_issue(const int32_t *status, const void *any, uint32_t f0,
+                                                          const PlaneArgs &pl) {
+  PlaneStatus s;
+#pragma unroll
+  for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) {
+    const bool on = status && i < pl.n_planes;
+    s.w[i] = __builtin_amdgcn_raw_buffer_load_b32(
+        uniform_rsrc(on ? (const void *)(status + f0 + (uint64_t)i * pl.frame_stride) : any, on ? 4u : 0u), 0, 0, 0);
+  }
+  return s;
+}
+__device__ __forceinline__ uint32_t plane_verdict(const PlaneStatus &s, int32_t *status, uint32_t p, bool writer) {
+  uint32_t st = 0u;
+#pragma unroll
+  for (int i = MH_MAX_PLANES - 1; i >= 0; --i) {
+    const uint32_t w = __builtin_amdgcn_readfirstlane(s.w[i]);
+    st = w ? w : st;
+  }
+  if (status && writer) status[p] = (int32_t)st;
+  return st;
+}
+// The plane's frame and raster base, opaque from here on: seen through, the sums' terms stay live
+// beside them through the body, and the raw 16-bit instantiations spilled three VGPRs.
+struct PlaneSlot {
+  uint32_t f;
+  uint8_t *out;
+};
+__device__ __forceinline__ PlaneSlot plane_slot(const DecodeArgs &a0, const PlaneArgs &pl, uint32_t f0, uint32_t p,
+                                                uint32_t c) {
+  uint32_t f = f0 + c * pl.frame_stride;
+  const uint64_t base = (uint64_t)a0.out + (uint64_t)p * a0.out_frame_stride + (uint64_t)c * pl.out_stride;
+  uint32_t base_lo = (uint32_t)base, base_hi = (uint32_t)(base >> 32);
+  asm volatile("" : "+s"(f), "+s"(base_lo), "+s"(base_hi));
+  return {f, (uint8_t *)(((uint64_t)base_hi << 32) | base_lo)};
+}
+
 template <bool kDelta, uint32_t kFmt>
 __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_planes_kernel(
     const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
     const int32_t *p_status, const mh_norm_crop *p_crops, uint32_t p_nb, uint32_t p_tiles_per_crop, uint32_t p_groups,
     uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_max_frame, uint32_t p_max_x0, uint32_t p_max_y0,
     uint64_t p_lut_stride, int32_t *p_cstatus, uint32_t p_odd_w, const PlaneArgs pl, const DecodeArgs a0) {
-  const uint32_t unit = blockIdx.x / p_groups, slice = blockIdx.x - unit * p_groups;
-  uint32_t p = unit, c = 0u;
-  if (pl.n_planes != 1u) {  // uniform: one plane skips the division, as region_rs does for one segment
-    p = unit / pl.n_planes;
-    c = unit - p * pl.n_planes;
-  }
-  const v4u32 cd = desc_load(p_crops + p);
+  const PlaneUnit u = plane_unit(p_groups, pl.n_planes);
+  const v4u32 cd = desc_load(p_crops + u.p);
   const uint32_t f0 = cd.x, x0 = cd.y, y0 = cd.z, flags = cd.w;
-  const bool writer = c == 0u && slice == 0u && threadIdx.x == 0u;
-  if ((f0 > p_max_frame) | (x0 > p_max_x0) | (y0 > p_max_y0) | ((flags & ~MH_CROP_MIRROR) != 0u) |
-      ((flags & p_odd_w) != 0u)) {  // workgroup-uniform
-    if (p_cstatus && writer) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
-  // f0 + (n_planes - 1) * frame_stride < n_frames from here on
-  uint32_t stv[MH_MAX_PLANES];
-#pragma unroll
-  for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) {
-    const bool on = p_status && i < pl.n_planes;
-    stv[i] = __builtin_amdgcn_raw_buffer_load_b32(
-        uniform_rsrc(on ? (const void *)(p_status + f0 + (uint64_t)i * pl.frame_stride) : (const void *)p_offsets,
-                     on ? 4u : 0u),
-        0, 0, 0);
-  }
-  uint32_t st = 0u;  // the first non-zero word in plane order
-#pragma unroll
-  for (int i = MH_MAX_PLANES - 1; i >= 0; --i) {
-    const uint32_t s = __builtin_amdgcn_readfirstlane(stv[i]);
-    st = s ? s : st;
-  }
-  if (p_cstatus && writer) p_cstatus[p] = (int32_t)st;
-  if (st != 0u) return;  // workgroup-uniform: a skipped sample, no plane of it is stored
-  (void)p_tiles_per_crop;
-  // The plane's frame and raster base, opaque from here on: seen through, the sums' terms stay live
-  // beside them through the body, and the raw 16-bit instantiations spilled three VGPRs.
-  uint32_t f = f0 + c * pl.frame_stride;
-  const uint64_t base = (uint64_t)a0.out + (uint64_t)p * a0.out_frame_stride + (uint64_t)c * pl.out_stride;
-  uint32_t base_lo = (uint32_t)base, base_hi = (uint32_t)(base >> 32);
-  asm volatile("" : "+s"(f), "+s"(base_lo), "+s"(base_hi));
-  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
-  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
-  DecodeArgs ac = a0;
-  ac.out = (uint8_t *)(((uint64_t)base_hi << 32) | base_lo);
-  ac.out_frame_stride = 0;
-  uint32_t sel = flags ? 0x04050607u : 0x03020100u;
-  float scale = c == 0u ? pl.scale[0] : c == 1u ? pl.scale[1] : c == 2u ? pl.scale[2] : pl.scale[3];
-  float bias = c == 0u ? pl.bias[0] : c == 1u ? pl.bias[1] : c == 2u ? pl.bias[2] : pl.bias[3];
-  asm volatile("" : "+v"(sel), "+v"(scale), "+v"(bias));
-  // one opaque word, as the normalised crops' entry
-  uint32_t rem = dx | (flags << 3) | (dy << 4) | (ow << 8);
-  asm volatile("" : "+s"(rem));
+  const bool writer = u.c == 0u && u.slice == 0u && threadIdx.x == 0u;
+  if (desc_bad(cd, f0 > p_max_frame, p_max_x0, p_max_y0, MH_CROP_MIRROR, p_odd_w))
+    return list_reject(p_cstatus, u.p, writer);
+  // workgroup-uniform: a skipped sample, no plane of it is stored
+  if (plane_verdict(plane_status_issue(p_status, p_offsets, f0, pl), p_cstatus, u.p, writer) != 0u) return;
+  const PlaneSlot ps = plane_slot(a0, pl, f0, u.p, u.c);
+  const DecodeArgs ac = slot_args(a0, ps.out);
+  const NormConsts nc = plane_consts(flags, pl, u.c);
+  const CropGeom g = norm_geom(x0, y0, p_w, p_h, flags);
   slice_decode<kDelta, NormRows<kFmt>>(
-      ac, p_offsets, p_frame_off, p_block_init, nullptr, p_nb, rows * p_segs, p_groups, f, slice,
+      ac, p_offsets, p_frame_off, p_block_init, nullptr, p_nb, g.rows * p_segs, p_groups, ps.f, u.slice,
       PreparedTable{p_luts, p_lut_stride},
-      NormMap{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, rem}, 0u, nullptr}},
-              sel, scale, bias});
+      NormMap{{{{ps.f, x0 >> 3, y0 >> 3, g.nblk, p_segs, g.rem}, 0u, nullptr}}, nc.sel, nc.scale, nc.bias});
 }
 
 // The crop entries over a frame SET (mh_decode_set_crops, mh_decode_set_crops_norm_planes): frames of
 // different sizes, frame f's geometry in the 16-byte record p_geoms[f]. The entry is its parent's with
 // a second dependent trip: desc_load and the verdict on the descriptor's own words; only then the
-// record (geom_load, wave-uniform as desc_load) and the verdict on it; then the crop against the
-// frame's own W_f x H_f, the limits formed from the accepted record (w <= W_f before W_f - w, so
-// nothing wraps). Behind the verdicts the workgroup's DecodeArgs get the frame's own grid: bw, nb and
-// the two arrays based at the frame's first block (first_block <= total_blocks - nb has passed, so
-// the sums stay inside the arrays; the maps' kOwnBase makes hdr_issue add nothing to them). The
-// offsets descriptor stays limited to the frame's nb * 4 bytes, so a frame's last block takes the
-// min(fbits, off + 1024) end and never reads a neighbour's first offset. Codes, table and status
-// word stay indexed by the frame number. p_total_blocks arrives where the parents' p_nb does;
-// p_max_x0 / p_max_y0 (from the set's maxima) are not used.
+// record (geom_load, wave-uniform as desc_load) and the verdict on it (geom_bad); then the crop
+// against the frame's own W_f x H_f (set_fit_bad). Behind the verdicts the workgroup's DecodeArgs get
+// the frame's own grid (set_frame): bw, nb and the two arrays based at the frame's first block
+// (first_block <= total_blocks - nb has passed, so the sums stay inside the arrays; the maps'
+// kOwnBase makes hdr_issue add nothing to them). The offsets descriptor stays limited to the frame's
+// nb * 4 bytes, so a frame's last block takes the min(fbits, off + 1024) end and never reads a
+// neighbour's first offset. Codes, table and status word stay indexed by the frame number.
+// p_total_blocks arrives where the parents' p_nb does; p_max_x0 / p_max_y0 (from the set's maxima)
+// are not used.
 __device__ __forceinline__ v4u32 geom_load(const mh_frame_geom *geoms, uint32_t f, bool on = true) {
   // off: a descriptor of zero records, whose load returns 0 without touching memory
   v4u32 d = __builtin_amdgcn_raw_buffer_load_b128(
@@ -2155,6 +2207,11 @@ __device__ __forceinline__ bool geom_bad(const v4u32 g, uint32_t total_blocks) {
   const uint32_t W = g.y, H = g.z;
   const uint32_t nb = ((W + 7u) >> 3) * ((H + 7u) >> 3);  // <= 2^26 for an accepted W, H
   return (g.w != 0u) | (W - 1u > 65534u) | (H - 1u > 65534u) | (nb > total_blocks) | (g.x > total_blocks - nb);
+}
+// the crop against the accepted record's W x H (step 3); the limits are formed from the record, and
+// the sizes are judged first: a wrapped limit is never the verdict
+__device__ __forceinline__ bool set_fit_bad(const v4u32 d, uint32_t W, uint32_t H, uint32_t w, uint32_t h) {
+  return (w > W) | (h > H) | (d.y > W - w) | (d.z > H - h);
 }
 // The frame's grid and bases, opaque from here on: seen through, the record's words stay live beside
 // them through the body, which has no SGPR to spare.
@@ -2180,38 +2237,23 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     const int32_t *p_status, const mh_crop *p_crops, uint32_t p_total_blocks, uint32_t p_tiles_per_crop,
     uint32_t p_groups, uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_nframes, uint32_t p_max_x0,
     uint32_t p_max_y0, uint64_t p_lut_stride, int32_t *p_cstatus, const mh_frame_geom *p_geoms, const DecodeArgs a0) {
-  const uint32_t p = blockIdx.x / p_groups, slice = blockIdx.x - p * p_groups;
-  const v4u32 cd = desc_load(p_crops + p);
-  const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z, reserved = cd.w;
-  const bool writer = p_cstatus && slice == 0 && threadIdx.x == 0;
-  if ((f >= p_nframes) | (reserved != 0u)) {  // workgroup-uniform
-    if (writer) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
+  const ListUnit u = list_unit(p_groups);
+  const v4u32 cd = desc_load(p_crops + u.p);
+  const uint32_t f = cd.x, x0 = cd.y, y0 = cd.z;
+  const bool writer = u.slice == 0 && threadIdx.x == 0;
+  if (desc_bad(cd, f >= p_nframes, ~0u, ~0u)) return list_reject(p_cstatus, u.p, writer);
   const v4u32 gd = geom_load(p_geoms, f);
-  if (geom_bad(gd, p_total_blocks)) {
-    if (writer) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
+  if (geom_bad(gd, p_total_blocks)) return list_reject(p_cstatus, u.p, writer);
   const uint32_t W = gd.y, H = gd.z;
-  if ((p_w > W) | (p_h > H) | (x0 > W - p_w) | (y0 > H - p_h)) {  // the sizes are judged first: a wrapped limit is never the verdict
-    if (writer) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
-  (void)p_tiles_per_crop;
-  (void)p_max_x0;
-  (void)p_max_y0;
+  if (set_fit_bad(cd, W, H, p_w, p_h)) return list_reject(p_cstatus, u.p, writer);
   const SetFrame sf = set_frame(p_offsets, p_block_init, gd.x, W, H);
-  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
-  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
-  DecodeArgs ac = a0;
-  ac.out = a0.out + (uint64_t)p * a0.out_frame_stride;
-  ac.out_frame_stride = 0;
+  const CropGeom g = crop_geom(x0, y0, p_w, p_h);
+  DecodeArgs ac = slot_args(a0, u.p);
   ac.bw = sf.bw;
   slice_decode<kDelta, CropRows>(
-      ac, sf.offsets, p_frame_off, sf.block_init, p_status, sf.nb, rows * p_segs, p_groups, f, slice,
+      ac, sf.offsets, p_frame_off, sf.block_init, p_status, sf.nb, g.rows * p_segs, p_groups, f, u.slice,
       PreparedTable{p_luts, p_lut_stride},
-      SetCropMap{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, dx | (dy << 4) | (ow << 8)}, p, p_cstatus}}});
+      SetCropMap{{{{f, x0 >> 3, y0 >> 3, g.nblk, p_segs, g.rem}, u.p, p_cstatus}}});
 }
 
 // ... and the samples of planes over a set. Step 2 covers the sample: every workgroup loads the
@@ -2226,32 +2268,15 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
     uint32_t p_groups, uint32_t p_segs, uint32_t p_w, uint32_t p_h, uint32_t p_max_frame, uint32_t p_max_x0,
     uint32_t p_max_y0, uint64_t p_lut_stride, int32_t *p_cstatus, uint32_t p_odd_w, const PlaneArgs pl,
     const mh_frame_geom *p_geoms, const DecodeArgs a0) {
-  const uint32_t unit = blockIdx.x / p_groups, slice = blockIdx.x - unit * p_groups;
-  uint32_t p = unit, c = 0u;
-  if (pl.n_planes != 1u) {
-    p = unit / pl.n_planes;
-    c = unit - p * pl.n_planes;
-  }
-  const v4u32 cd = desc_load(p_crops + p);
+  const PlaneUnit u = plane_unit(p_groups, pl.n_planes);
+  const v4u32 cd = desc_load(p_crops + u.p);
   const uint32_t f0 = cd.x, x0 = cd.y, y0 = cd.z, flags = cd.w;
-  const bool writer = p_cstatus && c == 0u && slice == 0u && threadIdx.x == 0u;
-  if ((f0 > p_max_frame) | ((flags & ~MH_CROP_MIRROR) != 0u)) {  // workgroup-uniform
-    if (writer) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
-  // f0 + (n_planes - 1) * frame_stride < n_frames from here on
+  const bool writer = u.c == 0u && u.slice == 0u && threadIdx.x == 0u;
+  if (desc_bad(cd, f0 > p_max_frame, ~0u, ~0u, MH_CROP_MIRROR)) return list_reject(p_cstatus, u.p, writer);
   v4u32 gd[MH_MAX_PLANES];
-  uint32_t stv[MH_MAX_PLANES];
 #pragma unroll
   for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) gd[i] = geom_load(p_geoms, f0 + i * pl.frame_stride, i < pl.n_planes);
-#pragma unroll
-  for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) {
-    const bool on = p_status && i < pl.n_planes;
-    stv[i] = __builtin_amdgcn_raw_buffer_load_b32(
-        uniform_rsrc(on ? (const void *)(p_status + f0 + (uint64_t)i * pl.frame_stride) : (const void *)p_offsets,
-                     on ? 4u : 0u),
-        0, 0, 0);
-  }
+  const PlaneStatus stv = plane_status_issue(p_status, p_offsets, f0, pl);
   const uint32_t W = gd[0].y, H = gd[0].z;
   bool bad = false;
   uint32_t first = gd[0].x;  // this workgroup's plane's
@@ -2259,49 +2284,21 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
   for (uint32_t i = 0; i < MH_MAX_PLANES; ++i) {
     const bool on = i < pl.n_planes;
     bad |= on & (geom_bad(gd[i], p_total_blocks) | (gd[i].y != W) | (gd[i].z != H));
-    first = c == i ? gd[i].x : first;
+    first = u.c == i ? gd[i].x : first;
   }
-  if (bad) {
-    if (writer) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
-  if ((p_w > W) | (p_h > H) | (x0 > W - p_w) | (y0 > H - p_h) | ((flags & p_odd_w) != 0u)) {
-    if (writer) p_cstatus[p] = MH_ERR_DIMS;
-    return;
-  }
-  uint32_t st = 0u;  // the first non-zero word in plane order
-#pragma unroll
-  for (int i = MH_MAX_PLANES - 1; i >= 0; --i) {
-    const uint32_t s = __builtin_amdgcn_readfirstlane(stv[i]);
-    st = s ? s : st;
-  }
-  if (writer) p_cstatus[p] = (int32_t)st;
-  if (st != 0u) return;  // workgroup-uniform: a skipped sample, no plane of it is stored
-  (void)p_tiles_per_crop;
-  (void)p_max_x0;
-  (void)p_max_y0;
+  if (bad) return list_reject(p_cstatus, u.p, writer);
+  if (set_fit_bad(cd, W, H, p_w, p_h) | mirror_bad(flags, p_odd_w)) return list_reject(p_cstatus, u.p, writer);
+  if (plane_verdict(stv, p_cstatus, u.p, writer) != 0u) return;  // a skipped sample, as the planes entry's
   const SetFrame sf = set_frame(p_offsets, p_block_init, first, W, H);
-  // as the planes entry: the plane's frame and raster base, opaque
-  uint32_t f = f0 + c * pl.frame_stride;
-  const uint64_t base = (uint64_t)a0.out + (uint64_t)p * a0.out_frame_stride + (uint64_t)c * pl.out_stride;
-  uint32_t base_lo = (uint32_t)base, base_hi = (uint32_t)(base >> 32);
-  asm volatile("" : "+s"(f), "+s"(base_lo), "+s"(base_hi));
-  const uint32_t dx = x0 & 7u, dy = y0 & 7u;
-  const uint32_t rows = (dy + p_h + 7u) >> 3, nblk = (dx + p_w + 7u) >> 3, ow = (p_w + 7u) >> 3;
-  DecodeArgs ac = a0;
-  ac.out = (uint8_t *)(((uint64_t)base_hi << 32) | base_lo);
-  ac.out_frame_stride = 0;
+  const PlaneSlot ps = plane_slot(a0, pl, f0, u.p, u.c);
+  DecodeArgs ac = slot_args(a0, ps.out);
   ac.bw = sf.bw;
-  uint32_t sel = flags ? 0x04050607u : 0x03020100u;
-  float scale = c == 0u ? pl.scale[0] : c == 1u ? pl.scale[1] : c == 2u ? pl.scale[2] : pl.scale[3];
-  float bias = c == 0u ? pl.bias[0] : c == 1u ? pl.bias[1] : c == 2u ? pl.bias[2] : pl.bias[3];
-  asm volatile("" : "+v"(sel), "+v"(scale), "+v"(bias));
-  uint32_t rem = dx | (flags << 3) | (dy << 4) | (ow << 8);
-  asm volatile("" : "+s"(rem));
+  const NormConsts nc = plane_consts(flags, pl, u.c);
+  const CropGeom g = norm_geom(x0, y0, p_w, p_h, flags);
   slice_decode<kDelta, NormRows<kFmt>>(
-      ac, sf.offsets, p_frame_off, sf.block_init, nullptr, sf.nb, rows * p_segs, p_groups, f, slice,
+      ac, sf.offsets, p_frame_off, sf.block_init, nullptr, sf.nb, g.rows * p_segs, p_groups, ps.f, u.slice,
       PreparedTable{p_luts, p_lut_stride},
-      SetNormMap{{{{{f, x0 >> 3, y0 >> 3, nblk, p_segs, rem}, 0u, nullptr}}, sel, scale, bias}});
+      SetNormMap{{{{{ps.f, x0 >> 3, y0 >> 3, g.nblk, p_segs, g.rem}, 0u, nullptr}}, nc.sel, nc.scale, nc.bias}});
 }
 
 template <bool kDelta>
@@ -3622,6 +3619,14 @@ struct ListCall : DecodeCall {
     total_blocks = blocks;
     return *this;
   }
+  // ... of samples of planes (kNormCrops): the *_shape twins pass no strides
+  ListCall &planes(uint32_t fmt, uint32_t n, const PlaneArgs *pl = nullptr) {
+    format = fmt;
+    n_planes = n;
+    plane_frame_stride = pl ? pl->frame_stride : 0u;
+    out_plane_stride = pl ? pl->out_stride : 0u;
+    return *this;
+  }
   ListCall(const ListCall &) = delete;  // rg points into this object
 };
 
@@ -3969,10 +3974,7 @@ int mh_decode_crops_norm_planes(const mh_frame *fr, const mh_norm_crop *d_crops,
   PlaneArgs pl;
   if (!plane_args(n_planes, plane_frame_stride, scale, bias, out_plane_stride, pl)) return MH_ERR_INVALID_ARG;
   ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
-  c.format = format;
-  c.n_planes = n_planes;
-  c.plane_frame_stride = pl.frame_stride;
-  c.out_plane_stride = pl.out_stride;
+  c.planes(format, n_planes, &pl);
   // the kernel's p_max_frame = n_frames - 1 - (n_planes - 1) * frame_stride (call_geometry: it does not wrap)
   return decode_list<PlanesFn>(kSlicePlanes, fr, c, d_crops, d_frame_status, d_crop_status, d_out, out_pitch,
                                out_crop_stride, stream, 1u + (n_planes - 1u) * pl.frame_stride, (w & 7u) ? 1u : 0u, pl);
@@ -3982,10 +3984,9 @@ int mh_decode_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, uint
                                       uint32_t n_planes, void *stream, uint32_t *groups_per_plane,
                                       uint32_t *waves_per_group) {
   if (n_planes == 0 || n_planes > MH_MAX_PLANES) return MH_ERR_INVALID_ARG;
-  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops);
-  c.format = format;
-  c.n_planes = n_planes;
-  return slice_shape_entry(kSlicePlanes, fr, c, stream, groups_per_plane, waves_per_group);
+  return slice_shape_entry(kSlicePlanes, fr,
+                           ListCall(DecodeCall::kNormCrops, w, h, 0u, n_crops).planes(format, n_planes), stream,
+                           groups_per_plane, waves_per_group);
 }
 
 // The crop entries over a frame set: their parents' calls with ListCall::over_set, the set kernels'
@@ -4017,11 +4018,7 @@ int mh_decode_set_crops_norm_planes(const mh_frame *fr, const mh_frame_geom *d_g
   PlaneArgs pl;
   if (!plane_args(n_planes, plane_frame_stride, scale, bias, out_plane_stride, pl)) return MH_ERR_INVALID_ARG;
   ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops, d_crops, d_luts, lut_stride_bytes);
-  c.over_set(d_geoms, total_blocks);
-  c.format = format;
-  c.n_planes = n_planes;
-  c.plane_frame_stride = pl.frame_stride;
-  c.out_plane_stride = pl.out_stride;
+  c.over_set(d_geoms, total_blocks).planes(format, n_planes, &pl);
   return decode_list<SetPlanesFn>(kSliceSetPlanes, fr, c, d_crops, d_frame_status, d_crop_status, d_out, out_pitch,
                                   out_crop_stride, stream, 1u + (n_planes - 1u) * pl.frame_stride,
                                   (w & 7u) ? 1u : 0u, pl, d_geoms);
@@ -4031,11 +4028,9 @@ int mh_decode_set_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, 
                                           uint32_t format, uint32_t n_planes, void *stream,
                                           uint32_t *groups_per_plane, uint32_t *waves_per_group) {
   if (n_planes == 0 || n_planes > MH_MAX_PLANES) return MH_ERR_INVALID_ARG;
-  ListCall c(DecodeCall::kNormCrops, w, h, 0u, n_crops);
-  c.over_set();
-  c.format = format;
-  c.n_planes = n_planes;
-  return slice_shape_entry(kSliceSetPlanes, fr, c, stream, groups_per_plane, waves_per_group);
+  return slice_shape_entry(kSliceSetPlanes, fr,
+                           ListCall(DecodeCall::kNormCrops, w, h, 0u, n_crops).over_set().planes(format, n_planes),
+                           stream, groups_per_plane, waves_per_group);
 }
 
 // mh_check's report, frame by frame under the frame's own table, and a verdict word per frame that

@@ -864,6 +864,13 @@ def decode_crops(frames: DeviceFrames, tables, crops, size, out: Optional[torch.
 _NORM_DTYPES = (torch.float16, torch.bfloat16, torch.float32)  # indexed by MH_NORM_*
 
 
+def _norm_raster(w: int, h: int, fmt: int, planes: tuple = ()) -> tuple:
+    """A normalised entry's slot [(C,) h, round_up(w, 8)], its dtype and its byte strides (row, [plane,] slot)."""
+    cols = (w + 7) // 8 * 8
+    pitch = cols * (2, 2, 4)[fmt]
+    return (*planes, h, cols), _NORM_DTYPES[fmt], (pitch, h * pitch, *(C * h * pitch for C in planes))
+
+
 def _host_norm_crops(frames: DeviceFrames, crops, w: int, h: int):
     """decode_crops_normalized's `crops` checked on the host: _host_crops' rules for (frame, x0, y0),
     plus a fourth column of flags -- MH_CROP_MIRROR only, and only on a width that is a multiple of 8."""
@@ -922,11 +929,9 @@ def decode_crops_normalized(frames: DeviceFrames, tables, crops, size, dtype, sc
     if not (finite_f32(scale) and finite_f32(bias)):
         raise ValueError(f"scale and bias must be finite in float32, not {scale!r}, {bias!r}")
     host = _host_norm_crops(frames, crops, w, h)
-    cols = (w + 7) // 8 * 8
-    pitch = cols * (2, 2, 4)[fmt]
     return _decode_list("decode_crops_normalized", "mh_decode_crops_norm", frames, tables, crops, host,
-                        (w, h, fmt, scale, bias), (h, cols), _NORM_DTYPES[fmt], (pitch, h * pitch), out, status,
-                        stream, extra_flags, skip_rejected)
+                        (w, h, fmt, scale, bias), *_norm_raster(w, h, fmt), out, status, stream, extra_flags,
+                        skip_rejected)
 
 
 def _plane_coefficients(scale, bias):
@@ -950,6 +955,38 @@ def _plane_stride(frames: DeviceFrames, n_planes: int, plane_stride) -> int:
     if ps < 0 or ps > 0xFFFFFFFF or (n_planes - 1) * ps >= frames.n_frames:
         raise ValueError(f"{n_planes} planes {ps} frames apart do not fit the {frames.n_frames} frames")
     return ps
+
+
+def _decode_planes(who: str, entry: str, frames: DeviceFrames, tables, crops, size, dtype, scale, bias, n_planes,
+                   plane_stride, out, status, stream, extra_flags: int, skip_rejected: bool):
+    """decode_crops_normalized_planes and its twin over a frame set (`frames` a DeviceFrameSet, which adds
+    `n_planes`, the planes' size check of a host list and the set's `head`)."""
+    w, h = _crop_size(frames, size)
+    fmt = _norm_format(dtype)
+    C, c_scale, c_bias = _plane_coefficients(scale, bias)
+    if n_planes is not None and int(n_planes) != C:
+        raise ValueError(f"n_planes = {n_planes}, but scale and bias hold {C} values")
+    ps = _plane_stride(frames, C, plane_stride)
+    host = _host_norm_crops(frames, crops, w, h)
+    over_set = isinstance(frames, DeviceFrameSet)
+    if host is not None:
+        f0 = host[:, 0].astype(np.int64)
+        bad = f0 + (C - 1) * ps >= frames.n_frames
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {C - 1} would be frame "
+                             f"{int(host[i, 0]) + (C - 1) * ps} of {frames.n_frames}")
+        if over_set:
+            lw, lh = frames.size_limits()
+            for c in range(1, C):
+                bad = (lw[f0 + c * ps] != lw[f0]) | (lh[f0 + c * ps] != lh[f0])
+                if bad.any():
+                    i = int(np.flatnonzero(bad)[0])
+                    raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {c} (frame "
+                                     f"{int(f0[i]) + c * ps}) is not of plane 0's size")
+    head = frames._head(frames.codes.get_device()) if over_set else ()
+    return _decode_list(who, entry, frames, tables, crops, host, (w, h, fmt, C, ps, c_scale, c_bias),
+                        *_norm_raster(w, h, fmt, (C,)), out, status, stream, extra_flags, skip_rejected, head)
 
 
 def decode_crops_normalized_planes_shape(frames: DeviceFrames, n_crops: int, size, dtype, n_planes: int,
@@ -984,22 +1021,8 @@ def decode_crops_normalized_planes(frames: DeviceFrames, tables, crops, size, dt
     out: a contiguous [n, C, h, round_up(w, 8)] tensor of `dtype` on the frames' device; None
     allocates a ZERO-FILLED one.
     status, tables, extra_flags, skip_rejected: decode_crops'."""
-    w, h = _crop_size(frames, size)
-    fmt = _norm_format(dtype)
-    C, c_scale, c_bias = _plane_coefficients(scale, bias)
-    ps = _plane_stride(frames, C, plane_stride)
-    host = _host_norm_crops(frames, crops, w, h)
-    if host is not None:
-        bad = host[:, 0].astype(np.int64) + (C - 1) * ps >= frames.n_frames
-        if bad.any():
-            i = int(np.flatnonzero(bad)[0])
-            raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {C - 1} would be frame "
-                             f"{int(host[i, 0]) + (C - 1) * ps} of {frames.n_frames}")
-    cols = (w + 7) // 8 * 8
-    pitch = cols * (2, 2, 4)[fmt]
-    return _decode_list("decode_crops_normalized_planes", "mh_decode_crops_norm_planes", frames, tables, crops, host,
-                        (w, h, fmt, C, ps, c_scale, c_bias), (C, h, cols), _NORM_DTYPES[fmt],
-                        (pitch, h * pitch, C * h * pitch), out, status, stream, extra_flags, skip_rejected)
+    return _decode_planes("decode_crops_normalized_planes", "mh_decode_crops_norm_planes", frames, tables, crops, size,
+                          dtype, scale, bias, None, plane_stride, out, status, stream, extra_flags, skip_rejected)
 
 
 def _frame_set(who: str, fs) -> "DeviceFrameSet":
@@ -1063,33 +1086,9 @@ def decode_set_crops_normalized_planes(fs: DeviceFrameSet, tables, crops, size, 
     Everything else -- crops, flags, scale, bias, plane_stride, out, status, tables -- is
     decode_crops_normalized_planes', with `tables` as in decode_set_crops."""
     fs = _frame_set("decode_set_crops_normalized_planes", fs)
-    w, h = _crop_size(fs, size)
-    fmt = _norm_format(dtype)
-    C, c_scale, c_bias = _plane_coefficients(scale, bias)
-    if n_planes is not None and int(n_planes) != C:
-        raise ValueError(f"n_planes = {n_planes}, but scale and bias hold {C} values")
-    ps = _plane_stride(fs, C, plane_stride)
-    host = _host_norm_crops(fs, crops, w, h)
-    if host is not None:
-        f0 = host[:, 0].astype(np.int64)
-        bad = f0 + (C - 1) * ps >= fs.n_frames
-        if bad.any():
-            i = int(np.flatnonzero(bad)[0])
-            raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {C - 1} would be frame "
-                             f"{int(host[i, 0]) + (C - 1) * ps} of {fs.n_frames}")
-        lw, lh = fs.size_limits()
-        for c in range(1, C):
-            bad = (lw[f0 + c * ps] != lw[f0]) | (lh[f0 + c * ps] != lh[f0])
-            if bad.any():
-                i = int(np.flatnonzero(bad)[0])
-                raise ValueError(f"crop {i} = {tuple(int(v) for v in host[i])}: plane {c} (frame "
-                                 f"{int(f0[i]) + c * ps}) is not of plane 0's size")
-    cols = (w + 7) // 8 * 8
-    pitch = cols * (2, 2, 4)[fmt]
-    head = fs._head(fs.codes.get_device())
-    return _decode_list("decode_set_crops_normalized_planes", "mh_decode_set_crops_norm_planes", fs, tables, crops,
-                        host, (w, h, fmt, C, ps, c_scale, c_bias), (C, h, cols), _NORM_DTYPES[fmt],
-                        (pitch, h * pitch, C * h * pitch), out, status, stream, extra_flags, skip_rejected, head)
+    return _decode_planes("decode_set_crops_normalized_planes", "mh_decode_set_crops_norm_planes", fs, tables, crops,
+                          size, dtype, scale, bias, n_planes, plane_stride, out, status, stream, extra_flags,
+                          skip_rejected)
 
 
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,
