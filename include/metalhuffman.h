@@ -724,7 +724,8 @@ int mh_decode_crops_norm_planes_shape(const mh_frame *frame, uint32_t n_crops, u
 /* is n frames, each with its own width, height and table; the two entries below decode crops of   */
 /* any mix of them in one launch, through the bodies of mh_decode_crops and                        */
 /* mh_decode_crops_norm_planes.                                                                    */
-/* Not covered: a set for the frame, region, window and scaled entries; mh_check_frames over a set */
+/* The frames of a set whole, each at its own size: mh_decode_set_frames, further below.            */
+/* Not covered: a set for the region, window and scaled entries; mh_check_frames over a set        */
 /* (a caller checks per size group and scatters the verdicts into one d_frame_status); sets in the */
 /* streams and the multi-GPU paths. (The set's device producer is mh_encode_set_device_async; what */
 /* it does not cover -- a shared table over a set, compaction of the code slots -- is listed there.)*/
@@ -807,6 +808,105 @@ int mh_decode_set_crops_norm_planes(const mh_frame *frame, const mh_frame_geom *
 int mh_decode_set_crops_norm_planes_shape(const mh_frame *frame, uint32_t n_crops, uint32_t w, uint32_t h,
                                           uint32_t format, uint32_t n_planes, void *stream,
                                           uint32_t *groups_per_plane, uint32_t *waves_per_group);
+
+/* ---------------------------------------------------------------------- */
+/* Every frame of a set WHOLE, each at its own size into its own raster, in one launch: the       */
+/* consumer that closes encode set -> tables -> decode without regrouping the frames by size into  */
+/* K mh_frame batches (K mh_decode_frames launches; n when every size differs).                    */
+/* The frames differ in size, so neither one pitch nor one workgroup count fits them all: frame    */
+/* f's raster and its share of the launch are two more 16-byte device records beside its           */
+/* mh_frame_geom, and a group map gives every workgroup of the launch its frame. All three come    */
+/* from mh_decode_set_plan (pure host code) or from the caller; the device validates every record  */
+/* before anything is addressed through it, as every set record.                                   */
+typedef struct {
+  uint64_t offset;      /* bytes from d_out to the frame's row 0; multiple of 8                    */
+  uint32_t pitch;       /* bytes per raster row; multiple of 8, >= round_up(W_f, 8), <= 2^20       */
+  uint32_t reserved;    /* must be 0                                                               */
+} mh_set_raster;        /* 16 bytes: where frame f is written */
+
+typedef struct {
+  uint32_t first_group; /* index of the frame's first workgroup in the launch                      */
+  uint32_t groups;      /* workgroups that share the frame, 1..2^20                                */
+  uint32_t reserved[2]; /* must be 0                                                               */
+} mh_set_share;         /* 16 bytes: how frame f's tiles are shared out. The slice count of a frame
+                           lives in this one record: its workgroups cannot disagree about it. */
+
+#define MH_DECODE_GROUP_WAVES 8 /* waves of a workgroup of the frame-slice kernels: each decodes a tile */
+
+/* `frame` is a set (the rules above mh_decode_set_crops: dims the maxima, d_frame_code_offsets,
+ * tables by frame number with lut_stride_bytes 0 for one shared table, MH_FLAG_NO_DELTA |
+ * MH_FLAG_ANY_ORDER only). Frame f is written as mh_decode_frames writes a frame: only rows
+ * y < H_f, and round_up(W_f, 8) bytes of each, at d_out + offset_f + y * pitch_f, bit-exact to
+ * mh_decode_frame_cpu; the rest of the pitch and every other byte of d_out are not touched.
+ * d_group_frame: device u32[n_groups]; the launch has n_groups workgroups of
+ * MH_DECODE_GROUP_WAVES waves, and workgroup g serves frame d_group_frame[g] as slice
+ * g - first_group of its `groups`: wave w of slice j decodes the frame's tiles j * 8 + w,
+ * + groups * 8, ... -- a tile is 64 consecutive blocks of the frame in block order, counted from
+ * the frame's own block 0, so every lane of every tile but a frame's last holds a block whatever
+ * the width.
+ * Device validation, by workgroup g, in this order, each step passing before anything is addressed
+ * through what it validates:
+ *  1. the group map: d_group_frame[g] >= n_frames -> the workgroup returns and writes nothing;
+ *  2. the frame's three records (they depend on f alone: two dependent trips, as the set crops'):
+ *     share: reserved != 0, groups == 0 or above 2^20, g < first_group or g - first_group >= groups
+ *       -> the workgroup returns and writes nothing: it is not one of the frame's. The share is
+ *       judged ahead of the other two records because it says which workgroup is the frame's slice
+ *       0, the writer of d_set_status[f]: a frame whose share AND geometry (or raster) are bad
+ *       reports nothing, not MH_ERR_DIMS;
+ *     geometry: judged exactly as mh_decode_set_crops' step 2 -> MH_ERR_DIMS;
+ *     raster: reserved != 0, offset % 8 != 0, pitch % 8 != 0, pitch < round_up(W_f, 8), pitch above
+ *       2^20 (every entry's pitch limit), or offset + (H_f - 1) * pitch + round_up(W_f, 8) >
+ *       out_bytes (formed so that nothing wraps) -> MH_ERR_CAPACITY;
+ *  3. d_frame_status[f] != 0 (optional input) skips the frame, as in every decode entry.
+ * No byte of a rejected or skipped frame's raster is written, and the other frames are decoded.
+ * d_set_status (optional, device int32[n_frames], must not alias d_frame_status ->
+ * MH_ERR_INVALID_ARG): one thread of the frame's slice 0 writes d_set_status[f] with a vector
+ * store: MH_OK, MH_ERR_DIMS, MH_ERR_CAPACITY, or the frame's non-zero status word. A word whose
+ * slice-0 workgroup never arrives (a corrupt map or share) is left as the caller set it.
+ * A stale or corrupt record may lose or repeat tiles of its own frame. It never moves a load
+ * outside d_block_offsets / d_block_init / d_geoms nor a store outside [d_out, d_out + out_bytes).
+ * Rasters that overlap are the caller's business: the planner's never do.
+ * Checks, all before any HIP call, in mh_decode_set_crops' order and with its codes:
+ * MH_ERR_INVALID_ARG: d_set_status == d_frame_status; NULL frame, d_out, d_block_offsets, d_codes,
+ * d_geoms, d_rasters, d_shares, d_group_frame, d_luts; total_blocks, n_groups or out_bytes 0;
+ * n_groups above 2^31 - 1; n_frames 0 or n_frames > 1 without d_frame_code_offsets; a flag outside
+ * the two. MH_ERR_DIMS: dims' maxima outside 1..65535. MH_ERR_ALIGN: d_codes, d_luts,
+ * lut_stride_bytes or a record array not 16-byte aligned; d_group_frame not 4-byte aligned; d_out
+ * not 8-byte aligned. MH_ERR_CAPACITY: codes_bytes < MH_CODES_PAD; lut_stride_bytes neither 0 nor
+ * >= mh_lut_bytes(). One kernel launch, asynchronous on `stream`. */
+int mh_decode_set_frames(const mh_frame *frame, const mh_frame_geom *d_geoms, uint32_t total_blocks,
+                         const mh_set_raster *d_rasters, const mh_set_share *d_shares,
+                         const uint32_t *d_group_frame, uint32_t n_groups,
+                         const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                         const int32_t *d_frame_status, int32_t *d_set_status,
+                         uint8_t *d_out, uint64_t out_bytes, void *stream);
+
+/* The planner's budget on `stream`'s device (no launch): the workgroups of the kernel resident on
+ * the device at once (CUs x the kernel's occupancy, the R of mh_decode_frames' shape rule) and the
+ * waves per workgroup. Only frame->flags is read (MH_FLAG_NO_DELTA selects the kernel). */
+int mh_decode_set_frames_shape(const mh_frame *frame, void *stream,
+                               uint32_t *resident_groups, uint32_t *waves_per_group);
+
+/* The records and the group map for mh_decode_set_frames from the host copy of the geometry
+ * records. Pure host code: no HIP, callable without a GPU.
+ * Rasters: dense, in frame order; with A = max(8, pitch_align), pitch_f = round_up(W_f, A) and
+ * every offset is rounded up to A; *out_bytes is the end of the last raster (offset + H * pitch).
+ * pitch_align: 0 or a power of two <= 4096.
+ * Groups: with tiles_f = ceil(NB_f / 64) and cap_f = ceil(tiles_f / MH_DECODE_GROUP_WAVES),
+ *   groups_f = clamp(round(group_budget * tiles_f / sum of tiles), 1, cap_f)   (half rounds up),
+ * so a budget of one resident round (mh_decode_set_frames_shape) gives each frame workgroups in
+ * proportion to its work, and no workgroup is left without a tile. first_group is the running
+ * sum; the map names frame f for groups_f consecutive workgroups; *n_groups is the sum.
+ * MH_ERR_INVALID_ARG: NULL h_geoms, n_groups or out_bytes; n_frames == 0; group_budget == 0; a
+ * bad pitch_align; group_capacity != 0 with a NULL output array. MH_ERR_DIMS: a record with
+ * reserved != 0, a width or height outside 1..65535, first_block + NB_f above 2^32, more than
+ * 2^31 - 1 workgroups, or a byte total above 2^64 - 1. MH_ERR_CAPACITY: group_capacity <
+ * *n_groups; *n_groups and *out_bytes are reported and no array is written, so a first call with
+ * capacity 0 (the three output arrays may then be NULL) sizes them. */
+int mh_decode_set_plan(uint32_t n_frames, const mh_frame_geom *h_geoms, uint32_t group_budget,
+                       uint32_t pitch_align, mh_set_raster *h_rasters, mh_set_share *h_shares,
+                       uint32_t *h_group_frame, uint32_t group_capacity,
+                       uint32_t *n_groups, uint64_t *out_bytes);
 
 /* For tests and tools: the table mh_decode_headers builds in LDS, copied out. One workgroup per
  * header runs the same builder and writes the 13-bit table (the first 18,464 bytes of a

@@ -31,6 +31,12 @@ of mdejong/MetalHuffman).
                                     frame SET -- frames of different sizes, a geometry record each -- so a
                                     sampled batch over images of many sizes is one launch, not one per size;
                                     codec.frame_set_layout is the host packer
+  * decoder.decode_set_frames / decode_set_frames_shape / DeviceSetPlan   every frame of a set WHOLE, each at
+                                    its own size into its own raster, one launch (a raster and a share record
+                                    per frame and a group map, validated on the device before use: a rejected
+                                    geometry is MH_ERR_DIMS, a rejected raster MH_ERR_CAPACITY, a skipped frame
+                                    its status word); codec.decode_set_plan is the host planner (no GPU needed).
+                                    Not covered: regions, windows and scaled decodes over a set
   * encoder.Encoder                 GPU encoder (encode / encode_async: no host sync)
   * encoder.BatchEncoder            n frames per call; AsyncEncodedBatch.decode(): encode ->
                                     n tables -> decode on one stream, no host sync;
@@ -42,7 +48,8 @@ of mdejong/MetalHuffman).
                                     frames, no transposed copy; codec.image_planes defines the planes
   * encoder.encode_set_async / encode_image_set_async   frames (planes of images) of DIFFERENT sizes, a table
                                     each, straight into the frame-set layout in three launches; AsyncEncodedSet
-                                    .frame_set() / .table_set() feed decode_set_crops* with no host sync;
+                                    .frame_set() / .table_set() feed decode_set_crops* with no host sync, and
+                                    .decode() is encode -> n tables -> decode_set_frames on one stream;
                                     codec.encode_set_plan is the host planner (no GPU needed)
   * stream                          streaming from host memory (config 5); HeaderFrameStream: a header per frame
   * dist                            frame sharding, single-frame bands, table broadcast
@@ -51,7 +58,7 @@ from ._native import (EXPORTS, LIB_PATH, MH_CODES_PAD, MH_CROP_MIRROR, MH_ENCODE
                       MH_FLAG_LANE_PAIRS,
                       MH_FLAG_NO_DELTA, MH_MAX_PLANES, MH_NORM_BF16, MH_NORM_F16, MH_NORM_F32, MHError, lib)
 from .codec import (BLOCK_DIM, EncodedFrame, FrameSetLayout, Huffman, block_grid, box_reduce, check_frame, code_lengths_limited,
-                    decode_frame_cpu, encode_frame, encode_set_plan, frame_histogram, frame_set_layout, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
+                    decode_frame_cpu, decode_set_plan, DecodeSetPlan, encode_frame, encode_set_plan, frame_histogram, frame_set_layout, image_planes, merge_blocks, norm_coefficients, norm_table, shared_header,
                     split_blocks)
 
 __all__ = [
@@ -60,6 +67,6 @@ __all__ = [
     "MH_ENCODE_LIMIT_LENGTHS", "code_lengths_limited", "box_reduce", "frame_histogram", "shared_header",
     "norm_table", "MH_NORM_F16", "MH_NORM_BF16", "MH_NORM_F32", "MH_CROP_MIRROR",
     "MH_MAX_PLANES", "norm_coefficients", "image_planes", "check_frame", "MH_ERR_STREAM",
-    "FrameSetLayout", "frame_set_layout", "encode_set_plan",
+    "FrameSetLayout", "frame_set_layout", "encode_set_plan", "decode_set_plan", "DecodeSetPlan",
 ]
 __version__ = "0.1.0"

@@ -12,6 +12,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MH_LIB") or os.path.join(_PKG, "libmetalhuffman_amd.so")
 
 MH_OK = 0
+MH_ERR_DIMS = -2
+MH_ERR_CAPACITY = -4
 MH_ERR_STREAM = -9  # a per-frame verdict of mh_check_frames / mh_check_headers: the report is not clean
 MH_FLAG_NO_DELTA = 0x1
 MH_FLAG_LANE_PAIRS = 0x2  # lane-pair single-frame decode: diagnostic library only (diag_lanepairs())
@@ -61,6 +63,7 @@ EXPORTS = (
     "mh_check_frames", "mh_check_frames_shape", "mh_check_headers", "mh_check_headers_shape",
     "mh_check_frame_cpu",
     "mh_encode_set_plan_bytes", "mh_encode_set_plan", "mh_encode_set_device_async",
+    "mh_decode_set_frames", "mh_decode_set_frames_shape", "mh_decode_set_plan",
 )
 
 
@@ -116,6 +119,19 @@ class mh_norm_crop(ctypes.Structure):
 class mh_frame_geom(ctypes.Structure):
     _fields_ = [("first_block", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+class mh_set_raster(ctypes.Structure):
+    """Where mh_decode_set_frames writes frame f: row y at d_out + offset + y * pitch."""
+    _fields_ = [("offset", ctypes.c_uint64), ("pitch", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class mh_set_share(ctypes.Structure):
+    """How frame f's tiles are shared out: workgroups [first_group, first_group + groups) of the launch."""
+    _fields_ = [("first_group", ctypes.c_uint32), ("groups", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+MH_DECODE_GROUP_WAVES = 8  # waves of a workgroup of the frame-slice kernels
 
 
 class mh_image_layout(ctypes.Structure):
@@ -273,6 +289,11 @@ def lib() -> ctypes.CDLL:
             set_name = name.replace("mh_decode_", "mh_decode_set_")
             getattr(L, set_name).argtypes = [args[0], _vp, ctypes.c_uint32] + list(args[1:])
             getattr(L, set_name + "_shape").argtypes = getattr(L, name + "_shape").argtypes
+        L.mh_decode_set_frames.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint32, _vp, _vp, _vp,
+                                           ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint64, _vp]
+        L.mh_decode_set_frames_shape.argtypes = [ctypes.POINTER(mh_frame), _vp, _u32p, _u32p]
+        L.mh_decode_set_plan.argtypes = [ctypes.c_uint32, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
+                                         ctypes.c_uint32, _u32p, _u64p]
         L.mh_box_reduce.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp,
                                     ctypes.c_size_t]
         L.mh_header_luts_device.argtypes = [_vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]

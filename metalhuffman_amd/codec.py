@@ -214,6 +214,46 @@ def encode_set_plan(sources, flags: int = 0) -> SetPlan:
     return SetPlan(plan[:size], totals)
 
 
+class DecodeSetPlan(NamedTuple):
+    """decode_set_plan's result, in the device's formats: what decode_set_frames uploads."""
+    rasters: np.ndarray      # u32[n, 4]: mh_set_raster records (offset low, offset high, pitch, 0)
+    shares: np.ndarray       # u32[n, 4]: mh_set_share records (first_group, groups, 0, 0)
+    group_frame: np.ndarray  # u32[n_groups]: the frame of every workgroup of the launch
+    n_groups: int
+    out_bytes: int
+
+    @property
+    def offsets(self) -> np.ndarray:
+        """int64[n]: each frame's byte offset into the output."""
+        return self.rasters[:, 0].astype(np.int64) | (self.rasters[:, 1].astype(np.int64) << 32)
+
+    @property
+    def pitches(self) -> np.ndarray:
+        return self.rasters[:, 2].astype(np.int64)
+
+
+def decode_set_plan(geoms, group_budget: int, pitch_align: int = 0) -> DecodeSetPlan:
+    """The host planner of decode_set_frames (mh_decode_set_plan; no GPU needed): from the set's
+    geometry records u32[n, 4] (first_block, width, height, 0) the rasters laid out densely in frame
+    order (pitch and offsets multiples of max(8, pitch_align)), and group_budget workgroups shared
+    out in proportion to the frames' tiles, at least one and at most ceil(tiles / 8) per frame.
+    MHError carries the planner's code."""
+    g = np.ascontiguousarray(geoms, np.uint32).reshape(-1, 4)
+    n = int(g.shape[0])
+    L = N.lib()
+    ng, ob = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    rc = L.mh_decode_set_plan(n, g.ctypes.data, group_budget, pitch_align, None, None, None, 0, ctypes.byref(ng),
+                              ctypes.byref(ob))
+    if rc != N.MH_ERR_CAPACITY:  # the sizing call's own answer; anything else is a refusal
+        N.check(rc, "mh_decode_set_plan")
+    rasters, shares = np.zeros((n, 4), np.uint32), np.zeros((n, 4), np.uint32)
+    group_frame = np.zeros(ng.value, np.uint32)
+    N.check(L.mh_decode_set_plan(n, g.ctypes.data, group_budget, pitch_align, rasters.ctypes.data, shares.ctypes.data,
+                                 group_frame.ctypes.data, ng.value, ctypes.byref(ng), ctypes.byref(ob)),
+            "mh_decode_set_plan")
+    return DecodeSetPlan(rasters, shares, group_frame, int(ng.value), int(ob.value))
+
+
 class Huffman:
     """Stateless mirror of the reference's `Huffman` class (Shared/Huffman.h)."""
 

@@ -811,12 +811,16 @@ struct FrameMap {
   static constexpr bool kRegion = false;
   static constexpr bool kCrop = false;
   static constexpr bool kOwnBase = false;
+  static constexpr bool kOwnTiles = false;  // tiles count through the batch (frame_of)
+  static constexpr bool kResume = false;    // batch_loop stays in its slow loop behind an oversize tile
   __device__ __forceinline__ void report(uint32_t, uint32_t) const {}
 };
 struct RegionMap {
   static constexpr bool kRegion = true;
   static constexpr bool kCrop = false;
   static constexpr bool kOwnBase = false;  // a.offsets / a.block_init are the batch's: frame f's entries at + f * a.nb
+  static constexpr bool kOwnTiles = false;  // (a region's tiles are frame relative by kRegion itself)
+  static constexpr bool kResume = false;
   static constexpr uint32_t kStep = 64u;  // blocks from one tile of a row to the next
   uint32_t f, bx0, by0, bw, S;
   // BoxRows only: the frame's pixels from the region's origin on, (W - 8 bx0) | (H - 8 by0) << 16
@@ -865,6 +869,26 @@ struct SetNormMap : NormMap {
   static constexpr bool kOwnBase = true;
 };
 
+// SetFrameMap (mh_decode_set_frames): FrameMap's tiles -- 64 consecutive blocks of the frame in block
+//   order, every lane of every tile but the frame's last holding a block -- over a frame SET. The
+//   frames differ in size, so no tile index runs through the set: tiles count from the frame's own
+//   block 0 (kOwnTiles: a.total_tiles == a.tiles_per_frame == the frame's tiles, no f * tiles and no
+//   tile -> frame division anywhere), the arrays are based at the frame's first block (kOwnBase) and
+//   the raster's base is the frame's own (slot 0, stride 0). `f` still addresses the codes, the table
+//   and the status word; report() carries the frame's status word into the set's.
+struct SetFrameMap {
+  static constexpr bool kRegion = false;
+  static constexpr bool kCrop = false;
+  static constexpr bool kOwnBase = true;
+  static constexpr bool kOwnTiles = true;
+  static constexpr bool kResume = true;  // back to the pipelined loop behind one oversize tile
+  uint32_t f;
+  int32_t *sstatus;  // d_set_status or null
+  __device__ __forceinline__ void report(uint32_t frame_status, uint32_t slice) const {
+    if (sstatus && slice == 0 && threadIdx.x == 0) sstatus[f] = (int32_t)frame_status;
+  }
+};
+
 struct TileHdrBase {
   uint32_t tile;      // wave-uniform; >= total_tiles: no tile
   uint32_t off;       // this lane's block start bit
@@ -909,6 +933,9 @@ __device__ __forceinline__ void hdr_issue(const DecodeArgs &a, uint32_t tile, ui
     region_rs(m, tile, h.r, h.s);
     f = m.f;
     b = (live ? (m.by0 + h.r) * a.bw + m.bx0 + Map::kStep * h.s : 0u) + lane;
+  } else if constexpr (Map::kOwnTiles) {
+    f = m.f;
+    b = (live ? tile * 64u : 0u) + lane;
   } else {
     f = live ? frame_of(a, tile) : 0u;
     b = (live ? (tile - f * a.tiles_per_frame) * 64u : 0u) + lane;
@@ -965,6 +992,9 @@ __device__ __forceinline__ TileOf<Map> hdr_resolve(const DecodeArgs &a, const Ti
     t.s = h.s;
     t.n = min(64u, m.bw - Map::kStep * h.s);
     t.b0 = (m.by0 + h.r) * a.bw + m.bx0 + Map::kStep * h.s;
+  } else if constexpr (Map::kOwnTiles) {
+    t.f = 0u;  // the raster's base is the frame's own
+    t.b0 = h.tile * 64u;
   } else {
     t.f = frame_of(a, h.tile);
     t.b0 = (h.tile - t.f * a.tiles_per_frame) * 64u;
@@ -1255,12 +1285,16 @@ template <bool kDelta, class Cfg, class Map = FrameMap, class Out = StoreRows>
 __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, uint8_t *stage,
                                            const uint8_t *lut, uint32_t t0, uint32_t gstride,
                                            const TileHdrOf<Map> &hc, bool synced MH_TS_PARAM, const Map &m = Map()) {
+  // the header of the loop's first tile: the caller's, or (Map::kResume, below) that of the tile at
+  // which the pipelined loop is entered again. By value: through a pointer it would live in scratch.
+  TileHdrOf<Map> h0 = hc;
+resume:
   TileHdrOf<Map> hn;
 #if MH_DIAG_STAMPS
   bool first_tile = true;
 #endif
   v4u32 R[kStageChunks];
-  TileOf<Map> cur = hdr_resolve(a, hc, lane, m);
+  TileOf<Map> cur = hdr_resolve(a, h0, lane, m);
   MH_STAMP(1);
   bool cur_staged = cur.tile < a.total_tiles && cur.span <= (uint32_t)kStageBytes;
   span_issue(a, cur, lane, R, cur_staged);
@@ -1321,6 +1355,15 @@ __device__ __forceinline__ void batch_loop(const DecodeArgs &a, uint32_t lane, u
     const TileOf<Map> tt = hdr_resolve(a, h, lane, m);
     const OutTile ot = out_tile<Map, Out>(a, tt, lane, m);
     decode_halves<kDelta, Cfg, Map>(a, tt, lane, lut, stage, ot.rsrc, ot.row0, !tt.valid, rows_of<Out>(a, tt, lane, m));
+    // Map::kResume: only the oversize tile itself is decoded here. The wave issues its next tile's
+    // header and enters the pipelined loop again, so one dense tile early in a frame does not put
+    // the wave's other tiles (about ten in a set launch) on the unpipelined path.
+    if constexpr (Map::kResume) {
+      t0 = next_tile(a, t, gstride);
+      if (t0 >= a.total_tiles) return;
+      hdr_issue(a, t0, lane, h0, m);
+      goto resume;
+    }
   }
 }
 
@@ -1824,7 +1867,10 @@ __device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_
   a.nb = p_nb;
   a.tiles_per_frame = p_tiles_per_frame;
   // this workgroup's tiles end with its frame
-  a.total_tiles = Map::kRegion ? p_tiles_per_frame : (f + 1u) * p_tiles_per_frame;
+  if constexpr (Map::kOwnTiles)
+    a.total_tiles = p_tiles_per_frame;  // a set's frame: tiles from its own block 0
+  else
+    a.total_tiles = Map::kRegion ? p_tiles_per_frame : (f + 1u) * p_tiles_per_frame;
   constexpr uint32_t nwaves = kMaxWavesPerWG;
   a.nwaves = nwaves;
   a.grid = G;
@@ -1836,7 +1882,11 @@ __device__ __forceinline__ void slice_decode(const DecodeArgs &a0, const uint32_
 #endif
   MH_STAMP(0);
 
-  const uint32_t t0 = min((Map::kRegion ? 0u : f * p_tiles_per_frame) + slice * nwaves + wave, a.total_tiles);
+  uint32_t t0;
+  if constexpr (Map::kOwnTiles)
+    t0 = min(slice * nwaves + wave, a.total_tiles);
+  else
+    t0 = min((Map::kRegion ? 0u : f * p_tiles_per_frame) + slice * nwaves + wave, a.total_tiles);
   TileHdrOf<Map> hc;
   const uint32_t stv = __builtin_amdgcn_raw_buffer_load_b32(
       uniform_rsrc(p_status ? (const void *)(p_status + f) : (const void *)p_offsets, p_status ? 4u : 0u), 0, 0, 0);
@@ -2299,6 +2349,85 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode
       ac, sf.offsets, p_frame_off, sf.block_init, nullptr, sf.nb, g.rows * p_segs, p_groups, ps.f, u.slice,
       PreparedTable{p_luts, p_lut_stride},
       SetNormMap{{{{{ps.f, x0 >> 3, y0 >> 3, g.nblk, p_segs, g.rem}, 0u, nullptr}}, nc.sel, nc.scale, nc.bias}});
+}
+
+// mh_decode_set_frames: every frame of a set whole, each at its own size into its own raster. The
+// grid is a list of workgroups, not of units of one size: workgroup g reads its frame number from
+// the group map (one trip), then the frame's three 16-byte records, which depend on f alone (the
+// second trip, as the set crops'): the geometry (geom_load / geom_bad), the share {first_group,
+// groups, 0, 0} that says which slice of the frame g is, and the raster {offset, pitch, 0} that says
+// where the frame is written. The slice count of a frame lives in its one share record, so the
+// frame's workgroups cannot disagree about it. Verdicts, each before anything is addressed through
+// what it judges:
+//   map word >= n_frames                       -> return, nothing written;
+//   share: reserved != 0, groups == 0 or > 2^20 (no frame has more tiles; it keeps G * 8 and every
+//     tile sum far from 2^32), g outside [first_group, first_group + groups)
+//                                              -> return, nothing written (not a workgroup of f);
+//   geometry rejected                          -> MH_ERR_DIMS;
+//   raster: reserved != 0, offset or pitch not a multiple of 8, pitch < round_up(W, 8) or > 2^20
+//     (every entry's pitch limit: a lane's row offset stays below 2^31), or the last row's end
+//     offset + (H - 1) pitch + round_up(W, 8) past out_bytes, formed so that nothing wraps
+//                                              -> MH_ERR_CAPACITY.
+// The two codes go to d_set_status[f] by slice 0's first thread; behind them SetFrameMap::report
+// writes the frame's status word there (0: MH_OK). A corrupt share or map can lose or repeat tiles of
+// its own frame only: offsets and block_init stay inside the frame's accepted [first, first + nb),
+// every store inside the accepted raster.
+__device__ __forceinline__ bool share_bad(const v4u32 s, uint32_t g) {
+  return ((s.z | s.w) != 0u) | (s.y - 1u > 0xFFFFFu) | (g < s.x) | (g - s.x >= s.y);
+}
+__device__ __forceinline__ bool raster_bad(const v4u32 r, uint32_t W, uint32_t H, uint64_t out_bytes) {
+  const uint64_t offset = ((uint64_t)r.y << 32) | r.x;
+  const uint32_t pitch = r.z, rw = (W + 7u) & ~7u;
+  const uint64_t tail = (uint64_t)(H - 1u) * pitch + rw;  // < 2^16 * 2^32 + 2^16
+  return (r.w != 0u) | (((r.x | pitch) & 7u) != 0u) | (pitch < rw) | (pitch > (1u << 20)) | (tail > out_bytes) |
+         (offset > out_bytes - tail);
+}
+__device__ __forceinline__ void set_reject(int32_t *status, uint32_t f, bool writer, int32_t code) {
+  if (status && writer) status[f] = code;
+}
+// The frame's raster, opaque as set_frame's values and for the same reason.
+struct SetRaster {
+  uint8_t *out;
+  uint32_t pitch;
+  uint64_t bytes;  // H * pitch
+};
+__device__ __forceinline__ SetRaster set_raster(uint8_t *out, const v4u32 r, uint32_t H) {
+  const uint64_t o = (uint64_t)out + (((uint64_t)r.y << 32) | r.x), n = (uint64_t)H * r.z;
+  uint32_t o_lo = (uint32_t)o, o_hi = (uint32_t)(o >> 32), n_lo = (uint32_t)n, n_hi = (uint32_t)(n >> 32), pitch = r.z;
+  asm volatile("" : "+s"(o_lo), "+s"(o_hi), "+s"(n_lo), "+s"(n_hi), "+s"(pitch));
+  return {(uint8_t *)(((uint64_t)o_hi << 32) | o_lo), pitch, ((uint64_t)n_hi << 32) | n_lo};
+}
+
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMaxWavesPerWG, kMinWavesPerEU) mh_decode_setframes_kernel(
+    const uint32_t *p_offsets, const uint64_t *p_frame_off, const uint8_t *p_block_init, const uint8_t *p_luts,
+    const int32_t *p_status, const uint32_t *p_group_frame, uint32_t p_total_blocks, uint32_t p_nframes,
+    uint64_t p_lut_stride, int32_t *p_sstatus, const mh_frame_geom *p_geoms, const mh_set_raster *p_rasters,
+    const mh_set_share *p_shares, uint64_t p_out_bytes, const DecodeArgs a0) {
+  const uint32_t g = blockIdx.x;
+  const uint32_t f = __builtin_amdgcn_readfirstlane(
+      __builtin_amdgcn_raw_buffer_load_b32(uniform_rsrc(p_group_frame + g, 4u), 0, 0, 0));
+  if (f >= p_nframes) return;
+  const v4u32 gd = geom_load(p_geoms, f);
+  const v4u32 sd = desc_load(p_shares + f);
+  const v4u32 rd = desc_load(p_rasters + f);
+  if (share_bad(sd, g)) return;
+  const uint32_t slice = g - sd.x, G = sd.y;
+  const bool writer = slice == 0u && threadIdx.x == 0u;
+  if (geom_bad(gd, p_total_blocks)) return set_reject(p_sstatus, f, writer, MH_ERR_DIMS);
+  const uint32_t W = gd.y, H = gd.z;
+  if (raster_bad(rd, W, H, p_out_bytes)) return set_reject(p_sstatus, f, writer, MH_ERR_CAPACITY);
+  const SetFrame sf = set_frame(p_offsets, p_block_init, gd.x, W, H);
+  const SetRaster sr = set_raster(a0.out, rd, H);
+  DecodeArgs af = slot_args(a0, sr.out);
+  af.w = W;
+  af.h = H;
+  af.bw = sf.bw;
+  af.bh = (H + 7u) >> 3;
+  af.out_pitch = sr.pitch;
+  af.out_frame_bytes = sr.bytes;
+  slice_decode<kDelta>(af, sf.offsets, p_frame_off, sf.block_init, p_status, sf.nb, (sf.nb + 63u) >> 6, G, f, slice,
+                       PreparedTable{p_luts, p_lut_stride}, SetFrameMap{f, p_sstatus});
 }
 
 template <bool kDelta>
@@ -3145,7 +3274,8 @@ enum SliceKernel {
   kSlicePlanes = kSliceNormCrops + 3,          // + the format
   kSliceSetCrops = kSlicePlanes + 3,           // the crops and the planes over a frame set
   kSliceSetPlanes,                             // + the format
-  kSliceKernels = kSliceSetPlanes + 3
+  kSliceSetFrames = kSliceSetPlanes + 3,       // the whole frames of a set
+  kSliceKernels
 };
 #if !MH_LANE_PAIRS
 // One row per kernel, [kDelta]: the row device_info() queries the occupancy of is the row
@@ -3160,6 +3290,7 @@ using NormCropsFn = decltype(&mh_decode_normcrops_kernel<false, MH_NORM_F16>);
 using PlanesFn = decltype(&mh_decode_planes_kernel<false, MH_NORM_F16>);
 using SetCropsFn = decltype(&mh_decode_setcrops_kernel<false>);
 using SetPlanesFn = decltype(&mh_decode_setplanes_kernel<false, MH_NORM_F16>);
+using SetFramesFn = decltype(&mh_decode_setframes_kernel<false>);
 using AnyKernel = void (*)();
 struct SliceRow {
   AnyKernel fn[2];
@@ -3194,8 +3325,10 @@ const SliceRow kSliceTable[] = {
                            mh_decode_setplanes_kernel<true, MH_NORM_BF16>),
     slice_row<SetPlanesFn>(mh_decode_setplanes_kernel<false, MH_NORM_F32>,
                            mh_decode_setplanes_kernel<true, MH_NORM_F32>),
+    slice_row<SetFramesFn>(mh_decode_setframes_kernel<false>, mh_decode_setframes_kernel<true>),
 };
 static_assert(sizeof(kSliceTable) / sizeof(kSliceTable[0]) == kSliceKernels, "one row per SliceKernel");
+static_assert(kMaxWavesPerWG == MH_DECODE_GROUP_WAVES, "mh_decode_set_plan caps a frame's groups by the waves of one");
 #endif
 struct DeviceInfo {
   std::mutex m;
@@ -3393,6 +3526,13 @@ struct DecodeCall {
   bool set = false;
   const void *geoms = nullptr;
   uint32_t total_blocks = 0;
+  // mh_decode_set_frames (kPrepared over a set): the rasters are described by the device records
+  // `rasters` beside `shares` and the group map `group_frame` (n_groups words), inside out_bytes at
+  // d_out; no pitch or stride arrives, so none of their rules applies, and stride 0 is one table
+  bool set_frames = false;
+  const void *rasters = nullptr, *shares = nullptr, *group_frame = nullptr;
+  uint32_t n_groups = 0;
+  uint64_t out_bytes = 0;
   // mh_check_frames / mh_check_headers (kPrepared / kHeaders): no raster and none of its rules, one
   // table for all frames at stride 0 as a region's, and `words`, the OR of the report's and the
   // verdict's addresses, 4-byte aligned
@@ -3402,6 +3542,7 @@ struct DecodeCall {
   // number of rasters, which is the number of units the grid is cut into
   RegionExtent re = {};
   uint32_t n_units = 0;
+  bool rasterless() const { return walk || set_frames; }  // no out_pitch / out_frame_stride to judge
   bool cropped() const { return kind == kCrops || kind == kNormCrops; }
   bool windowed() const { return kind == kWindows || cropped(); }
   bool regional() const { return kind == kRegion || windowed(); }
@@ -3473,6 +3614,9 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (regional && !c.rg) return MH_ERR_INVALID_ARG;
   if (windowed && (!c.windows || c.n_windows == 0)) return MH_ERR_INVALID_ARG;
   if (c.set && (!c.geoms || c.total_blocks == 0)) return MH_ERR_INVALID_ARG;
+  if (c.set_frames && (!c.rasters || !c.shares || !c.group_frame || c.n_groups == 0 || c.n_groups > 0x7FFFFFFFu ||
+                       c.out_bytes == 0))
+    return MH_ERR_INVALID_ARG;
   if (in_frame ? (!fr->d_table1 || !fr->d_table2) : !c.ptr) return MH_ERR_INVALID_ARG;
   if (fr->n_frames == 0 || (fr->n_frames > 1 && !fr->d_frame_code_offsets)) return MH_ERR_INVALID_ARG;
   const int rc = call_geometry(fr, c);
@@ -3490,10 +3634,13 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
       (n_rasters > 1 && (out_frame_stride & am)) || (c.n_planes > 1 && (c.out_plane_stride & am)))
     return MH_ERR_ALIGN;
   if (windowed && (((uintptr_t)c.windows | (uintptr_t)c.geoms) & 15u)) return MH_ERR_ALIGN;
+  if (c.set_frames && ((((uintptr_t)c.geoms | (uintptr_t)c.rasters | (uintptr_t)c.shares) & 15u) ||
+                       ((uintptr_t)c.group_frame & 3u)))
+    return MH_ERR_ALIGN;
   if (in_frame ? (((uintptr_t)fr->d_lut & 15u) != 0) : (prepared && (((uintptr_t)c.ptr & 15u) || (c.stride & 15u))))
     return MH_ERR_ALIGN;
   if (c.words & 3u) return MH_ERR_ALIGN;
-  if (!c.walk &&
+  if (!c.rasterless() &&
       (out_pitch < row_bytes || out_pitch > (1u << 20) || (n_rasters > 1 && out_frame_stride < out_pitch * c.re.ph)))
     return MH_ERR_CAPACITY;
   // planes: a plane holds its h rows, and a slot its planes -- (n_planes - 1) * out_plane_stride +
@@ -3505,7 +3652,7 @@ int check_decode_args(const mh_frame *fr, const uint8_t *d_out, size_t out_pitch
   if (fr->codes_bytes < MH_CODES_PAD) return MH_ERR_CAPACITY;
   if (fr->n_frames == 1 && !fr->d_frame_code_offsets && fr->codes_bytes > 0xFFFFFFF0ull)
     return MH_ERR_CAPACITY;
-  if (prepared && c.stride < (uint64_t)kPreparedBytes && !((regional || c.walk) && c.stride == 0))
+  if (prepared && c.stride < (uint64_t)kPreparedBytes && !((regional || c.rasterless()) && c.stride == 0))
     return MH_ERR_CAPACITY;  // mh_lut_bytes()
   return MH_OK;
 }
@@ -4031,6 +4178,56 @@ int mh_decode_set_crops_norm_planes_shape(const mh_frame *fr, uint32_t n_crops, 
   return slice_shape_entry(kSliceSetPlanes, fr,
                            ListCall(DecodeCall::kNormCrops, w, h, 0u, n_crops).over_set().planes(format, n_planes),
                            stream, groups_per_plane, waves_per_group);
+}
+
+// The whole frames of a set: the checks are the set crops' (a prepared-table call over a set, with the
+// records and the group map where the descriptors are and no pitch or stride to judge), and the grid
+// is the caller's group map, one workgroup per word. dims carry the set's maxima and size nothing.
+int mh_decode_set_frames(const mh_frame *fr, const mh_frame_geom *d_geoms, uint32_t total_blocks,
+                         const mh_set_raster *d_rasters, const mh_set_share *d_shares, const uint32_t *d_group_frame,
+                         uint32_t n_groups, const uint16_t *d_luts, uint64_t lut_stride_bytes,
+                         const int32_t *d_frame_status, int32_t *d_set_status, uint8_t *d_out, uint64_t out_bytes,
+                         void *stream) {
+  if (d_set_status && d_set_status == d_frame_status) return MH_ERR_INVALID_ARG;
+  DecodeCall c{DecodeCall::kPrepared, d_luts, lut_stride_bytes};
+  c.set = c.set_frames = true;
+  c.geoms = d_geoms;
+  c.total_blocks = total_blocks;
+  c.rasters = d_rasters;
+  c.shares = d_shares;
+  c.group_frame = d_group_frame;
+  c.n_groups = n_groups;
+  c.out_bytes = out_bytes;
+  const int rc = check_decode_args(fr, d_out, 0, 0, c);
+  if (rc != MH_OK) return rc;
+  DecodeArgs a{};
+  a.offsets = fr->d_block_offsets;
+  a.codes = fr->d_codes;
+  a.frame_off = fr->d_frame_code_offsets;
+  a.codes_bytes = fr->codes_bytes;
+  a.block_init = fr->d_block_init;
+  a.out = d_out;
+  const bool delta = !(fr->flags & MH_FLAG_NO_DELTA), any_order = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
+  const SetFramesFn kernel = reinterpret_cast<SetFramesFn>(kSliceTable[kSliceSetFrames].fn[delta ? 1 : 0]);
+  MH_LAUNCH(kernel, dim3(n_groups), dim3(kMaxWavesPerWG * 64), (hipStream_t)stream, any_order, a.offsets, a.frame_off,
+            a.block_init, reinterpret_cast<const uint8_t *>(d_luts), d_frame_status, d_group_frame, total_blocks,
+            fr->n_frames, lut_stride_bytes, d_set_status, d_geoms, d_rasters, d_shares, out_bytes, a);
+  return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+}
+
+// The planner's budget: the workgroups of the set-frames kernel resident on the device at once (CUs x
+// its occupancy, groups_for's R) and the waves of one. No launch.
+int mh_decode_set_frames_shape(const mh_frame *fr, void *stream, uint32_t *resident_groups,
+                               uint32_t *waves_per_group) {
+  if (!fr || !resident_groups || !waves_per_group) return MH_ERR_INVALID_ARG;
+  if (fr->flags & ~(MH_FLAG_NO_DELTA | MH_FLAG_ANY_ORDER)) return MH_ERR_INVALID_ARG;
+  const DeviceInfo *di = device_info((hipStream_t)stream);
+  if (!di) return MH_ERR_HIP;
+  const uint64_t r = (uint64_t)di->cus.load(std::memory_order_relaxed) *
+                     (uint64_t)di->occ_slice[kSliceSetFrames][(fr->flags & MH_FLAG_NO_DELTA) ? 0 : 1];
+  *resident_groups = (uint32_t)r;
+  *waves_per_group = kMaxWavesPerWG;
+  return MH_OK;
 }
 
 // mh_check's report, frame by frame under the frame's own table, and a verdict word per frame that

@@ -658,6 +658,57 @@ int mh_encode_set_plan(uint32_t n_frames, const mh_set_source *sources, uint32_t
   return MH_OK;
 }
 
+// mh_decode_set_frames' planner: the rasters laid out densely in frame order and the launch's
+// workgroups shared out in proportion to the frames' tiles. Two passes over the records: the first
+// judges them and counts, the second (only with room for the whole map) writes.
+int mh_decode_set_plan(uint32_t n_frames, const mh_frame_geom *h_geoms, uint32_t group_budget, uint32_t pitch_align,
+                       mh_set_raster *h_rasters, mh_set_share *h_shares, uint32_t *h_group_frame,
+                       uint32_t group_capacity, uint32_t *n_groups, uint64_t *out_bytes) {
+  if (!h_geoms || !n_groups || !out_bytes || n_frames == 0 || group_budget == 0) return MH_ERR_INVALID_ARG;
+  if (pitch_align > 4096u || (pitch_align & (pitch_align - 1u))) return MH_ERR_INVALID_ARG;
+  if (group_capacity != 0 && (!h_rasters || !h_shares || !h_group_frame)) return MH_ERR_INVALID_ARG;
+  const uint64_t A = pitch_align > 8u ? pitch_align : 8u;
+  const auto tiles_of = [](const mh_frame_geom &g) {
+    return (uint64_t)(((g.width + 7u) / 8u) * ((g.height + 7u) / 8u) + 63u) / 64u;  // NB <= 2^26
+  };
+  uint64_t sum = 0;
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    const mh_frame_geom &g = h_geoms[f];
+    if (g.reserved || g.width - 1u > MH_MAX_DIM - 1u || g.height - 1u > MH_MAX_DIM - 1u) return MH_ERR_DIMS;
+    const uint64_t nb = (uint64_t)((g.width + 7u) / 8u) * ((g.height + 7u) / 8u);
+    if ((uint64_t)g.first_block + nb > (1ull << 32)) return MH_ERR_DIMS;
+    sum += tiles_of(g);  // <= 2^32 * 2^20
+  }
+  // half rounds up: floor((2 budget tiles + sum) / (2 sum)), below 2^33 * 2^20 + 2^52
+  const auto groups_of = [&](uint64_t tiles) {
+    const uint64_t want = (2ull * group_budget * tiles + sum) / (2ull * sum);
+    const uint64_t cap = (tiles + MH_DECODE_GROUP_WAVES - 1u) / MH_DECODE_GROUP_WAVES;
+    return want < 1u ? 1ull : want > cap ? cap : want;
+  };
+  for (int pass = 0; pass < 2; ++pass) {
+    uint64_t groups = 0, bytes = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+      const mh_frame_geom &g = h_geoms[f];
+      const uint64_t pitch = (g.width + A - 1u) / A * A, offset = (bytes + A - 1u) / A * A;
+      const uint64_t size = pitch * g.height, gf = groups_of(tiles_of(g));
+      if (offset < bytes || offset + size < offset) return MH_ERR_DIMS;
+      if (pass) {
+        h_rasters[f] = mh_set_raster{offset, (uint32_t)pitch, 0u};
+        h_shares[f] = mh_set_share{(uint32_t)groups, (uint32_t)gf, {0u, 0u}};
+        for (uint64_t k = 0; k < gf; ++k) h_group_frame[groups + k] = f;
+      }
+      bytes = offset + size;
+      groups += gf;
+      if (groups > 0x7FFFFFFFull) return MH_ERR_DIMS;
+    }
+    if (pass) break;
+    *n_groups = (uint32_t)groups;
+    *out_bytes = bytes;
+    if (group_capacity < groups) return MH_ERR_CAPACITY;
+  }
+  return MH_OK;
+}
+
 const char *mh_error_string(int status) {
   switch (status) {
     case MH_OK: return "ok";

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .codec import EncodedFrame, block_grid, finite_f32, frame_set_layout
+from .codec import DecodeSetPlan, EncodedFrame, block_grid, decode_set_plan, finite_f32, frame_set_layout
 from .codec import norm_format as _norm_format
 
 ALIGN = 16  # frame code starts inside a packed batch (16-byte buffer loads)
@@ -1089,6 +1089,106 @@ def decode_set_crops_normalized_planes(fs: DeviceFrameSet, tables, crops, size, 
     return _decode_planes("decode_set_crops_normalized_planes", "mh_decode_set_crops_norm_planes", fs, tables, crops,
                           size, dtype, scale, bias, n_planes, plane_stride, out, status, stream, extra_flags,
                           skip_rejected)
+
+
+def decode_set_frames_shape(fs: DeviceFrameSet, stream: Optional[torch.cuda.Stream] = None,
+                            extra_flags: int = 0) -> tuple:
+    """(workgroups resident on the device at once, waves per workgroup) of decode_set_frames' kernel
+    (mh_decode_set_frames_shape): the group budget its planner is given."""
+    fr, dev_index = _slice_entry("decode_set_frames_shape", _frame_set("decode_set_frames_shape", fs), extra_flags)
+    r, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    N.check(N.lib().mh_decode_set_frames_shape(ctypes.byref(fr), _raw_stream_ptr(stream, dev_index), ctypes.byref(r),
+                                               ctypes.byref(w)), "mh_decode_set_frames_shape")
+    return int(r.value), int(w.value)
+
+
+@dataclasses.dataclass
+class DeviceSetPlan:
+    """A codec.DecodeSetPlan uploaded for decode_set_frames: the two record arrays, the group map,
+    and the host copy the frame views are cut by."""
+    plan: DecodeSetPlan
+    rasters: torch.Tensor      # u32 as int32[n, 4]
+    shares: torch.Tensor       # u32 as int32[n, 4]
+    group_frame: torch.Tensor  # u32 as int32[n_groups]
+
+    @classmethod
+    def upload(cls, plan: DecodeSetPlan, device="cuda") -> "DeviceSetPlan":
+        dev = _dev(device)
+        up = [torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32)).to(dev)
+              for a in (plan.rasters, plan.shares, plan.group_frame)]
+        return cls(plan, *up)
+
+
+def _set_plan(fs: DeviceFrameSet, plan, dev_index: int, stream, extra_flags: int) -> DeviceSetPlan:
+    """decode_set_frames' plan argument -> an uploaded plan: None plans from the set's host geometry
+    with the kernel's resident workgroups as the budget, once per set and kernel (cached on `fs`)."""
+    if isinstance(plan, DeviceSetPlan):
+        return plan
+    dev = fs.codes.device
+    with torch.cuda.stream(stream) if stream is not None else _NO_STREAM:
+        if plan is not None:
+            return DeviceSetPlan.upload(plan, dev)
+        key = (fs.sizes, extra_flags & N.MH_FLAG_NO_DELTA, dev_index)
+        cached = fs.__dict__.get("_set_plan")
+        if cached is None or cached[0] != key:
+            budget = decode_set_frames_shape(fs, stream, extra_flags)[0]
+            geoms = np.asarray([(0, w, h, 0) for w, h in fs.sizes], np.uint32)
+            cached = fs.__dict__["_set_plan"] = (key, DeviceSetPlan.upload(decode_set_plan(geoms, budget), dev))
+        return cached[1]
+
+
+def decode_set_frames(fs: DeviceFrameSet, tables, plan=None, out: Optional[torch.Tensor] = None,
+                      frame_status: Optional[torch.Tensor] = None, status=None,
+                      stream: Optional[torch.cuda.Stream] = None, extra_flags: int = 0):
+    """Every frame of a SET whole, each at its own size, in ONE launch (mh_decode_set_frames): the
+    images themselves from the set encoder's output, without regrouping the frames by size.
+    tables: a DeviceTableSet with one table per frame of the set, or one DeviceTables for all.
+    plan: a codec.DecodeSetPlan (uploaded here) or a DeviceSetPlan -- where each frame is written and
+    how the launch's workgroups are shared out; None plans from the set's sizes with one resident
+    round of the device as the budget and keeps the uploaded plan on `fs`. The device validates every
+    record: a frame whose raster record is rejected gets status MH_ERR_CAPACITY, one whose geometry is
+    rejected MH_ERR_DIMS, and neither is written.
+    out: a contiguous uint8 tensor of at least plan.out_bytes bytes on the set's device, 8-byte
+    aligned; None allocates a ZERO-FILLED one.
+    frame_status: int32[n] on the device, a non-zero word skips the frame (its raster untouched); None
+    takes a DeviceTableSet's build status.
+    status: True allocates, or an int32 [n] tensor receives, a word per frame (MH_OK, the two codes
+    above, or the frame's non-zero status word).
+    Returns a list of n uint8 tensors, frame f an [H_f, W_f] view into `out` (row stride the frame's
+    pitch); with `status`, (frames, status). Asynchronous on `stream`; no host synchronisation."""
+    fs = _frame_set("decode_set_frames", fs)
+    fr, dev_index = _slice_entry("decode_set_frames", fs, extra_flags)
+    luts, stride, fstatus = _region_tables("decode_set_frames", fs, tables, dev_index, frame_status is None)
+    if frame_status is not None:
+        _status_arg("frame_status", frame_status, fs, dev_index)
+        fstatus = frame_status
+    d_geoms, total_blocks = fs._head(dev_index)
+    dp = _set_plan(fs, plan, dev_index, stream, extra_flags)
+    p, n = dp.plan, fs.n_frames
+    if (dp.rasters.shape != (n, 4) or dp.shares.shape != (n, 4) or dp.group_frame.numel() != p.n_groups
+            or any(t.get_device() != dev_index or t.dtype is not torch.int32 or not t.is_contiguous()
+                   for t in (dp.rasters, dp.shares, dp.group_frame))):
+        raise ValueError(f"the plan must hold {n} raster and share records and its group map on cuda:{dev_index}")
+    with torch.cuda.stream(stream) if stream is not None else _NO_STREAM:
+        if out is None:
+            out = torch.zeros(p.out_bytes, dtype=torch.uint8, device=fs.codes.device)
+        sstatus = torch.empty(n, dtype=torch.int32, device=fs.codes.device) if status is True else status
+    if (out.dtype is not torch.uint8 or out.get_device() != dev_index or not out.is_contiguous()
+            or out.numel() < p.out_bytes):
+        raise ValueError(f"out must be a contiguous uint8 tensor of at least {p.out_bytes} bytes on cuda:{dev_index}")
+    if sstatus is not None:
+        _status_arg("status", sstatus, fs, dev_index)
+    rc = N.lib().mh_decode_set_frames(ctypes.byref(fr), d_geoms, total_blocks, dp.rasters.data_ptr(),
+                                      dp.shares.data_ptr(), dp.group_frame.data_ptr(), p.n_groups, luts.data_ptr(),
+                                      stride, fstatus.data_ptr() if fstatus is not None else None,
+                                      sstatus.data_ptr() if sstatus is not None else None, out.data_ptr(),
+                                      out.numel(), _raw_stream_ptr(stream, dev_index))
+    if rc:
+        N.check(rc, "mh_decode_set_frames")
+    base = out.storage_offset()  # as_strided counts from the storage's start, not from the view's
+    offs, pitches = p.offsets, p.pitches
+    frames = [out.as_strided((h, w), (int(pitches[f]), 1), base + int(offs[f])) for f, (w, h) in enumerate(fs.sizes)]
+    return (frames, sstatus) if status is not None else frames
 
 
 def decode_headers_shape(frames: DeviceFrames, stream: Optional[torch.cuda.Stream] = None,

@@ -574,3 +574,15 @@ class AsyncEncodedSet:
             ts = DeviceTableSet.from_canonical_headers(self.canon, self.canon.device, stream)
             ts.status = torch.where(self.status != 0, self.status, ts.status)
         return ts
+
+    def decode(self, out: Optional[torch.Tensor] = None, status=None,
+               stream: Optional[torch.cuda.Stream] = None):
+        """encode set -> n tables -> every frame decoded whole at its own size, on one stream with
+        no host synchronisation (decoder.decode_set_frames, one launch): a list of n uint8 [H_f, W_f]
+        views into `out` (with `status`, also the int32[n] status tensor). A frame the encoder or
+        the table build rejected is skipped on the device and its raster keeps what `out` held (zeros
+        when allocated here); the tables stay in `self.tables`, the frame set in `self.decoded_set`."""
+        from .decoder import decode_set_frames
+        self.tables = self.table_set(stream)
+        self.decoded_set = self.__dict__.get("decoded_set") or self.frame_set()
+        return decode_set_frames(self.decoded_set, self.tables, out=out, status=status, stream=stream)
