@@ -183,6 +183,27 @@ typedef struct {
 int mh_decode(const mh_frame *frame, uint8_t *d_out, size_t out_pitch,
               size_t out_frame_stride, void *stream);
 
+/* mh_decode with the frame's mid-block marks (mh_encode_frame_marks / mh_mid_marks; device
+ * memory, u32[NB], 4-byte aligned -- else MH_ERR_ALIGN with the other alignments; NULL is
+ * mh_decode itself). Every check, in mh_decode's order, is mh_decode's, and for valid marks every
+ * byte written equals mh_decode's. The marks are used when the launch is one frame with a prepared
+ * table (d_lut) and no frame-offset array, small enough for the single-frame kernel, and the marks
+ * lie within +-8 GiB of d_block_offsets (they travel as a 32-bit word distance; a producer lays
+ * them out beside the offsets): two lanes then decode each block, rows 0-3 from the block's offset
+ * and rows 4-7 from the mark, 32 steps each. Every other launch ignores the marks and is
+ * mh_decode's. MH_FLAG_NO_DELTA and MH_FLAG_ANY_ORDER as in mh_decode.
+ * Marks are not trusted: the bit count is clamped to 512 on the device, so the upper lane reads
+ * no further than a 64-step walk from the block's offset could, writes only rows 4-7 of its own
+ * block, and a wrong mark spoils those rows alone.
+ * Defective streams (mh_frame): item 1 there -- a specified block equals the reference walk -- holds
+ * through this entry when the marks are the walk's own, i.e. mh_mid_marks over the code bytes,
+ * offsets and tables AS DELIVERED to the decode. A producer's marks describe the bytes it wrote:
+ * over bytes damaged since, rows 4-7 of a block start from a point the walk may never reach and
+ * may differ from it (rows 0-3 and items 2 and 3 hold for any marks). A consumer that cannot vouch
+ * for its stream derives the marks again or calls mh_decode. */
+int mh_decode_marked(const mh_frame *frame, const uint32_t *d_mid_marks, uint8_t *d_out, size_t out_pitch,
+                     size_t out_frame_stride, void *stream);
+
 /* Debug mode of the decode contract: the reference walk of every block of
  * `frame` (see mh_frame: 64 steps from the block's offset over the real bytes of the frame's slot,
  * one thread per block, zero at or past the slot's end, whatever the offsets are -- NOT the
@@ -1434,6 +1455,37 @@ int mh_encode_huffman(const uint8_t *symbols, uint64_t n_symbols, uint32_t block
 int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
                     uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
                     uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init);
+
+/* Mid-block marks: a second, exact entry point in the middle of every block, so that two lanes
+ * can decode one block (mh_decode_marked). One u32 per block, in block order, beside the block
+ * offsets:
+ *   bits 0-15   the code bits from the block's offset to its symbol 32, the first symbol of block
+ *               row 4 (<= 32 x 16 = 512);
+ *   bits 16-23  the running `prev` byte the 64-step decode holds when it begins symbol 32 under the
+ *               frame's own flags: (block_init[b] or 0) + symbols 0..31, mod 256 -- pixel 31 of
+ *               the block -- and 0 under MH_FLAG_NO_DELTA, which has no running sum;
+ *   bits 24-31  0.
+ * The marks are a hint a producer adds for free; they change no other buffer of the frame.
+ *
+ * mh_encode_frame_marks is mh_encode_frame -- every argument, status and output byte -- that also
+ * writes the NB marks into mid_marks as it packs (NULL: mh_encode_frame itself). */
+int mh_encode_frame_marks(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                          uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
+                          uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init,
+                          uint32_t *mid_marks);
+
+/* The marks of a frame that arrives without them (the reference encoder's, a GPU encoder's): the
+ * reference walk (see mh_frame) of the first 32 steps of each of n_blocks blocks from
+ * block_offsets[b] over table1 / table2. Bytes at or past codes_bytes read as zero, a zero-width
+ * lookup repeats `prev` and does not advance, an escape past table2_entries is the zero entry; no
+ * byte outside the caller's buffers is read, whatever the offsets and the code bytes hold.
+ * block_init: NB bytes or NULL (ignored under MH_FLAG_NO_DELTA). flags: MH_FLAG_NO_DELTA only.
+ * For a frame of mh_encode_frame_marks the result equals the encoder's marks word for word.
+ * MH_ERR_INVALID_ARG (a NULL pointer but block_init, n_blocks == 0, another flag), MH_ERR_TABLE
+ * (table2_entries as in mh_decode). */
+int mh_mid_marks(const uint8_t *codes, uint64_t codes_bytes, const uint32_t *block_offsets,
+                 uint64_t n_blocks, const mh_lookup_symbol *table1, const mh_lookup_symbol *table2,
+                 uint32_t table2_entries, const uint8_t *block_init, uint32_t flags, uint32_t *mid_marks);
 
 /* Adds the symbol counts of one frame -- what mh_encode_frame would encode: split, per-block
  * deltas unless MH_FLAG_NO_DELTA, first delta zeroed when with_block_init -- into freq[256]

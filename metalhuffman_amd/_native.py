@@ -64,6 +64,7 @@ EXPORTS = (
     "mh_check_frame_cpu",
     "mh_encode_set_plan_bytes", "mh_encode_set_plan", "mh_encode_set_device_async",
     "mh_decode_set_frames", "mh_decode_set_frames_shape", "mh_decode_set_plan",
+    "mh_decode_marked", "mh_encode_frame_marks", "mh_mid_marks",
 )
 
 
@@ -212,6 +213,13 @@ def diag_lanepairs() -> ctypes.CDLL:
     return _diag_lp
 
 
+def has_mid_marks(L=None) -> bool:
+    """The library carries the mid-block marks' entries. Always true of the product library; an
+    A/B variant (MH_LIB) built from older sources has none, and frames are then encoded and
+    decoded without marks."""
+    return hasattr(L if L is not None else lib(), "mh_decode_marked")
+
+
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
@@ -230,6 +238,13 @@ def lib() -> ctypes.CDLL:
                     f"{LIB_PATH} was built from other sources (stamp {have[:16]}, sources {want[:16]}): "
                     "rebuild with `python -m metalhuffman_amd.build`")
         L.mh_decode.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
+        if has_mid_marks(L):
+            L.mh_decode_marked.argtypes = [ctypes.POINTER(mh_frame), _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]
+            L.mh_encode_frame_marks.argtypes = [_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p,
+                                                _u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _u32p,
+                                                _u8p, _u32p]
+            L.mh_mid_marks.argtypes = [_u8p, ctypes.c_uint64, _u32p, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32,
+                                       _u8p, ctypes.c_uint32, _u32p]
         L.mh_check.argtypes = [ctypes.POINTER(mh_frame), _vp, _vp]
         L.mh_check_frames.argtypes = [ctypes.POINTER(mh_frame), _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]
         L.mh_check_headers.argtypes = [ctypes.POINTER(mh_frame), _vp, _vp, _vp, _vp, _vp, _vp]

@@ -60,6 +60,24 @@ class EncodedFrame:
     block_offsets: np.ndarray   # u32[NB] bit offset of every 8x8 block
     block_init: Optional[np.ndarray] = None  # u8[NB] (INIT_ZERO_DELTA mode) or None
     flags: int = 0
+    # u32[NB] mid-block marks (metalhuffman.h: code bits to symbol 32 | prev << 16) or None: a hint
+    # for the single-frame decode, filled by encode_frame; with_mid_marks() derives them for any frame.
+    # Marks belong to the buffers they were made from. marks_for names those -- the (codes,
+    # block_offsets, block_init) arrays themselves -- and marks are used only while the frame still
+    # holds those very objects (valid_mid_marks): a frame given other code bytes, offsets or init
+    # bytes (dataclasses.replace, an assignment) has no marks until with_mid_marks() makes them
+    # again. Writing INTO the arrays is not seen: whoever does that clears or remakes the marks.
+    mid_marks: Optional[np.ndarray] = None
+    marks_for: Optional[tuple] = dataclasses.field(default=None, repr=False, compare=False)
+
+    def _buffers(self) -> tuple:
+        return (self.codes, self.block_offsets, self.block_init)
+
+    def valid_mid_marks(self) -> Optional[np.ndarray]:
+        """mid_marks if they were made for the buffers this frame holds now, else None."""
+        if self.mid_marks is None or self.marks_for is None:
+            return None
+        return self.mid_marks if all(a is b for a, b in zip(self.marks_for, self._buffers())) else None
 
     @property
     def block_width(self) -> int:
@@ -100,7 +118,27 @@ class EncodedFrame:
         band_offs = (offs[b0:b1].astype(np.int64) - 8 * base).astype(np.uint32)
         init = None if self.block_init is None else self.block_init[b0:b1].copy()
         height = min(self.height, 8 * by1) - 8 * by0
-        return EncodedFrame(self.width, height, self.canon, codes, band_offs, init, self.flags)
+        # a mark is relative to its own block's offset, so a band's marks are the frame's
+        marks = self.valid_mid_marks()
+        out = EncodedFrame(self.width, height, self.canon, codes, band_offs, init, self.flags)
+        if marks is not None:
+            out.mid_marks, out.marks_for = marks[b0:b1].copy(), out._buffers()
+        return out
+
+    def with_mid_marks(self) -> "EncodedFrame":
+        """This frame with its mid-block marks derived by the walk (mh_mid_marks): for frames that
+        arrive without them -- the reference encoder's, a GPU encoder's, a foreign header's."""
+        t1, t2 = self.tables()
+        t1 = np.ascontiguousarray(t1).view(np.uint8).reshape(-1)
+        t2 = np.ascontiguousarray(t2).view(np.uint8).reshape(-1)
+        offs = np.ascontiguousarray(self.block_offsets, np.uint32)
+        codes = np.ascontiguousarray(self.codes, np.uint8)
+        init = None if self.block_init is None else np.ascontiguousarray(self.block_init, np.uint8)
+        marks = np.zeros(self.n_blocks, np.uint32)
+        N.check(N.lib().mh_mid_marks(_p(codes), codes.size, _p(offs, _u32p), self.n_blocks, t1.ctypes.data,
+                                     t2.ctypes.data, t2.size // 2, _p(init) if init is not None else None,
+                                     self.flags & N.MH_FLAG_NO_DELTA, _p(marks, _u32p)), "mh_mid_marks")
+        return dataclasses.replace(self, mid_marks=marks, marks_for=self._buffers())
 
 
 class FrameSetLayout(NamedTuple):
@@ -483,10 +521,19 @@ def encode_frame(gray: np.ndarray, flags: int = 0, init_zero_delta: bool = False
         return EncodedFrame(w, h, canon, codes[: ln.value].copy(), offs, init, flags)
     canon = np.zeros(256, np.uint8)
     enc_flags = flags | (N.MH_ENCODE_LIMIT_LENGTHS if limit_lengths else 0)
-    N.check(N.lib().mh_encode_frame(_p(gray), w, h, enc_flags, _p(canon), _p(codes), cap, ctypes.byref(ln),
-                                    _p(offs, _u32p), _p(init) if init is not None else None),
+    if not N.has_mid_marks():  # an A/B variant library from older sources
+        N.check(N.lib().mh_encode_frame(_p(gray), w, h, enc_flags, _p(canon), _p(codes), cap, ctypes.byref(ln),
+                                        _p(offs, _u32p), _p(init) if init is not None else None),
+                "encode_frame")
+        return EncodedFrame(w, h, canon, codes[: ln.value].copy(), offs, init, flags)
+    marks = np.zeros(nb, np.uint32)
+    N.check(N.lib().mh_encode_frame_marks(_p(gray), w, h, enc_flags, _p(canon), _p(codes), cap, ctypes.byref(ln),
+                                          _p(offs, _u32p), _p(init) if init is not None else None,
+                                          _p(marks, _u32p)),
             "encode_frame")
-    return EncodedFrame(w, h, canon, codes[: ln.value].copy(), offs, init, flags)
+    ef = EncodedFrame(w, h, canon, codes[: ln.value].copy(), offs, init, flags, marks)
+    ef.marks_for = ef._buffers()
+    return ef
 
 
 def image_planes(images, first_channel: int = 0, n_planes=None, plane_major: bool = False) -> np.ndarray:

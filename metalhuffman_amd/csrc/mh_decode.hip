@@ -522,7 +522,10 @@ struct NormRows : CropRows {
 // at bits 1..kBits, i.e. the byte address of their u16 table entry; one add of the
 // entry's step word then advances sh and prev together (the low byte stays in
 // [kCur - 63, kCur], so it never borrows from prev).
-template <bool kDelta, class Cfg, class Src, class Out = StoreRows>
+// kRows: the block rows the lane decodes, 8 or -- half a block from a mid-block mark
+// (mh_decode_frame_marked_kernel) -- 4: 8 kRows steps from bit p with the running sum `prev`, stored
+// as rows 0 .. kRows - 1 from row0 on (the lane of rows 4-7 brings row0 + 4 * pitch).
+template <bool kDelta, class Cfg, int kRows = 8, class Src, class Out = StoreRows>
 __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut, uint32_t p,
                                              uint32_t prev, __amdgpu_buffer_rsrc_t out,
                                              uint32_t row0, uint32_t pitch, bool dead MH_ROWS_PARAM,
@@ -534,13 +537,13 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
     typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
     const lds_u32 wp = (lds_u32)(src.w + (p >> 5) * 4u);
     const uint32_t sh = p & 31u;
-    uint32_t w[17];
+    uint32_t w[2 * kRows + 1];
 #pragma unroll
-    for (int j = 0; j < 17; ++j) w[j] = wp[j];
+    for (int j = 0; j < 2 * kRows + 1; ++j) w[j] = wp[j];
     const uint32_t rbase = dead ? 0x80000000u : row0;
     uint32_t s = prev;
 #pragma unroll
-    for (uint32_t r = 0; r < 8; ++r) {
+    for (uint32_t r = 0; r < (uint32_t)kRows; ++r) {
       uint32_t c[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -695,11 +698,12 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
     // entry (the address is masked) and is dropped.
     uint32_t eL;
     uint32_t off = rbase;  // the row's store offset, advancing by pitch
+    constexpr uint32_t kPerTrip = kLazyRowsPerIter < kRows ? kLazyRowsPerIter : kRows;  // (half a block: one trip)
     MH_ISSUE_L();
 #pragma unroll 1
-    for (uint32_t r = 0; r < 8; r += (uint32_t)kLazyRowsPerIter) {
+    for (uint32_t r = 0; r < (uint32_t)kRows; r += kPerTrip) {
 #pragma unroll
-      for (uint32_t q = 0; q < (uint32_t)kLazyRowsPerIter; ++q) {
+      for (uint32_t q = 0; q < kPerTrip; ++q) {
         uint32_t o0 = 0, o1 = 0;
         uint32_t sv[4];  // S after each symbol of the current output word (delta mode)
         (void)sv;
@@ -723,7 +727,7 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
         // A trip's last lookup is a volatile read: it stays in front of the back-edge (a plain
         // one, dead on the loop's exit, is sunk into the next trip's head, behind the branch),
         // and the row store stays behind it, off the chain.
-        if (q + 1 == (uint32_t)kLazyRowsPerIter && kLazyRowsPerIter < 8) {
+        if (q + 1 == kPerTrip && kPerTrip < (uint32_t)kRows) {
           MH_ISSUE_LQ(const volatile);
         } else {
           MH_ISSUE_L();
@@ -735,7 +739,7 @@ __device__ __forceinline__ void decode_block(const Src &src, const uint8_t *lut,
     }
   } else {
 #pragma unroll
-  for (uint32_t r = 0; r < 8; ++r) {
+  for (uint32_t r = 0; r < (uint32_t)kRows; ++r) {
     uint32_t o0 = 0, o1 = 0;
     uint32_t sv[4];  // S after each symbol of the current output word (delta mode)
     (void)sv;
@@ -1156,8 +1160,9 @@ __device__ __forceinline__ Out rows_of(const DecodeArgs &a, const TileOf<Map> &t
   }
 }
 
+template <int kChunks>
 __device__ __forceinline__ void span_issue(const DecodeArgs &a, const TileBase &t, uint32_t lane,
-                                           v4u32 (&R)[kStageChunks], bool on = true) {
+                                           v4u32 (&R)[kChunks], bool on = true) {
   // Unconditional loads (no exec-masked branches, so the compiler can count them
   // in vmcnt); chunks past the span use an offset outside the descriptor's range,
   // which returns 0 without a memory access.
@@ -1166,18 +1171,18 @@ __device__ __forceinline__ void span_issue(const DecodeArgs &a, const TileBase &
   // one wave-uniform byte count, so the compiler cannot split the loads by `on`
   const uint32_t span = __builtin_amdgcn_readfirstlane(on ? t.span : 0u);
 #pragma unroll
-  for (int k = 0; k < kStageChunks; ++k) {
+  for (int k = 0; k < kChunks; ++k) {
     const uint32_t c = lane + 64u * k;
     const uint32_t off = c * 16u < span ? t.start + c * 16u : 0xFFFFFFF0u;
     R[k] = __builtin_amdgcn_raw_buffer_load_b128(rc, (int)off, 0, 0);
   }
 }
 
-template <bool kSwz = false>
-__device__ __forceinline__ void span_write(const TileBase &t, uint32_t lane, const v4u32 (&R)[kStageChunks],
+template <bool kSwz = false, int kChunks>
+__device__ __forceinline__ void span_write(const TileBase &t, uint32_t lane, const v4u32 (&R)[kChunks],
                                            uint8_t *stage) {
 #pragma unroll
-  for (int k = 0; k < kStageChunks; ++k) {
+  for (int k = 0; k < kChunks; ++k) {
     const uint32_t c = lane + 64u * k;
     if (c * 16u < t.span) {
       v4u32 v = R[k];
@@ -1203,6 +1208,23 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The unstaged paths' staging: `span` bytes of the frame's codes from byte `start` (16-aligned) into
+// the wave's window, 16 bytes per lane and trip, byte-swapped as span_write does. Loads past the
+// frame's bytes return 0 (the descriptor). Used by decode_halves and by the marked single-frame
+// kernel's oversize tile.
+template <bool kSwz = false>
+__device__ __forceinline__ void stage_window(__amdgpu_buffer_rsrc_t rc, uint32_t start, uint32_t span, uint32_t lane,
+                                             uint8_t *stage) {
+  for (uint32_t c = lane; c * 16u < span; c += 64u) {
+    v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(rc, (int)(start + c * 16u), 0, 0);
+    v.x = bswap32(v.x);
+    v.y = bswap32(v.y);
+    v.z = bswap32(v.z);
+    v.w = bswap32(v.w);
+    *reinterpret_cast<v4u32 *>(stage + (kSwz ? swz_off(c * 16u) : c * 16u)) = v;
+  }
 }
 
 // Oversize tile: stage + decode lanes [0,32) then [32,64), each from its own span.
@@ -1240,14 +1262,7 @@ __device__ __forceinline__ void decode_halves(const DecodeArgs &a, const TileOf<
     if (end - 16u > t.fb32) end = t.fb32 + 16u;  // as hdr_resolve: no wrapping sum
     const uint32_t span = min((end - start + 15u) & ~15u, (uint32_t)kStageBytes);
     __builtin_amdgcn_s_waitcnt(0);  // rare path: drain before reusing the window
-    for (uint32_t c = lane; c * 16u < span; c += 64u) {
-      v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(rc, (int)(start + c * 16u), 0, 0);
-      v.x = bswap32(v.x);
-      v.y = bswap32(v.y);
-      v.z = bswap32(v.z);
-      v.w = bswap32(v.w);
-      *reinterpret_cast<v4u32 *>(stage + (Cfg::kSwz ? swz_off(c * 16u) : c * 16u)) = v;
-    }
+    stage_window<Cfg::kSwz>(rc, start, span, lane, stage);
     wave_sync();
     if (lane >= first && lane < first + lanes) {
       LdsWords src{stage};
@@ -2699,6 +2714,37 @@ constexpr int kSmallMaxTilesPerCU = 4;   // launches up to this many tiles per C
 __shared__ __attribute__((aligned(16))) uint16_t s_lut_small[kLut14Entries];  // 14-bit, or 13-bit L1+L2
 static_assert(kLutBytes <= kLut14Bytes, "the 13-bit table fits the small kernel's LUT space");
 
+// the small kernels' step flavours (all with write-through row stores)
+using Small14 = StepCfg<kLut14Bits, false, false, false, kSmallStoreAux, true>;
+using Small13 = StepCfg<kLutBits, false, true, false, kSmallStoreAux, true>;
+using SmallFlat8 = StepCfg<kLutBits, false, false, false, kSmallStoreAux, false, true>;
+
+#if MH_DIAG_STAMPS
+// Diagnostic builds: a small-launch wave's stamps behind its decode (slots 4 to 7) and their write.
+// c3: the core clock at stamp 3 (MH_DIAG_CLOCK); rowv: the row clocks (MH_DIAG_ROWS).
+__device__ __forceinline__ void small_stamps(unsigned long long (&ts)[kDiagSlots], bool staged, unsigned long long c3,
+                                             uint32_t lane, uint32_t gw, uint32_t rowv) {
+  MH_STAMP(4);
+#if MH_DIAG_CLOCK
+  ts[5] = staged ? __builtin_amdgcn_s_memtime() - c3 : 0ull;  // core clocks of the decode
+#elif !MH_DIAG_ARGS
+  ts[5] = ts[4];
+#endif
+  __builtin_amdgcn_s_waitcnt(0);
+  MH_STAMP(6);
+  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // HW_REG_XCC_ID[3:0]
+  ts[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)__smid() << 32) | blockIdx.x;
+  if (lane == 0 && gw < (uint32_t)kDiagWaves)
+    for (int i = 0; i < kDiagSlots; ++i) g_stamps[gw * kDiagSlots + i] = ts[i];
+#if MH_DIAG_ROWS
+  if (lane < (uint32_t)kDiagRowSlots && gw < (uint32_t)kDiagWaves) g_rows[gw * kDiagRowSlots + lane] = rowv;
+#endif
+  (void)staged;
+  (void)c3;
+  (void)rowv;
+}
+#endif
+
 // The small-launch kernels' common tail, entered behind the table barrier with the tile's
 // span in flight in R: stage it, decode the tile with the step flavour the lengths word
 // picks (flat8 / l14, kernel-uniform), and (diagnostic builds) write the wave's stamps.
@@ -2716,15 +2762,11 @@ __device__ __forceinline__ void small_decode(const DecodeArgs &a, const Tile &t,
   const OutTile ot = out_tile(a, t, lane);
   const __amdgpu_buffer_rsrc_t out = ot.rsrc;
   const uint32_t row0 = ot.row0;
-  // the small kernel's step flavours (all with write-through row stores)
-  using Small14 = StepCfg<kLut14Bits, false, false, false, kSmallStoreAux, true>;
-  using Small13 = StepCfg<kLutBits, false, true, false, kSmallStoreAux, true>;
-  using SmallFlat8 = StepCfg<kLutBits, false, false, false, kSmallStoreAux, false, true>;
-#if MH_DIAG_STAMPS && MH_DIAG_CLOCK
+#if MH_DIAG_STAMPS
   unsigned long long c3 = 0;
+  uint32_t rowv = 0;
 #endif
 #if MH_DIAG_ROWS
-  uint32_t rowv = 0;
 #define MH_ROWS_ARG , &rowv
 #else
 #define MH_ROWS_ARG
@@ -2754,21 +2796,7 @@ __device__ __forceinline__ void small_decode(const DecodeArgs &a, const Tile &t,
     decode_halves<kDelta, Small13>(a, t, lane, lut, stage, out, row0, !t.valid);
   }
 #if MH_DIAG_STAMPS
-  MH_STAMP(4);
-#if MH_DIAG_CLOCK
-  ts[5] = staged ? __builtin_amdgcn_s_memtime() - c3 : 0ull;  // core clocks of the decode
-#elif !MH_DIAG_ARGS
-  ts[5] = ts[4];
-#endif
-  __builtin_amdgcn_s_waitcnt(0);
-  MH_STAMP(6);
-  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // HW_REG_XCC_ID[3:0]
-  ts[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)__smid() << 32) | blockIdx.x;
-  if (lane == 0 && gw < (uint32_t)kDiagWaves)
-    for (int i = 0; i < kDiagSlots; ++i) g_stamps[gw * kDiagSlots + i] = ts[i];
-#if MH_DIAG_ROWS
-  if (lane < (uint32_t)kDiagRowSlots && gw < (uint32_t)kDiagWaves) g_rows[gw * kDiagRowSlots + lane] = rowv;
-#endif
+  small_stamps(ts, staged, c3, lane, gw, rowv);
 #else
   (void)gw;
 #endif
@@ -2938,6 +2966,183 @@ __global__ void __launch_bounds__(64 * kSmallWaves) mh_decode_frame_kernel(
   small_decode<kDelta>(a, t, lane, R, live, staged, flat8 != 0u, l14, stage, lut,
                        blockIdx.x * nwaves + wave MH_TS_ARG);
 }
+
+#if !MH_LANE_PAIRS
+// ---- one frame with mid-block marks: two lanes per block, 32 steps each (mh_decode_marked) ----
+// mh_decode_frame_kernel's launch with half the chain. A mark (metalhuffman.h) is a second, exact
+// entry point at a block's symbol 32, so a wave serves 32 consecutive blocks: lanes l and l + 32
+// hold block 32 tile + l, the lower lane decodes rows 0-3 from the block's offset with the tile's
+// init, the upper lane rows 4-7 from offset + mark.bits with prev = mark.prev -- decode_block over
+// 4 rows, the same steps. Nothing is speculated and the lanes never meet.
+//   * Arguments: the marks pointer would make 16 dwords, two over the preload. nb is derived
+//     (bw * ceil(h / 8): one scalar multiply ahead of the first load) and the marks travel as their
+//     signed distance from the offsets in words (launch() takes mh_decode_frame_kernel where that
+//     does not fit 32 bits): 14 dwords again, no read of the kernarg segment.
+//   * Prologue order as there: offsets, and in the same trip the mark and the init byte; the table's
+//     loads behind them; the span; the LDS-only barrier. No third dependent trip.
+//   * 8 waves per workgroup: 192 workgroups for 2048x1536 as before, one table copy per CU, 4 table
+//     chunks per thread, two waves per SIMD. 4 waves (384 workgroups, MH_MID_WAVES=4) ran at the
+//     parent kernel's speed, 8 about 12 % above it: profiles/mid_marks_ab.txt.
+//   * Stage: 32 blocks span about half of what 64 do, so a wave keeps 3 chunks per lane (3072 bytes)
+//     in flight where mh_decode_frame_kernel keeps 5. A span over that (or an unknown one) is staged
+//     through the wave's whole window -- 32 blocks are at most 32 x 128 bytes and the span's slack --
+//     and decoded whole by the lower lanes, marks unused: wave-uniform, decided on the device.
+//   * Marks are not trusted: bits is clamped to 512, so an upper lane starts no further than a
+//     lower lane's 32nd step can reach and its 32 steps end where a 64-step lane's could. The span
+//     and stage guarantees are those of mh_decode_frame_kernel for any mark bytes; the upper lane
+//     stores rows 4-7 of its own block (row0 + 4 pitch, rows >= H outside the descriptor as ever).
+#ifndef MH_MID_WAVES            // 4: the A/B build of profiles/mid_marks_ab.txt
+#define MH_MID_WAVES 8
+#endif
+constexpr int kMidWaves = MH_MID_WAVES;
+constexpr int kMidChunks = 3;                          // 16-B chunks per lane held in flight
+constexpr int kMidStageBytes = kMidChunks * 64 * 16;   // the staged fast path's span limit
+constexpr uint32_t kMarkMaxBits = 32u * 16u;
+static_assert(kMidWaves <= kMaxWavesPerWG, "a window of s_stage per wave");
+static_assert(kMidStageBytes <= kStageBytes && 32 * 128 + 64 <= kStageBytes, "32 whole blocks fit a wave's window");
+template <bool kDelta>
+__global__ void __launch_bounds__(64 * kMidWaves) mh_decode_frame_marked_kernel(
+    const uint32_t *p_offsets, const uint16_t *p_lut, const uint8_t *p_codes, uint8_t *p_out,
+    const uint8_t *p_block_init, int32_t p_marks_words, uint32_t p_codes_bytes, uint32_t p_pitch, uint32_t p_bw_h) {
+  DecodeArgs a{};
+  a.offsets = p_offsets;
+  a.lut = p_lut;
+  a.codes = p_codes;
+  a.out = p_out;
+  a.block_init = p_block_init;
+  a.codes_bytes = p_codes_bytes;
+  a.out_pitch = p_pitch;
+  a.bw = p_bw_h >> kFrameBwShift;
+  a.h = p_bw_h & ((1u << kFrameBwShift) - 1u);
+  a.nb = a.bw * ((a.h + 7u) >> 3);
+  a.out_frame_bytes = (uint64_t)a.h * p_pitch;
+  const uint32_t ntiles = (a.nb + 31u) / 32u;
+  a.tiles_per_frame = a.total_tiles = ntiles;
+  const uint32_t *marks = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(p_offsets) +
+                                                             (int64_t)p_marks_words * 4);
+  const uint32_t lane = threadIdx.x & 63u, bl = lane & 31u;
+  const bool upper = lane >= 32u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t *stage = s_stage + wave * kStageBytes;
+  const uint8_t *lut = reinterpret_cast<const uint8_t *>(s_lut_small);
+  const uint8_t *prepared = reinterpret_cast<const uint8_t *>(a.lut);
+#if MH_DIAG_STAMPS
+  unsigned long long ts[kDiagSlots] = {};
+  unsigned long long c3 = 0;
+  uint32_t rowv = 0;
+#endif
+  MH_STAMP(0);
+  const uint32_t *lens = reinterpret_cast<const uint32_t *>(prepared + kMaxLenOff);
+  const uint32_t max_len = lens[0], flat8 = lens[2];
+  const uint32_t tile = __builtin_amdgcn_readfirstlane(min(blockIdx.x * (uint32_t)kMidWaves + wave, ntiles));
+  const bool live = tile < ntiles;
+  // the header's loads, branch-free as hdr_issue's: a wave without a tile reads through
+  // zero-record descriptors
+  const uint32_t b0 = live ? tile * 32u : 0u, b = b0 + bl;
+  const __amdgpu_buffer_rsrc_t ro = uniform_rsrc(a.offsets, live ? a.nb * 4u : 0u);
+  const uint32_t h_off = __builtin_amdgcn_raw_buffer_load_b32(ro, (int)(b * 4u), 0, 0);
+  const uint32_t h_nxt = __builtin_amdgcn_raw_buffer_load_b32(ro, (int)(b * 4u + 4u), 0, 0);
+  const __amdgpu_buffer_rsrc_t rm = uniform_rsrc(marks, live ? a.nb * 4u : 0u);
+  const uint32_t h_mark = __builtin_amdgcn_raw_buffer_load_b32(rm, (int)(b * 4u), 0, 0);
+  const __amdgpu_buffer_rsrc_t ri = uniform_rsrc(
+      a.block_init ? (const void *)a.block_init : (const void *)a.offsets, (live && a.block_init) ? a.nb : 0u);
+  const uint32_t h_init = __builtin_amdgcn_raw_buffer_load_b8(ri, (int)b, 0, 0);
+  constexpr int kLutLoads = kLut14Bytes / 16 / (64 * kMidWaves);
+  static_assert(kLut14Bytes == kLutLoads * 16 * 64 * kMidWaves, "whole table per pass");
+  v4u32 L[kLutLoads];
+  {
+    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(prepared + kLut14Off, (uint32_t)kLut14Bytes);
+#pragma unroll
+    for (int k = 0; k < kLutLoads; ++k)
+      L[k] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)((threadIdx.x + 64u * kMidWaves * k) * 16u), 0, 0);
+  }
+  // hdr_resolve for a tile of 32 blocks held twice
+  Tile t;
+  t.tile = tile;
+  t.f = 0u;
+  t.b0 = b0;
+  t.valid = b < a.nb;
+  t.fbeg = 0;
+  t.fb32 = p_codes_bytes;
+  const uint32_t fbits = t.fb32 > 0x1FFFFFFFu ? 0xFFFFFFFFu : t.fb32 * 8u;
+  const uint32_t end_l = (b + 1u < a.nb) ? h_nxt : min(fbits, h_off + 64u * 16u);
+  const uint32_t last = live ? min(31u, a.nb - 1u - b0) : 0u;  // last lane pair holding a block
+  const uint32_t sb = __builtin_amdgcn_readfirstlane(h_off);
+  const uint32_t eb = __builtin_amdgcn_readlane(end_l, last);
+  t.span_end_bits = eb;
+  t.start = (sb >> 3) & ~15u;
+  uint32_t end = (eb >> 3) + 24u;
+  if (end - 16u > t.fb32) end = t.fb32 + 16u;  // as hdr_resolve: no wrapping sum
+  t.span = end > t.start ? ((end - t.start + 15u) & ~15u) : 0xFFFFFFFFu;
+  t.p = t.valid ? h_off - t.start * 8u : 0u;
+  t.init = h_init & 0xFFu;
+  // the lane's own entry point: the block's offset and init, or the (clamped) mark
+  const uint32_t p = t.p + (upper ? min(h_mark & 0xFFFFu, kMarkMaxBits) : 0u);
+  const uint32_t prev = upper ? (h_mark >> 16) & 0xFFu : t.init;
+  asm volatile("" ::"v"(p), "v"(prev), "v"(t.p), "v"(t.init));
+  MH_STAMP(1);
+  const bool staged = live && t.span <= (uint32_t)kMidStageBytes;
+  v4u32 R[kMidChunks];
+  span_issue(a, t, lane, R, staged);
+  v4u32 *dst = reinterpret_cast<v4u32 *>(s_lut_small);
+#pragma unroll
+  for (int k = 0; k < kLutLoads; ++k) dst[threadIdx.x + 64u * kMidWaves * k] = L[k];
+  // keep the lengths word's wait below the span's loads and the table's stores
+  __builtin_amdgcn_sched_barrier(0);
+  const bool l14 = max_len <= (uint32_t)kLut14Bits;
+  if (__builtin_expect(!l14, 0)) {
+    constexpr uint32_t kChunks = kLutBytes / 16;
+    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(prepared, (uint32_t)kLutBytes);
+#pragma unroll 1
+    for (uint32_t c = threadIdx.x; c < kChunks; c += 64u * kMidWaves)
+      dst[c] = __builtin_amdgcn_raw_buffer_load_b128(rl, (int)(c * 16u), 0, 0);
+  }
+  lds_barrier();  // LDS only, as in mh_decode_small_kernel
+  MH_STAMP(2);
+  if (!live) return;  // no barrier below
+  const OutTile ot = out_tile(a, t, bl);
+  const uint32_t pitch = p_pitch;
+  const bool dead = !t.valid;
+#if MH_DIAG_ROWS
+#define MH_ROWS_ARG , &rowv
+#else
+#define MH_ROWS_ARG
+#endif
+  LdsWords src{stage};
+  if (__builtin_expect(staged, 1)) {
+    span_write(t, lane, R, stage);
+    wave_sync();
+    MH_STAMP(3);
+#if MH_DIAG_STAMPS && MH_DIAG_CLOCK
+    c3 = __builtin_amdgcn_s_memtime();
+#endif
+    const uint32_t row0 = ot.row0 + (upper ? 4u * pitch : 0u);
+    if (__builtin_expect(l14 && !flat8, 1))
+      decode_block<kDelta, Small14, 4>(src, lut, p, prev, ot.rsrc, row0, pitch, dead MH_ROWS_ARG);
+    else if (flat8)
+      decode_block<kDelta, SmallFlat8, 4>(src, lut, p, prev, ot.rsrc, row0, pitch, dead);
+    else
+      decode_block<kDelta, Small13, 4>(src, lut, p, prev, ot.rsrc, row0, pitch, dead MH_ROWS_ARG);
+  } else {
+    // the oversize (or unknown) span: the whole window from the tile's start, whole blocks on the
+    // lower lanes (decode_halves' staging, one pass of 32 whole blocks).
+    stage_window(codes_rsrc(a, t), t.start, min(t.span, (uint32_t)kStageBytes), lane, stage);
+    wave_sync();
+    if (!upper) {
+      if (flat8)
+        decode_block<kDelta, SmallFlat8>(src, lut, t.p, t.init, ot.rsrc, ot.row0, pitch, dead);
+      else if (l14)
+        decode_block<kDelta, Small14>(src, lut, t.p, t.init, ot.rsrc, ot.row0, pitch, dead MH_ROWS_NONE);
+      else
+        decode_block<kDelta, Small13>(src, lut, t.p, t.init, ot.rsrc, ot.row0, pitch, dead MH_ROWS_NONE);
+    }
+  }
+#undef MH_ROWS_ARG
+#if MH_DIAG_STAMPS
+  small_stamps(ts, staged, c3, lane, blockIdx.x * (uint32_t)kMidWaves + wave, rowv);
+#endif
+}
+#endif  // !MH_LANE_PAIRS
 
 #if MH_LANE_PAIRS
 // ---- lane-pair variant of the small-launch kernel (MH_FLAG_LANE_PAIRS, A/B) -------
@@ -3402,8 +3607,9 @@ const DeviceInfo *device_info(hipStream_t s) {
       hipLaunchKernelGGL(kernel, grid, block, 0, s, __VA_ARGS__);                                 \
   } while (0)
 
+// marks (mh_decode_marked): the frame's mid-block marks or null; used by the single-frame launch only
 template <bool kDelta>
-int launch(const DecodeArgs &a0, hipStream_t s, bool lane_pairs, bool any_order) {
+int launch(const DecodeArgs &a0, hipStream_t s, bool lane_pairs, bool any_order, const uint32_t *marks = nullptr) {
   DecodeArgs a = a0;
   const DeviceInfo *di = device_info(s);
   if (!di) return MH_ERR_HIP;
@@ -3427,6 +3633,21 @@ int launch(const DecodeArgs &a0, hipStream_t s, bool lane_pairs, bool any_order)
     const uint32_t nw = kSmallWaves;
     a.n_groups = (a.total_tiles + nw - 1) / nw;
     if (a.total_tiles == a.tiles_per_frame && !a.frame_off) {
+#if !MH_LANE_PAIRS
+      // ... with marks: two lanes per block, 32 blocks per wave. The marks travel as their distance
+      // from the offsets in words; marks out of a signed 32-bit word's reach (never a producer's
+      // layout, which puts them beside the offsets) are left unused.
+      const int64_t dist = (int64_t)(uintptr_t)marks - (int64_t)(uintptr_t)a.offsets;
+      if (marks && (dist & 3) == 0 && dist / 4 >= INT32_MIN && dist / 4 <= INT32_MAX) {
+        const uint32_t groups = ((a.nb + 31u) / 32u + kMidWaves - 1) / kMidWaves;
+        MH_LAUNCH(mh_decode_frame_marked_kernel<kDelta>, dim3(groups), dim3(kMidWaves * 64), s, any_order, a.offsets,
+                  a.lut, a.codes, a.out, a.block_init, (int32_t)(dist / 4), (uint32_t)a.codes_bytes,
+                  (uint32_t)a.out_pitch, (a.bw << kFrameBwShift) | a.h);
+        return hipGetLastError() == hipSuccess ? MH_OK : MH_ERR_HIP;
+      }
+#else
+      (void)marks;
+#endif
       // one frame, no frame-offset array: the entry whose arguments are all preloaded.
       // mh_decode has bounded what the 32-bit arguments hold (codes_bytes, pitch, dims).
       MH_LAUNCH(mh_decode_frame_kernel<kDelta>, dim3(a.n_groups), dim3(nw * 64), s, any_order, a.offsets, a.lut,
@@ -3943,14 +4164,22 @@ int mh_prepare_lut(const mh_lookup_symbol *d_table1, const mh_lookup_symbol *d_t
 #if MH_LANE_PAIRS
 int mh_diag_decode_lanepairs(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
                              void *stream) {
+  const uint32_t *d_mid_marks = nullptr;
 #else
 int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_frame_stride,
               void *stream) {
+  return mh_decode_marked(fr, nullptr, d_out, out_pitch, out_frame_stride, stream);
+}
+
+// mh_decode's body; the marks (optional) reach the single-frame launch alone.
+int mh_decode_marked(const mh_frame *fr, const uint32_t *d_mid_marks, uint8_t *d_out, size_t out_pitch,
+                     size_t out_frame_stride, void *stream) {
 #endif
   // MH_FLAG_LANE_PAIRS: honoured by the diagnostic library only; the product library accepts
   // it (callers built against round-4 libraries pass it) and decodes with the default kernels
   DecodeCall c{DecodeCall::kInFrame};
   c.allowed_flags |= MH_FLAG_LANE_PAIRS;
+  c.words = (uintptr_t)d_mid_marks;  // 4-byte aligned, judged with the other alignments
   int rc = check_decode_args(fr, d_out, out_pitch, out_frame_stride, c);
   if (rc != MH_OK) return rc;
   DecodeArgs a{};
@@ -3963,7 +4192,8 @@ int mh_decode(const mh_frame *fr, uint8_t *d_out, size_t out_pitch, size_t out_f
   hipStream_t s = (hipStream_t)stream;
   const bool lp = (fr->flags & MH_FLAG_LANE_PAIRS) != 0;
   const bool ao = (fr->flags & MH_FLAG_ANY_ORDER) != 0;
-  return (fr->flags & MH_FLAG_NO_DELTA) ? launch<false>(a, s, lp, ao) : launch<true>(a, s, lp, ao);
+  return (fr->flags & MH_FLAG_NO_DELTA) ? launch<false>(a, s, lp, ao, d_mid_marks)
+                                        : launch<true>(a, s, lp, ao, d_mid_marks);
 }
 
 #if !MH_LANE_PAIRS

@@ -170,7 +170,7 @@ struct BitWriter {
 
 int encode_symbols(const uint8_t *sym, uint64_t n, uint64_t stride, uint8_t canon[256],
                    uint8_t *codes, uint64_t codes_cap, uint64_t *codes_len, uint32_t *offsets,
-                   bool limit = false) {
+                   bool limit = false, uint32_t *mid_bits = nullptr) {
   uint64_t freq[256] = {0};
   for (uint64_t i = 0; i < n; ++i) freq[sym[i]]++;
   int rc = code_lengths(freq, canon);
@@ -190,6 +190,9 @@ int encode_symbols(const uint8_t *sym, uint64_t n, uint64_t stride, uint8_t cano
   BitWriter bw(codes);
   for (uint64_t i = 0; i < n; ++i) {
     if (offsets && (i % stride) == 0) offsets[i / stride] = (uint32_t)bw.nbits;
+    // the packer passes a block's middle as it writes: code bits from the block's offset to the
+    // symbol half a stride in (mh_encode_frame_marks; a block's first half is <= 32 x 16 bits)
+    if (mid_bits && (i % stride) == stride / 2) mid_bits[i / stride] = (uint32_t)bw.nbits - offsets[i / stride];
     const uint8_t s = sym[i];
     bw.put(cc[s], canon[s]);
   }
@@ -308,9 +311,10 @@ int mh_encode_huffman(const uint8_t *symbols, uint64_t n_symbols, uint32_t block
                         block_bit_offsets);
 }
 
-int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
-                    uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
-                    uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init) {
+int mh_encode_frame_marks(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                          uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
+                          uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init,
+                          uint32_t *mid_marks) {
   if (!gray || !canon_header || !codes || !codes_len || !block_offsets) return MH_ERR_INVALID_ARG;
   if (!width || !height || width > MH_MAX_DIM || height > MH_MAX_DIM) return MH_ERR_DIMS;
   const uint32_t bw = (width + 7) / 8, bh = (height + 7) / 8;
@@ -321,22 +325,67 @@ int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32
   if (!(flags & MH_FLAG_NO_DELTA)) {
     for (uint64_t b = 0; b < nb; ++b) {
       uint8_t *blk = blocks.data() + b * 64;
+      // the decoder's running sum when it begins symbol 32 is pixel 31 (block_init or not: the
+      // first delta is in the sum either way); read before the deltas replace the pixels
+      if (mid_marks) mid_marks[b] = (uint32_t)blk[31] << 16;
       mh_encode_signed_byte_deltas(blk, blk, 64);
       if (block_init) {  // AAPLRenderer.m:456-472
         block_init[b] = blk[0];
         blk[0] = 0;
       }
     }
-  } else if (block_init) {
-    std::memset(block_init, 0, nb);  // AAPLRenderer.m:517-523
+  } else {
+    if (block_init) std::memset(block_init, 0, nb);  // AAPLRenderer.m:517-523
+    if (mid_marks) std::memset(mid_marks, 0, nb * sizeof(uint32_t));
   }
   if (codes_cap < 2) return MH_ERR_CAPACITY;
+  std::vector<uint32_t> mid_bits(mid_marks ? nb : 0);
   rc = encode_symbols(blocks.data(), blocks.size(), 64, canon_header, codes, codes_cap - 2,
-                      codes_len, block_offsets, (flags & MH_ENCODE_LIMIT_LENGTHS) != 0);
+                      codes_len, block_offsets, (flags & MH_ENCODE_LIMIT_LENGTHS) != 0,
+                      mid_marks ? mid_bits.data() : nullptr);
   if (rc != MH_OK) return rc;
+  if (mid_marks)
+    for (uint64_t b = 0; b < nb; ++b) mid_marks[b] |= mid_bits[b];
   codes[*codes_len] = 0;  // renderer read-ahead (AAPLRenderer.m:576-585)
   codes[*codes_len + 1] = 0;
   *codes_len += 2;
+  return MH_OK;
+}
+
+int mh_encode_frame(const uint8_t *gray, uint32_t width, uint32_t height, uint32_t flags,
+                    uint8_t canon_header[256], uint8_t *codes, uint64_t codes_cap,
+                    uint64_t *codes_len, uint32_t *block_offsets, uint8_t *block_init) {
+  return mh_encode_frame_marks(gray, width, height, flags, canon_header, codes, codes_cap, codes_len,
+                               block_offsets, block_init, nullptr);
+}
+
+int mh_mid_marks(const uint8_t *codes, uint64_t codes_bytes, const uint32_t *block_offsets,
+                 uint64_t n_blocks, const mh_lookup_symbol *table1, const mh_lookup_symbol *table2,
+                 uint32_t table2_entries, const uint8_t *block_init, uint32_t flags, uint32_t *mid_marks) {
+  if (!codes || !block_offsets || !table1 || !table2 || !mid_marks || n_blocks == 0) return MH_ERR_INVALID_ARG;
+  if (flags & ~MH_FLAG_NO_DELTA) return MH_ERR_INVALID_ARG;
+  if (table2_entries < 256 || (table2_entries % 256) != 0 || table2_entries > MH_TABLE2_MAX_ENTRIES)
+    return MH_ERR_TABLE;
+  const bool delta = !(flags & MH_FLAG_NO_DELTA);
+  const auto byte_at = [&](uint64_t i) -> uint32_t { return i < codes_bytes ? codes[i] : 0u; };
+  for (uint64_t b = 0; b < n_blocks; ++b) {
+    uint64_t bit = block_offsets[b];
+    uint32_t prev = delta && block_init ? block_init[b] : 0u;
+    for (int k = 0; k < 32; ++k) {
+      const uint64_t by = bit >> 3;
+      const uint32_t w24 = (byte_at(by) << 16) | (byte_at(by + 1) << 8) | byte_at(by + 2);
+      const uint32_t pat = (w24 >> (8u - (uint32_t)(bit & 7u))) & 0xFFFFu;
+      mh_lookup_symbol e = table1[pat >> 8];
+      if (e.bitWidth == 0) {  // an escape; one past table2 is the all-zero entry, as in the kernels
+        const uint32_t idx = (uint32_t)e.symbol * 256u + (pat & 0xFFu);
+        e = idx < table2_entries ? table2[idx] : mh_lookup_symbol{0, 0};
+      }
+      if (e.bitWidth == 0) continue;  // a zero-width lookup repeats prev and does not advance
+      bit += e.bitWidth > 16 ? 16 : e.bitWidth;
+      prev = (prev + e.symbol) & 0xFFu;
+    }
+    mid_marks[b] = (uint32_t)(bit - block_offsets[b]) | ((delta ? prev : 0u) << 16);
+  }
   return MH_OK;
 }
 

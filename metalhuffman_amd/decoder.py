@@ -11,13 +11,14 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import dataclasses
+import zlib
 from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _native as N
-from .codec import DecodeSetPlan, EncodedFrame, block_grid, decode_set_plan, finite_f32, frame_set_layout
+from .codec import DecodeSetPlan, EncodedFrame, Huffman, block_grid, decode_set_plan, finite_f32, frame_set_layout
 from .codec import norm_format as _norm_format
 
 ALIGN = 16  # frame code starts inside a packed batch (16-byte buffer loads)
@@ -45,12 +46,22 @@ def _header_tensor(canon, dev: torch.device, convert: bool = True) -> torch.Tens
     return torch.from_numpy(np.ascontiguousarray(canon, np.uint8)).to(dev)
 
 
+def _tables_key(t1, t2) -> int:
+    """A checksum of host T1/T2 (generateSplitLookupTables' arrays): which code a table pair is.
+    Mid-block marks hold a running symbol sum, so they are good under their frame's own tables only."""
+    return zlib.crc32(np.ascontiguousarray(t2, np.uint8), zlib.crc32(np.ascontiguousarray(t1, np.uint8)))
+
+
 @dataclasses.dataclass
 class DeviceTables:
     """T1/T2 (+ the derived LDS table) resident on one device."""
     table1: torch.Tensor     # u8[512]
     table2: torch.Tensor     # u8[2 * entries]
     lut: Optional[torch.Tensor]  # u8[mh_lut_bytes()] from mh_prepare_lut, or None
+    # _tables_key of the host tables these were uploaded or built from (None: unknown, e.g. built
+    # from a header that is already a device tensor): decode() uses a frame's mid-block marks only
+    # under the tables of the frame's own code
+    key: Optional[int] = None
 
     @property
     def table2_entries(self) -> int:
@@ -62,7 +73,7 @@ class DeviceTables:
         dev = _dev(device)
         d1 = torch.from_numpy(np.ascontiguousarray(t1, np.uint8)).to(dev)
         d2 = torch.from_numpy(np.ascontiguousarray(t2, np.uint8)).to(dev)
-        tabs = cls(d1, d2, None)
+        tabs = cls(d1, d2, None, _tables_key(t1, t2))
         if prepare_lut:
             tabs.prepare_lut(stream)
         return tabs
@@ -88,6 +99,11 @@ class DeviceTables:
                 "mh_build_tables_device")
         tabs = cls(d1, d2, lut)
         tabs._meta = meta
+        if not isinstance(canon, torch.Tensor):
+            try:
+                tabs.key = _tables_key(*Huffman.generateSplitLookupTables(np.ascontiguousarray(canon, np.uint8)))
+            except (N.MHError, ValueError):  # a header the device will reject too (check_status)
+                pass
         return tabs
 
     def check_status(self) -> int:
@@ -167,6 +183,23 @@ class DeviceFrames:
     block_init: Optional[torch.Tensor] = None   # u8[n * NB]
     flags: int = 0
     code_bytes: int = 0                  # payload bytes (sum over frames, pad excluded)
+    # u32 as int32[n * NB] mid-block marks, or None: used by decode() of a single frame
+    # (mh_decode_marked); every other entry ignores them. One rule, EncodedFrame's: marks belong to
+    # the buffers they were made for, named by marks_for = (block_offsets, codes, block_init,
+    # tables key). decode() passes the marks only while the object still holds those very tensors
+    # and is given tables of that key (DeviceTables.key, the frames' own code); in every other case
+    # -- re-seated buffers, dataclasses.replace with other buffers, foreign or unkeyed tables, a
+    # batch -- the launch is mh_decode's. The tables are part of the rule because a mark holds a
+    # running symbol sum: decode() accepts any tables for any frames, and under another code the
+    # result is defined by the walk from the block's offset (the oracle's), which marks of the
+    # frame's own code would not reproduce.
+    mid_marks: Optional[torch.Tensor] = None
+    marks_for: Optional[tuple] = dataclasses.field(default=None, repr=False, compare=False)
+
+    def bind_mid_marks(self, marks: Optional[torch.Tensor], tables_key: Optional[int]) -> None:
+        """Attach marks made from this object's present buffers, valid under the tables of `tables_key`."""
+        self.mid_marks = marks
+        self.marks_for = (self.block_offsets, self.codes, self.block_init, tables_key)
 
     @property
     def n_blocks(self) -> int:
@@ -177,7 +210,9 @@ class DeviceFrames:
     def pack(cls, frames: Sequence[EncodedFrame], device="cuda", shared_table: bool = True) -> "DeviceFrames":
         """Upload frames (host arrays) into one packed device batch. shared_table=True
         (default): the frames must share one canonical table (decode()); False: any
-        headers, for decode_frames() with a DeviceTableSet."""
+        headers, for decode_frames() with a DeviceTableSet. When every frame has valid mid-block
+        marks (EncodedFrame.valid_mid_marks: made from the frame's present bytes) they are
+        uploaded too, in one buffer with the block offsets and right behind them."""
         dev = _dev(device)
         if not frames:
             raise ValueError("no frames")
@@ -200,9 +235,19 @@ class DeviceFrames:
         fco = None
         if len(frames) > 1:
             fco = torch.tensor(starts, dtype=torch.int64, device=dev)
-        return cls(w, h, len(frames), torch.from_numpy(offs.view(np.int32)).to(dev),
-                   torch.from_numpy(packed).to(dev), fco, init, fl,
-                   sum(f.payload_bytes for f in frames))
+        d_offs, d_marks = None, None
+        host_marks = [f.valid_mid_marks() for f in frames]
+        if all(m is not None for m in host_marks):
+            marks = np.concatenate(host_marks).astype(np.uint32)
+            both = torch.from_numpy(np.concatenate([offs, marks]).view(np.int32)).to(dev)
+            d_offs, d_marks = both[: offs.size], both[offs.size:]
+        else:
+            d_offs = torch.from_numpy(offs.view(np.int32)).to(dev)
+        out = cls(w, h, len(frames), d_offs, torch.from_numpy(packed).to(dev), fco, init, fl,
+                  sum(f.payload_bytes for f in frames))
+        if d_marks is not None:
+            out.bind_mid_marks(d_marks, _tables_key(*frames[0].tables()) if shared_table else None)
+        return out
 
 
 @dataclasses.dataclass
@@ -261,8 +306,27 @@ class DeviceFrameSet:
         return g.data_ptr(), self.total_blocks
 
 
+def _marks_ptr(frames: DeviceFrames, tables: Optional[DeviceTables]) -> Optional[int]:
+    """The marks' address if decode(frames, tables) may use them (DeviceFrames.marks_for), else None."""
+    m, bound = frames.mid_marks, frames.marks_for
+    if m is None or bound is None or tables is None:
+        return None
+    if (bound[0] is not frames.block_offsets or bound[1] is not frames.codes or bound[2] is not frames.block_init
+            or bound[3] is None or tables.key != bound[3]):
+        return None
+    if m.device != frames.codes.device or m.numel() != frames.block_offsets.numel() or not m.is_contiguous():
+        return None
+    return m.data_ptr()
+
+
 def _frame_entry(frames: DeviceFrames, tables: Optional[DeviceTables], extra_flags: int = 0):
-    """(mh_frame, device index) for (frames, tables), extra_flags ORed into the frames'
+    """(mh_frame, device index) for (frames, tables): _frame_cache's struct and its device."""
+    fr, cache = _frame_cache(frames, tables, extra_flags)
+    return fr, cache[3]
+
+
+def _frame_cache(frames: DeviceFrames, tables: Optional[DeviceTables], extra_flags: int = 0):
+    """(mh_frame, cache entry) for (frames, tables), extra_flags ORed into the frames'
     flags. Filling a ctypes struct field by field costs ~5.5 us of Python -- more than
     the 5.3 us decode of a 2048x1536 frame -- so the structs are kept on `frames` and
     reused while the buffers and sizes they were built from are the same objects (the
@@ -276,15 +340,17 @@ def _frame_entry(frames: DeviceFrames, tables: Optional[DeviceTables], extra_fla
     else:
         slot, t1, t2, lut = "_frs_cache", None, None, None
     refs = (frames.block_offsets, frames.codes, frames.frame_code_offsets, frames.block_init, t1, t2, lut)
+    marks = getattr(frames, "mid_marks", None)  # (a DeviceFrameSet has none)
     key = (id(refs[0]), id(refs[1]), id(refs[2]), id(refs[3]), id(t1), id(t2), id(lut),
-           frames.width, frames.height, frames.n_frames, frames.flags)
+           frames.width, frames.height, frames.n_frames, frames.flags, id(marks))
     cache = frames.__dict__.get(slot)
     if cache is None or cache[0] != key:
         dev = frames.codes.device
         if dev.type != "cuda" or any(t is not None and t.device != dev for t in refs):
             raise ValueError("tables and frames must live on the same HIP device" if tables is not None
                              else "the frames' buffers must live on one HIP device")
-        cache = (key, refs, {}, dev.index)
+        # [4], [5]: the marks decode() passes for this pair (and a reference that keeps them alive)
+        cache = (key, refs, {}, dev.index, _marks_ptr(frames, tables) if marks is not None else None, marks)
         frames.__dict__[slot] = cache
     fr = cache[2].get(extra_flags)
     if fr is None:
@@ -295,7 +361,7 @@ def _frame_entry(frames: DeviceFrames, tables: Optional[DeviceTables], extra_fla
                         N.mh_dims(frames.width, frames.height, bw, bh), frames.n_frames,
                         frames.flags | extra_flags)
         cache[2][extra_flags] = fr
-    return fr, cache[3]
+    return fr, cache
 
 
 def _frame_struct(frames: DeviceFrames, tables: DeviceTables, extra_flags: int = 0) -> N.mh_frame:
@@ -312,7 +378,8 @@ def decode(frames: DeviceFrames, tables: DeviceTables, out: Optional[torch.Tenso
     routes the call to the lane-pair diagnostic library, _native.diag_lanepairs()).
     The per-call host path is kept lean (a cached struct, the raw current stream): one
     frame decodes in ~5.3 us, so every microsecond of Python shows in eager loops."""
-    fr, dev_index = _frame_entry(frames, tables, extra_flags)
+    fr, cache = _frame_cache(frames, tables, extra_flags)
+    dev_index, marks = cache[3], cache[4]
     pitch = (frames.width + 7) // 8 * 8
     h = frames.height
     # _out_raster and _raw_stream_ptr inlined on purpose: two calls show on the 5.3 us single-frame path
@@ -333,6 +400,8 @@ def decode(frames: DeviceFrames, tables: DeviceTables, out: Optional[torch.Tenso
         sp = torch.cuda.current_stream(dev_index).cuda_stream
     if fr.flags & N.MH_FLAG_LANE_PAIRS:  # the diagnostic library's kernel (A/B only)
         rc = N.diag_lanepairs().mh_diag_decode_lanepairs(ctypes.byref(fr), out.data_ptr(), pitch, h * pitch, sp)
+    elif marks is not None:
+        rc = N.lib().mh_decode_marked(ctypes.byref(fr), marks, out.data_ptr(), pitch, h * pitch, sp)
     else:
         rc = N.lib().mh_decode(ctypes.byref(fr), out.data_ptr(), pitch, h * pitch, sp)
     if rc:

@@ -9,7 +9,9 @@ Stamps (s_memrealtime, 100 MHz) per wave: 0 entry, 1 first header resolved,
 --launches N stamps the last of N back-to-back launches, each on a frame set of its own
 (with --cold: all of them never decoded before, the flush in front of the first).
 --rows (MH_DIAG_ROWS build, small launches): core clocks of each of the 8 block rows of
-the chain, from the s_memtime stamps behind every row store.
+the chain, from the s_memtime stamps behind every row store. A single frame with mid-block
+marks takes mh_decode_frame_marked_kernel, whose lanes run 4 rows (32 steps) each: the same slots,
+rows 0-3 only. --no-marks drops the marks (mh_decode_frame_kernel in the same library).
 """
 import argparse
 import ctypes
@@ -43,6 +45,7 @@ ap.add_argument("--launches", type=int, default=1,
                 help="stamp the last of this many back-to-back launches, each on its own frame set")
 ap.add_argument("--rows", action="store_true",
                 help="MH_DIAG_ROWS build: core clocks per block row of the single-frame chain")
+ap.add_argument("--no-marks", action="store_true", help="decode without the frames' mid-block marks")
 args = ap.parse_args()
 
 lib = N.lib()
@@ -68,9 +71,17 @@ for k in range(1, args.launches):
         sets_before.append(efs)
 t1, t2 = efs[0].tables()
 tabs = D.DeviceTables.upload(t1, t2, "cuda")
-fr = D.DeviceFrames.pack(efs, "cuda")
-fr2 = D.DeviceFrames.pack(efs2, "cuda")
-frs_before = [D.DeviceFrames.pack(e, "cuda") for e in sets_before]
+def pack(e):
+    f = D.DeviceFrames.pack(e, "cuda")
+    if args.no_marks:
+        f.mid_marks = None
+    return f
+
+
+fr, fr2 = pack(efs), pack(efs2)
+frs_before = [pack(e) for e in sets_before]
+# a lane's chain: 4 rows from a mark in the marked single-frame kernel, else the block's 8
+chain_rows = 4 if (fr2.mid_marks is not None and fr2.n_frames == 1 and N.has_mid_marks()) else 8
 out = D.decode(fr, tabs)
 out2 = torch.empty_like(out)
 outs_before = [torch.empty_like(out) for _ in frs_before]
@@ -102,7 +113,7 @@ if args.clock:  # slot 5 = s_memtime cycles between stamps 3 and 4 (staged tiles
     ok = (cyc > 0) & (us > 0)
     mhz = cyc[ok] / us[ok]
     print(f"decode core cycles p50 {np.median(cyc[ok]):.0f} p90 {np.percentile(cyc[ok], 90):.0f}; "
-          f"per symbol p50 {np.median(cyc[ok]) / 64:.1f}; clock MHz p10 {np.percentile(mhz, 10):.0f} "
+          f"per symbol p50 {np.median(cyc[ok]) / (8 * chain_rows):.1f}; clock MHz p10 {np.percentile(mhz, 10):.0f} "
           f"p50 {np.median(mhz):.0f} p90 {np.percentile(mhz, 90):.0f}")
     st[:, 5] = st[:, 4]
 if args.args:  # slot 5 = the small-launch kernels' output arguments in registers (behind stamp 2)
@@ -116,14 +127,14 @@ if args.rows:  # lanes 0-7: s_memtime (low word) behind each row's store; lane 8
     assert lib.mh_diag_rows(rb, ctypes.c_size_t(8192 * 16)) == 8192 * 16
     rw = np.frombuffer(rb, dtype=np.uint32).reshape(-1, 16)[live].astype(np.int64)
     rw = rw[rw[:, 8] != 0]
-    edges = np.concatenate([rw[:, 8:9], rw[:, :8]], axis=1)
+    edges = np.concatenate([rw[:, 8:9], rw[:, :chain_rows]], axis=1)
     per_row = np.diff(edges, axis=1) & 0xFFFFFFFF
-    print(f"row clocks ({len(rw)} waves), cycles per symbol (8 symbols per row):")
-    for r in range(8):
+    print(f"row clocks ({len(rw)} waves, {chain_rows} rows per lane), cycles per symbol (8 symbols per row):")
+    for r in range(chain_rows):
         v = per_row[:, r] / 8.0
         print(f"  row {r}: p10 {np.percentile(v, 10):6.1f}  p50 {np.median(v):6.1f}  p90 {np.percentile(v, 90):6.1f}  "
               f"mean {v.mean():6.1f}")
-    tot = per_row.sum(axis=1) / 64.0
+    tot = per_row.sum(axis=1) / (8.0 * chain_rows)
     print(f"  all rows: p50 {np.median(tot):6.1f}  mean {tot.mean():6.1f} cycles per symbol")
 names = ["entry", "hdr", "lut", "staged", "tile0", "loop", "drain"]
 for i, nm in enumerate(names):
